@@ -107,6 +107,26 @@ def synth_batch(n_img, N, seed0, device, distribution="saag"):
     return [torch.stack(t).to(device) for t in (pos, scl, quat, col, opa)]
 
 
+DUMP_BYTES = 63_000_000  # --dump-outputs: all arrays together stay under 64 MB, .npy headers included
+
+
+def dump_outputs(outdir, arrays):
+    """--dump-outputs: each array as <outdir>/<name>.npy in float32.  Beyond DUMP_BYTES in all, every array keeps the same
+    fraction of its elements, flattened, at positions drawn from a fixed seed and kept in index order: the sample depends on
+    the array's size alone, so runs with the same arguments write the same elements."""
+    os.makedirs(outdir, exist_ok=True)
+    total = sum(a.size * 4 for a in arrays.values())
+    frac = min(1.0, DUMP_BYTES / total) if total else 1.0
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if frac < 1.0:
+            idx = np.sort(np.random.RandomState(0).choice(a.size, max(1, int(a.size * frac)), replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(outdir, name + ".npy"), a)
+    sys.stderr.write(f"bench.py: {len(arrays)} outputs of the last timed step -> {outdir}"
+                     + (f" (sampled: {frac:.3f} of each)\n" if frac < 1.0 else "\n"))
+
+
 def pmc_field_traffic(run_key):
     """config 5: HBM bytes per step of both field stages together (rocFFT + spectral kernels), same source."""
     if not os.path.exists(PMC_SUMMARY):
@@ -450,9 +470,17 @@ def main(argv=None):
                          "8 ranks: every rank must issue the same collectives in the same order")
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="rehearse launcher + rendezvous + collectives on CPU tensors (gloo), no GPU work, no bench line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed region, write what its LAST step computed (rank 0: image, depth map, every input "
+                         "gradient) as DIR/<name>.npy in float32, at most 64 MB in all (a fixed, seeded sample of each array "
+                         "beyond that).  The inputs are seeded: two builds run with the same arguments can be compared")
     args = ap.parse_args(argv)
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.stub_renderer or args.rendezvous_only):
+        raise SystemExit("--dump-outputs: the stub / rendezvous rehearsals compute no rasterizer outputs")
 
     # ---- launcher decision: BEFORE torch / fresnel_amd are imported or any GPU call is made ----
     if "WORLD_SIZE" not in os.environ:
@@ -533,6 +561,9 @@ def main(argv=None):
     gD = (torch.randn(per_gpu, S, S, generator=g) * 0.1).to(device)
     bucket = torch.zeros(DECODER_GRAD_FLOATS, device=device) if dist is not None else None
     grad_leaves = leaves + ([phases] if phases is not None else []) + ([wl] if is_asm else [])
+    grad_names = (["positions", "scales", "rotations", "colors", "opacities"] + (["phases"] if phases is not None else [])
+                  + (["wavelengths"] if is_asm else []))
+    last = {} if args.dump_outputs and rank == 0 else None  # --dump-outputs: the latest step's outputs (references, no copies)
 
     def step_loop():
         # reference call pattern, TGD:1209-1226: `for b in range(B): rendered, depth = renderer(out['positions'][b], ...,
@@ -548,10 +579,14 @@ def main(argv=None):
                               phases=None if phases is None else phases[b])
                 imgs.append(im)
                 deps.append(dp_)
+        img = torch.stack(imgs)
+        dep = None if is_asm else torch.stack(deps)
         if is_asm:
-            torch.autograd.backward([torch.stack(imgs)], [gI])
+            torch.autograd.backward([img], [gI])
         else:
-            torch.autograd.backward([torch.stack(imgs), torch.stack(deps)], [gI, gD])
+            torch.autograd.backward([img, dep], [gI, gD])
+        if last is not None:
+            last.update(image=img, depth=dep)
         if bucket is not None:
             dist.all_reduce(bucket)
 
@@ -567,6 +602,8 @@ def main(argv=None):
         else:
             img, dep = ren(*leaves, cam, return_depth=True, phases=phases)
             torch.autograd.backward([img, dep], [gI, gD])
+        if last is not None:
+            last.update(image=img, depth=None if is_asm else dep)
         if bucket is not None:
             dist.all_reduce(bucket)  # decoder-gradient bucket of the DP training step
 
@@ -588,6 +625,10 @@ def main(argv=None):
     # warm-up -> pair count -> cold timed region -> collectively agreed clock spin-up -> timed region: run_protocol
     compute_stages = ("splat_fwd", "field_fwd", "field_bwd", "splat_bwd") if is_asm else ("composite_fwd", "composite_bwd")
     res = run_protocol(step, torch.cuda.synchronize, dist, args, B, torch.zeros(1, device=device), compute_stages, count_pairs)
+    outputs = None
+    if last is not None:  # the timed region's last step, copied to the host before anything below runs the step again
+        outputs = {k: v.detach().cpu().numpy() for k, v in last.items() if v is not None}
+        outputs.update({"grad_" + n: t.grad.detach().cpu().numpy() for n, t in zip(grad_names, grad_leaves)})
     D_local, U_local, tile_w, pairs_local = res["extra"]
     dom_stage, spinup_steps = res["dom_stage"], res["spinup_steps"]
     warm_avg = res["sustained_avg"] if res["sustained_avg"] is not None else res["cold_avg"]
@@ -728,6 +769,8 @@ def main(argv=None):
                        "saturation_skip": bool(args.saturation_skip), "parallelism": f"image-wise dp{world}"},
             "roofline": roofline, "cpu_baseline": cpu_baseline,
         }
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, outputs)
         sys.stdout.flush()
         os.write(result_fd, (json.dumps(line) + "\n").encode())
     if dist is not None:

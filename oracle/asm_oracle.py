@@ -13,6 +13,23 @@ import torch
 from . import fgs_oracle as orc
 
 
+def _rounded_once(fn):
+    """`fn` on an fp32 / complex64 tensor evaluated in fp64 and rounded to the input's type once.  torch hands exp / sin / cos /
+    sqrt and the FFTs of a CPU tensor to vector-math and FFT kernels that the math library picks per host CPU, and in fp32 their
+    last bits differ from kernel to kernel; the ASM scenes amplify that to 2e-5 of the gradients, beyond the 1e-5 this
+    restatement is pinned to (tests/test_oracle_vs_golden.py).  Rounded once from fp64, the values are those of a correctly
+    rounded fp32 evaluation on every host.  fp64 runs (the referee) are unchanged."""
+    def f(x):
+        if x.dtype in (torch.float32, torch.complex64):
+            return fn(x.to(torch.float64 if x.dtype == torch.float32 else torch.complex128)).to(x.dtype)
+        return fn(x)
+    return f
+
+
+_exp, _sin, _cos, _sqrt = (_rounded_once(f) for f in (torch.exp, torch.sin, torch.cos, torch.sqrt))
+_fft2, _ifft2 = _rounded_once(torch.fft.fft2), _rounded_once(torch.fft.ifft2)
+
+
 def _prec(f64):
     import contextlib
     return orc.fp64() if f64 else contextlib.nullcontext()
@@ -55,7 +72,7 @@ def transfer_function(H, W, pixel_pitch, z, wl, dtype=torch.float32):
     fy = torch.fft.fftfreq(H, d=pixel_pitch, dtype=dtype)
     FX, FY = torch.meshgrid(fx, fy, indexing="xy")
     kz_sq = torch.clamp((1.0 / wl) ** 2 - FX ** 2 - FY ** 2, min=0)
-    return torch.exp(1j * 2 * torch.pi * z * torch.sqrt(kz_sq))
+    return _exp(1j * 2 * torch.pi * z * _sqrt(kz_sq))
 
 
 def propagate(field, z, wl, pixel_pitch=1.0 / 256.0):
@@ -63,7 +80,7 @@ def propagate(field, z, wl, pixel_pitch=1.0 / 256.0):
     H, W = field.shape
     rdt = torch.float64 if field.dtype == torch.complex128 else torch.float32
     Htf = transfer_function(H, W, pixel_pitch, torch.as_tensor(z, dtype=rdt), torch.as_tensor(wl, dtype=rdt), rdt)
-    return torch.fft.ifft2(torch.fft.fft2(field) * Htf)
+    return _ifft2(_fft2(field) * Htf)
 
 
 def render(pos, scale, quat, color, opacity, phases, wavelengths, cam, bg=(0.0, 0.0, 0.0), max_radius=64.0,
@@ -102,13 +119,13 @@ def render(pos, scale, quat, color, opacity, phases, wavelengths, cam, bg=(0.0, 
         ly, lx = torch.meshgrid(torch.arange(y0, y1, dtype=dtype), torch.arange(x0, x1, dtype=dtype), indexing="ij")
         dx, dy = lx - mean[i, 0], ly - mean[i, 1]
         m = conic[i, 0] * dx * dx + conic[i, 1] * dx * dy + conic[i, 2] * dy * dy
-        amp = torch.exp(-0.5 * m) * opa[i]
+        amp = _exp(-0.5 * m) * opa[i]
         p = int(plane_idx[i])
         for c in range(3):
             phc = ph[i, c] if ph.dim() == 2 else ph[i]
             pad = (x0, W - x1, y0, H - y1)
-            fields[p * 3 + c][0] = fields[p * 3 + c][0] + torch.nn.functional.pad(amp * col[i, c] * torch.cos(phc), pad)
-            fields[p * 3 + c][1] = fields[p * 3 + c][1] + torch.nn.functional.pad(amp * col[i, c] * torch.sin(phc), pad)
+            fields[p * 3 + c][0] = fields[p * 3 + c][0] + torch.nn.functional.pad(amp * col[i, c] * _cos(phc), pad)
+            fields[p * 3 + c][1] = fields[p * 3 + c][1] + torch.nn.functional.pad(amp * col[i, c] * _sin(phc), pad)
     total = [torch.zeros(H, W, dtype=torch.complex128 if dtype == torch.float64 else torch.complex64) for _ in range(3)]
     for p in range(num_planes):  # DR:1291-1313
         z = torch.tensor(focal_depth, dtype=dtype) - planes[p]                      # DR:1293-1295, in the run's dtype
@@ -117,9 +134,9 @@ def render(pos, scale, quat, color, opacity, phases, wavelengths, cam, bg=(0.0, 
             continue
         for c in range(3):
             Htf = transfer_function(H, W, pixel_pitch, z.to(dtype), wl[c], dtype)
-            total[c] = total[c] + torch.fft.ifft2(torch.fft.fft2(fc[c]) * Htf)
+            total[c] = total[c] + _ifft2(_fft2(fc[c]) * Htf)
     tf = torch.stack(total, dim=-1)                                   # (H,W,3) complex
-    rendered = torch.sqrt(tf.real ** 2 + tf.imag ** 2 + 1e-8)          # DR:1316-1319
+    rendered = _sqrt(tf.real ** 2 + tf.imag ** 2 + 1e-8)               # DR:1316-1319
     rendered = torch.clamp(rendered / rendered.max().clamp(min=1.0), 0, 1)
     total_amp = tf.abs().sum(dim=-1, keepdim=True).clamp(0, 1)         # DR:1327
     rendered = rendered + torch.tensor(bg, dtype=dtype).view(1, 1, 3) * (1 - total_amp)

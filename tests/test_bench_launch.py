@@ -149,3 +149,70 @@ def test_per_image_loop_line_on_the_gpu():
     assert out[False]["call_pattern"].startswith("batched") and out[True]["call_pattern"].startswith("per-image loop: 32 sequential")
     assert out[False]["config"]["pairs_per_step"] == out[True]["config"]["pairs_per_step"] > 0
     assert out[True]["ms_per_step"] > out[False]["ms_per_step"]  # 32 calls against one
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_under_test", BENCH)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    mod._import_compute()
+    return mod
+
+
+def test_dump_outputs_writes_float32_within_the_budget(tmp_path, monkeypatch):
+    """--dump-outputs: every array as <name>.npy in float32; under the budget whole and bit-exact, over it a sample of the same
+    fraction of each array at seeded positions, identical from run to run, that keeps the files under the budget."""
+    import numpy as np
+    bench = _bench_module()
+    rs = np.random.RandomState(1)
+    arrays = {"image": rs.standard_normal((2, 3, 40, 40)).astype(np.float32), "grad_opacities": rs.standard_normal(500)}
+    bench.dump_outputs(str(tmp_path / "whole"), arrays)
+    for k, v in arrays.items():
+        got = np.load(tmp_path / "whole" / (k + ".npy"))
+        assert got.dtype == np.float32 and got.shape == v.shape and np.array_equal(got, v.astype(np.float32))
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4000)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), arrays)
+    data = 0
+    for k, v in arrays.items():
+        a, b = np.load(tmp_path / "a" / (k + ".npy")), np.load(tmp_path / "b" / (k + ".npy"))
+        assert a.dtype == np.float32 and a.ndim == 1 and 0 < a.size < v.size and np.array_equal(a, b)
+        assert np.isin(a, v.astype(np.float32).reshape(-1)).all()  # a sample of the array's own elements
+        data += a.nbytes
+    assert data <= 4000
+
+
+def test_dump_outputs_is_refused_where_nothing_is_rendered(tmp_path):
+    r = subprocess.run([sys.executable, BENCH, "--stub-renderer", "--dump-outputs", str(tmp_path / "d")],
+                       capture_output=True, text=True, env=_clean_env(), timeout=300)
+    assert r.returncode != 0 and "--dump-outputs" in r.stderr and not (tmp_path / "d").exists()
+
+
+@pytest.mark.gpu
+def test_dump_outputs_on_the_gpu(tmp_path):
+    """--dump-outputs after a short real run: the image, the depth map and every input gradient of the timed region's last step;
+    the same arguments give the same outputs again, and the per-image loop computes what the batched call does.  (decoder-like
+    inputs: random rotations of anisotropic Gaussians, so that no gradient is zero by symmetry.)"""
+    import numpy as np
+    outs = {}
+    for tag, flag in (("a", []), ("b", []), ("loop", ["--per-image-loop"])):
+        r = subprocess.run([sys.executable, BENCH, "--workload", "config1", "--distribution", "decoder_like", "--steps", "3",
+                            "--warmup", "2", "--spinup-ms", "0", "--dump-outputs", str(tmp_path / tag)] + flag,
+                           capture_output=True, text=True, env=_clean_env(), timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        assert json.loads([l for l in r.stdout.splitlines() if l.strip()][0])["steps"] == 3
+        outs[tag] = {f[:-4]: np.load(tmp_path / tag / f) for f in sorted(os.listdir(tmp_path / tag))}
+    names = {"image", "depth"} | {"grad_" + k for k in ("positions", "scales", "rotations", "colors", "opacities")}
+    assert set(outs["a"]) == names, sorted(outs["a"])
+    shapes = {k: v.shape for k, v in outs["a"].items()}
+    assert shapes["image"] == (32, 3, 128, 128) and shapes["depth"] == (32, 128, 128), shapes
+    assert shapes["grad_positions"] == (32, 256, 3) and shapes["grad_opacities"] == (32, 256), shapes
+    for k, v in outs["a"].items():
+        m = float(np.abs(v).max())
+        assert v.dtype == np.float32 and np.isfinite(v).all() and m > 0, (k, v.dtype, m)
+        for other, tol in (("b", 1e-6), ("loop", 1e-4)):
+            w = outs[other][k]
+            assert w.shape == v.shape, (k, other, w.shape)
+            err = float(np.abs(w - v).max()) / m
+            assert err <= tol, f"{k}: {other} run {err:.2e} from the first (max |x| {m:.2e})"
