@@ -22,6 +22,7 @@ EXPORTED_SYMBOLS = [
     "fgs_asm_propagate_workspace_bytes", "fgs_asm_propagate_forward", "fgs_asm_propagate_backward",
     "fgs_spectral_workspace_bytes", "fgs_spectral_loss_forward", "fgs_spectral_loss_backward",
     "fgs_helmholtz_loss_forward", "fgs_helmholtz_loss_backward", "fgs_reduction_scratch_bytes",
+    "fgs_ssim_workspace_bytes", "fgs_ssim_forward", "fgs_ssim_backward",
 ]
 
 STAGES = ["project", "depth_sort", "dup_emit", "tile_sort", "tile_ranges", "composite_fwd",
@@ -71,6 +72,16 @@ class FgsSpectralDims(ctypes.Structure):
     _fields_ = [("images", ctypes.c_int32), ("channels", ctypes.c_int32), ("height", ctypes.c_int32),
                 ("width", ctypes.c_int32), ("mode", ctypes.c_int32), ("cutoff", ctypes.c_float),
                 ("high_weight", ctypes.c_float), ("focal_depth", ctypes.c_float), ("reserved", ctypes.c_int32)]
+
+
+FGS_SSIM_MAX_TAPS = 15
+FGS_SSIM_GRAD_X, FGS_SSIM_GRAD_Y, FGS_SSIM_NONNEGATIVE, FGS_SSIM_PER_IMAGE = 1, 2, 4, 8
+
+
+class FgsSsimDims(ctypes.Structure):
+    _fields_ = [("images", ctypes.c_int32), ("channels", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("width", ctypes.c_int32), ("taps", ctypes.c_float * FGS_SSIM_MAX_TAPS), ("num_taps", ctypes.c_int32),
+                ("c1", ctypes.c_float), ("c2", ctypes.c_float), ("flags", ctypes.c_int32)]
 
 
 class FgsError(RuntimeError):
@@ -128,10 +139,14 @@ def load():
     lib.fgs_helmholtz_loss_forward.argtypes = [i32, i32, i32, f32, f32] + [vp] * 5
     lib.fgs_helmholtz_loss_backward.argtypes = [i32, i32, i32, f32, f32] + [vp] * 4
     lib.fgs_reduction_scratch_bytes.argtypes = []
+    lib.fgs_ssim_workspace_bytes.argtypes = [cp(FgsSsimDims), cp(ctypes.c_size_t), cp(ctypes.c_size_t)]
+    lib.fgs_ssim_forward.argtypes = [cp(FgsSsimDims)] + [vp] * 6
+    lib.fgs_ssim_backward.argtypes = [cp(FgsSsimDims)] + [vp] * 8
     lib.fgs_reduction_scratch_bytes.restype = ctypes.c_size_t
     for fn in (lib.fgs_asm_propagate_workspace_bytes, lib.fgs_asm_propagate_forward, lib.fgs_asm_propagate_backward,
                lib.fgs_spectral_workspace_bytes, lib.fgs_spectral_loss_forward, lib.fgs_spectral_loss_backward,
-               lib.fgs_helmholtz_loss_forward, lib.fgs_helmholtz_loss_backward):
+               lib.fgs_helmholtz_loss_forward, lib.fgs_helmholtz_loss_backward,
+               lib.fgs_ssim_workspace_bytes, lib.fgs_ssim_forward, lib.fgs_ssim_backward):
         fn.restype = ctypes.c_int
     for fn in (lib.fgs_asm_workspace_bytes, lib.fgs_asm_forward, lib.fgs_asm_backward,
                lib.fgs_wave_workspace_bytes, lib.fgs_wave_forward, lib.fgs_wave_backward):

@@ -50,6 +50,7 @@ SOURCES = {
     "fgs_gather.hip": [],
     "fgs_fft.hip": NO_SLP,
     "fgs_spectral.hip": [],
+    "fgs_ssim.hip": [],
 }
 LINK_LIBS = ["-lhipfft"]
 

@@ -16,7 +16,8 @@ Kept from TGD (same flag names / defaults / behaviour):
   renderer choice   TileBasedRenderer(res, res, use_phase_blending, phase_amplitude)   TGD:1898-1907
   camera            fx = fy = 0.8*res, cx = cy = res/2, view = I                       TGD:1910-1917
   step              decoder -> render -> stack -> L1 + normalised-depth L1 (SSIM / LPIPS only when
-                    those packages exist, as TGD:53-65) -> NaN/Inf skip -> backward ->
+                    those packages exist, as TGD:53-65; --ssim_backend hip computes the SSIM term with this
+                    package's HIP kernels, fresnel_amd/losses.py, whether pytorch_msssim exists or not) -> NaN/Inf skip -> backward ->
                     clip_grad_norm_(1.0) -> AdamW(lr, weight_decay=1e-5) ; CosineAnnealingLR
                                                                     TGD:890, 922-930, 1255-1266, 1970-1971
   data order        a fresh permutation of the images every epoch (DataLoader(shuffle=True), TGD:1760-1767), drawn
@@ -85,6 +86,8 @@ class TrainingConfig:  # subset of TGD:97-162 that this path uses; same names an
     rgb_weight: float = 1.0
     depth_weight: float = 0.1
     ssim_weight: float = 0.5
+    ssim_backend: str = "msssim"  # "msssim": pytorch_msssim's term when the package is importable, none otherwise (TGD:53-65);
+                                  # "hip": the same term from fresnel_amd.losses.ssim (HIP kernels, needs a GPU)
     gaussians_per_patch: int = 4
     max_images: Optional[int] = None
     use_fresnel_zones: bool = False
@@ -244,16 +247,35 @@ def _global_mean_std(x, dp):
     return mean, torch.sqrt(s2 / max(n - 1, 1))
 
 
+SSIM_BACKENDS = ("msssim", "hip")
+
+
+def _ssim_term_fn(cfg: TrainingConfig):
+    """The SSIM function of the step, or None: pytorch_msssim's when importable (cfg.ssim_backend "msssim", the
+    reference's behaviour), the HIP kernels' always ("hip")."""
+    if cfg.ssim_backend == "msssim":
+        return ssim_fn if SSIM_AVAILABLE else None
+    if cfg.ssim_backend == "hip":
+        from .losses import ssim as hip_ssim
+        return hip_ssim
+    raise ValueError(f"unknown ssim_backend {cfg.ssim_backend!r}: one of {SSIM_BACKENDS}")
+
+
 def compute_losses(rendered, target, rendered_depth, target_depth, cfg: TrainingConfig, dp=None):
-    """L1 + (1-SSIM if available) + normalised depth L1 (TGD:890, 906-930).  Returns (total, terms): `terms` holds the
-    individual losses as DETACHED 0-d DEVICE tensors -- nothing here synchronises with the host (the reference's
-    `.item()` per term, TGD:891-1001, would cost a device round trip each)."""
+    """L1 + SSIM term + normalised depth L1 (TGD:890, 906-930).  The SSIM term, cfg.ssim_weight * (1 - SSIM(clamp(rendered,
+    0, 1), target)), comes from pytorch_msssim when that package is importable and is left out otherwise
+    (cfg.ssim_backend "msssim", TGD:53-65), or from fresnel_amd.losses.ssim's HIP kernels (cfg.ssim_backend "hip", CUDA/ROCm
+    tensors only).  Returns (total, terms): `terms` holds the individual losses as DETACHED 0-d DEVICE tensors -- nothing here
+    synchronises with the host (the reference's `.item()` per term, TGD:891-1001, would cost a device round trip each)."""
     d: Dict[str, torch.Tensor] = {}
     rgb = F.l1_loss(rendered, target)
     d["rgb"] = rgb.detach()
     total = cfg.rgb_weight * rgb
-    if SSIM_AVAILABLE and cfg.ssim_weight > 0:
-        s = 1.0 - ssim_fn(torch.clamp(rendered, 0, 1), target, data_range=1.0, size_average=True)
+    ssim_term = _ssim_term_fn(cfg) if cfg.ssim_weight > 0 else None
+    if ssim_term is not None:
+        if cfg.ssim_backend == "hip" and not rendered.is_cuda:
+            raise ValueError("ssim_backend 'hip' needs the rendered batch on a GPU: the HIP SSIM kernels have no CPU fallback")
+        s = 1.0 - ssim_term(torch.clamp(rendered, 0, 1), target, data_range=1.0, size_average=True)
         d["ssim"] = s.detach()
         total = total + cfg.ssim_weight * s
     if rendered_depth is not None and target_depth is not None:
@@ -490,6 +512,10 @@ def run_training(cfg: TrainingConfig, dp: Optional[DPContext] = None,
                  renderer_factory: Callable = default_renderer_factory, resume: Optional[str] = None,
                  log=print, hfts: Optional[HFTSConfig] = None):
     device = torch.device(cfg.device)
+    if cfg.ssim_backend not in SSIM_BACKENDS:
+        raise ValueError(f"unknown ssim_backend {cfg.ssim_backend!r}: one of {SSIM_BACKENDS}")
+    if cfg.ssim_backend == "hip" and device.type != "cuda":
+        raise ValueError("ssim_backend 'hip' needs a GPU device: the HIP SSIM kernels have no CPU fallback")
     dp = dp or DPContext(device=device if device.type == "cuda" else None)
     if cfg.batch_size % dp.world != 0:  # fail fast, before any rank can stall in a collective (see DPContext.shard)
         raise ValueError(f"--batch_size {cfg.batch_size} is not a multiple of the {dp.world} ranks")
@@ -610,7 +636,8 @@ def run_training(cfg: TrainingConfig, dp: Optional[DPContext] = None,
     return model, epoch_history
 
 
-def main(argv=None):
+def arg_parser() -> argparse.ArgumentParser:
+    """The command line of `main` (TGD:1401-1545 names and defaults)."""
     ap = argparse.ArgumentParser(description="Train the Gaussian decoder through the HIP rasterizer")
     c = TrainingConfig()
     ap.add_argument("--experiment", type=int, default=c.experiment)
@@ -651,7 +678,13 @@ def main(argv=None):
     ap.add_argument("--renderer", default="hip", choices=["hip"],
                     help="only the HIP rasterizer ships; there is no CPU fallback")
     ap.add_argument("--seed", type=int, default=0)
-    a = ap.parse_args(argv)
+    ap.add_argument("--ssim_backend", default=c.ssim_backend, choices=list(SSIM_BACKENDS),
+                    help="SSIM term: pytorch_msssim when importable (default, as the reference) or this package's HIP kernels")
+    return ap
+
+
+def main(argv=None):
+    a = arg_parser().parse_args(argv)
     if a.experiment != 2:
         raise SystemExit("only --experiment 2 (direct patch decoder) is on this repo's hot path")
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -673,7 +706,8 @@ def main(argv=None):
                          use_phase_retrieval_loss=a.use_phase_retrieval_loss or a.use_qsr,
                          phase_retrieval_weight=a.phase_retrieval_weight,
                          use_frequency_loss=a.use_frequency_loss, frequency_loss_weight=a.frequency_loss_weight,
-                         device=f"cuda:{local_rank}", seed=a.seed, hip_graph=a.hip_graph)
+                         device=f"cuda:{local_rank}", seed=a.seed, hip_graph=a.hip_graph,
+                         ssim_backend=a.ssim_backend)
     hfts = HFTSConfig(train_resolution=a.train_resolution, progressive_schedule=a.progressive_schedule,
                       stochastic_k=a.stochastic_k, fast_mode=a.fast_mode)
     dp = DPContext(device=torch.device(cfg.device))

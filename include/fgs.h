@@ -264,6 +264,32 @@ int fgs_helmholtz_loss_backward(int32_t images, int32_t height, int32_t width, f
                                 const float *residual, const float *g_loss, float *g_field, void *stream);
 size_t fgs_reduction_scratch_bytes(void);
 
+/* SSIM (pytorch_msssim.ssim, the SSIM term of the reference's training loss, TGD:904): Gaussian-window "valid" SSIM of
+ * images x channels planes height x width (fp32, contiguous), Wang et al. 2004.  taps[0..num_taps) = the 1-D window
+ * (odd count <= 15; applied along H, then W), c1 = (K1 data_range)^2, c2 = (K2 data_range)^2.
+ * out: a DEVICE scalar (the mean of the per-plane means), or (images,) with FGS_SSIM_PER_IMAGE (the mean over channels);
+ * FGS_SSIM_NONNEGATIVE clips the per-plane means at zero first.  FGS_SSIM_GRAD_X / _Y make the forward save the
+ * backward's per-pixel factor maps in `saved` (without either, only the per-plane means: no-grad forward).
+ * The backward reads `saved` and does not modify it (a second backward through the same forward is valid); g_out has the
+ * shape of out; g_x may be NULL, g_y may be NULL (not both), g_y needs FGS_SSIM_GRAD_Y; scratch is not read (may be NULL). */
+#define FGS_SSIM_MAX_TAPS 15
+#define FGS_SSIM_GRAD_X 1
+#define FGS_SSIM_GRAD_Y 2
+#define FGS_SSIM_NONNEGATIVE 4
+#define FGS_SSIM_PER_IMAGE 8
+typedef struct FgsSsimDims {
+    int32_t images, channels, height, width;
+    float taps[FGS_SSIM_MAX_TAPS];
+    int32_t num_taps;
+    float c1, c2;
+    int32_t flags;               /* FGS_SSIM_* */
+} FgsSsimDims;
+int fgs_ssim_workspace_bytes(const FgsSsimDims *dims, size_t *saved_bytes, size_t *scratch_bytes);
+int fgs_ssim_forward(const FgsSsimDims *dims, const float *x, const float *y, float *out, void *saved, void *scratch,
+                     void *stream);
+int fgs_ssim_backward(const FgsSsimDims *dims, const float *x, const float *y, const void *saved, const float *g_out,
+                      float *g_x, float *g_y, void *scratch, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * Importance-subsampling hand-off between decoder and rasterizer (--stochastic_k; reference
  * scripts/training/train_gaussian_decoder.py:1160-1187): the n_out Gaussians whose indices torch.multinomial
