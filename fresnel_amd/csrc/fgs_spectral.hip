@@ -170,7 +170,10 @@ __global__ __launch_bounds__(RT) void k_spec_pack(int mode, int C, size_t HW, si
 __device__ __forceinline__ float spec_weight(int mode, int kx, int ky, int W, int H, float cutoff, float high_weight) {
     if (mode != 0) return 1.0f;
     const float u = fftfreq(kx, W, 1.0f / (float)W), v = fftfreq(ky, H, 1.0f / (float)H);
-    return sqrtf(u * u + v * v) < cutoff ? 1.0f : high_weight;  // TGD:474-480, 509-521
+    // the reference's fp32 radius rounding for rounding: both squares and their sum rounded on their own, whatever the unit's
+    // contraction setting (as fgs_kz2) -- one fused multiply-add moves bins that lie on the circle across the `<`
+    const float r2 = fgs_rounded(fgs_rounded(u * u) + fgs_rounded(v * v));
+    return sqrtf(r2) < cutoff ? 1.0f : high_weight;  // TGD:474-480, 509-521
 }
 
 __global__ __launch_bounds__(RT) void k_spec_reduce(int mode, int W, int H, size_t n, float cutoff, float high_weight,

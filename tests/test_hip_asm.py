@@ -162,6 +162,130 @@ def test_asm_propagator_gradients_vs_torch_autograd():
     o1 = prop.propagate(f.detach()[..., 1], torch.tensor(0.37, device=dev), torch.tensor(0.041, device=dev))
     assert rel_to_max(o1.cpu().numpy(), ro[..., 1]) <= TOL
 
+
+def _propagate_torch(f0, gw, z0, wl0, pitch, dtype, band_limit=True):
+    """The propagator formula of the test above (DR:989-1047) under torch autograd in `dtype` (float32 -> complex64, float64 ->
+    complex128): the output and the gradients of Re sum(out conj(gw)) with respect to the field, z and the per-channel
+    wavelengths.  Without band limit kz = sqrt(kz^2) as the reference takes it: NaN where kz^2 < 0."""
+    H, W, C = f0.shape
+    cdt = torch.complex64 if dtype == torch.float32 else torch.complex128
+    f = torch.tensor(f0, dtype=cdt, requires_grad=True)
+    z = torch.tensor(z0, dtype=dtype, requires_grad=True)
+    wl = torch.tensor(np.asarray(wl0, np.float32).astype(np.float64), dtype=dtype, requires_grad=True)
+    fx = torch.fft.fftfreq(W, d=pitch, dtype=dtype)
+    fy = torch.fft.fftfreq(H, d=pitch, dtype=dtype)
+    FX, FY = torch.meshgrid(fx, fy, indexing="xy")
+    outs = []
+    for c in range(C):
+        raw = (1.0 / wl[c]) ** 2 - FX ** 2 - FY ** 2
+        if band_limit:
+            kz = torch.where(raw > 0, torch.sqrt(torch.where(raw > 0, raw, torch.ones_like(raw))), torch.zeros_like(raw))
+        else:
+            kz = torch.sqrt(raw)
+        outs.append(torch.fft.ifft2(torch.fft.fft2(f[..., c]) * torch.exp(1j * 2 * torch.pi * z * kz)))
+    out = torch.stack(outs, -1)
+    (out * torch.tensor(gw, dtype=cdt).conj()).real.sum().backward()
+    return [out.detach().numpy(), f.grad.numpy(), z.grad.numpy(), wl.grad.numpy()]
+
+
+def _kz2_64(H, W, pitch, wl):
+    fx, fy = np.fft.fftfreq(W, d=pitch), np.fft.fftfreq(H, d=pitch)
+    return (1.0 / np.float64(np.float32(wl))) ** 2 - fx[None, :] ** 2 - fy[:, None] ** 2
+
+
+PROP_PITCH = 1.0 / 64.0
+PROP_WAVELENGTHS = np.array([0.0535, 0.0425, 0.0705], np.float32)
+
+
+@pytest.mark.parametrize("H,W,C", [(256, 256, 3), (512, 256, 3), (1024, 36, 1), (128, 100, 3), (64, 12, 1)])
+def test_asm_propagator_column_path_vs_torch_autograd(H, W, C):
+    """AngularSpectrumPropagator on fgs_fft2_exec's column path (power-of-two heights: k_colfft_plain<LOGN, TC> both ways in
+    the forward and in the backward): output, dL/dfield, dL/dz and dL/dwavelength per channel against torch autograd of the
+    formula in complex128, under the referee rule (helpers.assert_with_referee; the formula's own complex64 run is the fp32
+    reference).  256 x 256 / 512 x 256: <8, 16> / <9, 16>, full tiles; 1024 x 36: <10, 8>, partial tile; 128 x 100 / 64 x 12:
+    <7, 16> / <6, 16>, partial tiles.  k_prop_apply_bwd runs one block row per channel of at most 1024 / C blocks: at
+    512 x 256 x 3 the 512 blocks a channel needs are clamped to 341 (gx C <= 1024), which grid-strides and changes the layout
+    of the dz / dlambda partial sums.  Band limit on with evanescent bins in every channel; the wavelengths keep every bin at
+    least 1e-4 (relative) off the evanescent boundary, where dkz/dlambda = -1 / (lambda^3 kz) weights a bin by 1 / kz."""
+    from fresnel_amd.renderer import AngularSpectrumPropagator
+    from helpers import assert_with_referee
+    dev = _cuda()
+    rs = np.random.RandomState(H + W + C)
+    f0 = (rs.standard_normal((H, W, C)) + 1j * rs.standard_normal((H, W, C))).astype(np.complex64)
+    gw = (rs.standard_normal((H, W, C)) + 1j * rs.standard_normal((H, W, C))).astype(np.complex64)
+    wl0, z0 = PROP_WAVELENGTHS[:C], 0.37
+    for lam in wl0:
+        kz2, il2 = _kz2_64(H, W, PROP_PITCH, lam), (1.0 / np.float64(lam)) ** 2
+        assert (kz2 < 0).any() and (kz2 > 0).any() and (np.abs(kz2) > 1e-4 * il2).all(), lam
+    prop = AngularSpectrumPropagator(H, W, pixel_pitch=PROP_PITCH).to(dev)
+    f = torch.tensor(f0, device=dev, requires_grad=True)
+    z = torch.tensor(z0, device=dev, requires_grad=True)
+    wl = torch.tensor(wl0, device=dev, requires_grad=True)
+    out = prop.propagate(f, z, wl)
+    (out * torch.tensor(gw, device=dev).conj()).real.sum().backward()
+    got = [out.detach().cpu().numpy(), f.grad.cpu().numpy(), z.grad.cpu().numpy(), wl.grad.cpu().numpy()]
+    r32 = _propagate_torch(f0, gw, z0, wl0, PROP_PITCH, torch.float32)
+    r64 = _propagate_torch(f0, gw, z0, wl0, PROP_PITCH, torch.float64)
+    for a, b32, b64, what in zip(got, r32, r64, ["output", "dL/dfield", "dL/dz", "dL/dwavelength"]):
+        assert np.isfinite(a).all(), what
+        assert_with_referee(a, b32, b64, f"{H}x{W}x{C} {what}")
+
+
+@pytest.mark.parametrize("H,W", [(64, 12), (256, 256), (1024, 36), (96, 200)])
+def test_asm_propagator_plane_waves_known_answer(H, W):
+    """One plane wave e^{i 2 pi (kx x / W + ky y / H)} per channel comes out multiplied by exp(i 2 pi z kz(kx, ky)) at every
+    pixel: channel 0 a negative-x bin (kx = W - 3, ky = 5), channel 1 on the Nyquist row (kx = 1, ky = H / 2), channel 2 the
+    Nyquist corner (W / 2, H / 2), evanescent at its wavelength (band limit: kz = 0, the wave passes unchanged).  A bin
+    permutation that the inverse pass undoes again would survive a round trip, not this: the wave would pick up another
+    bin's kz.  Column path at the power-of-two heights (full, partial and below-one-tile widths), rocFFT's 2-D plan at 96."""
+    from fresnel_amd.renderer import AngularSpectrumPropagator
+    dev = _cuda()
+    pitch, z0, wl0 = 1.0 / 32.0, 0.3, np.array([0.05, 0.041, 0.0635], np.float32)
+    bins = [(W - 3, 5), (1, H // 2), (W // 2, H // 2)]
+    y, x = np.mgrid[0:H, 0:W].astype(np.float64)
+    field = np.stack([np.exp(2j * np.pi * (kx * x / W + ky * y / H)) for kx, ky in bins], -1)
+    want = np.empty_like(field)
+    for c, (kx, ky) in enumerate(bins):
+        kz2 = _kz2_64(H, W, pitch, wl0[c])[ky, kx]
+        assert (kz2 < 0) == (c == 2), (c, kz2)
+        want[..., c] = field[..., c] * np.exp(2j * np.pi * z0 * np.sqrt(max(kz2, 0.0)))
+    prop = AngularSpectrumPropagator(H, W, pixel_pitch=pitch).to(dev)
+    out = prop.propagate(torch.tensor(field.astype(np.complex64), device=dev), torch.tensor(z0, device=dev),
+                         torch.tensor(wl0, device=dev))
+    assert rel_to_max(out.cpu().numpy(), want) <= TOL
+
+
+def test_asm_propagator_without_band_limit():
+    """band_limit=False (256 x 256 x 3, column path).  No evanescent bin (pitch 1/16: |f| <= 8 sqrt 2 < 1 / lambda): the
+    output and every gradient are bitwise those of band_limit=True.  Evanescent bins (pitch 1/64): the output is non-finite
+    everywhere, as the reference's, which takes sqrt of the negative kz^2 (DR:989-996)."""
+    from fresnel_amd.renderer import AngularSpectrumPropagator
+    dev = _cuda()
+    H, W, C = 256, 256, 3
+    rs = np.random.RandomState(17)
+    f0 = (rs.standard_normal((H, W, C)) + 1j * rs.standard_normal((H, W, C))).astype(np.complex64)
+    gw = (rs.standard_normal((H, W, C)) + 1j * rs.standard_normal((H, W, C))).astype(np.complex64)
+    wl0, z0 = PROP_WAVELENGTHS, 0.37
+
+    def run(pitch, band_limit, backward=True):
+        prop = AngularSpectrumPropagator(H, W, pixel_pitch=pitch, band_limit=band_limit).to(dev)
+        f = torch.tensor(f0, device=dev, requires_grad=True)
+        z = torch.tensor(z0, device=dev, requires_grad=True)
+        wl = torch.tensor(wl0, device=dev, requires_grad=True)
+        out = prop.propagate(f, z, wl)
+        if not backward:
+            return [out.detach()]
+        (out * torch.tensor(gw, device=dev).conj()).real.sum().backward()
+        return [out.detach(), f.grad, z.grad, wl.grad]
+
+    assert all((_kz2_64(H, W, 1.0 / 16.0, lam) > 0).all() for lam in wl0)
+    for a, b, what in zip(run(1.0 / 16.0, True), run(1.0 / 16.0, False), ["output", "dL/dfield", "dL/dz", "dL/dwavelength"]):
+        assert torch.isfinite(a).all() and torch.equal(a, b), what
+    assert all((_kz2_64(H, W, PROP_PITCH, lam) < 0).any() for lam in wl0)
+    (out,) = run(PROP_PITCH, False, backward=False)
+    assert not torch.isfinite(out).any()
+    assert not np.isfinite(_propagate_torch(f0, gw, z0, wl0, PROP_PITCH, torch.float64, band_limit=False)[0]).any()
+
 def test_asm_batched_nonsquare_vs_oracle():
     """B=2, 160x96 frame (H != W exercises the fx/fy axes), anisotropic Gaussians spread over many
     depth planes, per-channel phases, custom plane/focal settings; forward + gradients vs the oracle."""
@@ -198,20 +322,25 @@ def test_asm_batched_nonsquare_vs_oracle():
     _assert_wavelength_grad(out["grad_wavelengths"], gw, "vs the oracle", want64=gw64)
 
 
-@pytest.mark.parametrize("W,H", [(72, 64), (80, 64), (368, 64), (96, 128), (96, 256), (40, 1024)])
+@pytest.mark.parametrize("W,H", [(72, 64), (80, 64), (368, 64), (96, 128), (96, 256), (40, 1024), (704, 64)])
 def test_asm_column_fused_transforms_vs_oracle(W, H):
     """Power-of-two heights take the column-fused path (rocFFT rows + k_colfft_fwd / k_colfft_bwd: our own radix-8
     column FFT in LDS and registers, fused with the transfer-function recurrence, the plane sums and their adjoints)
     when the width is a whole number of column tiles -- every log2(H) class of the kernels (64 = 8^2 and 512 = 8^3 close
     with a register butterfly, 128 / 256 / 1024 with a radix-2 / radix-4 pass), the 8-column tile of H = 1024 -- and
     rocFFT's 2-D plans otherwise (72 x 64); 368 x 64: 138 blocks, i.e. four plane groups of two planes for six planes -- the
-    last group is empty, and the transfer-function table holds every second plane only; two images, per-channel phases;
-    image and all gradients incl. the wavelengths' against the oracle (torch.fft on the CPU).
+    last group is empty, and the transfer-function table holds every second plane only; 704 x 64: 44 column tiles, i.e.
+    132 amplitude-maximum slots for three channels, more than the 128 of RED_BLOCKS, so the inverse transform is the plain
+    column pass (k_colfft_plain<6, 16, INV>) followed by k_asm_max -- the one renderer route through that pass at a
+    power-of-two height; two images, per-channel phases; image and all gradients incl. the wavelengths' against the oracle
+    (torch.fft on the CPU).
     (NOT 352 x 64 with these seeds: image 0 then has a pixel whose summed amplitude is 0.9999993 / 1.0000002 depending on the
-    summation order -- the clamp of DR:1327 -- and every gradient moves by 1e-3 with the side it falls on)"""
+    summation order -- the clamp of DR:1327 -- and every gradient moves by 1e-3 with the side it falls on; DESIGN.md section 2.
+    704 x 64 takes 250 Gaussians for the same reason: with 300, image 1 has a pixel 4e-6 from that clamp, with 250 the closest
+    of both images is 3e-5 away.)"""
     from oracle import asm_oracle, fgs_oracle as orc
     from fresnel_amd.renderer import Camera
-    N, Bn = 300, 2
+    N, Bn = (250 if (W, H) == (704, 64) else 300), 2
     bg = (0.05, 0.1, 0.15)
     rs = np.random.RandomState(W + H)
     per = []
