@@ -18,38 +18,27 @@
 //
 // Compiled WITHOUT fast-math: the transfer-function phase reaches ~200 rad, so sin/cos need the
 // accurate range reduction of sincosf.
+//
+// This unit is the angular-spectrum renderer only.  The splat kernel, the phasor table and the per-image reductions it shares
+// with the WaveFieldRenderer are in fgs_splat.h; that renderer (fgs_wave_*) is a unit of its own, fgs_wavefield.hip.
 #include <hipfft/hipfft.h>
 #include <type_traits>
-#include "fgs_internal.h"
-#include "fgs_wave.h"
+#include "fgs_splat.h"
 #include "fgs_colfft.h"
 
 namespace {
-
-// an (image, plane) pair -- or, with `tiles` = lists per image, an image -- with no list entry at all: seg_off is the
-// exclusive scan of every list's depth-segment count in key order (key = (b P + p) T + t; k_tile_post writes it on both
-// list-building paths, [lists + 1] entries), so a key range without entries is a range without units.  (NOT `ranges`: the
-// radix path leaves the ranges of empty lists zeroed.)
-__device__ __forceinline__ bool asm_plane_empty(const uint32_t *__restrict__ seg_off, uint32_t bp, uint32_t tiles) {
-    return seg_off[(size_t)(bp + 1u) * tiles] == seg_off[(size_t)bp * tiles];
-}
-
-constexpr float NEG_HALF_LOG2E = -0.72134752044448170368f;
-constexpr int ACH = 64;
-constexpr int ASM_FWD_PARTS = 4;  // list parts (waves) per (image, plane, tile) in the forward splat
-constexpr uint32_t ASM_ONE_WAVE_LISTS = 24576;  // from this many lists per launch on: one wave per list in the forward splat (measured: 16 384 lists 0.105 ms with four parts vs 0.139 with one, 131 072 lists 0.83 vs 0.345)
-constexpr int RED_BLOCKS = 128;   // blocks (= partials) per image of the per-image scalar reductions, see below
 
 struct AsmPlan {
     FgsAsmDims a;
     FgsPlan base;        // projection + binning with layers = num_planes
     size_t HW;
+    float inv_ndx, inv_ndy;  // the frequency grids' 1 / (n d)
     // saved sections (after base.L.total_bytes)
     size_t v_field;      // float2 [B][P][3][H][W]  plane fields -> spectra (kept for the backward)
     size_t v_htab;       // float2 [3][P][H][W]     transfer functions H_pc, then [3][H][W] their plane-to-plane factor D_c (asm_transfer_block)
     size_t v_total;      // float2 [B][3][H][W]     total field U (unnormalised inverse FFT)
     size_t v_scal;       // float  [B]              per-image maxval
-    size_t v_ccs;        // float  [B][N][8]        phasors c cos(phi), c sin(phi) per channel (k_asm_phasors)
+    size_t v_ccs;        // float  [B][N][8]        phasors c cos(phi), c sin(phi) per channel (asm_phasors_block)
     size_t v_tw;         // float2 [H/2]            twiddles of the column-fused transforms
     size_t v_zsum;       // float2 [B][3][H][W]     Z_c = sum_p z_p F_pc H_pc (column-fused path): all the backward needs of the
                          //                         spectra for dL/dlambda, so the spectra themselves are never stored
@@ -65,8 +54,6 @@ struct AsmPlan {
     size_t work_big, work_small;
 };
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 int make_asm_plan(const FgsAsmDims *a, AsmPlan *p, bool need_fft) {
     if (!a) { fgs_set_error("null dims"); return FGS_EINVAL; }
     if (a->num_planes < 1 || a->num_planes > 64 || (a->phase_channels != 1 && a->phase_channels != 3) ||
@@ -75,17 +62,16 @@ int make_asm_plan(const FgsAsmDims *a, AsmPlan *p, bool need_fft) {
                       (double)a->pixel_pitch);
         return FGS_EINVAL;
     }
-    FgsDims d{};
-    d.batch = a->batch; d.num_gaussians = a->num_gaussians; d.width = a->width; d.height = a->height;
-    d.max_radius = a->max_radius;
-    for (int i = 0; i < 3; ++i) d.background[i] = a->background[i];
-    d.use_phase = 0; d.phase_amplitude = 0.0f; d.num_cameras = a->num_cameras;
-    d.bin_mode = a->bin_mode;
+    const FgsDims d = splat_base_dims(a->batch, a->num_gaussians, a->width, a->height, a->max_radius, a->background,
+                                      a->num_cameras, a->bin_mode);
     p->a = *a;
     const int rc = fgs_make_plan(&d, &p->base, a->num_planes, false);
     if (rc) return rc;
     const size_t B = a->batch, P = a->num_planes, HW = (size_t)a->width * a->height;
     p->HW = HW;
+    // torch.fft.fftfreq(n, d) = arange * (float)(1.0 / (n * d)) with d the reference's Python float (a double): DR:959-961
+    p->inv_ndx = (float)(1.0 / ((double)a->width * a->pixel_pitch));
+    p->inv_ndy = (float)(1.0 / ((double)a->height * a->pixel_pitch));
     // (The forward splat keeps its longest-lists-first order over the whole launch.  Grouping it by image, last image first, so that
     // rocFFT's ascending row pass finds the planes it reads first in the memory-side cache, was measured at config 5, 8 images: row pass
     // 300 -> 261 us, k_colfft_fwd -4 us, but the splat itself 249 -> 312 us and k_tile_post 9 -> 22 us: net +1 %.)
@@ -217,31 +203,6 @@ __device__ __forceinline__ void asm_transfer_block(uint32_t blk, int W, int H, i
     }
 }
 
-// ccs[g] = (c_r cos phi_r, c_g cos phi_g, c_b cos phi_b, c_r sin phi_r | c_g sin phi_g, c_b sin phi_b, 0, 0)  DR:1274-1283
-__device__ __forceinline__ void asm_phasors_block(uint32_t blk, uint32_t total, int phase_channels,
-                                                  const float *__restrict__ color, const float *__restrict__ phase,
-                                                  float *__restrict__ ccs) {
-    const uint32_t g = blk * 256 + threadIdx.x;
-    if (g >= total) return;
-    float cc[3], cs[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float ph = phase_channels == 3 ? phase[3 * (size_t)g + c] : phase[g];
-        float sn, co;
-        sincosf(ph, &sn, &co);
-        const float col = color[3 * (size_t)g + c];
-        cc[c] = col * co; cs[c] = col * sn;
-    }
-    float4 *o = reinterpret_cast<float4 *>(ccs + (size_t)g * 8);
-    o[0] = make_float4(cc[0], cc[1], cc[2], cs[0]);
-    o[1] = make_float4(cs[1], cs[2], 0.0f, 0.0f);
-}
-
-__global__ __launch_bounds__(256) void k_asm_phasors(uint32_t total, int phase_channels, const float *__restrict__ color,
-                                                     const float *__restrict__ phase, float *__restrict__ ccs) {
-    asm_phasors_block(blockIdx.x, total, phase_channels, color, phase, ccs);
-}
-
 // Everything of an ASM forward that depends on the inputs alone, in ONE launch (a one-image step is 45 launches of a few
 // microseconds each): blocks [0, nb_ph) the phasors, [nb_ph, nb_ph + nb_tr) the transfer functions, the last block the
 // twiddles of the column-fused transforms (N = 0: none).
@@ -264,209 +225,6 @@ __global__ __launch_bounds__(256) void k_asm_prep(uint32_t nb_ph, uint32_t nb_tr
     }
 }
 
-// One wave per (image, plane, tile); lane = one pixel of each of the four 8x8 sub-tiles.
-// BWD = false: accumulate field += a * c * (cos phi, sin phi) with a = exp(-m/2) * opacity (DR:1263-1283).
-// BWD = true : read the field gradient and reduce the twelve per-Gaussian sums into a gradient row.
-// WAVE = true (WaveFieldRenderer, DR:832-891): a single layer, and additionally the amplitude-weighted
-// depth sums (sum a*depth, sum a) in `dw`; gradient rows are 16 floats wide (slot 12 = dL/ddepth).
-// NP = waves per block of the forward (list parts), 1 for the backward.  `ccs` = the Gaussians' phasors c cos(phi),
-// c sin(phi) per channel ([B*N][8] floats, k_asm_phasors): the accurate sincosf runs once per Gaussian instead of three
-// times per (tile, plane) duplicate at staging time, forward and backward.
-template <bool BWD, bool WAVE, int NP>
-__global__ __launch_bounds__(64 * NP) void k_asm_splat(
-    uint32_t tiles, uint32_t tiles_x, uint32_t P, uint32_t W, uint32_t H, uint32_t dcap,
-    const uint32_t *__restrict__ tile_order, const uint32_t *__restrict__ ranges,
-    const uint32_t *__restrict__ dup_ids, const float *__restrict__ rec, const float *__restrict__ ccs,
-    const uint32_t *__restrict__ dup_off, float2 *__restrict__ field, float *__restrict__ grad_rows,
-    float2 *__restrict__ dw, const uint32_t *__restrict__ counters, const uint32_t *__restrict__ seg_off,
-    const uint32_t *__restrict__ seg_tile, uint32_t seg_len) {
-    // Forward: the splat is a plain sum, so the list is cut into NP parts, one per wave (own LDS staging, no block
-    // barrier in the walk) and the partial fields are added in part order at the end -- a launch of few, long lists is
-    // latency-bound by the longest (NP = 4); a launch with enough lists to fill the chip (the ASM renderer's (image,
-    // plane, tile) lists of a few dozen entries) runs one wave per list with 4 KB of LDS instead of 35 (NP = 1).
-    // Backward: one wave per depth-segment unit.
-    static_assert(!BWD || NP == 1, "the backward is one wave per unit");
-    __shared__ float4 sh0[NP * ACH], sh1[NP * ACH], sh2[NP * ACH], sh3[NP * ACH];
-    __shared__ uint32_t shm[NP * ACH], she[BWD ? ACH : 1];
-    __shared__ float part[NP == 1 ? 1 : (NP - 1) * (WAVE ? 32 : 24) * 64];
-    __shared__ __attribute__((aligned(16))) float red[BWD ? 13 * FGS_RED_PITCH : 4];  // wave_sum_addtid scratch (backward)
-    // Forward: one block per (image, plane, tile), longest lists first.  Backward: the splat carries no state
-    // along a list, so the work unit is a depth segment of FGS_SEG list entries (unit list of k_tile_order;
-    // the grid is sized from the capacity, surplus blocks leave at once) -- balanced however uneven the lists.
-    uint32_t key, seg = 0;
-    if (BWD) {
-        const uint32_t nunits = counters[2];
-        if (blockIdx.x >= nunits) return;
-        // units in DESCENDING key order: the row transform in front of this kernel wrote the planes in ascending order, the last
-        // 256 MB of them are still in the memory-side cache (-1 %: the kernel is VALU-bound)
-        const uint32_t unit = nunits - 1u - blockIdx.x;
-        key = seg_tile[unit];
-        seg = unit - seg_off[key];
-    } else {
-#ifdef FGS_SPLAT_ORDER_GROUPS
-        key = tile_order ? tile_order[NP == 1 ? fgs_xcd_remap(blockIdx.x, gridDim.x) : blockIdx.x] : blockIdx.x;  // (b*P + p)*T + t
-#else
-        key = tile_order ? tile_order[blockIdx.x] : blockIdx.x;  // (b*P + p)*T + t
-#endif
-    }
-    const uint32_t bp = key / tiles, t = key - bp * tiles;
-    const uint32_t ty = t / tiles_x, tx = t - ty * tiles_x;
-    const uint32_t X0 = tx * FGS_TILE, Y0 = ty * FGS_TILE;
-    const uint32_t lane = threadIdx.x & 63u, lx = lane & 7u, ly = lane >> 3;
-    const uint32_t wave = NP > 1 ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : 0u;
-    const uint32_t wofs = wave * ACH;  // this wave's slice of the staging arrays
-    float fx0 = (float)(X0 + lx), fy0 = (float)(Y0 + ly);
-    asm("" : "+v"(fx0), "+v"(fy0));  // hoisted for good
-    uint32_t start = ranges[2 * key] + seg * seg_len;
-    uint32_t end = BWD ? min(ranges[2 * key + 1], start + seg_len) : ranges[2 * key + 1];
-    if (NP > 1) {  // this wave's part of the list (whole chunks)
-        const uint32_t per = ((end - start + NP * ACH - 1) / (NP * ACH)) * ACH;
-        start = min(end, start + wave * per);
-        end = min(end, start + per);
-    }
-    const size_t HW = (size_t)W * H;
-    float2 *fbase = field + (size_t)bp * 3 * HW;  // [b][p][c][y][x]
-    float re[4][3], im[4][3];  // FWD: accumulators.  BWD: field gradient at this lane's pixels
-    float wd[4], ww[4];        // WAVE: sum a*depth, sum a   (BWD: their gradients)
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-        const uint32_t px = X0 + 8u * (s & 1) + lx, py = Y0 + 8u * (s >> 1) + ly;
-        wd[s] = 0.0f; ww[s] = 0.0f;
-        if (WAVE && BWD && px < W && py < H) {
-            const float2 g = dw[(size_t)bp * HW + (size_t)py * W + px];
-            wd[s] = g.x; ww[s] = g.y;
-        }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            re[s][c] = 0.0f; im[s][c] = 0.0f;
-            if (BWD && px < W && py < H) {
-                const float2 g = fbase[(size_t)c * HW + (size_t)py * W + px];
-                re[s][c] = g.x; im[s][c] = g.y;
-            }
-        }
-    }
-    for (uint32_t base = start; base < end; base += ACH) {
-        const uint32_t n = min((uint32_t)ACH, end - base);
-        if (lane < n) {
-            const uint32_t gid = dup_ids[base + lane];
-            const float4 *r = reinterpret_cast<const float4 *>(rec + (size_t)gid * FGS_REC_FLOATS);
-            const float4 q0 = r[0], q1 = r[1], q2 = r[2];
-            const uint32_t bbx = __float_as_uint(q2.z), bby = __float_as_uint(q2.w);
-            // touched sub-tiles + the pixel bits of the tile (bit i: column X0 + i inside the bbox, bit 16 + i: row Y0 + i): in the
-            // list loop a lane turns its column / row bits into all-ones / zero masks (v_bfe_i32) and and-s them onto G -- no
-            // per-pixel compare / select, as on the blend path (issue costs: DESIGN.md section 4)
-            uint32_t sflags, pbits;
-            stage_decode(X0, Y0, bbx, bby, 1.0f, sflags, pbits);
-            shm[wofs + lane] = sflags & 15u;
-            if (BWD) {
-                const uint32_t tx0 = (bbx & 0xFFFFu) / FGS_TILE, tx1 = ((bbx >> 16) - 1) / FGS_TILE, ty0 = (bby & 0xFFFFu) / FGS_TILE;
-                she[lane] = dup_off[gid] + (ty - ty0) * (tx1 - tx0 + 1) + (tx - tx0);
-            }
-            const float4 *pz = reinterpret_cast<const float4 *>(ccs + (size_t)gid * 8);
-            const float4 z0 = pz[0], z1 = pz[1];  // cc[0..2], cs[0] | cs[1..2]
-            // conic pre-multiplied by K = -log2(e) / 2: G = exp2(K m) without a multiply per pixel (the backward's
-            // dL/dconic = -1/2 dG/dm' ... is formed from the unscaled moments, below)
-            sh0[wofs + lane] = make_float4(q0.x, q0.y, q0.z * NEG_HALF_LOG2E, q0.w * NEG_HALF_LOG2E);  // u, v, K ca, K cbc
-            sh1[wofs + lane] = make_float4(q1.x * NEG_HALF_LOG2E, q1.y, __uint_as_float(pbits), 0.0f);   // K cd, op, pixel bits
-            sh2[wofs + lane] = z0;
-            sh3[wofs + lane] = make_float4(z1.x, z1.y, q2.y, 0.0f);  // .z = depth (WAVE)
-        }
-        __builtin_amdgcn_wave_barrier();  // wave-private staging: one wave's LDS instructions execute in order
-        for (uint32_t j = 0; j < n; ++j) {
-            const float4 q0 = sh0[wofs + j], q1 = sh1[wofs + j], q2 = sh2[wofs + j], q3 = sh3[wofs + j];
-            const uint32_t msk = __builtin_amdgcn_readfirstlane(shm[wofs + j]);
-            const uint32_t pbits = __float_as_uint(q1.z);
-            const uint32_t mxs[2] = {(uint32_t)__builtin_amdgcn_sbfe((int)pbits, lx, 1), (uint32_t)__builtin_amdgcn_sbfe((int)pbits, lx + 8u, 1)};
-            const uint32_t mys[2] = {(uint32_t)__builtin_amdgcn_sbfe((int)pbits, 16u + ly, 1), (uint32_t)__builtin_amdgcn_sbfe((int)pbits, 24u + ly, 1)};
-            const float ca = q0.z, cbc = q0.w, cd = q1.x, op = q1.y;
-            const float cc[3] = {q2.x, q2.y, q2.z}, cs[3] = {q2.w, q3.x, q3.y};
-            float v_u = 0, v_v = 0, v_ca = 0, v_cbc = 0, v_cd = 0, v_op = 0, v_dep = 0;
-            float v_cc[3] = {0, 0, 0}, v_cs[3] = {0, 0, 0};
-            const float dz = q3.z;
-            // the lane's two column / row offsets once per entry (no int -> float conversion in the list loop)
-            const float dxs[2] = {fx0 - q0.x, fx0 + 8.0f - q0.x}, dys[2] = {fy0 - q0.y, fy0 + 8.0f - q0.y};
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                if (!((msk >> s) & 1u)) continue;
-                const float dx = dxs[s & 1], dy = dys[s >> 1];
-                // (this unit is compiled with -ffp-contract=off -- build.py -- so the FMAs of the two VALU-bound loops, this one and
-                // the column butterflies of fgs_colfft.h, are written out: sums of same-signed or well-separated terms, where
-                // fusing is harmless; measured: dL/dlambda of K5 / G9 / G16 unchanged, config 5 back from 1.99 to 1.89 ms)
-                const float m = fmaf(ca * dx, dx, fmaf(cbc * dx, dy, (cd * dy) * dy));  // K m
-                const float G = __uint_as_float(__float_as_uint(__builtin_amdgcn_exp2f(m)) & (mxs[s & 1] & mys[s >> 1]));
-                const float a = G * op;  // amplitude, DR:1270-1271 (no clamp on this path)
-                if (!BWD) {
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) { re[s][c] = fmaf(a, cc[c], re[s][c]); im[s][c] = fmaf(a, cs[c], im[s][c]); }
-                    if (WAVE) { wd[s] = fmaf(a, dz, wd[s]); ww[s] += a; }  // DR:890-891
-                } else {
-                    float da = 0.0f;
-                    if (WAVE) { da = fmaf(wd[s], dz, ww[s]); v_dep = fmaf(a, wd[s], v_dep); }
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        da = fmaf(cc[c], re[s][c], fmaf(cs[c], im[s][c], da));
-                        v_cc[c] = fmaf(a, re[s][c], v_cc[c]); v_cs[c] = fmaf(a, im[s][c], v_cs[c]);
-                    }
-                    // moments of t = dL/da G about the Gaussian's mean: {1, dx, dy, dx^2, dx dy, dy^2}.  The chain through
-                    // a = G op and m (dL/dm = -1/2 t op; dL/d(u, v) = -dL/dm (2 ca dx + cbc dy, cbc dx + 2 cd dy), linear in the
-                    // first moments) is applied once per Gaussian, in double, by k_project_bwd: 7 VALU per pass instead of 13
-                    const float t = da * G;
-                    v_op += t;
-                    const float tx = t * dx, ty = t * dy;
-                    v_u += tx; v_v += ty;
-                    v_ca = fmaf(tx, dx, v_ca); v_cbc = fmaf(tx, dy, v_cbc); v_cd = fmaf(ty, dy, v_cd);
-                }
-            }
-            if (BWD) {
-                constexpr int NV = WAVE ? 13 : 12;
-                float vals[NV] = {v_u, v_v, v_ca, v_cbc, v_cd, v_op, v_cc[0], v_cc[1], v_cc[2], v_cs[0], v_cs[1], v_cs[2]};
-                if (WAVE) vals[NV - 1] = v_dep;
-                const float tot = wave_sum_addtid<NV>(red, vals, lane);  // conflict-free parking, as in the blend backward
-                const uint32_t e = she[j];
-                if ((lane & 3u) == 3u && lane < 4u * NV && e < dcap)
-                    grad_rows[(size_t)e * (WAVE ? 16 : FGS_GROW_FLOATS) + (lane >> 2)] = tot;
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
-    }
-    if (!BWD && NP > 1) {
-        // add the partial fields in part order (wave 0 = part 0 accumulates parts 1, 2, ...): deterministic
-        constexpr int NF = WAVE ? 32 : 24;
-        if (wave != 0) {
-            float *pp = part + ((size_t)(wave - 1) * NF) * 64 + lane;
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-#pragma unroll
-                for (int c = 0; c < 3; ++c) { pp[(s * 6 + c) * 64] = re[s][c]; pp[(s * 6 + 3 + c) * 64] = im[s][c]; }
-                if (WAVE) { pp[(24 + 2 * s) * 64] = wd[s]; pp[(25 + 2 * s) * 64] = ww[s]; }
-            }
-        }
-        __syncthreads();
-        if (wave != 0) return;
-        for (int w = 1; w < NP; ++w) {
-            const float *pp = part + ((size_t)(w - 1) * NF) * 64 + lane;
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-#pragma unroll
-                for (int c = 0; c < 3; ++c) { re[s][c] += pp[(s * 6 + c) * 64]; im[s][c] += pp[(s * 6 + 3 + c) * 64]; }
-                if (WAVE) { wd[s] += pp[(24 + 2 * s) * 64]; ww[s] += pp[(25 + 2 * s) * 64]; }
-            }
-        }
-    }
-    if (!BWD) {
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const uint32_t px = X0 + 8u * (s & 1) + lx, py = Y0 + 8u * (s >> 1) + ly;
-            if (px < W && py < H) {
-#pragma unroll
-                for (int c = 0; c < 3; ++c)
-                    fbase[(size_t)c * HW + (size_t)py * W + px] = make_float2(re[s][c], im[s][c]);
-                if (WAVE) dw[(size_t)bp * HW + (size_t)py * W + px] = make_float2(wd[s], ww[s]);
-            }
-        }
-    }
-}
-
 // acc[b][c][k] = sum_p F[b][p][c][k] * H[c][p][k]
 __global__ __launch_bounds__(256) void k_asm_accumulate(size_t HW, int B, int P, const float2 *__restrict__ field,
                                                         const float2 *__restrict__ htab,
@@ -483,36 +241,6 @@ __global__ __launch_bounds__(256) void k_asm_accumulate(size_t HW, int B, int P,
         s.x += t.x; s.y += t.y;
     }
     acc[i] = s;
-}
-
-// ---- per-image scalars (maximum, dL/dM, number of maxima, dL/dlambda) as TWO-LEVEL reductions -------------------
-// One partial per block, RED_BLOCKS blocks per image; the consumers' blocks fold the partials themselves (one value per
-// thread, fixed order).  Round 1 reduced these with one device-scope atomic per wave on a single address per image;
-// such atomics serialise at ~50 ns each on this part: k_asm_output_bwd1 took 54 us for one image and 419 us for
-// eight, k_asm_max 26 / 191 us -- both read 6-9 MB per image -- and the float sums came out in arrival order.
-
-__device__ __forceinline__ float block_max_256(float v) {  // all 256 threads call; every thread gets the result
-    __shared__ float wmax[4];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    __syncthreads();  // (protects wmax against the previous use)
-    if ((threadIdx.x & 63u) == 0) wmax[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
-}
-__device__ __forceinline__ float2 block_sum2_256(float a, float b) {  // fixed order: xor tree, then waves 0..3
-    __shared__ float2 wsum[4];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); }
-    __syncthreads();
-    if ((threadIdx.x & 63u) == 0) wsum[threadIdx.x >> 6] = make_float2(a, b);
-    __syncthreads();
-    return make_float2((wsum[0].x + wsum[1].x) + (wsum[2].x + wsum[3].x), (wsum[0].y + wsum[1].y) + (wsum[2].y + wsum[3].y));
-}
-// maximum of an image's RED_BLOCKS block maxima (every thread of the block gets it)
-__device__ __forceinline__ float image_max(const float *__restrict__ pmax, int b) {
-    static_assert(RED_BLOCKS <= 256, "one partial per thread");
-    return block_max_256(threadIdx.x < RED_BLOCKS ? pmax[(size_t)b * RED_BLOCKS + threadIdx.x] : 0.0f);
 }
 
 // ---- column-fused 2-D transforms (power-of-two heights) ------------------------------------------------------------
@@ -973,12 +701,6 @@ __global__ __launch_bounds__(256) void k_asm_output_bwd1(size_t HW, float inv_hw
     if (threadIdx.x == 0) psum[(size_t)b * RED_BLOCKS + blockIdx.x] = t;
 }
 
-// (gM, count) of image b from the block partials (every thread of the block gets them)
-__device__ __forceinline__ float2 image_sums(const float2 *__restrict__ psum, int b) {
-    const float2 v = threadIdx.x < RED_BLOCKS ? psum[(size_t)b * RED_BLOCKS + threadIdx.x] : make_float2(0.0f, 0.0f);
-    return block_sum2_256(v.x, v.y);
-}
-
 // pass 2: gradient w.r.t. the (unnormalised) total field, written over `gtot`
 __global__ __launch_bounds__(256) void k_asm_output_bwd2(size_t HW, float inv_hw, float bg0, float bg1, float bg2,
                                                          const float2 *__restrict__ total,
@@ -1073,181 +795,6 @@ __global__ __launch_bounds__(256) void k_asm_wavelength_grad(uint32_t n, const d
     if (threadIdx.x == 0) g_wavelengths[blockIdx.x] = (float)((part[0] + part[1]) + (part[2] + part[3]));
 }
 
-
-// ---------------------------------------------------------------------------------------------
-// WaveFieldRenderer (DR:689-926): order-independent complex accumulation without
-// depth planes or propagation; intensity -> sqrt -> per-image max normalisation -> background
-// where the total amplitude is low; depth map = sum(a depth) / (sum a + 1e-8).
-// ---------------------------------------------------------------------------------------------
-struct WavePix {
-    float r[3], n[3], v[3], tasq, ta, M;
-};
-
-__device__ __forceinline__ void wave_pixel_forward(const float2 u[3], float maxval, const float bg[3], WavePix &o) {
-    o.M = maxval < 1.0f ? 1.0f : maxval;
-    float isum = 0.0f;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float I = u[c].x * u[c].x + u[c].y * u[c].y;
-        isum += I;
-        o.r[c] = sqrtf(I + 1e-8f);                           // DR:898
-        const float q = o.r[c] / o.M;                        // DR:902-905
-        o.n[c] = q < 0.0f ? 0.0f : (q > 1.0f ? 1.0f : q);
-    }
-    o.tasq = sqrtf(isum + 1e-8f);                            // DR:908
-    o.ta = o.tasq < 0.0f ? 0.0f : (o.tasq > 1.0f ? 1.0f : o.tasq);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) o.v[c] = o.n[c] + bg[c] * (1.0f - o.ta);
-}
-
-__global__ __launch_bounds__(256) void k_wave_max(size_t HW, const float2 *__restrict__ field, float *__restrict__ pmax) {
-    const int b = blockIdx.y;
-    float mx = 0.0f;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < 3 * HW; i += (size_t)gridDim.x * 256) {
-        const float2 u = field[(size_t)b * 3 * HW + i];
-        mx = fmaxf(mx, sqrtf(u.x * u.x + u.y * u.y + 1e-8f));
-    }
-    mx = block_max_256(mx);
-    if (threadIdx.x == 0) pmax[(size_t)b * RED_BLOCKS + blockIdx.x] = mx;
-}
-
-__global__ __launch_bounds__(256) void k_wave_output(size_t HW, float bg0, float bg1, float bg2,
-                                                     const float2 *__restrict__ field, const float2 *__restrict__ dw,
-                                                     const float *__restrict__ pmax, float *__restrict__ scal,
-                                                     float *__restrict__ out, float *__restrict__ out_depth,
-                                                     const uint32_t *__restrict__ seg_off, uint32_t lists_per_image) {
-    const int b = blockIdx.y;
-    const float maxval = image_max(pmax, b);
-    if (blockIdx.x == 0 && threadIdx.x == 0) scal[b] = maxval;  // kept for the backward
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= HW) return;
-    const float bg[3] = {bg0, bg1, bg2};
-    if (asm_plane_empty(seg_off, (uint32_t)b, lists_per_image)) {  // no visible Gaussian: plain background, zero depth (DR:801-808)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) out[((size_t)b * 3 + c) * HW + i] = bg[c];
-        out_depth[(size_t)b * HW + i] = 0.0f;
-        return;
-    }
-    const float2 u[3] = {field[((size_t)b * 3 + 0) * HW + i], field[((size_t)b * 3 + 1) * HW + i],
-                         field[((size_t)b * 3 + 2) * HW + i]};
-    WavePix o;
-    wave_pixel_forward(u, maxval, bg, o);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float v = o.v[c];
-        out[((size_t)b * 3 + c) * HW + i] = v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v);
-    }
-    const float2 d = dw[(size_t)b * HW + i];
-    out_depth[(size_t)b * HW + i] = d.x / (d.y + 1e-8f);      // DR:924
-}
-
-__global__ __launch_bounds__(256) void k_wave_output_bwd1(size_t HW, float bg0, float bg1, float bg2,
-                                                          const float2 *__restrict__ field, const float *__restrict__ scal,
-                                                          const float *__restrict__ g_out, float2 *__restrict__ psum) {
-    const int b = blockIdx.y;
-    float gM = 0.0f, cnt = 0.0f;
-    const float bg[3] = {bg0, bg1, bg2};
-    const float maxval = scal[b];
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < HW; i += (size_t)gridDim.x * 256) {
-        const float2 u[3] = {field[((size_t)b * 3 + 0) * HW + i], field[((size_t)b * 3 + 1) * HW + i],
-                             field[((size_t)b * 3 + 2) * HW + i]};
-        WavePix o;
-        wave_pixel_forward(u, maxval, bg, o);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float gv = (o.v[c] >= 0.0f && o.v[c] <= 1.0f) ? g_out[((size_t)b * 3 + c) * HW + i] : 0.0f;
-            const float q = o.r[c] / o.M;
-            const float gq = (q >= 0.0f && q <= 1.0f) ? gv : 0.0f;
-            gM -= gq * o.r[c] / (o.M * o.M);
-            if (o.r[c] == maxval) cnt += 1.0f;
-        }
-    }
-    const float2 t = block_sum2_256(gM, cnt);
-    if (threadIdx.x == 0) psum[(size_t)b * RED_BLOCKS + blockIdx.x] = t;
-}
-
-__global__ __launch_bounds__(256) void k_wave_output_bwd2(size_t HW, float bg0, float bg1, float bg2,
-                                                          const float2 *__restrict__ field,
-                                                          const float2 *__restrict__ dw, const float *__restrict__ scal,
-                                                          const float2 *__restrict__ psum,
-                                                          const float *__restrict__ g_out,
-                                                          const float *__restrict__ g_depth, float2 *__restrict__ gfield,
-                                                          float2 *__restrict__ gdw) {
-    const int b = blockIdx.y;
-    const float2 sums = image_sums(psum, b);
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= HW) return;
-    const float2 u[3] = {field[((size_t)b * 3 + 0) * HW + i], field[((size_t)b * 3 + 1) * HW + i],
-                         field[((size_t)b * 3 + 2) * HW + i]};
-    const float bg[3] = {bg0, bg1, bg2};
-    const float maxval = scal[b];
-    const float cntm = sums.y;
-    const float gMshare = (maxval >= 1.0f && cntm > 0.0f) ? sums.x / cntm : 0.0f;
-    WavePix o;
-    wave_pixel_forward(u, maxval, bg, o);
-    float gv[3], gta = 0.0f;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        gv[c] = (o.v[c] >= 0.0f && o.v[c] <= 1.0f) ? g_out[((size_t)b * 3 + c) * HW + i] : 0.0f;
-        gta -= gv[c] * bg[c];
-    }
-    // ta = clamp(sqrt(sum_c I_c + 1e-8), 0, 1): d ta / d I_c = 1 / (2 tasq) inside the clamp
-    const float gIsum = (o.tasq >= 0.0f && o.tasq <= 1.0f) ? gta / (2.0f * o.tasq) : 0.0f;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float q = o.r[c] / o.M;
-        float gr = ((q >= 0.0f && q <= 1.0f) ? gv[c] : 0.0f) / o.M;
-        if (o.r[c] == maxval) gr += gMshare;
-        const float gI = gr / (2.0f * o.r[c]) + gIsum;
-        gfield[((size_t)b * 3 + c) * HW + i] = make_float2(2.0f * gI * u[c].x, 2.0f * gI * u[c].y);
-    }
-    // depth_map = Ad / (Wt + 1e-8)
-    const float2 d = dw[(size_t)b * HW + i];
-    const float gdm = g_depth[(size_t)b * HW + i];
-    const float den = d.y + 1e-8f;
-    gdw[(size_t)b * HW + i] = make_float2(gdm / den, -gdm * d.x / (den * den));
-}
-
-struct WavePlan {
-    FgsWaveDims w;
-    FgsPlan base;
-    size_t HW, v_field, v_dw, v_scal, v_ccs, v_total_bytes, c_gfield, c_gdw, c_rows, c_part, c_total_bytes;
-};
-
-int make_wave_plan(const FgsWaveDims *w, WavePlan *p) {
-    if (!w) { fgs_set_error("null dims"); return FGS_EINVAL; }
-    if (w->phase_channels != 1 && w->phase_channels != 3) { fgs_set_error("invalid phase_channels"); return FGS_EINVAL; }
-    FgsDims d{};
-    d.batch = w->batch; d.num_gaussians = w->num_gaussians; d.width = w->width; d.height = w->height;
-    d.max_radius = w->max_radius;
-    for (int i = 0; i < 3; ++i) d.background[i] = w->background[i];
-    d.num_cameras = w->num_cameras;
-    p->w = *w;
-    const int rc = fgs_make_plan(&d, &p->base, 1, false);
-    if (rc) return rc;
-    const size_t B = w->batch, HW = (size_t)w->width * w->height;
-    p->HW = HW;
-    size_t o = p->base.L.total_bytes;
-    p->v_field = o; o = align256(o + B * 3 * HW * 8);
-    p->v_dw = o; o = align256(o + B * HW * 8);
-    p->v_scal = o; o = align256(o + B * 4 * 4);
-    p->v_ccs = o; o = align256(o + B * (size_t)w->num_gaussians * 8 * 4);
-    p->v_total_bytes = o;
-    o = p->base.s_total;
-    p->c_gfield = o; o = align256(o + B * 3 * HW * 8);
-    p->c_gdw = o; o = align256(o + B * HW * 8);
-    p->c_rows = o; o = align256(o + p->base.L.dup_capacity * 16 * 4);
-    p->c_part = o; o = align256(o + B * RED_BLOCKS * 8);  // float2 [B][RED_BLOCKS] block partials of the per-image scalars
-    p->c_total_bytes = o;
-    return FGS_OK;
-}
-
-int check_ptrs(const void *const *ptrs, int n, const char *who) {
-    for (int i = 0; i < n; ++i)
-        if (!ptrs[i]) { fgs_set_error("%s: null pointer argument #%d", who, i); return FGS_EINVAL; }
-    return FGS_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -1283,19 +830,15 @@ int fgs_asm_forward(const FgsAsmDims *dims, const float *cameras, const float *p
     float2 *htab = reinterpret_cast<float2 *>(sv + p.v_htab);
     float2 *total = reinterpret_cast<float2 *>(sv + p.v_total);
     float *scal = reinterpret_cast<float *>(sv + p.v_scal);
-    const uint32_t grid = (uint32_t)B * P * p.base.tiles;
     float *ccs = reinterpret_cast<float *>(sv + p.v_ccs);
     const uint32_t ngauss = (uint32_t)B * (uint32_t)a.num_gaussians;
-    // torch.fft.fftfreq(n, d) = arange * (float)(1.0 / (n * d)) with d the reference's Python float (a double): DR:959-961
-    const float inv_ndx = (float)(1.0 / ((double)W * a.pixel_pitch));
-    const float inv_ndy = (float)(1.0 / ((double)H * a.pixel_pitch));
     {
         // the column kernels read H at the first plane of each plane group only (and D); the rocFFT 2-D path reads every plane
         const int pstride = p.col_logn ? (P + p.col_pg - 1) / p.col_pg : 1, np = (P + pstride - 1) / pstride;
         const size_t nh = 3 * (size_t)(np + 1) * (size_t)(W / 2 + 1) * (size_t)(H / 2 + 1);  // one quadrant, mirrored; + the step factors D
         const uint32_t nb_ph = (ngauss + 255) / 256, nb_tr = (uint32_t)((nh + 255) / 256);
         hipLaunchKernelGGL(k_asm_prep, dim3(nb_ph + nb_tr + 1), dim3(256), 0, st, nb_ph, nb_tr, ngauss, a.phase_channels,
-                           color, phase, ccs, W, H, P, a.depth_near, a.depth_far, a.focal_depth, inv_ndx, inv_ndy,
+                           color, phase, ccs, W, H, P, a.depth_near, a.depth_far, a.focal_depth, p.inv_ndx, p.inv_ndy,
                            wavelengths, htab, p.col_logn ? H : 0, reinterpret_cast<float2 *>(sv + p.v_tw), pstride);
         FGS_LAUNCH_CHECK("k_asm_prep");
     }
@@ -1303,17 +846,7 @@ int fgs_asm_forward(const FgsAsmDims *dims, const float *cameras, const float *p
     // skips them (DR:1302)
     const uint32_t *seg_off_d = reinterpret_cast<const uint32_t *>(sv + p.base.L.seg_off);
     fgs_stage_begin(ST_SPLAT_FWD, st);
-#define FGS_SPLAT_FWD(WV, NPV, DW)                                                                                     \
-    hipLaunchKernelGGL((k_asm_splat<false, WV, NPV>), dim3(grid), dim3(64 * NPV), 0, st, (uint32_t)p.base.tiles,       \
-                       (uint32_t)p.base.L.tiles_x, (uint32_t)P, (uint32_t)W, (uint32_t)H,                              \
-                       (uint32_t)p.base.L.dup_capacity, reinterpret_cast<const uint32_t *>(sv + p.base.L.tile_order),  \
-                       reinterpret_cast<const uint32_t *>(sv + p.base.L.ranges),                                       \
-                       reinterpret_cast<const uint32_t *>(sv + p.base.L.dup_ids),                                      \
-                       reinterpret_cast<const float *>(sv + p.base.L.rec), ccs,                                        \
-                       reinterpret_cast<const uint32_t *>(sv + p.base.L.dup_off), field, (float *)nullptr, DW,         \
-                       (const uint32_t *)nullptr, (const uint32_t *)nullptr, (const uint32_t *)nullptr, 0u)
-    // one wave per list once the launch has enough lists to fill the chip, else four list parts per list
-    if (grid >= ASM_ONE_WAVE_LISTS) FGS_SPLAT_FWD(false, 1, (float2 *)nullptr); else FGS_SPLAT_FWD(false, ASM_FWD_PARTS, (float2 *)nullptr);
+    launch_splat_fwd<false>(p.base, sv, (uint32_t)P, ccs, field, (float2 *)nullptr, st);
     FGS_LAUNCH_CHECK("k_asm_splat");
     fgs_stage_end(ST_SPLAT_FWD, st);
     fgs_stage_begin(ST_FIELD_FWD, st);
@@ -1401,9 +934,6 @@ int fgs_asm_backward(const FgsAsmDims *dims, const float *cameras, const float *
     FGS_LAUNCH_CHECK("k_asm_output_bwd2");
     // adjoint of the unnormalised inverse FFT is the unnormalised forward FFT
     if ((rc = fgs_fft2_exec(H, W, B * 3, gtot, HIPFFT_FORWARD, sc + p.c_fftwork, st))) return rc;
-    // torch.fft.fftfreq(n, d) = arange * (float)(1.0 / (n * d)) with d the reference's Python float (a double): DR:959-961
-    const float inv_ndx = (float)(1.0 / ((double)W * a.pixel_pitch));
-    const float inv_ndy = (float)(1.0 / ((double)H * a.pixel_pitch));
     unsigned nwl = (unsigned)(((size_t)B * HW + 255) / 256);
     if (p.col_logn) {
         // gF = gAcc conj(H) and the inverse transform down the columns in one pass (k_colfft_bwd), then rocFFT rows
@@ -1413,7 +943,7 @@ int fgs_asm_backward(const FgsAsmDims *dims, const float *cameras, const float *
         nwl = (unsigned)((W + TCV - 1) / TCV) * (unsigned)(B * p.col_pg);                                             \
         hipLaunchKernelGGL((k_colfft_bwd<LG, TCV>), dim3((unsigned)((W + TCV - 1) / TCV), 3, B * p.col_pg),          \
                            dim3((1 << LG) * TCV / COLFFT_PER), 0, st, W, P, p.col_pg, a.depth_near, a.depth_far,      \
-                           a.focal_depth, inv_ndx, inv_ndy, wavelengths, gtot, htab, tw, field, pwl,                  \
+                           a.focal_depth, p.inv_ndx, p.inv_ndy, wavelengths, gtot, htab, tw, field, pwl,                  \
                            reinterpret_cast<const uint32_t *>(sv + p.base.L.seg_off),                                 \
                            (uint32_t)p.base.tiles, reinterpret_cast<const float2 *>(sv + p.v_zsum));                 \
     } while (0)
@@ -1428,7 +958,7 @@ int fgs_asm_backward(const FgsAsmDims *dims, const float *cameras, const float *
         FGS_LAUNCH_CHECK("k_colfft_bwd");
     } else {
         hipLaunchKernelGGL(k_asm_accumulate_bwd, dim3(nwl, 3), dim3(256), 0, st, W, H, B, P, a.depth_near, a.depth_far,
-                           a.focal_depth, inv_ndx, inv_ndy, wavelengths, gtot, htab, field, pwl);
+                           a.focal_depth, p.inv_ndx, p.inv_ndy, wavelengths, gtot, htab, field, pwl);
         FGS_LAUNCH_CHECK("k_asm_accumulate_bwd");
     }
     hipLaunchKernelGGL(k_asm_wavelength_grad, dim3(3), dim3(256), 0, st, nwl, pwl, g_wavelengths);
@@ -1441,127 +971,14 @@ int fgs_asm_backward(const FgsAsmDims *dims, const float *cameras, const float *
     }
     fgs_stage_end(ST_FIELD_BWD, st);
     fgs_stage_begin(ST_SPLAT_BWD, st);
-    const uint32_t grid = (uint32_t)p.base.L.seg_capacity;  // depth-segment units
     float *rows = reinterpret_cast<float *>(sc + p.base.s_grows);
-    hipLaunchKernelGGL((k_asm_splat<true, false, 1>), dim3(grid), dim3(64), 0, st, (uint32_t)p.base.tiles,
-                       (uint32_t)p.base.L.tiles_x, (uint32_t)P, (uint32_t)W, (uint32_t)H,
-                       (uint32_t)p.base.L.dup_capacity,
-                       reinterpret_cast<const uint32_t *>(sv + p.base.L.tile_order),
-                       reinterpret_cast<const uint32_t *>(sv + p.base.L.ranges),
-                       reinterpret_cast<const uint32_t *>(sv + p.base.L.dup_ids),
-                       reinterpret_cast<const float *>(sv + p.base.L.rec), reinterpret_cast<const float *>(sv + p.v_ccs),
-                       reinterpret_cast<const uint32_t *>(sv + p.base.L.dup_off), field, rows, (float2 *)nullptr,
-                       reinterpret_cast<const uint32_t *>(sv + p.base.L.counters),
-                       reinterpret_cast<const uint32_t *>(sv + p.base.L.seg_off),
-                       reinterpret_cast<const uint32_t *>(sv + p.base.L.seg_tile), (uint32_t)p.base.L.seg_len);
+    launch_splat_bwd<false>(p.base, sv, (uint32_t)P, reinterpret_cast<const float *>(sv + p.v_ccs), field, rows,
+                            (float2 *)nullptr, st);
     FGS_LAUNCH_CHECK("k_asm_splat_bwd");
     fgs_stage_end(ST_SPLAT_BWD, st);
     fgs_stage_begin(ST_PROJECT_BWD, st);
     if ((rc = fgs_launch_asm_project_bwd(p.base, cameras, pos, scale, quat, color, phase, a.phase_channels, sv, rows,
                                          g_pos, g_scale, g_quat, g_color, g_opacity, g_phase, st)))
-        return rc;
-    fgs_stage_end(ST_PROJECT_BWD, st);
-    return FGS_OK;
-}
-
-int fgs_wave_workspace_bytes(const FgsWaveDims *dims, size_t *saved_bytes, size_t *scratch_bytes) {
-    WavePlan p;
-    const int rc = make_wave_plan(dims, &p);
-    if (rc) return rc;
-    if (saved_bytes) *saved_bytes = p.v_total_bytes;
-    if (scratch_bytes) *scratch_bytes = p.c_total_bytes;
-    return FGS_OK;
-}
-
-int fgs_wave_forward(const FgsWaveDims *dims, const float *cameras, const float *pos, const float *scale,
-                     const float *quat, const float *color, const float *opacity, const float *phase,
-                     float *out_rgb, float *out_depth, void *saved, void *scratch, void *stream) {
-    WavePlan p;
-    int rc = make_wave_plan(dims, &p);
-    if (rc) return rc;
-    const void *ptrs[] = {cameras, pos, scale, quat, color, opacity, phase, out_rgb, out_depth, saved, scratch};
-    if ((rc = check_ptrs(ptrs, 11, "fgs_wave_forward"))) return rc;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    char *sv = reinterpret_cast<char *>(saved), *sc = reinterpret_cast<char *>(scratch);
-    const int B = p.w.batch, W = p.w.width, H = p.w.height;
-    const size_t HW = p.HW;
-    fgs_stage_begin(ST_PROJECT, st);
-    if ((rc = fgs_launch_project(p.base, cameras, pos, scale, quat, color, opacity, sv, st))) return rc;
-    fgs_stage_end(ST_PROJECT, st);
-    if ((rc = fgs_launch_binning(p.base, sv, sc, st))) return rc;
-    fgs_stage_begin(ST_SPLAT_FWD, st);
-    float2 *field = reinterpret_cast<float2 *>(sv + p.v_field);
-    float2 *dw = reinterpret_cast<float2 *>(sv + p.v_dw);
-    float *scal = reinterpret_cast<float *>(sv + p.v_scal);
-    const uint32_t grid = (uint32_t)B * p.base.tiles, P = 1;
-    float *ccs = reinterpret_cast<float *>(sv + p.v_ccs);
-    const uint32_t ngauss = (uint32_t)B * (uint32_t)p.w.num_gaussians;
-    hipLaunchKernelGGL(k_asm_phasors, dim3((ngauss + 255) / 256), dim3(256), 0, st, ngauss, p.w.phase_channels, color, phase, ccs);
-    FGS_LAUNCH_CHECK("k_asm_phasors");
-    if (grid >= ASM_ONE_WAVE_LISTS) FGS_SPLAT_FWD(true, 1, dw); else FGS_SPLAT_FWD(true, ASM_FWD_PARTS, dw);
-#undef FGS_SPLAT_FWD
-    FGS_LAUNCH_CHECK("k_wave_splat");
-    fgs_stage_end(ST_SPLAT_FWD, st);
-    fgs_stage_begin(ST_FIELD_FWD, st);
-    float *pmax = reinterpret_cast<float *>(sc + p.c_part);
-    hipLaunchKernelGGL(k_wave_max, dim3(RED_BLOCKS, B), dim3(256), 0, st, HW, field, pmax);
-    FGS_LAUNCH_CHECK("k_wave_max");
-    hipLaunchKernelGGL(k_wave_output, dim3((unsigned)((HW + 255) / 256), B), dim3(256), 0, st, HW, p.w.background[0],
-                       p.w.background[1], p.w.background[2], field, dw, pmax, scal, out_rgb, out_depth,
-                       reinterpret_cast<const uint32_t *>(sv + p.base.L.seg_off), (uint32_t)p.base.tiles);
-    FGS_LAUNCH_CHECK("k_wave_output");
-    fgs_stage_end(ST_FIELD_FWD, st);
-    return FGS_OK;
-}
-
-int fgs_wave_backward(const FgsWaveDims *dims, const float *cameras, const float *pos, const float *scale,
-                      const float *quat, const float *color, const float *opacity, const float *phase,
-                      void *saved, void *scratch, const float *g_rgb, const float *g_depth, float *g_pos,
-                      float *g_scale, float *g_quat, float *g_color, float *g_opacity, float *g_phase,
-                      void *stream) {
-    WavePlan p;
-    int rc = make_wave_plan(dims, &p);
-    if (rc) return rc;
-    const void *ptrs[] = {cameras, pos, scale, quat, color, opacity, phase, saved, scratch, g_rgb, g_depth,
-                          g_pos, g_scale, g_quat, g_color, g_opacity, g_phase};
-    if ((rc = check_ptrs(ptrs, 17, "fgs_wave_backward"))) return rc;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    char *sv = reinterpret_cast<char *>(saved), *sc = reinterpret_cast<char *>(scratch);
-    const int B = p.w.batch, W = p.w.width, H = p.w.height;
-    const size_t HW = p.HW;
-    float2 *field = reinterpret_cast<float2 *>(sv + p.v_field);
-    float2 *dw = reinterpret_cast<float2 *>(sv + p.v_dw);
-    float *scal = reinterpret_cast<float *>(sv + p.v_scal);
-    float2 *gfield = reinterpret_cast<float2 *>(sc + p.c_gfield);
-    float2 *gdw = reinterpret_cast<float2 *>(sc + p.c_gdw);
-    float *rows = reinterpret_cast<float *>(sc + p.c_rows);
-    fgs_stage_begin(ST_FIELD_BWD, st);
-    const dim3 gpix((unsigned)((HW + 255) / 256), B);
-    float2 *psum = reinterpret_cast<float2 *>(sc + p.c_part);
-    hipLaunchKernelGGL(k_wave_output_bwd1, dim3(RED_BLOCKS, B), dim3(256), 0, st, HW, p.w.background[0],
-                       p.w.background[1], p.w.background[2], field, scal, g_rgb, psum);
-    FGS_LAUNCH_CHECK("k_wave_output_bwd1");
-    hipLaunchKernelGGL(k_wave_output_bwd2, gpix, dim3(256), 0, st, HW, p.w.background[0], p.w.background[1],
-                       p.w.background[2], field, dw, scal, psum, g_rgb, g_depth, gfield, gdw);
-    FGS_LAUNCH_CHECK("k_wave_output_bwd2");
-    fgs_stage_end(ST_FIELD_BWD, st);
-    fgs_stage_begin(ST_SPLAT_BWD, st);
-    const uint32_t grid = (uint32_t)p.base.L.seg_capacity;  // depth-segment units
-    hipLaunchKernelGGL((k_asm_splat<true, true, 1>), dim3(grid), dim3(64), 0, st, (uint32_t)p.base.tiles,
-                       (uint32_t)p.base.L.tiles_x, 1u, (uint32_t)W, (uint32_t)H, (uint32_t)p.base.L.dup_capacity,
-                       reinterpret_cast<const uint32_t *>(sv + p.base.L.tile_order),
-                       reinterpret_cast<const uint32_t *>(sv + p.base.L.ranges),
-                       reinterpret_cast<const uint32_t *>(sv + p.base.L.dup_ids),
-                       reinterpret_cast<const float *>(sv + p.base.L.rec), reinterpret_cast<const float *>(sv + p.v_ccs),
-                       reinterpret_cast<const uint32_t *>(sv + p.base.L.dup_off), gfield, rows, gdw,
-                       reinterpret_cast<const uint32_t *>(sv + p.base.L.counters),
-                       reinterpret_cast<const uint32_t *>(sv + p.base.L.seg_off),
-                       reinterpret_cast<const uint32_t *>(sv + p.base.L.seg_tile), (uint32_t)p.base.L.seg_len);
-    FGS_LAUNCH_CHECK("k_wave_splat_bwd");
-    fgs_stage_end(ST_SPLAT_BWD, st);
-    fgs_stage_begin(ST_PROJECT_BWD, st);
-    if ((rc = fgs_launch_asm_project_bwd(p.base, cameras, pos, scale, quat, color, phase, p.w.phase_channels, sv, rows,
-                                         g_pos, g_scale, g_quat, g_color, g_opacity, g_phase, st, true)))
         return rc;
     fgs_stage_end(ST_PROJECT_BWD, st);
     return FGS_OK;

@@ -275,7 +275,7 @@ __global__ __launch_bounds__(256) void k_row_sum(int32_t total, int32_t N, uint3
 // contiguous 48-byte gradient rows in a fixed order (deterministic), then chains
 // (dL/dmean2d, dL/dconic, dL/ddepth) to (dL/dpos, dL/dscale, dL/dquat), recomputing the forward
 // intermediates from the inputs (cheaper than saving ~60 floats per Gaussian).
-// MODE 1 (ASM): rows come from the angular-spectrum splat backward (k_asm_splat<BWD>, fgs_asm.hip) and hold the MOMENTS of
+// MODE 1 (ASM): rows come from the angular-spectrum splat backward (k_asm_splat<BWD>, fgs_splat.h) and hold the MOMENTS of
 //   t = dL/da G about the Gaussian's mean (round 4): slots 0-1 the first moments (sum t dx, sum t dy), 2-4 the second moments
 //   (sum t dx^2, sum t dx dy, sum t dy^2), 5 the zeroth (sum t = dL/dopacity before the chain), 6-8 dL/d(c cos phi)[3],
 //   9-11 dL/d(c sin phi)[3].  The chain through a = G opacity and m is applied HERE, once per Gaussian, in double:

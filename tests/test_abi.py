@@ -38,6 +38,14 @@ def test_binding_symbol_list_matches_header():
     assert sorted(_binding.EXPORTED_SYMBOLS) == declared_symbols()
 
 
+def test_build_lists_exactly_the_units_in_csrc():
+    """build() skips a listed source that is missing and ignores a present one that is not listed; the link is -shared, so
+    either mistake would surface only as an undefined symbol at load time."""
+    from fresnel_amd import build
+    present = {f for f in os.listdir(build.CSRC) if f.endswith((".hip", ".cpp"))}
+    assert present == set(build.SOURCES)
+
+
 def test_workspace_and_layout():
     from fresnel_amd import _binding as B
     d = B.make_dims(2, 1000, 100, 72, tuning=dict(tile_w=16))
