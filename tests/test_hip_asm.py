@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import load_golden, oracle_camera, rel_to_max, synth_aniso
+from helpers import assert_wavelength_grad as _assert_wavelength_grad, load_golden, oracle_camera, rel_to_max, synth_aniso
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
@@ -32,37 +32,6 @@ def _hip_asm(arrs, phases, wl, cam, W, H, bg, gI=None, **kw):
         out["grad_phases"] = ph.grad.cpu().numpy()
         out["grad_wavelengths"] = wlt.grad.cpu().numpy()
     return out
-
-
-def _assert_wavelength_grad(got, want, where="", want64=None):
-    """dL/dlambda within the parity tolerance: 1e-4 of max against `want`, like every other gradient (asserted at 1e-3 until
-    round 4: the HIP chain lost its digits to FMA contraction in the ASM unit, now compiled without -- fresnel_amd/build.py).
-    With `want64` (the same evaluation in double) the fixtures' referee rule applies (helpers.referee): dL/dlambda is a sum over
-    all frequencies that cancels to a fraction of its terms and weights the near-evanescent ones by 1 / kz, and on some scenes
-    ANY fp32 evaluation -- torch's autograd of the oracle included -- is a few 1e-4 from the fp64 one; there the fp64 run
-    referees and the result may be as far from it as helpers.REFEREE_FACTOR times the fp32 evaluation is, no further.
-    (Round 4 also found the frequency grid itself off by an ulp for some sizes: the C ABI carried the pixel pitch as a float, and
-    (float)(1 / (96 * (double)0.005f)) is 2.0833335 where torch.fft.fftfreq's (float)(1 / (96 * 0.005)) is 2.0833333 -- every
-    96-sample axis at pitch 1/200 in these tests.  The near-evanescent terms of dL/dlambda, weighted by 1 / kz, turned that into
-    1.2e-4 ... 1.6e-4 on four oracle-based scenes, identically on the column-FFT path and the rocFFT 2-D path and with an exact
-    exp in the splat -- profiles/r04_dlambda_probe.txt.  The pitch is a double in include/fgs.h now.)
-    Channels where `want` is NaN (a frequency exactly ON the evanescent boundary: torch's autograd of sqrt(clamp(.)) is 0 * inf
-    there; the library defines dkz/dlambda = 0, include/fgs.h) are compared where finite / against `want64`."""
-    from helpers import referee_tolerance
-    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
-    fin = np.isfinite(want)
-    assert np.isfinite(got).all() and fin.any(), (where, got, want)
-    if want64 is None:
-        err, tol, ref = rel_to_max(got[fin], want[fin]), TOL, want
-    else:
-        want64 = np.asarray(want64, np.float64)
-        m = float(np.abs(want64).max())
-        spread = float(np.abs(want - want64)[fin].max() / m)
-        use64, tol = referee_tolerance(spread)
-        err, ref = (float(np.abs(got - want64).max() / m), want64) if use64 else (rel_to_max(got[fin], want[fin]), want)
-    print(f"dL/dlambda {where}: {err:.2e} (tolerance {tol:.1e})")  # (shown with pytest -s / -rP: the sweeps' record)
-    assert err <= tol, f"dL/dlambda {where}: {err:.2e} > {tol:.1e} (got {got}, want {ref})"
-    return err
 
 
 def _oracle_wavelength_grad64(*args, **kw):

@@ -11,7 +11,8 @@ import pytest
 import torch
 
 from helpers import rel_to_max, synth_decoder_like, synth_saag
-from test_hip_parity import TOL, _check_integer_stages, _hip_render, _hip_stages
+from sweep_support import check_integer_stages as _check_integer_stages, hip_stages as _hip_stages
+from test_hip_parity import TOL, _hip_render
 
 pytestmark = pytest.mark.gpu
 KEYS = ["positions", "scales", "rotations", "colors", "opacities"]

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from helpers import TBR_CASES, load_golden, oracle_camera, rel_to_max, synth_aniso, synth_saag
+from sweep_support import check_integer_stages as _check_integer_stages, hip_stages as _hip_stages
 
 pytestmark = pytest.mark.gpu
 
@@ -56,56 +57,9 @@ def _hip_render(arrs, cam, W, H, bg, phases=None, use_phase=False, amp=0.25, gra
     return out
 
 
-def _hip_stages(arrs, cam, W, H, bg=(0, 0, 0), tuning=None):
-    """Integer stages of one forward (B,N,.) via the raw C-ABI entry; numpy views."""
-    from fresnel_amd import renderer as R
-    dev = _cuda()
-    ts = [torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in arrs]
-    cfg = R._Cfg(W, H, bg, 64, False, 0.25, tuning=tuning)
-    camt = R.pack_cameras(cam, dev)
-    img, dep, saved, dims, _ = R.forward_raw(*ts, None, camt, cfg)
-    torch.cuda.synchronize()
-    st = R.inspect_saved(saved, dims)
-    out = {k: (v.cpu().numpy() if torch.is_tensor(v) else v) for k, v in st.items()}
-    out["image"], out["depth"] = img.cpu().numpy(), dep.cpu().numpy()
-    return out
-
-
 def _oracle(arrs, ocam, bg, phases=None, amp=0.25):
     from oracle import fgs_oracle as orc
     return orc.render(*arrs, ocam, bg=bg, phases=phases, phase_amp=amp)
-
-
-def _check_integer_stages(st, b, r, W, H):
-    """HIP integer stages of image b vs oracle Rendered r: all bit-exact."""
-    from oracle import fgs_oracle as orc
-    N = r.pos.shape[0]
-    rec = st["rec"][b]
-    key = st["depth_key"][b].view(np.uint32)
-    vis_h = (key != 0xFFFFFFFF)
-    assert np.array_equal(vis_h, r.proj["visible"].astype(bool)), "visibility differs"
-    bbx = np.ascontiguousarray(rec[:, 10]).view(np.uint32)
-    bby = np.ascontiguousarray(rec[:, 11]).view(np.uint32)
-    bbox_h = np.stack([bbx & 0xFFFF, bbx >> 16, bby & 0xFFFF, bby >> 16], 1).astype(np.int32)
-    assert np.array_equal(bbox_h[vis_h], r.proj["bbox"][vis_h]), "bbox differs"
-    # canonical depth order: visible subsequence of the HIP order == oracle's
-    order_h = st["order"][b]
-    nv = int(vis_h.sum())
-    assert np.array_equal(order_h[:nv], r.vis_sorted), "depth order differs"
-    # the projected floats feeding those decisions are bit-identical too (canonical fp32)
-    assert np.array_equal(np.ascontiguousarray(rec[vis_h, 0:2]).view(np.uint32), np.ascontiguousarray(r.proj["mean2d"][vis_h]).view(np.uint32))
-    assert np.array_equal(np.ascontiguousarray(rec[vis_h, 9]).view(np.uint32), np.ascontiguousarray(r.proj["depth"][vis_h]).view(np.uint32))
-    # per-tile lists
-    ranges_o, ids_o = orc.tile_lists(r.vis_sorted, r.proj["bbox"], W, H, 16, tile_w=int(st["layout"].tile_w))
-    T = len(ranges_o) - 1
-    rg = st["ranges"][b]
-    dup = st["dup_ids"]
-    for t in range(T):
-        s, e = int(rg[t, 0]), int(rg[t, 1])
-        exp = ids_o[ranges_o[t]:ranges_o[t + 1]]
-        assert e - s == len(exp), f"tile {t}: list length {e - s} != {len(exp)}"
-        if len(exp):
-            assert np.array_equal(dup[s:e] - b * N, exp), f"tile {t}: list differs"
 
 
 @pytest.mark.parametrize("tile_w", [16, 32])

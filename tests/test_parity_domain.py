@@ -189,7 +189,8 @@ def _hip(g, gI, gD, W, H, phases=None, use_phase=False, amp=0.25, tuning=None):
 @pytest.mark.gpu
 @pytest.mark.parametrize("tile_w", [16, 32])
 def test_hip_vs_g13_midsize(tile_w):
-    from test_hip_parity import _camera_from_golden, _check_integer_stages, _hip_stages, _oracle
+    from sweep_support import check_integer_stages as _check_integer_stages, hip_stages as _hip_stages
+    from test_hip_parity import _camera_from_golden, _oracle
     g = load_golden("G13_midsize1024_256")
     W, H = [int(v) for v in g["size"]]
     out = _hip(g, *upstream_grads(int(g["seed_up"]), H, W), W, H, tuning=dict(tile_w=tile_w))
@@ -315,7 +316,8 @@ def test_hip_vs_g16_config5_image(batch):
     scene as image 0 of 1 / image 3 of 8: image and every gradient against the reference itself, dL/dlambda (one image: the
     wavelengths are shared by a batch) against its fp64 run."""
     from helpers import synth_saag
-    from test_hip_asm import _assert_wavelength_grad, _hip_asm
+    from helpers import assert_wavelength_grad as _assert_wavelength_grad
+    from test_hip_asm import _hip_asm
     from fresnel_amd.renderer import Camera
     g = load_golden("G16_config5_image_512")
     arrs, phases, gI, S = _g16_scene(g)
