@@ -23,6 +23,8 @@ EXPORTED_SYMBOLS = [
     "fgs_spectral_workspace_bytes", "fgs_spectral_loss_forward", "fgs_spectral_loss_backward",
     "fgs_helmholtz_loss_forward", "fgs_helmholtz_loss_backward", "fgs_reduction_scratch_bytes",
     "fgs_ssim_workspace_bytes", "fgs_ssim_forward", "fgs_ssim_backward",
+    "fgs_pixel_loss_workspace_bytes", "fgs_pixel_loss_stage1", "fgs_pixel_loss_stage2", "fgs_pixel_loss_stage3",
+    "fgs_pixel_loss_forward", "fgs_pixel_loss_backward",
 ]
 
 STAGES = ["project", "depth_sort", "dup_emit", "tile_sort", "tile_ranges", "composite_fwd",
@@ -84,6 +86,23 @@ class FgsSsimDims(ctypes.Structure):
                 ("c1", ctypes.c_float), ("c2", ctypes.c_float), ("flags", ctypes.c_int32)]
 
 
+FGS_PIXEL_MAX_BOUNDARIES = 65
+FGS_PIXEL_RGB, FGS_PIXEL_DENSITY, FGS_PIXEL_BOUNDARY, FGS_PIXEL_HARD_MASK, FGS_PIXEL_DEPTH = 1, 2, 4, 8, 16
+# slots of the pixel loss's `stats` array of doubles (include/fgs.h); the CROSS-RANK pairs a data-parallel caller sums after
+# stage 1, 2 and 3
+(FGS_PIXEL_STAT_RGB, FGS_PIXEL_STAT_BOUNDARY, FGS_PIXEL_STAT_DEPTH, FGS_PIXEL_STAT_SUM_X, FGS_PIXEL_STAT_SUM_Y,
+ FGS_PIXEL_STAT_SSD_X, FGS_PIXEL_STAT_SSD_Y, FGS_PIXEL_STAT_SGN, FGS_PIXEL_STAT_SGN_U) = range(9)
+FGS_PIXEL_STAT_SLOTS = 16
+FGS_PIXEL_CROSS_RANK = {1: slice(3, 5), 2: slice(5, 7), 3: slice(7, 9)}
+
+
+class FgsPixelLossDims(ctypes.Structure):
+    _fields_ = [("images", ctypes.c_int32), ("height", ctypes.c_int32), ("width", ctypes.c_int32),
+                ("flags", ctypes.c_int32), ("world", ctypes.c_int32), ("vlm_weight", ctypes.c_float),
+                ("threshold", ctypes.c_float), ("num_boundaries", ctypes.c_int32),
+                ("boundaries", ctypes.c_float * FGS_PIXEL_MAX_BOUNDARIES)]
+
+
 class FgsError(RuntimeError):
     pass
 
@@ -143,6 +162,16 @@ def load():
     lib.fgs_ssim_forward.argtypes = [cp(FgsSsimDims)] + [vp] * 6
     lib.fgs_ssim_backward.argtypes = [cp(FgsSsimDims)] + [vp] * 8
     lib.fgs_reduction_scratch_bytes.restype = ctypes.c_size_t
+    pd = cp(FgsPixelLossDims)
+    lib.fgs_pixel_loss_workspace_bytes.argtypes = [pd, cp(ctypes.c_size_t), cp(ctypes.c_size_t)]
+    lib.fgs_pixel_loss_stage1.argtypes = [pd] + [vp] * 9
+    lib.fgs_pixel_loss_stage2.argtypes = [pd] + [vp] * 5
+    lib.fgs_pixel_loss_stage3.argtypes = [pd] + [vp] * 6
+    lib.fgs_pixel_loss_forward.argtypes = [pd] + [vp] * 9
+    lib.fgs_pixel_loss_backward.argtypes = [pd] + [vp] * 12
+    for fn in (lib.fgs_pixel_loss_workspace_bytes, lib.fgs_pixel_loss_stage1, lib.fgs_pixel_loss_stage2,
+               lib.fgs_pixel_loss_stage3, lib.fgs_pixel_loss_forward, lib.fgs_pixel_loss_backward):
+        fn.restype = ctypes.c_int
     for fn in (lib.fgs_asm_propagate_workspace_bytes, lib.fgs_asm_propagate_forward, lib.fgs_asm_propagate_backward,
                lib.fgs_spectral_workspace_bytes, lib.fgs_spectral_loss_forward, lib.fgs_spectral_loss_backward,
                lib.fgs_helmholtz_loss_forward, lib.fgs_helmholtz_loss_backward,

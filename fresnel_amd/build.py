@@ -54,6 +54,10 @@ SOURCES = {
     "fgs_fft.hip": NO_SLP,
     "fgs_spectral.hip": [],
     "fgs_ssim.hip": [],
+    # no fast-math (a NaN / Inf in the rendered batch must reach the loss: the step's NaN/Inf skip reads it) and no FMA
+    # contraction (the forward's third stage and the backward form the normalised depths with the same roundings, so the
+    # backward's sgn(u - v) is the one the forward summed)
+    "fgs_pixel_loss.hip": ["-ffp-contract=off"],
 }
 LINK_LIBS = ["-lhipfft"]
 

@@ -1,12 +1,15 @@
 """Dataset side of the training harness: this repo's counterpart of the reference's ImageDataset
 (scripts/training/train_gaussian_decoder.py:525-675) for the tensors the rasterizer path consumes.
 
-    ImageDataset(data_dir, image_size, feature_cache_dir=None, max_images=None, feature_dim=384)[i] ->
+    ImageDataset(data_dir, image_size, feature_cache_dir=None, max_images=None, feature_dim=384, load_vlm_density=False)[i] ->
         {'image' (3,S,S) in [0,1], 'features' (feature_dim,37,37), 'depth' (1,S,S), 'has_saag', 'saag_*', 'name'}
+        and, with load_vlm_density, 'vlm_density' (1,S,S) + 'has_vlm_density'
 
 Same file discovery (jpg / jpeg / png / webp, both cases, sorted, max_images prefix), the same cache file names and
 layouts (fresnel_amd/io.py), the same fall-backs (zero features / zero depth / empty SAAG when a cache is missing).
-Colour-jitter augmentation and the VLM density maps are not part of the rasterizer path and are left out.
+The VLM density maps (`features/{name}_vlm_density.npy`, a square grid; TGD:649-663) are read with load_vlm_density: resized to
+the image with corner-aligned bilinear interpolation -- what the reference's scipy.ndimage.zoom(order=1) computes -- plus 0.5,
+and all ones when the file is missing or unreadable.  Colour-jitter augmentation is not part of the rasterizer path and is left out.
 """
 from pathlib import Path
 from typing import Dict, List, Optional
@@ -19,11 +22,12 @@ from . import io as fio
 
 class ImageDataset:
     def __init__(self, data_dir: str, image_size: int = 256, feature_cache_dir: Optional[str] = None,
-                 max_images: Optional[int] = None, feature_dim: int = 384):
+                 max_images: Optional[int] = None, feature_dim: int = 384, load_vlm_density: bool = False):
         self.data_dir = Path(data_dir)
         self.image_size = image_size
         self.feature_cache_dir = Path(feature_cache_dir) if feature_cache_dir else self.data_dir / "features"
         self.feature_dim = feature_dim
+        self.load_vlm_density = load_vlm_density
         self.feature_suffix = fio.feature_cache_suffix(feature_dim)
         paths: List[Path] = []
         for ext in ["*.jpg", "*.jpeg", "*.png", "*.webp"]:
@@ -51,6 +55,25 @@ class ImageDataset:
         depth = fio.load_depth_cache(str(dpath), S) if dpath.exists() else torch.zeros(1, S, S)
         return name, image, features, depth
 
+    def vlm_density(self, name: str):
+        """(density (1,S,S), found): the VLM density grid of image `name` at the image size, in [0.5, 1.5] for a grid in
+        [0, 1] (TGD:649-663); uniform weighting (ones) when the file is missing or cannot be used."""
+        S = self.image_size
+        path = self.feature_cache_dir / f"{name}_vlm_density.npy"
+        if path.exists():
+            try:
+                grid = torch.from_numpy(np.load(path)).double()
+                if grid.dim() != 2 or grid.shape[0] != grid.shape[1] or grid.shape[0] < 1:
+                    raise ValueError(f"density grid of shape {tuple(grid.shape)}")
+                if grid.shape[0] == 1:
+                    full = grid.expand(S, S)
+                else:  # zoom(order=1) samples the grid corner to corner
+                    full = torch.nn.functional.interpolate(grid[None, None], size=(S, S), mode="bilinear", align_corners=True)[0, 0]
+                return (0.5 + full).float().unsqueeze(0).contiguous(), True
+            except Exception:  # as the reference: an unreadable map means uniform weighting, not a failed run
+                pass
+        return torch.ones(1, S, S), False
+
     def __getitem__(self, idx: int) -> Dict[str, torch.Tensor]:
         name, image, features, depth = self._step_tensors(idx)
         spath = self.feature_cache_dir / f"{name}_saag.bin"
@@ -62,18 +85,24 @@ class ImageDataset:
         else:
             item.update(saag_positions=torch.zeros(0, 3), saag_scales=torch.zeros(0, 3), saag_rotations=torch.zeros(0, 4),
                         saag_colors=torch.zeros(0, 3), saag_opacities=torch.zeros(0))
+        if self.load_vlm_density:
+            item["vlm_density"], item["has_vlm_density"] = self.vlm_density(name)
         return item
 
     def host_item(self, idx: int):
-        """(image (3,S,S), features (37,37,C) patch-major as the decoder takes them, depth (1,S,S)) on the host: what the
+        """(image (3,S,S), features (37,37,C) patch-major as the decoder takes them, depth (1,S,S)[, density (1,S,S)]) on the host: what the
         training loop's prefetch threads load ahead of the step (fresnel_amd/train.py BatchPrefetcher)."""
-        _, image, features, depth = self._step_tensors(idx)  # (not self[idx]: the SAAG binaries are not part of a step)
+        name, image, features, depth = self._step_tensors(idx)  # (not self[idx]: the SAAG binaries are not part of a step)
+        if self.load_vlm_density:  # the fourth tensor of a --use_vlm_guidance step
+            return image, features.permute(1, 2, 0).contiguous(), depth, self.vlm_density(name)[0]
         return image, features.permute(1, 2, 0).contiguous(), depth
 
     def batch(self, indices, device):
-        """(images (B,3,S,S), features (B,37,37,C) patch-major as the decoder takes them, depth (B,1,S,S))."""
+        """(images (B,3,S,S), features (B,37,37,C) patch-major as the decoder takes them, depth (B,1,S,S)[, density (B,1,S,S)])."""
         items = [self[i] for i in indices]
         images = torch.stack([it["image"] for it in items]).to(device)
         feats = torch.stack([it["features"].permute(1, 2, 0) for it in items]).to(device)
         depth = torch.stack([it["depth"] for it in items]).to(device)
+        if self.load_vlm_density:
+            return images, feats, depth, torch.stack([it["vlm_density"] for it in items]).to(device)
         return images, feats, depth

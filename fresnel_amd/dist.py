@@ -48,6 +48,14 @@ class DPContext:
         import torch.distributed.nn.functional as dnf
         return dnf.all_reduce(t, op=dist.ReduceOp.SUM)
 
+    def sum_in_place(self, t: torch.Tensor) -> torch.Tensor:
+        """Sum of a small contiguous device tensor over the ranks, in place and outside autograd: the staged statistics of
+        the fused pixel loss (fresnel_amd/losses.py pixel_losses), whose backward needs no collective.  Identity when not
+        distributed."""
+        if self.enabled:
+            dist.all_reduce(t, op=dist.ReduceOp.SUM)
+        return t
+
     def broadcast_parameters(self, module):
         if self.enabled:
             for p in list(module.parameters()) + list(module.buffers()):

@@ -17,7 +17,11 @@ Kept from TGD (same flag names / defaults / behaviour):
   camera            fx = fy = 0.8*res, cx = cy = res/2, view = I                       TGD:1910-1917
   step              decoder -> render -> stack -> L1 + normalised-depth L1 (SSIM / LPIPS only when
                     those packages exist, as TGD:53-65; --ssim_backend hip computes the SSIM term with this
-                    package's HIP kernels, fresnel_amd/losses.py, whether pytorch_msssim exists or not) -> NaN/Inf skip -> backward ->
+                    package's HIP kernels, fresnel_amd/losses.py, whether pytorch_msssim exists or not); the L1 weighted by
+                    the VLM density maps with --use_vlm_guidance / --vlm_weight (TGD:875-888) and the Fresnel-zone boundary
+                    emphasis term with --use_fresnel_zones --boundary_weight W (TGD:941-953; W defaults to 0 here, 0.1 in the
+                    reference); --pixel_loss_backend hip takes L1, boundary and depth terms from one family of HIP kernels
+                    (fresnel_amd/losses.py pixel_losses) -> NaN/Inf skip -> backward ->
                     clip_grad_norm_(1.0) -> AdamW(lr, weight_decay=1e-5) ; CosineAnnealingLR
                                                                     TGD:890, 922-930, 1255-1266, 1970-1971
   data order        a fresh permutation of the images every epoch (DataLoader(shuffle=True), TGD:1760-1767), drawn
@@ -88,6 +92,13 @@ class TrainingConfig:  # subset of TGD:97-162 that this path uses; same names an
     ssim_weight: float = 0.5
     ssim_backend: str = "msssim"  # "msssim": pytorch_msssim's term when the package is importable, none otherwise (TGD:53-65);
                                   # "hip": the same term from fresnel_amd.losses.ssim (HIP kernels, needs a GPU)
+    use_vlm_guidance: bool = False   # weight the L1 term by the dataset's VLM density maps (TGD:140-141, 875-888)
+    vlm_weight: float = 0.5
+    boundary_weight: float = 0.0     # Fresnel-zone boundary emphasis term (TGD:146, 941-953), active under use_fresnel_zones.
+                                     # The reference's default is 0.1; it is 0 here so that runs configured before the term
+                                     # existed compute what they computed: pass --boundary_weight 0.1 for the reference's loss
+    pixel_loss_backend: str = "torch"  # "torch": L1 / boundary / depth terms as torch expressions; "hip": the same terms from
+                                       # fresnel_amd.losses.pixel_losses (HIP kernels, needs a GPU)
     gaussians_per_patch: int = 4
     max_images: Optional[int] = None
     use_fresnel_zones: bool = False
@@ -138,6 +149,10 @@ class SyntheticDataset:
         feats = torch.randn(Fs, Fs, self.cfg.feature_dim, generator=g) * 0.5
         dlow = torch.rand(1, 4, 4, generator=g)
         depth = F.interpolate(dlow[None], size=(S, S), mode="bilinear", align_corners=False)[0]
+        if self.cfg.use_vlm_guidance:  # a smooth density map in [0.5, 1.5], the range ImageDataset produces (TGD:659-661)
+            vlow = torch.rand(1, 6, 6, generator=g)
+            density = 0.5 + F.interpolate(vlow[None], size=(S, S), mode="bilinear", align_corners=False)[0]
+            return image, feats, depth, density
         return image, feats, depth
 
     def __len__(self):
@@ -248,6 +263,7 @@ def _global_mean_std(x, dp):
 
 
 SSIM_BACKENDS = ("msssim", "hip")
+PIXEL_LOSS_BACKENDS = ("torch", "hip")
 
 
 def _ssim_term_fn(cfg: TrainingConfig):
@@ -261,14 +277,40 @@ def _ssim_term_fn(cfg: TrainingConfig):
     raise ValueError(f"unknown ssim_backend {cfg.ssim_backend!r}: one of {SSIM_BACKENDS}")
 
 
-def compute_losses(rendered, target, rendered_depth, target_depth, cfg: TrainingConfig, dp=None):
-    """L1 + SSIM term + normalised depth L1 (TGD:890, 906-930).  The SSIM term, cfg.ssim_weight * (1 - SSIM(clamp(rendered,
+def compute_losses(rendered, target, rendered_depth, target_depth, cfg: TrainingConfig, dp=None, vlm_density=None):
+    """L1 + SSIM term + normalised depth L1 + zone-boundary term (TGD:875-953).  The SSIM term, cfg.ssim_weight * (1 - SSIM(clamp(rendered,
     0, 1), target)), comes from pytorch_msssim when that package is importable and is left out otherwise
     (cfg.ssim_backend "msssim", TGD:53-65), or from fresnel_amd.losses.ssim's HIP kernels (cfg.ssim_backend "hip", CUDA/ROCm
-    tensors only).  Returns (total, terms): `terms` holds the individual losses as DETACHED 0-d DEVICE tensors -- nothing here
+    tensors only).  The L1 is weighted by (1 - vlm_weight) + vlm_weight * vlm_density when a density map (B,1,h,w) is given,
+    cfg.use_vlm_guidance is set and cfg.vlm_weight > 0 (TGD:875-888); the boundary term, cfg.boundary_weight * mean(mask *
+    mean_c |rendered - target|) with the mask of cfg.num_fresnel_zones zones on (0, 1), is added under cfg.use_fresnel_zones
+    when cfg.boundary_weight > 0 and a target depth exists (TGD:943-953, 1952-1959).  cfg.pixel_loss_backend "hip" takes the
+    L1, boundary and depth terms from fresnel_amd.losses.pixel_losses (CUDA/ROCm tensors only; under data parallelism two or
+    three small sum all-reduces forward and none backward), "torch" from the expressions below.  Returns (total, terms):
+    `terms` holds the individual losses as DETACHED 0-d DEVICE tensors -- nothing here
     synchronises with the host (the reference's `.item()` per term, TGD:891-1001, would cost a device round trip each)."""
     d: Dict[str, torch.Tensor] = {}
-    rgb = F.l1_loss(rendered, target)
+    if cfg.pixel_loss_backend not in PIXEL_LOSS_BACKENDS:
+        raise ValueError(f"unknown pixel_loss_backend {cfg.pixel_loss_backend!r}: one of {PIXEL_LOSS_BACKENDS}")
+    use_vlm = vlm_density is not None and cfg.use_vlm_guidance and cfg.vlm_weight > 0
+    use_boundary = cfg.use_fresnel_zones and cfg.boundary_weight > 0 and target_depth is not None
+    px = None
+    if cfg.pixel_loss_backend == "hip":
+        if not rendered.is_cuda:
+            raise ValueError("pixel_loss_backend 'hip' needs the rendered batch on a GPU: the HIP pixel-loss kernels have no CPU fallback")
+        from .losses import pixel_losses
+        dist_on = dp is not None and dp.enabled
+        px = pixel_losses(rendered, target, rendered_depth, target_depth, density=vlm_density if use_vlm else None,
+                          vlm_weight=cfg.vlm_weight, zones=cfg.num_fresnel_zones if use_boundary else None,
+                          reduce_fn=dp.sum_in_place if dist_on else None, world=dp.world if dist_on else 1)
+        rgb = px["rgb"]
+    elif use_vlm:
+        w = vlm_density.detach()
+        if w.shape[-2:] != rendered.shape[-2:]:
+            w = F.interpolate(w, size=rendered.shape[-2:], mode="bilinear", align_corners=False)
+        rgb = (torch.abs(rendered - target) * ((1.0 - cfg.vlm_weight) + cfg.vlm_weight * w)).mean()
+    else:
+        rgb = F.l1_loss(rendered, target)
     d["rgb"] = rgb.detach()
     total = cfg.rgb_weight * rgb
     ssim_term = _ssim_term_fn(cfg) if cfg.ssim_weight > 0 else None
@@ -278,13 +320,26 @@ def compute_losses(rendered, target, rendered_depth, target_depth, cfg: Training
         s = 1.0 - ssim_term(torch.clamp(rendered, 0, 1), target, data_range=1.0, size_average=True)
         d["ssim"] = s.detach()
         total = total + cfg.ssim_weight * s
-    if rendered_depth is not None and target_depth is not None:
+    if px is not None:
+        if "depth" in px:
+            d["depth"] = px["depth"].detach()
+            total = total + cfg.depth_weight * px["depth"]
+    elif rendered_depth is not None and target_depth is not None:
         rd_mean, rd_std = _global_mean_std(rendered_depth, dp)
         td_mean, td_std = _global_mean_std(target_depth, dp)
         dl = F.l1_loss((rendered_depth - rd_mean) / torch.clamp(rd_std, min=1e-4),
                        (target_depth - td_mean) / torch.clamp(td_std, min=1e-4))
         d["depth"] = dl.detach()
         total = total + cfg.depth_weight * dl
+    if use_boundary:  # TGD:943-953
+        if px is not None:
+            bl = px["boundary"]
+        else:
+            from .losses import fresnel_boundary_mask
+            mask = fresnel_boundary_mask(target_depth, cfg.num_fresnel_zones, (0.0, 1.0))
+            bl = (torch.abs(rendered - target).mean(dim=1) * mask).mean()
+        d["boundary"] = bl.detach()
+        total = total + cfg.boundary_weight * bl
     if cfg.wave_equation_weight > 0:  # TGD:957-964
         from .losses import wave_equation_loss
         we = wave_equation_loss(rendered, cfg.wavelength, pixel_spacing=1.0 / cfg.image_size)
@@ -417,7 +472,10 @@ def train_step(model, renderer, camera, batch, optimizer, cfg: TrainingConfig, d
                hfts: Optional[HFTSConfig] = None, epoch: int = 0, train_res: Optional[int] = None,
                pose_rng: Optional[np.random.RandomState] = None, sample_gen: Optional[torch.Generator] = None):
     """One optimizer step on this rank's image shard, without a host synchronisation.  Returns a StepResult."""
-    images, feats, depth = batch
+    if cfg.use_vlm_guidance:
+        images, feats, depth, density = batch
+    else:
+        (images, feats, depth), density = batch, None
     res = train_res or cfg.image_size
     # progressive Gaussian growing (TGD:1069-1076) and the batch's pose (TGD:1078-1098)
     num_gaussians = hfts.get_gaussians_per_patch(epoch, cfg.epochs, cfg.gaussians_per_patch) if hfts is not None else None
@@ -440,7 +498,7 @@ def train_step(model, renderer, camera, batch, optimizer, cfg: TrainingConfig, d
                                 out["opacities"], render_camera, return_depth=True, phases=phases)
     target = F.interpolate(images, size=(res, res), mode="bilinear", align_corners=False)
     tdepth = F.interpolate(depth, size=(res, res), mode="bilinear", align_corners=False).squeeze(1)
-    loss, terms = compute_losses(rendered, target, rdepth, tdepth, cfg, dp)
+    loss, terms = compute_losses(rendered, target, rdepth, tdepth, cfg, dp, vlm_density=density)
     # NaN/Inf batch skip (TGD:1255-1258), decided on the device and by ALL ranks together: the flag and the loss ride
     # behind the gradients in the one all-reduce of the step
     bad = (~torch.isfinite(loss.detach())).float()
@@ -476,7 +534,8 @@ def make_dataset(cfg: TrainingConfig, log=print):
     stand-in (the reference fabricates test images itself when the directory is empty, TGD:1748-1758)."""
     if cfg.data_dir and os.path.isdir(cfg.data_dir):
         from .data import ImageDataset
-        ds = ImageDataset(cfg.data_dir, cfg.image_size, max_images=cfg.max_images, feature_dim=cfg.feature_dim)
+        ds = ImageDataset(cfg.data_dir, cfg.image_size, max_images=cfg.max_images, feature_dim=cfg.feature_dim,
+                          load_vlm_density=cfg.use_vlm_guidance)
         if len(ds) > 0:
             if ds[0]["features"].shape[-1] != cfg.feature_size:
                 raise ValueError(f"feature caches are 37x37 patch grids; got feature_size={cfg.feature_size}")
@@ -516,6 +575,10 @@ def run_training(cfg: TrainingConfig, dp: Optional[DPContext] = None,
         raise ValueError(f"unknown ssim_backend {cfg.ssim_backend!r}: one of {SSIM_BACKENDS}")
     if cfg.ssim_backend == "hip" and device.type != "cuda":
         raise ValueError("ssim_backend 'hip' needs a GPU device: the HIP SSIM kernels have no CPU fallback")
+    if cfg.pixel_loss_backend not in PIXEL_LOSS_BACKENDS:
+        raise ValueError(f"unknown pixel_loss_backend {cfg.pixel_loss_backend!r}: one of {PIXEL_LOSS_BACKENDS}")
+    if cfg.pixel_loss_backend == "hip" and device.type != "cuda":
+        raise ValueError("pixel_loss_backend 'hip' needs a GPU device: the HIP pixel-loss kernels have no CPU fallback")
     dp = dp or DPContext(device=device if device.type == "cuda" else None)
     if cfg.batch_size % dp.world != 0:  # fail fast, before any rank can stall in a collective (see DPContext.shard)
         raise ValueError(f"--batch_size {cfg.batch_size} is not a multiple of the {dp.world} ranks")
@@ -652,6 +715,10 @@ def arg_parser() -> argparse.ArgumentParser:
     ap.add_argument("--use_fresnel_zones", type=int, nargs="?", const=8, default=0,
                     help="quantise depth into N zones (TGD flag; bare flag = 8)")
     ap.add_argument("--num_fresnel_zones", type=int, default=c.num_fresnel_zones)
+    ap.add_argument("--boundary_weight", type=float, default=c.boundary_weight,
+                    help="zone-boundary emphasis term under --use_fresnel_zones (TGD:146; the reference's default is 0.1)")
+    ap.add_argument("--use_vlm_guidance", action="store_true", help="weight the L1 term by the VLM density maps (TGD:1443)")
+    ap.add_argument("--vlm_weight", type=float, default=c.vlm_weight, help="TGD:1445")
     ap.add_argument("--use_phase_blending", action="store_true")
     ap.add_argument("--phase_amplitude", type=float, default=c.phase_amplitude)
     ap.add_argument("--use_edge_aware", action="store_true", help="smaller Gaussians at depth edges (TGD:1455)")
@@ -680,6 +747,8 @@ def arg_parser() -> argparse.ArgumentParser:
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--ssim_backend", default=c.ssim_backend, choices=list(SSIM_BACKENDS),
                     help="SSIM term: pytorch_msssim when importable (default, as the reference) or this package's HIP kernels")
+    ap.add_argument("--pixel_loss_backend", default=c.pixel_loss_backend, choices=list(PIXEL_LOSS_BACKENDS),
+                    help="L1 / boundary / depth terms: torch expressions (default) or this package's fused HIP kernels")
     return ap
 
 
@@ -707,7 +776,9 @@ def main(argv=None):
                          phase_retrieval_weight=a.phase_retrieval_weight,
                          use_frequency_loss=a.use_frequency_loss, frequency_loss_weight=a.frequency_loss_weight,
                          device=f"cuda:{local_rank}", seed=a.seed, hip_graph=a.hip_graph,
-                         ssim_backend=a.ssim_backend)
+                         ssim_backend=a.ssim_backend, boundary_weight=a.boundary_weight,
+                         use_vlm_guidance=a.use_vlm_guidance, vlm_weight=a.vlm_weight,
+                         pixel_loss_backend=a.pixel_loss_backend)
     hfts = HFTSConfig(train_resolution=a.train_resolution, progressive_schedule=a.progressive_schedule,
                       stochastic_k=a.stochastic_k, fast_mode=a.fast_mode)
     dp = DPContext(device=torch.device(cfg.device))

@@ -290,6 +290,76 @@ int fgs_ssim_forward(const FgsSsimDims *dims, const float *x, const float *y, fl
 int fgs_ssim_backward(const FgsSsimDims *dims, const float *x, const float *y, const void *saved, const float *g_out,
                       float *g_x, float *g_y, void *scratch, void *stream);
 
+/* Per-pixel block of the training loss (TGD:873-953): three means over this process's images (fp32, contiguous, DEVICE)
+ *   rgb       mean over images x 3 x H x W of w |rendered - target|, w = (1 - vlm_weight) + vlm_weight density with
+ *             FGS_PIXEL_DENSITY (density (images,1,H,W), TGD:877-888), else w = 1 (TGD:890)
+ *   boundary  mean over images x H x W of mask mean_c |rendered - target| (TGD:945-951); mask =
+ *             sigmoid((10 / threshold) (threshold - min_k |target_depth - boundaries[k]|)), or (min_k ... < threshold)
+ *             with FGS_PIXEL_HARD_MASK (the reference's FresnelZones.compute_boundary_mask)
+ *   depth     mean over images x H x W of |u - v|, u = (rendered_depth - mean) / max(std, 1e-4), v the same of
+ *             target_depth (TGD:922-928); mean and unbiased two-pass std are taken over N = images x H x W x world
+ *             pixels: every rank's batch
+ * out = float[3] {rgb, boundary, depth}; a term that is not requested is written as 0.
+ *
+ * stats = double[FGS_PIXEL_STAT_SLOTS] (fgs_pixel_loss_workspace_bytes: stats_bytes).  The mean, the std and the gradient's
+ * two global sums are three DEPENDENT reductions, so the forward is staged; every stage reads and writes named slots:
+ *   stage1  one pass over all inputs    writes RGB, BOUNDARY (local sums), SUM_X, SUM_Y and out[0], out[1] (out[2] = 0)
+ *   stage2  reads SUM_X, SUM_Y          writes SSD_X, SSD_Y = sum (x - mean)^2 of rendered_depth / target_depth
+ *   stage3  reads SUM_*, SSD_*          writes DEPTH (local sum |u - v|), SGN = sum sgn(u - v), SGN_U = sum sgn(u - v) u, out[2]
+ * SUM_*, SSD_*, SGN and SGN_U are CROSS-RANK slots: a data-parallel caller (world > 1) sum-all-reduces SUM_X..SUM_Y after
+ * stage1, SSD_X..SSD_Y after stage2 and SGN..SGN_U after stage3 (each pair is contiguous); the backward then needs no
+ * collective.  Stages 2 and 3 are only needed (and only valid) with FGS_PIXEL_DEPTH.  fgs_pixel_loss_forward enqueues the
+ * stages back to back: the single-process case (world = 1).
+ *
+ * Backward: ONE pointwise launch, no reduction; reads the inputs and stats, modifies neither.  g_rgb / g_boundary /
+ * g_depth: DEVICE scalars, the upstream gradients of the three terms (NULL = 0).  sgn(a - b) = (a > b) - (a < b): 0 on a tie.
+ *   g_rendered       = sgn(rendered - target) (g_rgb w + g_boundary mask) / (images x 3 x H x W)
+ *   g_rendered_depth = g_depth (q - Q / N - gate P u / (N - 1)) / s,  q = sgn(u - v) / (images x H x W),
+ *                      Q = SGN / (images x H x W), P = SGN_U / (images x H x W), s = max(std, 1e-4), gate = (std >= 1e-4)
+ * which, with the cross-rank slots summed, is the gradient of the SUM of the ranks' depth terms (what differentiable
+ * all-reduces of the statistics give).  g_rendered may be NULL without FGS_PIXEL_RGB and _BOUNDARY, g_rendered_depth
+ * without FGS_PIXEL_DEPTH.  A NaN / Inf in rendered or rendered_depth makes the term it enters non-finite. */
+#define FGS_PIXEL_MAX_BOUNDARIES 65
+#define FGS_PIXEL_RGB 1
+#define FGS_PIXEL_DENSITY 2      /* needs FGS_PIXEL_RGB */
+#define FGS_PIXEL_BOUNDARY 4
+#define FGS_PIXEL_HARD_MASK 8
+#define FGS_PIXEL_DEPTH 16
+#define FGS_PIXEL_STAT_RGB 0
+#define FGS_PIXEL_STAT_BOUNDARY 1
+#define FGS_PIXEL_STAT_DEPTH 2
+#define FGS_PIXEL_STAT_SUM_X 3   /* x = rendered_depth */
+#define FGS_PIXEL_STAT_SUM_Y 4   /* y = target_depth */
+#define FGS_PIXEL_STAT_SSD_X 5
+#define FGS_PIXEL_STAT_SSD_Y 6
+#define FGS_PIXEL_STAT_SGN 7
+#define FGS_PIXEL_STAT_SGN_U 8
+#define FGS_PIXEL_STAT_SLOTS 16  /* 9 used */
+typedef struct FgsPixelLossDims {
+    int32_t images, height, width;
+    int32_t flags;               /* FGS_PIXEL_*: at least one term */
+    int32_t world;               /* ranks whose batches share the depth statistics (>= 1); images x H x W x world >= 2 */
+    float vlm_weight;            /* FGS_PIXEL_DENSITY */
+    float threshold;             /* FGS_PIXEL_BOUNDARY: > 0 */
+    int32_t num_boundaries;      /* FGS_PIXEL_BOUNDARY: 1 ... 65, strictly increasing */
+    float boundaries[FGS_PIXEL_MAX_BOUNDARIES];
+} FgsPixelLossDims;
+int fgs_pixel_loss_workspace_bytes(const FgsPixelLossDims *dims, size_t *stats_bytes, size_t *scratch_bytes);
+int fgs_pixel_loss_stage1(const FgsPixelLossDims *dims, const float *rendered, const float *target,
+                          const float *rendered_depth, const float *target_depth, const float *density, float *out,
+                          void *stats, void *scratch, void *stream);
+int fgs_pixel_loss_stage2(const FgsPixelLossDims *dims, const float *rendered_depth, const float *target_depth,
+                          void *stats, void *scratch, void *stream);
+int fgs_pixel_loss_stage3(const FgsPixelLossDims *dims, const float *rendered_depth, const float *target_depth, float *out,
+                          void *stats, void *scratch, void *stream);
+int fgs_pixel_loss_forward(const FgsPixelLossDims *dims, const float *rendered, const float *target,
+                           const float *rendered_depth, const float *target_depth, const float *density, float *out,
+                           void *stats, void *scratch, void *stream);
+int fgs_pixel_loss_backward(const FgsPixelLossDims *dims, const float *rendered, const float *target,
+                            const float *rendered_depth, const float *target_depth, const float *density,
+                            const void *stats, const float *g_rgb, const float *g_boundary, const float *g_depth,
+                            float *g_rendered, float *g_rendered_depth, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * Importance-subsampling hand-off between decoder and rasterizer (--stochastic_k; reference
  * scripts/training/train_gaussian_decoder.py:1160-1187): the n_out Gaussians whose indices torch.multinomial
