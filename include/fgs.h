@@ -15,6 +15,22 @@
  *   - functions enqueue work on `stream` and return; they never allocate, never
  *     synchronise and are re-entrant per (stream, workspace);
  *   - return 0 on success, negative FGS_E* on error; fgs_last_error() gives the text.
+ *
+ * Buffer contract (every compute entry; checked by tests/test_workspace_hygiene.py):
+ *   - The caller owns and sizes `saved`, `scratch`, `stats` (fgs_*_workspace_bytes) and every output / gradient tensor.
+ *     Their content on entry is UNDEFINED: a call never depends on it (no buffer has to be cleared, a `scratch` that
+ *     served another call of any shape may be handed over as it is) and never writes outside the reported sizes.
+ *   - Every element of every output and gradient tensor is written by the call that returns it (culled Gaussians,
+ *     unselected rows and terms that were not requested get zeros).  Of `saved` only the part a call uses is written:
+ *     unused capacity (list entries beyond the duplicate count, segment slots beyond the unit count) stays undefined.
+ *   - Alignment: give `saved`, `scratch` and `stats` at least 256 bytes (the sections inside them are laid out in 256-byte
+ *     steps and read with 16-byte loads) and input, output and gradient tensors at least 16 bytes.  The tests hand out
+ *     512-byte aligned buffers, as torch's allocator does; no smaller alignment is exercised.
+ *   - Inputs are never modified.  `saved` goes unchanged through fgs_backward and fgs_ssim_backward (so a second
+ *     fgs_ssim_backward on it is valid) and `stats` through fgs_pixel_loss_backward; fgs_asm_backward and
+ *     fgs_spectral_loss_backward CONSUME `saved` (fields / spectra are overwritten by their gradients), and
+ *     fgs_wave_backward takes it non-const as well: one backward per forward there.  (By their signatures fgs_count_pairs
+ *     takes `saved` and fgs_helmholtz_loss_backward `residual` as const; no test looks at those two.)
  */
 #ifndef FGS_H
 #define FGS_H
@@ -97,7 +113,9 @@ typedef struct FgsSavedLayout {
     size_t dup_off;    /* uint32 [B][N]: first duplicate slot of each Gaussian (emission
                                          order = image, depth rank, tile row, tile column)   */
     size_t counters;   /* uint32 [16]: [0] total duplicates D, [1] overflow flag, [2] depth-segment units U,
-                                       [4] seg_len and [5] fwd_variant the forward ran with          */
+                                       [4] seg_len and [5] fwd_variant the forward ran with; [2], [4], [5] are
+                                       written on the non-phase path only (with use_phase there are no depth
+                                       segments and the three words stay undefined), the rest is never written */
     size_t ranges;     /* uint32 [B*T][2]: [start,end) into dup_ids per (image,tile)      */
     size_t tile_order; /* uint32 [B*T]: (image,tile) indices, longest lists first: the launch
                                          order of the composite kernels (scheduling only)    */
