@@ -38,7 +38,7 @@ class FgsDims(ctypes.Structure):
                 ("use_phase", ctypes.c_int32), ("phase_amplitude", ctypes.c_float),
                 ("num_cameras", ctypes.c_int32), ("saturation_skip", ctypes.c_int32),
                 ("seg_len", ctypes.c_int32), ("fwd_variant", ctypes.c_int32), ("bin_mode", ctypes.c_int32),
-                ("tile_w", ctypes.c_int32), ("sort_mode", ctypes.c_int32)]
+                ("tile_w", ctypes.c_int32), ("sort_mode", ctypes.c_int32), ("dup_capacity", ctypes.c_uint32)]
 
 
 class FgsSavedLayout(ctypes.Structure):
@@ -198,8 +198,12 @@ def check(rc, what):
 
 
 def make_dims(batch, num_gaussians, width, height, max_radius=64.0, background=(0.0, 0.0, 0.0),
-              use_phase=False, phase_amplitude=0.25, num_cameras=1, saturation_skip=False, tuning=None):
-    """`tuning`: optional dict of FgsDims overrides {seg_len, fwd_variant, bin_mode, tile_w, sort_mode} (0 / absent = automatic)."""
+              use_phase=False, phase_amplitude=0.25, num_cameras=1, saturation_skip=False, tuning=None, dup_capacity=0):
+    """`tuning`: optional dict of FgsDims overrides {seg_len, fwd_variant, bin_mode, tile_w, sort_mode} (0 / absent = automatic).
+    `dup_capacity`: room for that many (tile, Gaussian) duplicates instead of the worst case (0 = worst case; a call that needs
+    more overflows: NaN images, zero gradients, saved.counters[1] = 1 -- include/fgs.h)."""
+    if isinstance(dup_capacity, bool) or int(dup_capacity) != dup_capacity or not 0 <= int(dup_capacity) <= 0xFFFFFFFF:
+        raise FgsError(f"dup_capacity must be an integer in [0, 2^32), got {dup_capacity!r}")
     d = FgsDims()
     d.batch, d.num_gaussians, d.width, d.height = int(batch), int(num_gaussians), int(width), int(height)
     d.max_radius = float(max_radius)
@@ -213,6 +217,7 @@ def make_dims(batch, num_gaussians, width, height, max_radius=64.0, background=(
         if k not in ("seg_len", "fwd_variant", "bin_mode", "tile_w", "sort_mode"):
             raise FgsError(f"unknown tuning field {k!r}")
         setattr(d, k, int(v))
+    d.dup_capacity = int(dup_capacity)
     return d
 
 

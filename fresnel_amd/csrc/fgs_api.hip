@@ -55,6 +55,41 @@ void fgs_stage_end(int stage, hipStream_t st) {
     g_open[stage] = nullptr;
 }
 
+// ---- duplicate-capacity overflow (FgsDims.dup_capacity; include/fgs.h, buffer contract) --------------------------------------
+// A hinted forward whose duplicates did not fit left every list empty (k_tile_post) and the flag in saved.counters[1]; the
+// composite kernels then wrote the background.  These fills turn that into the contract's outcome: every output word the quiet
+// NaN, every gradient zero.  ONE launch per entry point, enqueued only when the plan is hinted (the default path's launches
+// are what they were); a block reads the flag once and leaves when it is clear, which is the cost of a call that fits.
+namespace {
+struct FillList { float *p[6]; unsigned long long n[6]; };  // up to six fp32 tensors (16-byte aligned: include/fgs.h) and their lengths
+
+__global__ __launch_bounds__(256) void k_overflow_fill(const uint32_t *__restrict__ counters, FillList f, uint32_t word) {
+    if (counters[1] == 0u) return;
+    const float v = __uint_as_float(word);
+    const float4 v4 = make_float4(v, v, v, v);
+    const size_t stride = (size_t)gridDim.x * 256, t = (size_t)blockIdx.x * 256 + threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        float *q = f.p[k];
+        const size_t n = f.n[k], n4 = n >> 2;  // (n = 0: unused slot)
+        for (size_t i = t; i < n4; i += stride) reinterpret_cast<float4 *>(q)[i] = v4;
+        for (size_t i = (n4 << 2) + t; i < n; i += stride) q[i] = v;
+    }
+}
+
+int launch_overflow_fill(const char *saved, const FgsPlan &p, const FillList &f, uint32_t word, hipStream_t st) {
+    size_t total = 0;
+    for (int k = 0; k < 6; ++k) total += f.n[k];
+    size_t grid = (total / 4 + 255) / 256;
+    if (grid > 2048) grid = 2048;
+    if (grid < 1) grid = 1;
+    hipLaunchKernelGGL(k_overflow_fill, dim3((unsigned)grid), dim3(256), 0, st,
+                       reinterpret_cast<const uint32_t *>(saved + p.L.counters), f, word);
+    FGS_LAUNCH_CHECK("k_overflow_fill");
+    return FGS_OK;
+}
+}  // namespace
+
 extern "C" {
 
 const char *fgs_last_error(void) { return g_err; }
@@ -88,9 +123,9 @@ int fgs_stage_timing_read(float *ms, int32_t *count) {
 #ifndef FGS_BUILD_DEFINES
 #define FGS_BUILD_DEFINES "(defines not recorded)"
 #endif
-const char *fgs_version(void) { return "fgs-hip 0.2 (gfx950) EXPERIMENT BUILD, NOT THE PRODUCT: " FGS_BUILD_DEFINES; }
+const char *fgs_version(void) { return "fgs-hip 0.3 (gfx950) EXPERIMENT BUILD, NOT THE PRODUCT: " FGS_BUILD_DEFINES; }
 #else
-const char *fgs_version(void) { return "fgs-hip 0.2 (gfx950)"; }
+const char *fgs_version(void) { return "fgs-hip 0.3 (gfx950)"; }
 #endif
 
 int fgs_workspace_bytes(const FgsDims *dims, size_t *saved_bytes, size_t *scratch_bytes) {
@@ -135,6 +170,11 @@ int fgs_forward(const FgsDims *dims, const float *cameras, const float *pos, con
     fgs_stage_begin(ST_COMPOSITE_FWD, st);
     if ((rc = fgs_launch_composite_fwd(p, phase, sv, out_rgb, out_depth, st))) return rc;
     fgs_stage_end(ST_COMPOSITE_FWD, st);
+    if (p.capacity_hinted) {  // overflow: the whole call's images become the quiet NaN
+        const size_t hw = (size_t)p.d.width * p.d.height, B = p.d.batch;
+        const FillList f = {{out_rgb, out_depth, nullptr, nullptr, nullptr, nullptr}, {B * 3 * hw, B * hw, 0, 0, 0, 0}};
+        if ((rc = launch_overflow_fill(sv, p, f, 0x7FC00000u, st))) return rc;
+    }
     return FGS_OK;
 }
 
@@ -168,6 +208,14 @@ int fgs_backward(const FgsDims *dims, const float *cameras, const float *pos, co
                                      reinterpret_cast<float *>(sc + p.s_rsum))))
         return rc;
     fgs_stage_end(ST_PROJECT_BWD, st);
+    if (p.capacity_hinted) {
+        // overflow: no list was walked above (no depth-segment unit, every range empty), so the rows the projection backward
+        // summed were never written -- every gradient is zero by contract
+        const size_t bn = (size_t)p.d.batch * p.d.num_gaussians;
+        const FillList f = {{g_pos, g_scale, g_quat, g_color, g_opacity, p.d.use_phase ? g_phase : nullptr},
+                            {bn * 3, bn * 3, bn * 4, bn * 3, bn, p.d.use_phase ? bn : 0}};
+        if ((rc = launch_overflow_fill(sv, p, f, 0u, st))) return rc;
+    }
     return FGS_OK;
 }
 

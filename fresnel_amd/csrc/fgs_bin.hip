@@ -55,7 +55,7 @@ __global__ __launch_bounds__(256) void k_dup_blocksum(uint32_t total, uint32_t N
     if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
 }
 
-// single block: in-place exclusive scan of bsum[0..n), total -> counters[0] (clamped), overflow flag
+// single block: in-place exclusive scan of bsum[0..n), total -> counters[0] (clamped) and counters[3] (not clamped), overflow flag
 __global__ __launch_bounds__(256) void k_dup_scan_bsum(uint32_t n, uint32_t *__restrict__ bsum,
                                                        uint32_t *__restrict__ counters, uint32_t dcap) {
     unsigned long long carry = 0;
@@ -71,6 +71,7 @@ __global__ __launch_bounds__(256) void k_dup_scan_bsum(uint32_t n, uint32_t *__r
     if (threadIdx.x == 0) {
         counters[0] = carry > dcap ? dcap : (uint32_t)carry;
         counters[1] = carry > dcap ? 1u : 0u;
+        counters[3] = carry > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)carry;  // the demand, whatever the capacity
     }
 }
 
@@ -288,7 +289,7 @@ __global__ __launch_bounds__(256) void k_mask_count(uint32_t B, uint32_t N, uint
                                                     uint32_t *__restrict__ counters, uint32_t dcap) {
     if (blockIdx.x == gridDim.x - 1) {
         // last block: in-place exclusive scan of the block sums of k_mask_build (duplicate offsets in depth order,
-        // image-major), total -> counters[0] (clamped), overflow flag -> counters[1]
+        // image-major), total -> counters[0] (clamped) and counters[3] (the demand, not clamped), overflow flag -> counters[1]
         unsigned long long carry = 0;
         for (uint32_t base = 0; base < nrb; base += 256) {
             const uint32_t i = base + threadIdx.x;
@@ -302,6 +303,7 @@ __global__ __launch_bounds__(256) void k_mask_count(uint32_t B, uint32_t N, uint
         if (threadIdx.x == 0) {
             counters[0] = carry > dcap ? dcap : (uint32_t)carry;
             counters[1] = carry > dcap ? 1u : 0u;
+            counters[3] = carry > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)carry;  // the demand, whatever the capacity
         }
         return;
     }
@@ -348,7 +350,8 @@ __global__ __launch_bounds__(256) void k_mask_emit(uint32_t B, uint32_t N, uint3
                                                    const uint32_t *__restrict__ tile_count,
                                                    const uint32_t *__restrict__ ranges,
                                                    const uint32_t *__restrict__ bsum,
-                                                   uint32_t *__restrict__ dup_ids, uint32_t *__restrict__ dup_off) {
+                                                   uint32_t *__restrict__ dup_ids, uint32_t *__restrict__ dup_off,
+                                                   const uint32_t *__restrict__ counters) {
     __shared__ uint32_t park[4][ME_CAP];
     if (blockIdx.x < nrb) {
         // duplicate offsets of one block of depth ranks: dup_off[g] = first gradient-row / emission slot of Gaussian
@@ -361,6 +364,7 @@ __global__ __launch_bounds__(256) void k_mask_emit(uint32_t B, uint32_t N, uint3
         if (r < N) dup_off[g] = bsum[blockIdx.x] + ex;
         return;
     }
+    if (counters[1] != 0u) return;  // duplicate-capacity overflow: every list is empty (k_tile_post), nothing to emit
     // consecutive tiles' lists are adjacent in dup_ids: an XCD gets a contiguous run of tiles (whole images at B = 8)
     const uint32_t ntb = gridDim.x - nrb;
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
@@ -457,6 +461,7 @@ __global__ __launch_bounds__(256) void k_mask_count_group(uint32_t B, uint32_t N
         if (threadIdx.x == 0) {
             counters[0] = carry > dcap ? dcap : (uint32_t)carry;
             counters[1] = carry > dcap ? 1u : 0u;
+            counters[3] = carry > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)carry;  // the demand, whatever the capacity
         }
         return;
     }
@@ -487,7 +492,8 @@ __global__ __launch_bounds__(256) void k_mask_emit_group(uint32_t B, uint32_t N,
                                                          const uint32_t *__restrict__ tile_count,
                                                          const uint32_t *__restrict__ ranges,
                                                          const uint32_t *__restrict__ bsum,
-                                                         uint32_t *__restrict__ dup_ids, uint32_t *__restrict__ dup_off) {
+                                                         uint32_t *__restrict__ dup_ids, uint32_t *__restrict__ dup_off,
+                                                         const uint32_t *__restrict__ counters) {
     __shared__ uint32_t park[16][MG_CAP];
     if (blockIdx.x < nrb) {  // duplicate offsets of one block of depth ranks (as in k_mask_emit)
         const uint32_t b = blockIdx.x / bpi, blk = blockIdx.x - b * bpi;
@@ -498,6 +504,7 @@ __global__ __launch_bounds__(256) void k_mask_emit_group(uint32_t B, uint32_t N,
         if (r < N) dup_off[g] = bsum[blockIdx.x] + ex;
         return;
     }
+    if (counters[1] != 0u) return;  // duplicate-capacity overflow: every list is empty (k_tile_post), nothing to emit
     const uint32_t ntb = gridDim.x - nrb;
     const uint32_t glane = threadIdx.x & 15u, grp = threadIdx.x >> 4;
     const uint32_t list = fgs_xcd_remap(blockIdx.x - nrb, ntb) * 16u + grp;
@@ -568,7 +575,8 @@ __global__ __launch_bounds__(256) void k_mask_emit_block(uint32_t B, uint32_t N,
                                                          const uint32_t *__restrict__ tile_count,
                                                          const uint32_t *__restrict__ ranges,
                                                          const uint32_t *__restrict__ bsum,
-                                                         uint32_t *__restrict__ dup_ids, uint32_t *__restrict__ dup_off) {
+                                                         uint32_t *__restrict__ dup_ids, uint32_t *__restrict__ dup_off,
+                                                         const uint32_t *__restrict__ counters) {
     constexpr uint32_t CAP = 4u * ME_CAP;
     __shared__ uint32_t park[CAP];
     __shared__ uint32_t wtot[4];
@@ -581,6 +589,7 @@ __global__ __launch_bounds__(256) void k_mask_emit_block(uint32_t B, uint32_t N,
         if (r < N) dup_off[g] = bsum[blockIdx.x] + ex;
         return;
     }
+    if (counters[1] != 0u) return;  // duplicate-capacity overflow: every list is empty (k_tile_post), nothing to emit
     const uint32_t ntb = gridDim.x - nrb;  // = number of lists
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint32_t tile = fgs_xcd_remap(blockIdx.x - nrb, ntb);
@@ -712,8 +721,10 @@ __device__ __forceinline__ uint32_t tile_len(const uint32_t *__restrict__ lens, 
 __global__ __launch_bounds__(256) void k_tile_pre(uint32_t ntiles, const uint32_t *__restrict__ ranges,
                                                   const uint32_t *__restrict__ lens, uint32_t seg_len,
                                                   unsigned long long *__restrict__ pre64,
-                                                  uint32_t *__restrict__ bhist, uint32_t ngroups) {
+                                                  uint32_t *__restrict__ bhist, uint32_t ngroups,
+                                                  const uint32_t *__restrict__ counters) {
     __shared__ uint32_t hist[TO_MAX_COLS];
+    const bool ovf = counters[1] != 0u;  // duplicate-capacity overflow: every list counts as empty (see k_tile_post)
     __shared__ unsigned long long wsum[4];
     const uint32_t ncols = 64u * ngroups;
     for (uint32_t i = threadIdx.x; i < ncols; i += 256) hist[i] = 0;
@@ -724,7 +735,7 @@ __global__ __launch_bounds__(256) void k_tile_pre(uint32_t ntiles, const uint32_
     for (int k = 0; k < 4; ++k) {
         const uint32_t t = t0 + k;
         if (t < ntiles) {
-            const uint32_t len = tile_len(lens, ranges, t);
+            const uint32_t len = ovf ? 0u : tile_len(lens, ranges, t);
             v += ((unsigned long long)len << 32) | ((len + seg_len - 1) / seg_len);
             atomicAdd(&hist[64u * tile_group(t, ntiles, ngroups) + length_bucket(len)], 1u);
         }
@@ -749,6 +760,11 @@ __global__ __launch_bounds__(256) void k_tile_post(uint32_t ntiles, uint32_t *__
     __shared__ uint32_t col_before[TO_MAX_COLS], col_total[TO_MAX_COLS];
     const uint32_t ncols = 64u * ngroups;
     const uint32_t nblk = gridDim.x, blk = blockIdx.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    // Duplicate-capacity overflow (FgsDims.dup_capacity below what the scene needs; the flag was written by the kernel that
+    // totalled the duplicates, before this launch on both binning paths): the lists do not fit, so NONE exists -- every length
+    // is taken as 0 here and in k_tile_pre, which leaves every range [0, 0), no depth-segment unit and an arbitrary launch
+    // order.  This is the funnel every consumer goes through: no composite / splat kernel walks a list entry of such a call.
+    const bool ovf = counters[1] != 0u;
     // (1) sums of the blocks before this one (and of all blocks)
     {
         unsigned long long before = 0, all = 0;
@@ -843,7 +859,7 @@ __global__ __launch_bounds__(256) void k_tile_post(uint32_t ntiles, uint32_t *__
     unsigned long long v = 0;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        len[k] = (t0 + k < ntiles) ? tile_len(lens, ranges, t0 + k) : 0u;
+        len[k] = (t0 + k < ntiles && !ovf) ? tile_len(lens, ranges, t0 + k) : 0u;
         v += ((unsigned long long)len[k] << 32) | ((len[k] + seg_len - 1) / seg_len);
     }
     unsigned long long x = v;
@@ -862,7 +878,7 @@ __global__ __launch_bounds__(256) void k_tile_post(uint32_t ntiles, uint32_t *__
         const uint32_t t = t0 + k;
         if (t >= ntiles) break;
         const uint32_t n = (len[k] + seg_len - 1) / seg_len, off = (uint32_t)off64, lstart = (uint32_t)(off64 >> 32);
-        if (lens) { ranges[2 * t] = lstart; ranges[2 * t + 1] = lstart + len[k]; }
+        if (lens || ovf) { ranges[2 * t] = lstart; ranges[2 * t + 1] = lstart + len[k]; }  // (radix path: known already, unless emptied)
         if (seg_off) {
             seg_off[t] = off;
             for (uint32_t u = 0; u < n; ++u) seg_tile[off + u] = t;
@@ -888,7 +904,7 @@ static int launch_tile_tables(uint32_t ntiles, uint32_t *ranges, const uint32_t 
     uint32_t *bhist = scratch_words + 2 * (size_t)nblk;  // [nblk][64 * ngroups]
     // (k_tile_post walking all lengths itself instead of this launch: 21.6 us against 4.8 + 9.2 at config 3 -- the
     // bucket histogram's same-address LDS atomics)
-    hipLaunchKernelGGL(k_tile_pre, dim3(nblk), dim3(256), 0, st, ntiles, ranges, lens, seg_len, pre64, bhist, ngroups);
+    hipLaunchKernelGGL(k_tile_pre, dim3(nblk), dim3(256), 0, st, ntiles, ranges, lens, seg_len, pre64, bhist, ngroups, counters);
     FGS_LAUNCH_CHECK("k_tile_pre");
     hipLaunchKernelGGL(k_tile_post, dim3(nblk), dim3(256), 0, st, ntiles, ranges, lens, tile_order, seg_off, seg_tile,
                        counters, seg_len, fwd_variant, pre64, bhist, ngroups);
@@ -1028,17 +1044,17 @@ int fgs_launch_binning(const FgsPlan &p, char *saved, char *scratch, hipStream_t
         fgs_stage_begin(ST_TILE_SORT, st);
 #define FGS_MASK_EMIT(W) hipLaunchKernelGGL(k_mask_emit<W>, dim3(nrb + ntb), dim3(256), 0, st, B, N, layers, plane_start, \
                                             (uint32_t)p.tiles, tiles_x, lines, w64p, nrb, bpi, dcap, masks, order,         \
-                                            tile_count, ranges, bsum, dup_ids, dup_off)
+                                            tile_count, ranges, bsum, dup_ids, dup_off, counters)
 #define FGS_MASK_EMIT_BLOCK(W) hipLaunchKernelGGL(k_mask_emit_block<W>, dim3(nrb + ntiles_all), dim3(256), 0, st, B, N, layers, \
                                                   plane_start, (uint32_t)p.tiles, tiles_x, lines, w64p, nrb, bpi, dcap, masks, \
-                                                  order, tile_count, ranges, bsum, dup_ids, dup_off)
+                                                  order, tile_count, ranges, bsum, dup_ids, dup_off, counters)
         // few lists (<= 8192: the blend path's frames; the ASM renderer's (image, plane, tile) lists are many and short)
         // over more than 128 rank words (N > 8192 per image): a block per list, a quarter of the rank words per wave.
         // Measured: config 3 (4096 lists of ~1000 entries) 40 -> 28 us, decoder-like (~2500 entries) 119 -> 38 us;
         // config 2 (N = 8192, ~130 entries per list) 13 -> 17 us, so it keeps the wave-per-list kernel.
         if (grouped) {
             hipLaunchKernelGGL(k_mask_emit_group, dim3(nrb + ngb), dim3(256), 0, st, B, N, layers, plane_start, (uint32_t)p.tiles,
-                               tiles_x, lines, w64p, nrb, bpi, dcap, masks, order, tile_count, ranges, bsum, dup_ids, dup_off);
+                               tiles_x, lines, w64p, nrb, bpi, dcap, masks, order, tile_count, ranges, bsum, dup_ids, dup_off, counters);
         } else if (ntiles_all <= FGS_EMIT_BLOCK_MAX_LISTS && wpl >= 4) {
             if (wpl == 4) FGS_MASK_EMIT_BLOCK(1); else FGS_MASK_EMIT_BLOCK(2);
         } else if (wpl == 1) FGS_MASK_EMIT(1); else if (wpl == 2) FGS_MASK_EMIT(2); else if (wpl == 4) FGS_MASK_EMIT(4); else FGS_MASK_EMIT(8);

@@ -70,8 +70,13 @@ int fgs_make_plan(const FgsDims *d, FgsPlan *p, int layers, bool segment_ckpt) {
     int spany = (int)((2.0 * (double)d->max_radius + 1.0) / FGS_TILE) + 2;
     if (spany > ty) spany = ty;
     p->tiles_per_gauss = span * spany;
-    const size_t dcap = B * N * (size_t)p->tiles_per_gauss;
-    if (dcap >= (1ull << 32) - 256) { fgs_set_error("duplicate capacity exceeds 2^32"); return FGS_EINVAL; }
+    const size_t worst = B * N * (size_t)p->tiles_per_gauss;
+    if (worst >= (1ull << 32) - 256) { fgs_set_error("duplicate capacity exceeds 2^32"); return FGS_EINVAL; }
+    // FgsDims.dup_capacity: the caller's statement of how many duplicates the scene has.  Every list-dependent section and
+    // launch grid below is sized by `dcap`; nothing that picks a work split looks at it (a hinted call that fits is the
+    // unhinted call bit for bit), and a scene that needs more overflows in a defined way (include/fgs.h, buffer contract).
+    p->capacity_hinted = d->dup_capacity != 0 && (size_t)d->dup_capacity < worst;
+    const size_t dcap = p->capacity_hinted ? (size_t)d->dup_capacity : worst;
     uint32_t bits = 0;
     while ((1ull << bits) < B * (size_t)layers * p->tiles) ++bits;
     p->tile_key_bits = bits;

@@ -32,6 +32,8 @@ struct FgsPlan {
     int32_t tile_w;           // tile width in pixels: 16, or 32 on the blend path (FgsDims.tile_w / automatic)
     int32_t tiles;            // tiles per image
     int32_t tiles_per_gauss;  // worst-case tiles touched by one Gaussian
+    bool capacity_hinted;     // FgsDims.dup_capacity is below the worst case: L.dup_capacity is the hint and the call may overflow
+                              // (the entry points then enqueue the flag-checking fill kernels, fgs_api.hip)
     uint32_t tile_key_bits;   // bits of (image*T + tile)
     // resolved tuning (FgsDims.seg_len / fwd_variant / bin_mode with FGS_TUNE_AUTO replaced by the choice)
     int32_t fwd_parts;        // list parts of the depth-split forward; 0 = the row-split forward (k_composite_fwd)

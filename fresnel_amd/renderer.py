@@ -15,6 +15,7 @@ libfgs_hip.so through the C ABI of include/fgs.h.  There is NO CPU fallback: cal
 renderer without CUDA tensors or without the built library raises.
 """
 import ctypes
+import math
 from typing import Optional, Sequence, Tuple, Union
 
 import torch
@@ -176,7 +177,9 @@ class _Cfg:
     """Static (non-tensor) configuration of one renderer call."""
 
     def __init__(self, width, height, background, max_radius, use_phase, phase_amplitude, saturation_skip=False,
-                 tuning=None, pair_counter=None):
+                 tuning=None, pair_counter=None, dup_capacity=0, workspace=None):
+        self.dup_capacity = int(dup_capacity)  # FgsDims.dup_capacity of a fixed-capacity call (0 = worst case)
+        self.workspace = workspace             # the renderer's _Workspace (policy + per-shape record), or None
         self.pair_counter = pair_counter  # optional device int64[1 | 3]: [0] += composited Gaussian-pixels, [1] += tile duplicates, [2] += Gaussians of every forward
         self.saturation_skip = bool(saturation_skip)
         self.tuning = dict(tuning) if tuning else None  # FgsDims.seg_len / fwd_variant / bin_mode overrides
@@ -192,19 +195,140 @@ class _Cfg:
 _DIMS_CACHE: dict = {}
 
 
-def _dims_for(Bn, N, cfg, use_phase, num_cameras):
+def _shape_key(Bn, N, cfg, use_phase, num_cameras):
+    """Everything but the duplicate capacity that FgsDims is made of: one CapacityTracker per such key."""
     tuning = getattr(cfg, "tuning", None)
-    key = (Bn, N, cfg.width, cfg.height, cfg.max_radius, cfg.background, use_phase, cfg.phase_amplitude, num_cameras,
-           getattr(cfg, "saturation_skip", False), tuple(sorted(tuning.items())) if tuning else None)
+    return (Bn, N, cfg.width, cfg.height, cfg.max_radius, cfg.background, use_phase, cfg.phase_amplitude, num_cameras,
+            getattr(cfg, "saturation_skip", False), tuple(sorted(tuning.items())) if tuning else None)
+
+
+def _dims_for(Bn, N, cfg, use_phase, num_cameras, dup_capacity=0):
+    """-> (FgsDims, saved bytes, scratch bytes, byte offset of saved.counters) for the call shape and capacity."""
+    tuning = getattr(cfg, "tuning", None)
+    key = _shape_key(Bn, N, cfg, use_phase, num_cameras) + (int(dup_capacity),)
     hit = _DIMS_CACHE.get(key)
     if hit is None:
         dims = B.make_dims(Bn, N, cfg.width, cfg.height, cfg.max_radius, cfg.background, use_phase=use_phase,
                            phase_amplitude=cfg.phase_amplitude, num_cameras=num_cameras,
-                           saturation_skip=getattr(cfg, "saturation_skip", False), tuning=tuning)
+                           saturation_skip=getattr(cfg, "saturation_skip", False), tuning=tuning, dup_capacity=dup_capacity)
         if len(_DIMS_CACHE) > 256:
             _DIMS_CACHE.clear()
-        hit = _DIMS_CACHE[key] = (dims,) + tuple(B.workspace_bytes(dims))
+        hit = _DIMS_CACHE[key] = (dims,) + tuple(B.workspace_bytes(dims)) + (int(B.saved_layout(dims).counters),)
     return hit
+
+
+# ---- right-sized workspaces (FgsDims.dup_capacity) ------------------------------------------------------------------------------
+def quantise_capacity(x: int) -> int:
+    """The smallest value >= x with at most four significant bits: steps of at most 12.5 %, so a demand that wanders a
+    little settles on ONE capacity (one FgsDims, one block size for torch's caching allocator)."""
+    x = int(x)
+    if x <= 16:
+        return max(x, 1)
+    step = 1 << (x.bit_length() - 4)
+    return (x + step - 1) // step * step
+
+
+class CapacityTracker:
+    """Host-only policy of the adaptive workspace mode, one per call shape: turns the duplicate demands that completed
+    forwards reported (saved.counters[3]) into the capacity hint of the next forward.
+
+        capacity = quantise_capacity(ceil(margin x max(demand of the last `window` observations))),  0 (= worst case) before
+        the first observation and whenever that reaches the worst case.
+
+    `margin` and `window` are policy defaults, not measured quantities.  An overflowed call reports its demand like any
+    other, so the call after its readback has room."""
+    margin = 1.25
+    window = 8
+
+    def __init__(self, worst_case: int, margin: Optional[float] = None, window: Optional[int] = None):
+        self.worst_case = int(worst_case)
+        if margin is not None:
+            self.margin = float(margin)
+        if window is not None:
+            self.window = int(window)
+        if not self.margin >= 1.0 or self.window < 1:
+            raise ValueError("CapacityTracker: margin >= 1 and window >= 1")
+        self.demands: list = []   # the last `window` demands, oldest first
+        self.last_demand = None   # of the last completed observation
+        self.overflows = 0        # observations whose call had overflowed
+
+    def observe(self, demand: int, overflowed: bool = False):
+        self.demands.append(int(demand))
+        del self.demands[:-self.window]
+        self.last_demand = int(demand)
+        self.overflows += 1 if overflowed else 0
+
+    def capacity(self) -> int:
+        """FgsDims.dup_capacity for the next call (0 = worst case)."""
+        if not self.demands:
+            return 0
+        peak = max(self.demands)
+        want = quantise_capacity(max(math.ceil(self.margin * peak), peak, 1))
+        return 0 if want >= self.worst_case else want
+
+
+class _ShapeState:
+    """Tracker + the asynchronous readback of one call shape: a small ring of pinned host slots, each with an event."""
+    SLOTS = 4
+
+    def __init__(self, worst_case):
+        self.tracker = CapacityTracker(worst_case)
+        self.slots = []      # [pinned int32[4], event, busy]
+        self.pending = []    # busy slots, oldest first
+        self.capacity = 0    # of the last call
+        self.bytes = 0       # saved + scratch of the last call
+
+    def poll(self):
+        """Fold in the readbacks that have completed; never waits."""
+        while self.pending and self.pending[0][1].query():
+            slot = self.pending.pop(0)
+            c = slot[0].tolist()
+            self.tracker.observe(c[3] & 0xFFFFFFFF, overflowed=c[1] != 0)
+            slot[2] = False
+
+    def read_back(self, counters):
+        """Enqueue the copy of saved.counters[0:4] to a free pinned slot (none free: this call goes unobserved)."""
+        slot = next((s for s in self.slots if not s[2]), None)
+        if slot is None:
+            if len(self.slots) >= self.SLOTS:
+                return
+            slot = [torch.empty(4, dtype=torch.int32, pin_memory=True), torch.cuda.Event(), False]
+            self.slots.append(slot)
+        slot[0].copy_(counters, non_blocking=True)
+        slot[1].record()
+        slot[2] = True
+        self.pending.append(slot)
+
+
+class _Workspace:
+    """Workspace policy of one renderer and what workspace_stats() reports: per call shape, the capacity and the bytes of the last
+    call.  mode "adaptive" also learns the capacity from the previous forwards of the shape without a host synchronisation (its
+    first call runs at the worst case); "worst" and "fixed" only keep the record."""
+
+    def __init__(self, mode="worst", fixed=0):
+        self.mode, self.fixed = mode, int(fixed)
+        self.shapes: dict = {}
+
+    def state(self, key, worst_case_of):
+        st = self.shapes.get(key)
+        if st is None:
+            st = self.shapes[key] = _ShapeState(worst_case_of())
+        return st
+
+    def stats(self) -> dict:
+        return {k: dict(last_demand=st.tracker.last_demand, capacity=st.capacity, bytes=st.bytes,
+                        overflows=st.tracker.overflows) for k, st in self.shapes.items()}
+
+
+def parse_workspace(workspace):
+    """TileBasedRenderer's `workspace` argument -> ("worst" | "adaptive" | "fixed", fixed capacity)."""
+    if isinstance(workspace, str):
+        if workspace in ("worst", "adaptive"):
+            return workspace, 0
+        raise ValueError(f"workspace must be 'worst', 'adaptive' or a positive duplicate capacity, got {workspace!r}")
+    if isinstance(workspace, bool) or not isinstance(workspace, int) or not 1 <= workspace <= 0xFFFFFFFF:
+        raise ValueError(f"workspace must be 'worst', 'adaptive' or a positive duplicate capacity, got {workspace!r}")
+    return "fixed", int(workspace)
 
 
 # `scratch` lives only for the duration of one fgs_forward / fgs_backward call, and calls on one stream run in order: ONE
@@ -213,7 +337,10 @@ def _dims_for(Bn, N, cfg, use_phase, num_cameras):
 _SCRATCH: dict = {}
 
 
-def _scratch_for(dev, nbytes):
+def _scratch_for(dev, nbytes, shrink=False):
+    # `shrink` (calls of a renderer whose workspace is not "worst"): a cached buffer more than twice the request is replaced --
+    # the first, worst-case call of an adaptive renderer would otherwise keep a worst-case scratch for the life of the process.
+    # Default renderers keep the grow-only buffer.
     # under stream capture (torch.cuda.graph) the buffer must come from the graph's own memory pool and belong to that graph alone:
     # a cached buffer would be baked into the graph AND handed to later eager calls on a stream with the same handle
     if torch.cuda.is_current_stream_capturing():
@@ -221,13 +348,14 @@ def _scratch_for(dev, nbytes):
     key = (dev.index, _raw_stream(dev.index if dev.index is not None else torch.cuda.current_device()) if _raw_stream is not None
            else torch.cuda.current_stream(dev).cuda_stream)
     buf = _SCRATCH.get(key)
-    if buf is None or buf.numel() < nbytes:
+    if buf is None or buf.numel() < nbytes or (shrink and buf.numel() > 2 * nbytes):
         buf = _SCRATCH[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     return buf
 
 
 def release_scratch():
-    """Drop the cached scratch buffers (their memory goes back to torch's caching allocator)."""
+    """Drop the cached scratch buffers (their memory goes back to torch's caching allocator; torch.cuda.empty_cache() then
+    returns it to the device).  Safe at any time: the next call allocates again."""
     _SCRATCH.clear()
 
 
@@ -249,15 +377,33 @@ def forward_raw(positions, scales, rotations, colors, opacities, phases, cam_ten
     pos, scl, rot, col, opa = _f32c(positions), _f32c(scales), _f32c(rotations), _f32c(colors), _f32c(opacities)
     ph = _f32c(phases) if (cfg.use_phase and phases is not None) else None
     cam_tensor = _f32c(cam_tensor)
-    dims, saved_bytes, scratch_bytes = _dims_for(Bn, N, cfg, ph is not None, cam_tensor.shape[0])
+    ws = getattr(cfg, "workspace", None)
+    capacity = getattr(cfg, "dup_capacity", 0)
+    state, adaptive = None, False
+    if ws is not None:
+        args = (Bn, N, cfg, ph is not None, cam_tensor.shape[0])
+        state = ws.state(_shape_key(*args), lambda: int(B.saved_layout(_dims_for(*args)[0]).dup_capacity))
+        capacity = ws.fixed
+        # (under stream capture: no polling and no readback -- the captured graph freezes the capacity in hand)
+        adaptive = ws.mode == "adaptive" and not torch.cuda.is_current_stream_capturing()
+        if ws.mode == "adaptive":
+            if adaptive:
+                state.poll()
+            capacity = state.tracker.capacity()
+    dims, saved_bytes, scratch_bytes, counters_off = _dims_for(Bn, N, cfg, ph is not None, cam_tensor.shape[0], capacity)
+    shrink = ws is not None and ws.mode != "worst"  # (the functional entry with a fixed dup_capacity keeps the grow-only cache)
     with _on_device(dev):
         saved = torch.empty(saved_bytes, dtype=torch.uint8, device=dev)
-        scratch = _scratch_for(dev, scratch_bytes)
+        scratch = _scratch_for(dev, scratch_bytes, shrink)
         out_rgb = torch.empty((Bn, 3, cfg.height, cfg.width), dtype=torch.float32, device=dev)
         out_depth = torch.empty((Bn, cfg.height, cfg.width), dtype=torch.float32, device=dev)
         B.check(lib.fgs_forward(ctypes.byref(dims), _ptr(cam_tensor), _ptr(pos), _ptr(scl), _ptr(rot),
                                 _ptr(col), _ptr(opa), _ptr(ph), _ptr(out_rgb), _ptr(out_depth),
                                 _ptr(saved), _ptr(scratch), _stream_handle()), "fgs_forward")
+        if state is not None:
+            state.capacity, state.bytes = capacity, saved_bytes + scratch_bytes
+            if adaptive:
+                state.read_back(saved[counters_off:counters_off + 16].view(torch.int32))
     return out_rgb, out_depth, saved, dims, (pos, scl, rot, col, opa, ph)
 
 
@@ -283,7 +429,9 @@ class GaussianRenderer(torch.autograd.Function):
                 cfg.pair_counter[1:2] += saved[L.counters:L.counters + 4].view(torch.int32).to(torch.int64)
                 cfg.pair_counter[2:3] += int(dims.batch) * int(dims.num_gaussians)
         ctx.dims = dims
-        ctx.scratch_bytes = _dims_for(pos.shape[0], pos.shape[1], cfg, ph is not None, cam_tensor.shape[0])[2]
+        ctx.scratch_bytes = _dims_for(pos.shape[0], pos.shape[1], cfg, ph is not None, cam_tensor.shape[0], dims.dup_capacity)[2]
+        ws = getattr(cfg, "workspace", None)
+        ctx.shrink_scratch = ws is not None and ws.mode != "worst"
         ctx.has_phase = ph is not None
         ctx.save_for_backward(pos, scl, rot, col, opa, ph if ph is not None else pos.new_empty(0),
                               cam_tensor, saved)
@@ -300,7 +448,7 @@ class GaussianRenderer(torch.autograd.Function):
         g_depth = (g_depth if g_depth is not None else torch.zeros(dims.batch, dims.height, dims.width, device=dev))
         g_rgb, g_depth = _f32c(g_rgb), _f32c(g_depth)
         with _on_device(dev):
-            scratch = _scratch_for(dev, ctx.scratch_bytes)
+            scratch = _scratch_for(dev, ctx.scratch_bytes, ctx.shrink_scratch)
             g_pos, g_scl, g_rot = torch.empty_like(pos), torch.empty_like(scl), torch.empty_like(rot)
             g_col, g_opa = torch.empty_like(col), torch.empty_like(opa)
             g_ph = torch.empty_like(ph) if ph is not None else None
@@ -313,15 +461,20 @@ class GaussianRenderer(torch.autograd.Function):
 
 def render_batch(positions, scales, rotations, colors, opacities, cameras, width, height,
                  background=(0.0, 0.0, 0.0), max_radius=64, phases=None, use_phase_blending=False,
-                 phase_amplitude=0.25, cam_tensor=None, saturation_skip=False, tuning=None, pair_counter=None):
+                 phase_amplitude=0.25, cam_tensor=None, saturation_skip=False, tuning=None, pair_counter=None,
+                 dup_capacity=0, workspace=None):
     """Functional batched entry point: tensors are (B,N,.); cameras is one Camera (shared by
     the batch, as in the reference's training loop TGD:1209-1223) or a list of B Cameras.
     `saturation_skip` (off by default = the reference's behaviour, every list entry composited): stop
-    compositing 8x8 sub-tiles whose accumulated alpha has reached 1.0f (FgsDims.saturation_skip)."""
+    compositing 8x8 sub-tiles whose accumulated alpha has reached 1.0f (FgsDims.saturation_skip).
+    `dup_capacity` (0 = worst case): size the workspaces for that many (tile, Gaussian) duplicates (FgsDims.dup_capacity); a
+    call that needs more returns NaN images and zero gradients.  `workspace`: a renderer's policy object instead."""
+    if workspace is not None and dup_capacity:
+        raise ValueError("render_batch: give a fixed dup_capacity or an adaptive workspace, not both")
     if cam_tensor is None:
         cam_tensor = pack_cameras(cameras, positions.device)
     cfg = _Cfg(width, height, background, max_radius, use_phase_blending and phases is not None,
-               phase_amplitude, saturation_skip, tuning, pair_counter)
+               phase_amplitude, saturation_skip, tuning, pair_counter, dup_capacity, workspace)
     return GaussianRenderer.apply(positions, scales, rotations, colors, opacities, phases, cam_tensor, cfg)
 
 
@@ -338,8 +491,14 @@ class TileBasedRenderer(nn.Module):
     def __init__(self, image_width: int, image_height: int,
                  background: Tuple[float, float, float] = (0.0, 0.0, 0.0), max_radius: int = 64,
                  use_phase_blending: bool = False, phase_amplitude: float = 0.25,
-                 saturation_skip: bool = False):
+                 saturation_skip: bool = False, workspace: Union[str, int] = "worst"):
         super().__init__()
+        # workspace: "worst" (default: room for every Gaussian touching every tile its radius cap allows), "adaptive" (per call
+        # shape, the capacity the previous forwards needed x a margin, learnt without a host synchronisation; a scene that
+        # outgrows it gives ONE call of NaN images and zero gradients -- which a training step skips -- and the next has room)
+        # or an int (fixed FgsDims.dup_capacity)
+        self.workspace_mode, self.dup_capacity = parse_workspace(workspace)
+        self._workspace = _Workspace(self.workspace_mode, self.dup_capacity)
         self.saturation_skip = saturation_skip  # extension, off by default (see render_batch)
         self.tuning = None  # optional FgsDims work-split overrides (tests / A-B runs); never changes results
         self.pair_counter = None  # set to a device int64[1 | 3] tensor to accumulate composited Gaussian-pixels [, tile duplicates, Gaussians] (metrics)
@@ -377,12 +536,18 @@ class TileBasedRenderer(nn.Module):
         img, depth = render_batch(positions, scales, rotations, colors, opacities, camera, self.width,
                                   self.height, bg, self.max_radius, phases if use_phase else None,
                                   use_phase, self.phase_amplitude, saturation_skip=self.saturation_skip,
-                                  tuning=self.tuning, pair_counter=self.pair_counter)
+                                  tuning=self.tuning, pair_counter=self.pair_counter, workspace=self._workspace)
         if not batched:
             img, depth = img[0], depth[0]
         if return_depth:
             return img, depth
         return img
+
+    def workspace_stats(self) -> dict:
+        """Per call shape: {shape key: dict(last_demand, capacity, bytes, overflows)} -- the capacity of the last call (0 = worst
+        case) and its saved + scratch bytes; with workspace="adaptive" also the demand of the last COMPLETED readback (None
+        before the first, and in the other modes) and the overflows those readbacks showed.  Host values only."""
+        return self._workspace.stats()
 
 
 def inspect_saved(saved: torch.Tensor, dims) -> dict:

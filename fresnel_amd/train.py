@@ -130,6 +130,9 @@ class TrainingConfig:  # subset of TGD:97-162 that this path uses; same names an
     hip_graph: bool = False   # replay the whole step (decoder, rasterizer, losses, backward, all-reduce, clip, AdamW) from
                               # ONE captured HIP graph: the library never allocates or synchronises and the step has no
                               # host decision left, so it is capturable; pays when the step is host-launch-bound
+    workspace: str = "worst"  # rasterizer workspaces: "worst" (sized for the radius cap) | "adaptive" (sized by the duplicates
+                              # the previous steps needed, TileBasedRenderer(workspace="adaptive"); a step whose scene outgrew
+                              # the capacity renders NaN and is dropped by the NaN/Inf skip, the next one has room)
 
 
 class SyntheticDataset:
@@ -378,7 +381,7 @@ def default_renderer_factory(cfg: TrainingConfig, device, res: Optional[int] = N
         renderer = WaveFieldRenderer(res, res).to(device)
     else:                       # TGD:1898-1906
         renderer = TileBasedRenderer(res, res, use_phase_blending=cfg.use_phase_blending,
-                                     phase_amplitude=cfg.phase_amplitude).to(device)
+                                     phase_amplitude=cfg.phase_amplitude, workspace=cfg.workspace).to(device)
         if cfg.use_fresnel_zones:
             # the decoder snaps depths to `num_fresnel_zones` values (GDM:834-841): the zone-key depth sort then needs one
             # radix pass instead of four (FgsDims.sort_mode, fgs_sort.hip); a work-split choice, the order is the same
@@ -546,6 +549,22 @@ def make_dataset(cfg: TrainingConfig, log=print):
     return SyntheticDataset(n_items, cfg), n_items
 
 
+def check_workspace_options(workspace: str, hip_graph: bool):
+    """--workspace adaptive learns the duplicate capacity from step to step; a captured graph would freeze the capacity of the
+    step it was captured at (and replay no readback), so the two are refused together."""
+    if workspace not in ("worst", "adaptive"):
+        raise ValueError(f"unknown workspace {workspace!r}: one of ('worst', 'adaptive')")
+    if workspace == "adaptive" and hip_graph:
+        raise ValueError("--workspace adaptive cannot be combined with --hip_graph: a captured graph freezes the duplicate "
+                         "capacity; use --workspace worst with --hip_graph")
+
+
+def _workspace_metrics(renderer):
+    """(MB of `saved` + `scratch` of the last rasterizer call of every shape, overflows seen): host values, no synchronisation."""
+    stats = renderer.workspace_stats() if hasattr(renderer, "workspace_stats") else {}
+    return sum(v["bytes"] for v in stats.values()) / 2.0 ** 20, sum(v["overflows"] for v in stats.values())
+
+
 def _make_renderer(renderer_factory, cfg, device, train_res):
     """Factories take (cfg, device) or (cfg, device, res): chosen from the signature (a TypeError raised INSIDE a
     three-argument factory must not be mistaken for a two-argument one)."""
@@ -579,6 +598,7 @@ def run_training(cfg: TrainingConfig, dp: Optional[DPContext] = None,
         raise ValueError(f"unknown pixel_loss_backend {cfg.pixel_loss_backend!r}: one of {PIXEL_LOSS_BACKENDS}")
     if cfg.pixel_loss_backend == "hip" and device.type != "cuda":
         raise ValueError("pixel_loss_backend 'hip' needs a GPU device: the HIP pixel-loss kernels have no CPU fallback")
+    check_workspace_options(cfg.workspace, cfg.hip_graph)
     dp = dp or DPContext(device=device if device.type == "cuda" else None)
     if cfg.batch_size % dp.world != 0:  # fail fast, before any rank can stall in a collective (see DPContext.shard)
         raise ValueError(f"--batch_size {cfg.batch_size} is not a multiple of the {dp.world} ranks")
@@ -672,6 +692,7 @@ def run_training(cfg: TrainingConfig, dp: Optional[DPContext] = None,
         epoch_history.append(losses)
         steps = max(len(shards), 1)
         metrics = {"step_ms": elapsed / steps * 1e3, "skipped_batches": len(shards) - int(nb)}
+        metrics["workspace_mb"], metrics["capacity_overflows"] = _workspace_metrics(renderer)
         if pair_counter is not None:
             pairs, dups, gauss = vals[-3], vals[-2], vals[-1]
             metrics["pairs_per_s"] = pairs / max(elapsed, 1e-9)
@@ -742,6 +763,8 @@ def arg_parser() -> argparse.ArgumentParser:
     ap.add_argument("--frequency_loss_weight", type=float, default=c.frequency_loss_weight)
     ap.add_argument("--resume", default=None)
     ap.add_argument("--hip_graph", action="store_true", help="replay the whole training step from one captured HIP graph")
+    ap.add_argument("--workspace", default=c.workspace, choices=["worst", "adaptive"],
+                    help="rasterizer workspaces sized for the worst case (default) or by the duplicates the previous steps needed")
     ap.add_argument("--renderer", default="hip", choices=["hip"],
                     help="only the HIP rasterizer ships; there is no CPU fallback")
     ap.add_argument("--seed", type=int, default=0)
@@ -754,6 +777,10 @@ def arg_parser() -> argparse.ArgumentParser:
 
 def main(argv=None):
     a = arg_parser().parse_args(argv)
+    try:
+        check_workspace_options(a.workspace, a.hip_graph)
+    except ValueError as e:
+        raise SystemExit(str(e))
     if a.experiment != 2:
         raise SystemExit("only --experiment 2 (direct patch decoder) is on this repo's hot path")
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -778,7 +805,7 @@ def main(argv=None):
                          device=f"cuda:{local_rank}", seed=a.seed, hip_graph=a.hip_graph,
                          ssim_backend=a.ssim_backend, boundary_weight=a.boundary_weight,
                          use_vlm_guidance=a.use_vlm_guidance, vlm_weight=a.vlm_weight,
-                         pixel_loss_backend=a.pixel_loss_backend)
+                         pixel_loss_backend=a.pixel_loss_backend, workspace=a.workspace)
     hfts = HFTSConfig(train_resolution=a.train_resolution, progressive_schedule=a.progressive_schedule,
                       stochastic_k=a.stochastic_k, fast_mode=a.fast_mode)
     dp = DPContext(device=torch.device(cfg.device))

@@ -31,6 +31,13 @@
  *     fgs_spectral_loss_backward CONSUME `saved` (fields / spectra are overwritten by their gradients), and
  *     fgs_wave_backward takes it non-const as well: one backward per forward there.  (By their signatures fgs_count_pairs
  *     takes `saved` and fgs_helmholtz_loss_backward `residual` as const; no test looks at those two.)
+ *   - Duplicate-capacity overflow (fgs_forward with FgsDims.dup_capacity below what the scene needs: saved.counters[3] >
+ *     FgsSavedLayout.dup_capacity) is a DEFINED outcome of a successful call, not an error return -- the entry points never
+ *     synchronise, so only the device knows.  No byte outside the reported sizes is written and no index taken from an unwritten
+ *     list entry is ever dereferenced.  counters[1] = 1 and counters[3] = the demand; every (image, tile) list is empty (`ranges`
+ *     all [s, s); seg_off[B * T] = counters[2] = 0 on the blend path); every element of out_rgb and out_depth, for every image of
+ *     the call, is the quiet NaN 0x7FC00000.  fgs_backward on such a `saved` writes zero to every element of every gradient tensor
+ *     and walks no list; `saved` stays const through it.  The next call on the same stream and scratch is unaffected.
  */
 #ifndef FGS_H
 #define FGS_H
@@ -95,6 +102,13 @@ typedef struct FgsDims {
                                recounting its image (<= 65 536 Gaussians) | 4 = the same with 8-bit digits | 6 = 8-bit digits,
                                the blocks' digit counts handed off between them instead of recounted (bounded wait) | 8 = the
                                two-launch passes for any size | 10 = as automatic.  Valid values: 0 ... 11.                 */
+    uint32_t dup_capacity;  /* capacity hint: room for this many (tile, Gaussian) duplicates in the lists and in everything sized by
+                               them (dup_ids, segment tables and checkpoints, phase checkpoints, sort buffers, gradient rows).
+                               0 = the worst case B * N * (tiles a Gaussian of max_radius can touch); a value at or above the
+                               worst case is treated as 0.  Never changes a tuning choice: a call whose duplicates fit computes
+                               bit for bit what the unhinted call computes.  One that does not fit OVERFLOWS -- a defined outcome
+                               of a successful call, see the buffer contract above; saved.counters[3] then tells how much room
+                               the scene needs.  (Last field: the layout of every field before it is that of fgs-hip 0.2.) */
 } FgsDims;
 
 /* Camera record on the DEVICE: FGS_CAMERA_FLOATS floats per camera (Camera, DR:27-52):
@@ -112,10 +126,12 @@ typedef struct FgsSavedLayout {
     size_t order;      /* uint32 [B][N]: Gaussian ids in canonical depth order (DR:527)   */
     size_t dup_off;    /* uint32 [B][N]: first duplicate slot of each Gaussian (emission
                                          order = image, depth rank, tile row, tile column)   */
-    size_t counters;   /* uint32 [16]: [0] total duplicates D, [1] overflow flag, [2] depth-segment units U,
-                                       [4] seg_len and [5] fwd_variant the forward ran with; [2], [4], [5] are
-                                       written on the non-phase path only (with use_phase there are no depth
-                                       segments and the three words stay undefined), the rest is never written */
+    size_t counters;   /* uint32 [16]: [0] total duplicates D (clamped to dup_capacity), [1] overflow flag,
+                                       [2] depth-segment units U, [3] duplicates the call NEEDS (unclamped, saturating at
+                                       0xFFFFFFFF; == [0] when the call fits), [4] seg_len and [5] fwd_variant the forward
+                                       ran with; [2], [4], [5] are written on the non-phase path only (with use_phase
+                                       there are no depth segments and the three words stay undefined), [6..15] are
+                                       never written */
     size_t ranges;     /* uint32 [B*T][2]: [start,end) into dup_ids per (image,tile)      */
     size_t tile_order; /* uint32 [B*T]: (image,tile) indices, longest lists first: the launch
                                          order of the composite kernels (scheduling only)    */
@@ -125,7 +141,7 @@ typedef struct FgsSavedLayout {
     size_t phase_ckpt; /* float  [slots][8][64] (use_phase only): per-pixel (A, Phi) of a tile's four 8 x 8 sub-tiles (planes w and
                           4 + w) in front of every 8th entry THAT TOUCHES sub-tile w within a 64-entry block of the
                           tile's list; slot = start/8 + block offset/8 + group + tile                     */
-    size_t dup_capacity; /* Dcap (elements, not bytes)                                    */
+    size_t dup_capacity; /* Dcap (elements, not bytes): the worst case, or FgsDims.dup_capacity below it */
     int32_t tiles_x, tiles_y;
     /* Depth segments (non-phase path): a tile's list is cut into segments of FGS_SEG entries; each
      * segment is one work unit of the backward, so a launch is balanced however uneven the lists are. */
