@@ -18,6 +18,7 @@ EXPORTED_SYMBOLS = [
     "fgs_last_error", "fgs_version", "fgs_stage_timing_enable", "fgs_stage_timing_read",
     "fgs_asm_workspace_bytes", "fgs_asm_forward", "fgs_asm_backward",
     "fgs_wave_workspace_bytes", "fgs_wave_forward", "fgs_wave_backward",
+    "fgs_fourier_workspace_bytes", "fgs_fourier_forward", "fgs_fourier_backward",
     "fgs_gather_forward", "fgs_gather_backward",
     "fgs_asm_propagate_workspace_bytes", "fgs_asm_propagate_forward", "fgs_asm_propagate_backward",
     "fgs_spectral_workspace_bytes", "fgs_spectral_loss_forward", "fgs_spectral_loss_backward",
@@ -68,6 +69,12 @@ class FgsWaveDims(ctypes.Structure):
                 ("width", ctypes.c_int32), ("height", ctypes.c_int32),
                 ("max_radius", ctypes.c_float), ("background", ctypes.c_float * 3),
                 ("phase_channels", ctypes.c_int32), ("num_cameras", ctypes.c_int32)]
+
+
+class FgsFourierDims(ctypes.Structure):
+    _fields_ = [("batch", ctypes.c_int32), ("num_gaussians", ctypes.c_int32),
+                ("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("background", ctypes.c_float * 3), ("num_cameras", ctypes.c_int32)]
 
 
 class FgsSpectralDims(ctypes.Structure):
@@ -144,6 +151,11 @@ def load():
     lib.fgs_wave_workspace_bytes.argtypes = [cp(FgsWaveDims), cp(ctypes.c_size_t), cp(ctypes.c_size_t)]
     lib.fgs_wave_forward.argtypes = [cp(FgsWaveDims)] + [vp] * 12
     lib.fgs_wave_backward.argtypes = [cp(FgsWaveDims)] + [vp] * 18
+    lib.fgs_fourier_workspace_bytes.argtypes = [cp(FgsFourierDims), cp(ctypes.c_size_t), cp(ctypes.c_size_t)]
+    lib.fgs_fourier_forward.argtypes = [cp(FgsFourierDims)] + [vp] * 10
+    lib.fgs_fourier_backward.argtypes = [cp(FgsFourierDims)] + [vp] * 15
+    for fn in (lib.fgs_fourier_workspace_bytes, lib.fgs_fourier_forward, lib.fgs_fourier_backward):
+        fn.restype = ctypes.c_int
     i32 = ctypes.c_int32
     lib.fgs_gather_forward.argtypes = [i32, i32, i32, i32] + [vp] * 14
     lib.fgs_gather_backward.argtypes = [i32, i32, i32, i32] + [vp] * 14

@@ -50,6 +50,9 @@ SOURCES = {
     "fgs_composite.hip": ["-ffast-math", "-fno-finite-math-only"] + NO_SLP + SCHED,
     "fgs_asm.hip": SPLAT_FLAGS,
     "fgs_wavefield.hip": SPLAT_FLAGS,
+    # no FMA contraction: forward and backward recompute the per-pixel normalisation / background / clamp chain with the same
+    # roundings, so the backward's clamp masks are the forward's (the fp32 MFMAs are FMA chains whatever the flag says)
+    "fgs_fourier.hip": ["-ffp-contract=off"],
     "fgs_gather.hip": [],
     "fgs_fft.hip": NO_SLP,
     "fgs_spectral.hip": [],

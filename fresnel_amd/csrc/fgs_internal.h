@@ -40,6 +40,18 @@ int fgs_launch_asm_project_bwd(const FgsPlan &p, const float *cams, const float 
                                float *g_quat, float *g_color, float *g_opacity, float *g_phase, hipStream_t st,
                                bool wave_rows = false);
 
+// FourierGaussianRenderer (fgs_fourier.hip).  Record of one Gaussian: FGS_FOURIER_REC_FLOATS floats, all zero but the opacity
+// when it is culled.  `sums` [B*N][12]: dL/du, dL/dv, dL/d(a + d), dL/dw[3] (w = colour x opacity), six zeros.
+#define FGS_FOURIER_REC_FLOATS 8
+enum { FR_U = 0, FR_V, FR_IS /* 1 / s */, FR_WR, FR_WG, FR_WB, FR_VIS /* uint32 1 | 0 */, FR_OP };
+int fgs_launch_fourier_project(int32_t B, int32_t N, int32_t W, int32_t H, int32_t num_cameras, const float *cams,
+                               const float *pos, const float *scale, const float *quat, const float *color,
+                               const float *opacity, float *frec, hipStream_t st);
+int fgs_launch_fourier_project_bwd(int32_t B, int32_t N, int32_t num_cameras, const float *cams, const float *pos,
+                                   const float *scale, const float *quat, const float *color, const float *frec,
+                                   const float *sums, float *g_pos, float *g_scale, float *g_quat, float *g_color,
+                                   float *g_opacity, hipStream_t st);
+
 // Stable LSD radix sort of (key,val) uint32 pairs over `num_segs` independent segments.
 // Segment s covers elements [s*seg_stride, s*seg_stride + len) with len = seg_len (host) or
 // *seg_len_dev (device, single segment).  Sorts bits [0, key_bits).  The sorted result is

@@ -188,6 +188,39 @@ __global__ __launch_bounds__(256) void k_project(
     }
 }
 
+// FourierGaussianRenderer (DR:1500-1774) projection: the same project_one, so (u, v, depth) are bit for bit k_project's, then
+// the reference's own visibility test (DR:1641-1643, strict, fp32) and its isotropic footprint (DR:1667-1670, DR:1726):
+// sigma = sqrt((a + d) / 2 + 1e-8), s = 2 sigma^2 + 1e-8.  Record: u, v, 1 / s, w = colour x opacity, visibility, opacity.  A culled
+// Gaussian's record is all zeros but the opacity (its mean may be inf / NaN: nothing of it is kept), so its factor rows are zero.
+__global__ __launch_bounds__(256) void k_fourier_project(
+    int32_t N, int32_t W, int32_t H, int32_t num_cameras, const float *__restrict__ cams, const float *__restrict__ pos,
+    const float *__restrict__ scale, const float *__restrict__ quat, const float *__restrict__ color,
+    const float *__restrict__ opacity, float *__restrict__ frec) {
+    const int32_t n = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
+    if (n >= N) return;
+    const int32_t idx = b * N + n;
+    const float *__restrict__ cam = cams + (num_cameras > 1 ? b : 0) * FGS_CAMERA_FLOATS;
+    const float p[3] = {pos[3 * idx], pos[3 * idx + 1], pos[3 * idx + 2]};
+    const float s[3] = {scale[3 * idx], scale[3 * idx + 1], scale[3 * idx + 2]};
+    const float4 q4 = reinterpret_cast<const float4 *>(quat)[idx];
+    const float q[4] = {q4.x, q4.y, q4.z, q4.w};
+    Proj o;
+    project_one(cam, cam[16], cam[17], cam[18], cam[19], p, s, q, o);
+    const bool vis = (o.dep > cam[20]) && (o.dep < cam[21]) && (o.u > -(float)W) && (o.u < (float)(2 * W)) &&
+                     (o.v > -(float)H) && (o.v < (float)(2 * H));
+    const float op = opacity[idx];
+    float4 r0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), r1 = make_float4(0.0f, 0.0f, 0.0f, op);
+    if (vis) {
+        const float sigma = __fsqrt_rn(__fdiv_rn(o.a + o.d, 2.0f) + 1e-8f);
+        const float den = 2.0f * (sigma * sigma) + 1e-8f;
+        r0 = make_float4(o.u, o.v, __fdiv_rn(1.0f, den), color[3 * idx] * op);
+        r1 = make_float4(color[3 * idx + 1] * op, color[3 * idx + 2] * op, __uint_as_float(1u), op);
+    }
+    float4 *out = reinterpret_cast<float4 *>(frec + (size_t)idx * FGS_FOURIER_REC_FLOATS);
+    out[0] = r0;
+    out[1] = r1;
+}
+
 // Gradient-row reduction + projection backward (autograd of DR:98-195 + DR:578-579).
 // Blend path, first half of the projection backward: sum every Gaussian's contiguous 40-byte gradient rows (moments
 // of dL/dG about the mean, colour and depth sums; k_composite_bwd) in a fixed order -- FOUR lanes per Gaussian in
@@ -283,6 +316,10 @@ __global__ __launch_bounds__(256) void k_row_sum(int32_t total, int32_t N, uint3
 //   contract between the two translation units.  Colour and phase gradients are formed here and no gradient flows through
 //   depth (the depth only selects the plane, DR:1147-1148).
 // MODE 2 (WaveFieldRenderer): ASM rows widened to 16 floats, slot 12 = dL/ddepth (amplitude-weighted depth map)
+// MODE 3 (FourierGaussianRenderer, PRESUM only): `grad_rows` holds per Gaussian (dL/du, dL/dv, t = dL/d(a + d), dL/dw[3]) with
+//   w = colour x opacity (k_fourier_bwd, fgs_fourier.hip) and `rec` the 8-float Fourier records.  The footprint depends on the
+//   covariance through its trace alone, so the covariance adjoint is dSigma2 = diag(t, t) as it stands: no chain through the
+//   regularised inverse.  No gradient flows through depth.
 // PRESUM: the rows were already summed by k_row_sum (blend path): ONE thread per Gaussian reads its ten totals from
 // `grad_rows` (= the per-Gaussian sums, [input index][12] floats) -- all 64 lanes of a wave run the double-precision adjoint
 // instead of every fourth, and the streaming part no longer runs at this kernel's 3 waves per SIMD (160 VGPRs).
@@ -308,7 +345,7 @@ __global__ __launch_bounds__(256) void k_project_bwd(
     // the adjoint take 29 us at config 3
     const int32_t idx = live ? (PRESUM ? ri : b * N + (int32_t)order[ri]) : 0;
     float gp[3] = {0, 0, 0}, gs[3] = {0, 0, 0}, gq[4] = {0, 0, 0, 0};
-    constexpr bool ASM = MODE != 0;
+    constexpr bool ASM = MODE == 1 || MODE == 2;
     constexpr int ROWF = MODE == 2 ? 16 : FGS_GROW_FLOATS;
     float acc[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     if constexpr (PRESUM) {
@@ -387,6 +424,13 @@ __global__ __launch_bounds__(256) void k_project_bwd(
     const float kcon = ASM ? -0.5f * op_asm : 1.0f;
     const float g_conic[3] = {kcon * s0.z, kcon * s0.w, kcon * s1.x};
     float g_depth = s2.y;
+    if constexpr (MODE == 3) {
+        g_depth = 0.0f;
+        const float op = rec[(size_t)idx * FGS_FOURIER_REC_FLOATS + FR_OP];
+        const float dw[3] = {s0.w, s1.x, s1.y};
+        g_opacity[idx] = (dw[0] * color[3 * idx] + dw[1] * color[3 * idx + 1]) + dw[2] * color[3 * idx + 2];
+        g_color[3 * idx] = dw[0] * op; g_color[3 * idx + 1] = dw[1] * op; g_color[3 * idx + 2] = dw[2] * op;
+    } else {
     g_opacity[idx] = s1.y;
     if (!ASM) {
         if (g_phase) g_phase[idx] = s2.z;
@@ -407,7 +451,10 @@ __global__ __launch_bounds__(256) void k_project_bwd(
         }
         if (phase_channels != 3) g_phase[idx] = gph;
     }
-    if (depth_key[idx] != 0xFFFFFFFFu) {
+    }
+    const bool visible = MODE == 3 ? __float_as_uint(rec[(size_t)idx * FGS_FOURIER_REC_FLOATS + FR_VIS]) != 0u
+                                   : depth_key[idx] != 0xFFFFFFFFu;
+    if (visible) {
         // Projection adjoint in DOUBLE precision, recomputing the projection from the fp32 inputs.  The kernel is
         // bound by the gradient-row reads, so this costs nothing measurable, and it keeps the chain through the
         // regularised 2x2 covariance inverse accurate for needle / disc Gaussians (scale ratios of 100:1 and
@@ -464,6 +511,9 @@ __global__ __launch_bounds__(256) void k_project_bwd(
         const double Y[2][2] = {{dr * rdet, -cb * rdet}, {-cc * rdet, ar * rdet}};
         const double GY[2][2] = {{g_conic[0], g_conic[1]}, {g_conic[1], g_conic[2]}};
         double tmp[2][2], G2[2][2];
+        if constexpr (MODE == 3) {
+            G2[0][0] = G2[1][1] = (double)s0.z; G2[0][1] = G2[1][0] = 0.0;  // the covariance adjoint itself
+        } else {
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -472,6 +522,7 @@ __global__ __launch_bounds__(256) void k_project_bwd(
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int j = 0; j < 2; ++j) G2[i][j] = -(tmp[i][0] * Y[j][0] + tmp[i][1] * Y[j][1]);
+        }
         // dL/dSigma = J^T G2 J
         double GS[3][3];
 #pragma unroll
@@ -640,5 +691,26 @@ int fgs_launch_asm_project_bwd(const FgsPlan &p, const float *cams, const float 
                        g_quat, g_color, g_opacity, g_phase, color, phase, phase_channels, 1u,
                        reinterpret_cast<const float *>(saved + p.L.rec));
     FGS_LAUNCH_CHECK("k_asm_project_bwd");
+    return FGS_OK;
+}
+
+int fgs_launch_fourier_project(int32_t B, int32_t N, int32_t W, int32_t H, int32_t num_cameras, const float *cams,
+                               const float *pos, const float *scale, const float *quat, const float *color,
+                               const float *opacity, float *frec, hipStream_t st) {
+    hipLaunchKernelGGL(k_fourier_project, dim3((unsigned)((N + 255) / 256), (unsigned)B), dim3(256), 0, st, N, W, H,
+                       num_cameras, cams, pos, scale, quat, color, opacity, frec);
+    FGS_LAUNCH_CHECK("k_fourier_project");
+    return FGS_OK;
+}
+
+int fgs_launch_fourier_project_bwd(int32_t B, int32_t N, int32_t num_cameras, const float *cams, const float *pos,
+                                   const float *scale, const float *quat, const float *color, const float *frec,
+                                   const float *sums, float *g_pos, float *g_scale, float *g_quat, float *g_color,
+                                   float *g_opacity, hipStream_t st) {
+    const int32_t total = B * N;
+    hipLaunchKernelGGL((k_project_bwd<3, true>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, total, N,
+                       num_cameras, 0u, cams, pos, scale, quat, nullptr, nullptr, nullptr, nullptr, sums, g_pos, g_scale,
+                       g_quat, g_color, g_opacity, nullptr, color, nullptr, 0, 1u, frec);
+    FGS_LAUNCH_CHECK("k_fourier_project_bwd");
     return FGS_OK;
 }

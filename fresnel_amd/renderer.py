@@ -905,3 +905,103 @@ class WaveFieldRenderer(_HostBackground, nn.Module):
         if not batched:
             img, dep = img[0], dep[0]
         return (img, dep) if return_depth else img
+
+
+# ------------------------------------------------------------------------------------------------
+# FourierGaussianRenderer (DR:1500-1774; --experiment 4 --use_phase_blending, TGD:1877-1890)
+# ------------------------------------------------------------------------------------------------
+class FourierRenderer(torch.autograd.Function):
+    """fgs_fourier_forward / fgs_fourier_backward: batched FourierGaussianRenderer (DR:1500-1774) as a separable fp32 matrix
+    product.  `saved` goes unchanged through the backward, so a retained graph may be differentiated again."""
+
+    @staticmethod
+    def forward(ctx, positions, scales, rotations, colors, opacities, cam_tensor, cfg):
+        if not positions.is_cuda:
+            raise B.FgsError("FourierRenderer (HIP) needs CUDA/ROCm tensors; there is no CPU fallback")
+        lib = B.load()
+        Bn, N = positions.shape[0], positions.shape[1]
+        dev = positions.device
+        pos, scl, rot, col, opa = [_f32c(t) for t in (positions, scales, rotations, colors, opacities)]
+        cam_tensor = cam_tensor.contiguous().float()
+        d = B.FgsFourierDims()
+        d.batch, d.num_gaussians, d.width, d.height = Bn, N, cfg["width"], cfg["height"]
+        for i in range(3):
+            d.background[i] = float(cfg["background"][i])
+        d.num_cameras = cam_tensor.shape[0]
+        sb, cb = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        with _on_device(dev):
+            B.check(lib.fgs_fourier_workspace_bytes(ctypes.byref(d), ctypes.byref(sb), ctypes.byref(cb)),
+                    "fgs_fourier_workspace_bytes")
+            saved = torch.empty(sb.value, dtype=torch.uint8, device=dev)
+            scratch = torch.empty(cb.value, dtype=torch.uint8, device=dev)
+            out = torch.empty(Bn, 3, cfg["height"], cfg["width"], dtype=torch.float32, device=dev)
+            B.check(lib.fgs_fourier_forward(ctypes.byref(d), _ptr(cam_tensor), _ptr(pos), _ptr(scl), _ptr(rot), _ptr(col),
+                                            _ptr(opa), _ptr(out), _ptr(saved), _ptr(scratch), _stream_handle()),
+                    "fgs_fourier_forward")
+        ctx.dims, ctx.scratch_bytes = d, cb.value
+        ctx.save_for_backward(pos, scl, rot, col, opa, cam_tensor, saved)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        lib = B.load()
+        pos, scl, rot, col, opa, cam_tensor, saved = ctx.saved_tensors
+        d = ctx.dims
+        dev = pos.device
+        g_out = g_out.contiguous().float()
+        with _on_device(dev):
+            scratch = torch.empty(ctx.scratch_bytes, dtype=torch.uint8, device=dev)
+            g_pos, g_scl, g_rot = torch.empty_like(pos), torch.empty_like(scl), torch.empty_like(rot)
+            g_col, g_opa = torch.empty_like(col), torch.empty_like(opa)
+            B.check(lib.fgs_fourier_backward(ctypes.byref(d), _ptr(cam_tensor), _ptr(pos), _ptr(scl), _ptr(rot), _ptr(col),
+                                             _ptr(opa), _ptr(saved), _ptr(scratch), _ptr(g_out), _ptr(g_pos), _ptr(g_scl),
+                                             _ptr(g_rot), _ptr(g_col), _ptr(g_opa), _stream_handle()),
+                    "fgs_fourier_backward")
+        return g_pos, g_scl, g_rot, g_col, g_opa, None, None
+
+
+class FourierGaussianRenderer(_HostBackground, nn.Module):
+    """Drop-in for the reference's FourierGaussianRenderer (DR:1500-1774), HIP backed: a dense, order-independent sum of
+    isotropic Gaussians (sigma^2 = half the trace of the projected covariance), normalised by the image maximum and composed
+    with the background.  As in the reference, `phases` and the wavelengths do not reach the image (`wavelengths.grad` stays
+    None) and the depth map of `return_depth=True` is all zeros.  Batched (B,N,.) inputs render B images per call, each
+    normalised by its own maximum, with one camera or B cameras."""
+
+    def __init__(self, image_width: int, image_height: int, background=(0.0, 0.0, 0.0), wavelength_r: float = 0.0635,
+                 wavelength_g: float = 0.05, wavelength_b: float = 0.041, learnable_wavelengths: bool = True,
+                 focal_depth: float = 0.5):
+        super().__init__()
+        self.width, self.height = image_width, image_height
+        self.focal_depth = focal_depth
+        self._init_background(background)
+        wavelengths = torch.tensor([wavelength_r, wavelength_g, wavelength_b])
+        if learnable_wavelengths:
+            self.wavelengths = nn.Parameter(wavelengths)
+        else:
+            self.register_buffer("wavelengths", wavelengths)
+        self.learnable_wavelengths = learnable_wavelengths
+        self.wavelength_min, self.wavelength_max = 0.01, 0.5
+
+    def _get_constrained_wavelengths(self) -> torch.Tensor:
+        return torch.clamp(torch.abs(self.wavelengths), self.wavelength_min, self.wavelength_max)
+
+    def forward(self, positions, scales, rotations, colors, opacities, camera, return_depth: bool = False,
+                phases: Optional[torch.Tensor] = None):
+        batched = positions.dim() == 3
+        if not batched:
+            positions, scales, rotations = positions[None], scales[None], rotations[None]
+            colors, opacities = colors[None], opacities[None]
+        cfg = dict(width=self.width, height=self.height, background=self._background_host())
+        img = FourierRenderer.apply(positions, scales, rotations, colors, opacities,
+                                    pack_cameras(camera, positions.device), cfg)
+        if not batched:
+            img = img[0]
+        if return_depth:
+            shape = (img.shape[0], self.height, self.width) if batched else (self.height, self.width)
+            return img, torch.zeros(shape, device=img.device)  # DR:1758-1764: the depth map is all zeros
+        return img
+
+    def extra_repr(self) -> str:
+        lam = self._get_constrained_wavelengths()
+        return (f"size=({self.height}, {self.width}), λ_rgb=[{lam[0]:.4f}, {lam[1]:.4f}, {lam[2]:.4f}], "
+                f"learnable={self.learnable_wavelengths}")

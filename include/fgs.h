@@ -27,7 +27,8 @@
  *     steps and read with 16-byte loads) and input, output and gradient tensors at least 16 bytes.  The tests hand out
  *     512-byte aligned buffers, as torch's allocator does; no smaller alignment is exercised.
  *   - Inputs are never modified.  `saved` goes unchanged through fgs_backward and fgs_ssim_backward (so a second
- *     fgs_ssim_backward on it is valid) and `stats` through fgs_pixel_loss_backward; fgs_asm_backward and
+ *     fgs_ssim_backward on it is valid), through fgs_fourier_backward (likewise) and `stats` through
+ *     fgs_pixel_loss_backward; fgs_asm_backward and
  *     fgs_spectral_loss_backward CONSUME `saved` (fields / spectra are overwritten by their gradients), and
  *     fgs_wave_backward takes it non-const as well: one backward per forward there.  (By their signatures fgs_count_pairs
  *     takes `saved` and fgs_helmholtz_loss_backward `residual` as const; no test looks at those two.)
@@ -253,6 +254,41 @@ int fgs_wave_backward(const FgsWaveDims *dims, const float *cameras, const float
                       void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * FourierGaussianRenderer (DR:1500-1774; --experiment 4 --use_phase_blending, TGD:1877-1890): a dense, order-independent sum of
+ * ISOTROPIC Gaussians over the whole frame.  Per image, in fp32:
+ *   visible   near < depth < far, -W < u < 2W, -H < v < 2H (strict, DR:1641-1643); others contribute nothing, zero gradients
+ *   footprint sigma = sqrt((a + d) / 2 + 1e-8) of the raw 2-D covariance, s = 2 sigma^2 + 1e-8 (DR:1667-1670, DR:1726)
+ *   F_c       = sum_i colour_ic opacity_i exp(-((x - u_i)^2 + (y - v_i)^2) / s_i) on integer pixel coordinates (DR:1723-1736),
+ *               evaluated as the matrix product Gy^T diag(w_c) Gx of the separable factors on the fp32 matrix cores
+ *   m         = max over (c, y, x) of F; F /= m when m > 1e-8 (DR:1741-1743; decided on the device); the gradient flows
+ *               through m to the arg-max element (ties: the lowest flat index)
+ *   out       = clamp(F + background_c clamp(1 - sum_c F_c, 0, 1), 0, 1) (DR:1746-1751); both clamps pass the gradient on the
+ *               closed interval
+ * No visible Gaussian: out = clamp(background), every gradient zero.  Phases, wavelengths and the depth map do not enter
+ * (DR:1758-1764: the depth map is all zeros; the binding returns it).  Pointer order of fgs_wave_*, without phase and depth.
+ * `saved` layout (256-byte aligned sections, in this order; CONST through fgs_fourier_backward, which may be repeated on it):
+ *   rec   float  [B][N][8]    u, v, 1 / s, w_r, w_g, w_b (w = colour x opacity), visible (uint32 1 | 0), opacity;
+ *                             a culled Gaussian's record is all zeros but the opacity
+ *   F     float  [B][3][H][W] the un-normalised accumulation
+ *   scal         [B][2]       m (float) and its flat index in (3, H, W) (uint32)
+ * Every element of out_rgb and of the five gradient tensors is written.  The backward uses no atomics: its results are
+ * bitwise reproducible from run to run. */
+typedef struct FgsFourierDims {
+    int32_t batch, num_gaussians, width, height;
+    float background[3];
+    int32_t num_cameras;     /* 1 or B */
+} FgsFourierDims;
+
+int fgs_fourier_workspace_bytes(const FgsFourierDims *dims, size_t *saved_bytes, size_t *scratch_bytes);
+int fgs_fourier_forward(const FgsFourierDims *dims, const float *cameras, const float *pos, const float *scale,
+                        const float *quat, const float *color, const float *opacity, float *out_rgb, void *saved,
+                        void *scratch, void *stream);
+int fgs_fourier_backward(const FgsFourierDims *dims, const float *cameras, const float *pos, const float *scale,
+                         const float *quat, const float *color, const float *opacity, const void *saved, void *scratch,
+                         const float *g_rgb, float *g_pos, float *g_scale, float *g_quat, float *g_color,
+                         float *g_opacity, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Standalone angular-spectrum propagation: replaces AngularSpectrumPropagator.propagate (DR:1000-1065) and its
  * autograd.  field / out / g_* are (C, H, W) interleaved complex64 (the reference's (H, W, C) layout is permuted by
  * the binding); z = DEVICE scalar propagation distance; wavelengths = DEVICE (C,).  `spectrum` (C,H,W complex) receives
@@ -416,6 +452,8 @@ int fgs_gather_backward(int32_t batch, int32_t n_in, int32_t n_out, int32_t phas
  * the record.  Stage order: project, depth_sort, dup_emit, tile_sort, tile_ranges, composite_fwd,
  * composite_bwd, project_bwd, and for the splat renderers (ASM / wave field): splat_fwd, field_fwd (FFTs,
  * transfer function, plane sum, normalisation and output), field_bwd (their adjoints), splat_bwd.
+ * The Fourier renderer reports its projection under project, the forward product under splat_fwd, maximum and output under
+ * field_fwd, the gradient image under field_bwd, the backward product under splat_bwd and the adjoint under project_bwd.
  * enable: 0 = off, 1 = all stages, otherwise a mask with bit (stage + 1) per selected stage -- every event
  * pair costs a few microseconds of stream time, so a benchmark times only the kernel it reports.
  * (The only entry points that allocate or synchronise; never called by the product path.) */
