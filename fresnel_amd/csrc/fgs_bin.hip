@@ -982,7 +982,8 @@ int fgs_launch_binning(const FgsPlan &p, char *saved, char *scratch, hipStream_t
     } else if ((rc = fgs_launch_radix_sort(keys0, vals0, keys1, vals1, layered_direct ? nullptr : order, &ks, &vs, N, nullptr, N, N,
                                            B, 32, hist, st, depth_key, N,
                                            (layered_direct || !(p.d.sort_mode & 1)) ? nullptr : reinterpret_cast<const uint32_t *>(saved + p.s_keybits),
-                                           (N + 255u) / 256u, p.d.sort_mode >> 1))) {
+                                           (N + 255u) / 256u, p.d.sort_mode >> 1, reinterpret_cast<const uint32_t *>(saved + p.s_keybits),
+                                           reinterpret_cast<uint32_t *>(scratch + p.s_bucket)))) {
         return rc;
     }
     if (p.depth_ordered && layered_direct) {

@@ -66,10 +66,17 @@ int fgs_launch_radix_sort(uint32_t *keys_in, uint32_t *vals_in, uint32_t *keys_a
                           const uint32_t *key_stats = nullptr /* depth sort: k_project's per-block OR / AND of the visible keys:
                                                                  sort by the bits that vary, skip the passes nobody needs */,
                           uint32_t key_recs = 0 /* records per segment */,
-                          int pass_mode = 0 /* 0 = automatic (fused single-launch passes for segments of <= 4096 keys) | 1 = fused
-                                               passes, 11-bit digits, up to 64 K keys | 2 = fused passes, 8-bit digits | 3 = fused
-                                               passes, 8-bit digits, per-block histograms HANDED OFF between the blocks through `hist`
-                                               (which the caller cleared beforehand: fgs_sort.hip) */);
+                          int pass_mode = 0 /* FgsDims.sort_mode >> 1.  0 = automatic: host-known segments of <= 8192 keys by ONE launch,
+                                               all passes in LDS; larger ones with `key_range` by the bucket sort (one bucket pass
+                                               over memory, then every bucket in LDS), else by the two-launch 8-bit passes | 1 = fused
+                                               passes (one launch each), 11-bit digits, up to 64 K keys | 2 = fused passes, 8-bit
+                                               digits | 3 = fused passes, 8-bit digits, per-block histograms HANDED OFF between the
+                                               blocks through `hist` (which the caller cleared beforehand: fgs_sort.hip) | 4 = the
+                                               two-launch passes at any size | 5 = as automatic */,
+                          const uint32_t *key_range = nullptr /* depth sort: k_project's records again (smallest visible key in the
+                                                                 fourth word, the largest behind the records), `key_recs` per segment:
+                                                                 what the bucket sort takes its digit from */,
+                          uint32_t *bucket_tab = nullptr /* scratch of num_segs * FGS_SORT_BUCKET_WORDS words for the bucket sort */);
 
 int fgs_launch_binning(const FgsPlan &p, char *saved, char *scratch, hipStream_t st);
 

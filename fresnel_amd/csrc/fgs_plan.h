@@ -27,8 +27,9 @@ struct FgsPlan {
     FgsSavedLayout L;
     int32_t layers;           // independent tile grids per image (ASM depth planes; 1 for TBR)
     size_t s_layer;           // saved: uint32 [B][N] layer of each Gaussian (layers > 1 only)
-    size_t s_keybits;         // saved: uint32 [B][ceil(N / 256)][4]: per projection block, OR / AND of the visible depth keys and
-                              // the visible / culled flags (k_project -> the depth sort's choice of radix passes, fgs_sort.hip)
+    size_t s_keybits;         // saved: uint32 [B][ceil(N / 256)][4]: per projection block, OR / AND of the visible depth keys, the
+                              // visible / culled flags and the smallest visible key, then uint32 [B][ceil(N / 256)]: the largest
+                              // (k_project -> the depth sort's choice of radix passes and of its bucket digit, fgs_sort.hip)
     int32_t tile_w;           // tile width in pixels: 16, or 32 on the blend path (FgsDims.tile_w / automatic)
     int32_t tiles;            // tiles per image
     int32_t tiles_per_gauss;  // worst-case tiles touched by one Gaussian
@@ -56,6 +57,7 @@ struct FgsPlan {
     size_t s_grows;           // float [Dcap][12]: per-duplicate gradient rows (composite bwd -> reduce)
     size_t s_plane;           // uint32 [B][layers + 1]: first depth rank of every layer (layered direct binning)
     size_t s_rsum;            // float [B*N][12]: per-Gaussian totals of the blend path's rows (k_row_sum -> k_project_bwd)
+    size_t s_bucket;          // uint32 [B][FGS_SORT_BUCKET_WORDS]: the bucket depth sort's per-image table (fgs_sort.hip)
 };
 
 // `segment_ckpt`: reserve the per-segment forward checkpoints of the tile-based compositing path (the splat
@@ -68,5 +70,8 @@ void fgs_set_error(const char *fmt, ...);
 /* 64-bit rank words per mask line of the mask binning (fgs_bin.hip), padded to a multiple of 8 */
 static inline uint32_t fgs_mask_words(uint32_t n) { return (((n + 63u) / 64u) + 7u) & ~7u; }
 #define FGS_SORT_HANDOFF_PASSES 4
+/* per-image table of the bucket depth sort: 257 bucket boundaries (exclusive prefix of the 256 digit totals and their sum),
+   the image's smallest visible key, the digit's shift, one spare word */
+#define FGS_SORT_BUCKET_WORDS 260
 size_t fgs_radix_hist_bytes(uint32_t seg_capacity, uint32_t num_segs);
 uint32_t fgs_radix_blocks_per_seg(uint32_t seg_capacity, uint32_t num_segs);

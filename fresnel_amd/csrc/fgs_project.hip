@@ -166,24 +166,34 @@ __global__ __launch_bounds__(256) void k_project(
     }
     // Which bits of the depth keys VARY over an image's visible Gaussians decides how many radix passes its depth sort needs
     // (fgs_sort.hip: the keys are compressed to those bits -- zone-snapped depths, BASELINE config 4, differ in 3 bits and sort
-    // in one pass instead of four).  Per block: OR and AND of the visible keys and the visible / culled flags, three words;
+    // in one pass instead of four).  Per block: OR and AND of the visible keys, the visible / culled flags and the smallest
+    // visible key, four words, and the largest one in a table behind the records;
     // every block of the sort folds the <= N / 256 records of its image.  No atomics, no extra launch.
     {
         const bool visk = key != 0xFFFFFFFFu;
         uint32_t vor = visk ? key : 0u, vand = key;  // (a culled key is all ones: neutral for the AND)
+        // the smallest and the largest visible key as well: the bucket pass of the depth sort of large images spreads the keys
+        // between them over its 255 buckets (the OR is no usable maximum: it leaves a benchmark image in 5 buckets)
+        uint32_t vmin = key, vmax = vor;             // (a culled key is neutral for the minimum, 0 for the maximum)
 #pragma unroll
-        for (int o2 = 32; o2 > 0; o2 >>= 1) { vor |= __shfl_xor(vor, o2, 64); vand &= __shfl_xor(vand, o2, 64); }
+        for (int o2 = 32; o2 > 0; o2 >>= 1) {
+            vor |= __shfl_xor(vor, o2, 64); vand &= __shfl_xor(vand, o2, 64);
+            vmin = min(vmin, (uint32_t)__shfl_xor(vmin, o2, 64)); vmax = max(vmax, (uint32_t)__shfl_xor(vmax, o2, 64));
+        }
         const uint32_t fl = (__ballot(visk) != 0ull ? 2u : 0u) | (__ballot(n < N && !visk) != 0ull ? 1u : 0u);
-        __shared__ uint32_t wv[4][3];
+        __shared__ uint32_t wv[4][5];
         const uint32_t wave = threadIdx.x >> 6;
-        if ((threadIdx.x & 63u) == 0) { wv[wave][0] = vor; wv[wave][1] = vand; wv[wave][2] = fl; }
+        if ((threadIdx.x & 63u) == 0) { wv[wave][0] = vor; wv[wave][1] = vand; wv[wave][2] = fl; wv[wave][3] = vmin; wv[wave][4] = vmax; }
         __syncthreads();
         if (threadIdx.x == 0) {
             uint32_t *o3 = key_bits + ((size_t)b * gridDim.x + blockIdx.x) * 4;
             o3[0] = (wv[0][0] | wv[1][0]) | (wv[2][0] | wv[3][0]);
             o3[1] = (wv[0][1] & wv[1][1]) & (wv[2][1] & wv[3][1]);
             o3[2] = (wv[0][2] | wv[1][2]) | (wv[2][2] | wv[3][2]);
-            o3[3] = 0u;  // (the record's fourth word: nobody reads it, but `saved` holds no uninitialised words)
+            o3[3] = min(min(wv[0][3], wv[1][3]), min(wv[2][3], wv[3][3]));  // 0xFFFFFFFF: no visible key in this block
+            // the maxima follow the [B][blocks][4] records as one word per block
+            key_bits[(size_t)gridDim.y * gridDim.x * 4 + (size_t)b * gridDim.x + blockIdx.x] =
+                max(max(wv[0][4], wv[1][4]), max(wv[2][4], wv[3][4]));
         }
     }
 }

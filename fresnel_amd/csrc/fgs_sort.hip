@@ -140,17 +140,61 @@ __device__ __forceinline__ uint32_t key_digit(const KeyPlan &kp, uint32_t key, u
     return key == 0xFFFFFFFFu ? kp.cull : (d & kp.vmask);
 }
 
-template <bool COMPRESSED>
+// ---- bucket digit (the bucket depth sort, further down) ------------------------------------------------------------------------
+// An image's visible keys lie in [kmin, kmax]; digit = (key - kmin) >> shift with the smallest shift that maps kmax - kmin to <= 254
+// spreads them over at most 255 buckets in key order (equal keys share a bucket), a culled key (0xFFFFFFFF) has bucket 255 alone.
+// Row of an image in `bucket_tab`: [0, 256] the bucket boundaries, then kmin and shift.
+constexpr uint32_t BK_KMIN = 257u, BK_SHIFT = 258u;
+
+__device__ __forceinline__ uint32_t bucket_digit(uint32_t key, uint32_t kmin, uint32_t shift) {
+    const uint32_t d = (key - kmin) >> shift;
+    return key == 0xFFFFFFFFu ? 255u : (d < 254u ? d : 254u);  // (the clamp binds for no key of a consistent record: an index stays an index)
+}
+
+// every thread of the block returns {kmin, shift} of segment `seg`, folded from k_project's records; `kb` = 2 * RS_WAVES words of LDS
+__device__ __forceinline__ void bucket_fold(const uint32_t *__restrict__ recs, uint32_t nrec, uint32_t nseg, uint32_t seg, uint32_t *kb,
+                                            uint32_t &kmin, uint32_t &shift) {
+    const uint32_t *__restrict__ maxima = recs + (size_t)nseg * nrec * 4u + (size_t)seg * nrec;
+    uint32_t lo = 0xFFFFFFFFu, hi = 0u;
+    for (uint32_t i = threadIdx.x; i < nrec; i += RS_THREADS) {
+        lo = min(lo, recs[((size_t)seg * nrec + i) * 4u + 3u]);
+        hi = max(hi, maxima[i]);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { lo = min(lo, (uint32_t)__shfl_xor(lo, o, 64)); hi = max(hi, (uint32_t)__shfl_xor(hi, o, 64)); }
+    const uint32_t wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63u) == 0) { kb[2 * wave] = lo; kb[2 * wave + 1] = hi; }
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < RS_WAVES; ++w) { lo = min(lo, kb[2 * w]); hi = max(hi, kb[2 * w + 1]); }
+    if (lo > hi) { kmin = 0u; shift = 0u; return; }  // no visible key: every key goes to bucket 255
+    const uint32_t range = hi - lo;
+    uint32_t s = range > 254u ? 24u - (uint32_t)__clz((int)range) : 0u;  // range >> s < 256
+    if ((range >> s) > 254u) ++s;
+    kmin = lo; shift = s;
+}
+
+// BUCKET (the bucket pass of the bucket depth sort, further down): the digit is bucket_digit of the image's {kmin, shift}, which
+// every block folds from k_project's records (`key_bits`) and block 0 of the image leaves in `bucket_tab` for the later kernels.
+template <bool COMPRESSED, bool BUCKET = false>
 __global__ __launch_bounds__(RS_THREADS) void k_radix_upsweep(
     const uint32_t *__restrict__ keys, uint32_t seg_len, const uint32_t *__restrict__ seg_len_dev,
     uint32_t seg_capacity, uint32_t seg_stride, uint32_t shift, uint32_t dmask, uint32_t *__restrict__ hist,
-    const uint32_t *__restrict__ key_bits, uint32_t key_recs, uint32_t pass) {
+    const uint32_t *__restrict__ key_bits, uint32_t key_recs, uint32_t pass, uint32_t *__restrict__ bucket_tab) {
     __shared__ uint32_t h[256];
     __shared__ uint32_t kb[24];
     KeyPlan kp;
     if (COMPRESSED) {
         kp = key_plan(key_bits, key_recs, blockIdx.y, pass, kb);
         if (pass >= kp.live) return;  // this segment is sorted already
+    }
+    uint32_t kmin = 0u;
+    if (BUCKET) {
+        bucket_fold(key_bits, key_recs, gridDim.y, blockIdx.y, kb, kmin, shift);
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            uint32_t *tab = bucket_tab + (size_t)blockIdx.y * FGS_SORT_BUCKET_WORDS;
+            tab[BK_KMIN] = kmin; tab[BK_SHIFT] = shift; tab[BK_SHIFT + 1] = 0u;
+        }
     }
     h[threadIdx.x] = 0;
     __syncthreads();
@@ -161,7 +205,8 @@ __global__ __launch_bounds__(RS_THREADS) void k_radix_upsweep(
         for (int u = 0; u < 4; ++u) k[u] = i + u * RS_THREADS < r.end ? keys[i + u * RS_THREADS] : 0u;
 #pragma unroll
         for (int u = 0; u < 4; ++u)
-            if (i + u * RS_THREADS < r.end) atomicAdd(&h[COMPRESSED ? key_digit(kp, k[u], pass) : (k[u] >> shift) & dmask], 1u);
+            if (i + u * RS_THREADS < r.end)
+                atomicAdd(&h[BUCKET ? bucket_digit(k[u], kmin, shift) : COMPRESSED ? key_digit(kp, k[u], pass) : (k[u] >> shift) & dmask], 1u);
     }
     __syncthreads();
     // layout: hist[(seg*256 + digit) * bps + blk]
@@ -193,13 +238,16 @@ __global__ __launch_bounds__(256) void k_radix_scan(uint32_t *__restrict__ hist,
     if (lane == 0) dtot[row] = carry;
 }
 
-template <bool COMPRESSED>
+template <bool COMPRESSED, bool BUCKET = false>
 __global__ __launch_bounds__(RS_THREADS) void k_radix_downsweep(
     const uint32_t *__restrict__ keys_in, const uint32_t *__restrict__ vals_in,
     uint32_t *__restrict__ keys_out, uint32_t *__restrict__ vals_out, uint32_t seg_len,
     const uint32_t *__restrict__ seg_len_dev, uint32_t seg_capacity, uint32_t seg_stride, uint32_t shift,
     uint32_t dmask, const uint32_t *__restrict__ hist, const uint32_t *__restrict__ dtot, uint32_t idx_mod,
-    const uint32_t *__restrict__ key_bits, uint32_t key_recs, uint32_t pass, uint32_t *__restrict__ vals_final) {
+    const uint32_t *__restrict__ key_bits, uint32_t key_recs, uint32_t pass, uint32_t *__restrict__ vals_final,
+    uint32_t *__restrict__ bucket_tab) {
+    // BUCKET: the digit is bucket_digit of the {kmin, shift} that the upsweep left in the image's row of `bucket_tab`, and block 0 of
+    // the image adds the 257 bucket boundaries (the digit totals' exclusive prefix and their sum) to that row.
     // dtot == nullptr: `hist` holds the RAW per-block digit counts and this block forms its own prefix (sum over the
     // blocks before it, total over all of them) -- no k_radix_scan launch; used when a segment has few blocks (the
     // depth sort, every launch of which sits at the launch floor).
@@ -217,6 +265,11 @@ __global__ __launch_bounds__(RS_THREADS) void k_radix_downsweep(
         kp = key_plan(key_bits, key_recs, blockIdx.y, pass, kb);
         if (pass >= kp.live) return;                        // this segment is sorted already
         if (pass + 1u == kp.live) vals_out = vals_final;    // its last live pass: the payload goes to its final place
+    }
+    uint32_t kmin = 0u;
+    if (BUCKET) {
+        kmin = bucket_tab[(size_t)blockIdx.y * FGS_SORT_BUCKET_WORDS + BK_KMIN];
+        shift = bucket_tab[(size_t)blockIdx.y * FGS_SORT_BUCKET_WORDS + BK_SHIFT];
     }
     const SegInfo r = block_range(seg_len, seg_len_dev, seg_capacity, seg_stride);
     const uint32_t seg0 = blockIdx.y * seg_stride;
@@ -292,6 +345,11 @@ __global__ __launch_bounds__(RS_THREADS) void k_radix_downsweep(
 #pragma unroll
         for (int w = 0; w < RS_WAVES; ++w) pre += (w < (int)wave) ? wtot[w] : 0u;
         run_off[tid] = seg0 + pre + (s - t) + mine;
+        if (BUCKET && blockIdx.x == 0) {
+            uint32_t *tab = bucket_tab + (size_t)blockIdx.y * FGS_SORT_BUCKET_WORDS;
+            tab[tid] = pre + (s - t);
+            if (tid == 255u) tab[256] = pre + s;
+        }
     }
     __syncthreads();
     // Ranking against the wave's OWN running digit counters in LDS (a wave's LDS operations execute in program
@@ -301,7 +359,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_radix_downsweep(
         uint32_t lrank[4], dig[4];
 #pragma unroll
         for (int it = 0; it < 4; ++it) {
-            const uint32_t digit = COMPRESSED ? key_digit(kp, key[it], pass) : (key[it] >> shift) & dmask;
+            const uint32_t digit = BUCKET ? bucket_digit(key[it], kmin, shift) : COMPRESSED ? key_digit(kp, key[it], pass) : (key[it] >> shift) & dmask;
             dig[it] = digit;
             uint32_t rank, count;
             match_rank<8>(digit, valid[it], rank, count);
@@ -754,6 +812,247 @@ __global__ __launch_bounds__(SL_THREADS) void k_sort_segment_lds(
     }
 }
 
+// ---- BUCKET SORT (depth sort of host-known segments of more than 8192 keys) -----------------------------------------------------
+// A two-launch pass costs its launch boundaries and two memory round trips, not its bytes (profiles/r05_ab_sort_passes.txt), so the
+// four passes of a large image are replaced by ONE pass over memory on a most-significant digit and in-LDS sorts of what it leaves:
+//   (1) k_radix_upsweep<false, true> / k_radix_downsweep<false, true>: the stable scatter by bucket_digit -- the image's keys spread
+//       over <= 255 buckets in key order, the culled ones in bucket 255, (key, index) pairs grouped by bucket in the ping-pong buffers,
+//       the bucket boundaries in `bucket_tab`;
+//   (2) k_bucket_sort: one 256-thread block per (image, bucket) sorts its bucket where it lies by the ceil(shift / 8) low bytes of
+//       key - kmin that the bucket digit did not consume -- stable 8-bit passes in LDS, a pass whose histogram has one populated bin
+//       skipped -- and writes the payload to `order` at bucket offset + rank.  A bucket of equal keys (shift 0) and the culled
+//       bucket are in index order already (stability of (1)) and are only copied;
+//   (3) k_bucket_sort_large: buckets above BK_CAP pairs, 32 blocks of 1024 threads per image, block x taking the buckets x, x + 32, ...:
+//       up to 8192 pairs in LDS like (2), above that by radix passes through the bucket's own range of the two global buffers.
+// Which class a bucket falls into is decided on the device from its boundaries; a block of the other class leaves at once.  No
+// block waits for another.  The benchmark's images (32 768 Gaussians) populate ~120 buckets of <= ~1700 keys.
+constexpr int BK_CH = 8, BK_CAP = RS_THREADS * BK_CH;
+
+// Stable sort of `cnt` <= WAVES * 64 * CH (key, payload) pairs by the low 8 * passes bits of key - kmin; the payloads go to out[rank].
+// A pass is k_sort_segment_lds's (its comments apply); ONE pair buffer is enough, since every thread holds its pairs in registers
+// while the block scatters.  `wtot`: 8 words.
+template <int WAVES, int CH>
+__device__ __forceinline__ void bucket_sort_lds(const uint32_t *__restrict__ kin, const uint32_t *__restrict__ vin,
+                                                uint32_t *__restrict__ out, uint32_t cnt, uint32_t kmin, uint32_t passes, uint32_t *ks,
+                                                uint32_t *vs, uint32_t (*wcnt)[256], uint32_t *wtot) {
+    constexpr uint32_t THREADS = WAVES * 64;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t nch = (cnt + THREADS - 1u) / THREADS;  // chunks per wave (<= CH)
+    const uint32_t w0 = wave * nch * 64u;                 // wave w owns the pairs [w0, w0 + 64 nch)
+    uint32_t key[CH], val[CH];
+    bool valid[CH];
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+        const uint32_t i = w0 + (uint32_t)c * 64u + lane;
+        valid[c] = (uint32_t)c < nch && i < cnt;
+        key[c] = valid[c] ? kin[i] - kmin : 0u;
+        val[c] = valid[c] ? vin[i] : 0u;
+    }
+    __syncthreads();  // (a block that sorts several buckets: the previous one's LDS is no longer read)
+    if (tid < 4u) wtot[4u + tid] = 0u;  // pass p has a single populated bin
+#pragma unroll
+    for (int k = 0; k < 4; ++k) wcnt[wave][lane + 64u * k] = 0u;
+    for (uint32_t p = 0; p < passes; ++p) {
+        const uint32_t shift = 8u * p;
+        const bool last = p + 1u == passes;
+        uint32_t lrank[CH], dig[CH];
+#pragma unroll
+        for (int c = 0; c < CH; ++c) {
+            if ((uint32_t)c >= nch) continue;  // block-uniform
+            const uint32_t digit = (key[c] >> shift) & 0xFFu;
+            dig[c] = digit;
+            uint32_t rank, count;
+            match_rank<8>(digit, valid[c], rank, count);
+            const uint32_t prev = valid[c] ? wcnt[wave][digit] : 0u;
+            lrank[c] = prev + rank;
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            if (valid[c] && rank == 0) wcnt[wave][digit] = prev + count;
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        }
+        __syncthreads();
+        uint32_t cw[WAVES], acc = 0u, sc = 0u;
+        if (tid < 256u) {
+#pragma unroll
+            for (int w = 0; w < WAVES; ++w) cw[w] = wcnt[w][tid];
+#pragma unroll
+            for (int w = 0; w < WAVES; ++w) { const uint32_t x = cw[w]; cw[w] = acc; acc += x; }
+            sc = acc;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const uint32_t v = __shfl_up(sc, o, 64);
+                if ((int)lane >= o) sc += v;
+            }
+            if (lane == 63u) wtot[wave] = sc;
+            if (acc == cnt) wtot[4u + p] = 1u;
+        }
+        __syncthreads();
+        if (wtot[4u + p]) {  // block-uniform: all keys share this digit, the pass would move nothing
+            if (last) {
+#pragma unroll
+                for (int c = 0; c < CH; ++c)
+                    if (valid[c]) out[w0 + (uint32_t)c * 64u + lane] = val[c];
+                break;
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) wcnt[wave][lane + 64u * k] = 0u;  // (the wave's own row; the others' reads of it are behind the barrier)
+            continue;
+        }
+        if (tid < 256u) {
+            uint32_t base = sc - acc;
+#pragma unroll
+            for (int w = 0; w < 3; ++w) base += (w < (int)wave) ? wtot[w] : 0u;
+#pragma unroll
+            for (int w = 0; w < WAVES; ++w) wcnt[w][tid] = base + cw[w];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int c = 0; c < CH; ++c) {
+            if (valid[c]) {  // (false for c >= nch)
+                uint32_t dst = wcnt[wave][dig[c]] + lrank[c];
+                dst = dst < cnt ? dst : cnt - 1u;
+                if (last) out[dst] = val[c];
+                else { ks[dst] = key[c]; vs[dst] = val[c]; }
+            }
+        }
+        if (last) break;
+        __syncthreads();  // the pass's output is in place; the counters are free
+#pragma unroll
+        for (int k = 0; k < 4; ++k) wcnt[wave][lane + 64u * k] = 0u;
+#pragma unroll
+        for (int c = 0; c < CH; ++c) {
+            const uint32_t i = w0 + (uint32_t)c * 64u + lane;
+            if (valid[c]) { key[c] = ks[i]; val[c] = vs[i]; }
+        }
+    }
+}
+
+// one bucket's boundaries inside its segment, clamped to it (they are device-side counts)
+__device__ __forceinline__ void bucket_bounds(const uint32_t *__restrict__ tab, uint32_t d, uint32_t seg_len, uint32_t &b, uint32_t &cnt) {
+    uint32_t e = tab[d + 1u];
+    b = tab[d];
+    e = e < seg_len ? e : seg_len;
+    b = b < e ? b : e;
+    cnt = e - b;
+}
+
+__device__ __forceinline__ uint32_t bucket_passes(const uint32_t *__restrict__ tab) {
+    const uint32_t shift = tab[BK_SHIFT];
+    return ((shift < 32u ? shift : 32u) + 7u) / 8u;
+}
+
+__global__ __launch_bounds__(RS_THREADS) void k_bucket_sort(
+    const uint32_t *__restrict__ keys, const uint32_t *__restrict__ vals, uint32_t *__restrict__ order, uint32_t seg_len,
+    uint32_t seg_stride, const uint32_t *__restrict__ bucket_tab) {
+    __shared__ uint32_t ks[BK_CAP], vs[BK_CAP];
+    __shared__ uint32_t wcnt[RS_WAVES][256];
+    __shared__ uint32_t wtot[8];
+    const uint32_t *__restrict__ tab = bucket_tab + (size_t)blockIdx.y * FGS_SORT_BUCKET_WORDS;
+    const uint32_t d = blockIdx.x;
+    uint32_t b, cnt;
+    bucket_bounds(tab, d, seg_len, b, cnt);
+    if (cnt == 0u) return;
+    const uint32_t passes = d == 255u ? 0u : bucket_passes(tab);
+    const size_t base = (size_t)blockIdx.y * seg_stride + b;
+    if (passes == 0u) {  // culled keys, or one key value per bucket: in index order already
+        for (uint32_t i = threadIdx.x; i < cnt; i += RS_THREADS) order[base + i] = vals[base + i];
+        return;
+    }
+    if (cnt > (uint32_t)BK_CAP) return;  // k_bucket_sort_large's
+    bucket_sort_lds<RS_WAVES, BK_CH>(keys + base, vals + base, order + base, cnt, tab[BK_KMIN], passes, ks, vs, wcnt, wtot);
+}
+
+// A bucket of more than 8192 pairs (a few depth values shared by thousands of Gaussians next to a wide spread of the others): stable
+// 8-bit passes through the bucket's own range of the two global buffers by this block alone -- histogram with LDS atomics, rounds
+// of 1024 keys ranked by wave64 ballots, the sixteen waves' counts summed per key.  Slow, and bounded: `passes` rounds of cnt keys.
+__device__ __forceinline__ void bucket_sort_global(uint32_t *ka, uint32_t *va, uint32_t *kb, uint32_t *vb, uint32_t *out, uint32_t cnt,
+                                                   uint32_t kmin, uint32_t passes, uint32_t *h, uint32_t *run, uint32_t (*wcnt)[256],
+                                                   uint32_t *wtot) {
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    for (uint32_t p = 0; p < passes; ++p) {
+        const uint32_t shift = 8u * p;
+        __syncthreads();  // the previous pass's pairs are in memory, nobody reads the LDS words below any more
+        if (tid < 256u) h[tid] = 0u;
+        if (tid == 0u) wtot[4] = 0u;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) wcnt[wave][lane + 64u * k] = 0u;
+        __syncthreads();
+        for (uint32_t i = tid; i < cnt; i += SL_THREADS) atomicAdd(&h[((ka[i] - kmin) >> shift) & 0xFFu], 1u);
+        __syncthreads();
+        uint32_t t = 0u, sc = 0u;
+        if (tid < 256u) {
+            t = h[tid];
+            sc = t;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const uint32_t v = __shfl_up(sc, o, 64);
+                if ((int)lane >= o) sc += v;
+            }
+            if (lane == 63u) wtot[wave] = sc;
+            if (t == cnt) wtot[4] = 1u;
+        }
+        __syncthreads();
+        if (wtot[4]) continue;  // block-uniform: a single populated bin
+        if (tid < 256u) {
+            uint32_t base = sc - t;
+#pragma unroll
+            for (int w = 0; w < 3; ++w) base += (w < (int)wave) ? wtot[w] : 0u;
+            run[tid] = base;
+        }
+        __syncthreads();
+        for (uint32_t r0 = 0; r0 < cnt; r0 += SL_THREADS) {
+            const uint32_t i = r0 + tid;
+            const bool valid = i < cnt;
+            const uint32_t key = valid ? ka[i] : 0u, val = valid ? va[i] : 0u;
+            const uint32_t digit = ((key - kmin) >> shift) & 0xFFu;
+            uint32_t rank, count;
+            match_rank<8>(digit, valid, rank, count);
+            if (valid && rank == 0) wcnt[wave][digit] = count;
+            __syncthreads();
+            if (valid) {
+                uint32_t dst = run[digit] + rank;
+#pragma unroll
+                for (int w = 0; w < SL_WAVES; ++w) dst += (w < (int)wave) ? wcnt[w][digit] : 0u;
+                dst = dst < cnt ? dst : cnt - 1u;
+                kb[dst] = key; vb[dst] = val;
+            }
+            __syncthreads();
+            if (tid < 256u) {
+                uint32_t tot = 0u;
+#pragma unroll
+                for (int w = 0; w < SL_WAVES; ++w) { tot += wcnt[w][tid]; wcnt[w][tid] = 0u; }
+                run[tid] += tot;
+            }
+            __syncthreads();
+        }
+        uint32_t *x = ka; ka = kb; kb = x;
+        x = va; va = vb; vb = x;
+    }
+    __syncthreads();
+    for (uint32_t i = tid; i < cnt; i += SL_THREADS) out[i] = va[i];
+}
+
+__global__ __launch_bounds__(SL_THREADS) void k_bucket_sort_large(
+    uint32_t *keys, uint32_t *vals, uint32_t *keys_alt, uint32_t *vals_alt, uint32_t *order, uint32_t seg_len, uint32_t seg_stride,
+    const uint32_t *bucket_tab) {
+    __shared__ uint32_t ks[SL_CAP], vs[SL_CAP];
+    __shared__ uint32_t wcnt[SL_WAVES][256];
+    __shared__ uint32_t wtot[8];
+    __shared__ uint32_t h[256], run[256];
+    const uint32_t *tab = bucket_tab + (size_t)blockIdx.y * FGS_SORT_BUCKET_WORDS;
+    const uint32_t passes = bucket_passes(tab), kmin = tab[BK_KMIN];
+    if (passes == 0u) return;  // (k_bucket_sort copies such buckets whatever their size)
+    for (uint32_t d = blockIdx.x; d < 255u; d += gridDim.x) {
+        uint32_t b, cnt;
+        bucket_bounds(tab, d, seg_len, b, cnt);
+        if (cnt <= (uint32_t)BK_CAP) continue;  // k_bucket_sort's
+        const size_t base = (size_t)blockIdx.y * seg_stride + b;
+        if (cnt <= (uint32_t)SL_CAP)
+            bucket_sort_lds<SL_WAVES, SL_CH>(keys + base, vals + base, order + base, cnt, kmin, passes, ks, vs, wcnt, wtot);
+        else
+            bucket_sort_global(keys + base, vals + base, keys_alt + base, vals_alt + base, order + base, cnt, kmin, passes, h, run, wcnt, wtot);
+    }
+}
+
 // blocks per segment of the fused pass: ~2048 keys of its own per block (ranking costs ~6x the histogram per key), <= 16 (every
 // block reads the whole segment), <= 4096 blocks per launch
 uint32_t fused_blocks_per_seg(uint32_t seg_len, uint32_t num_segs) {
@@ -775,7 +1074,8 @@ int fgs_launch_radix_sort(uint32_t *keys_in, uint32_t *vals_in, uint32_t *keys_a
                           uint32_t seg_len, const uint32_t *seg_len_dev, uint32_t seg_capacity,
                           uint32_t seg_stride, uint32_t num_segs, uint32_t key_bits, uint32_t *hist,
                           hipStream_t st, const uint32_t *keys_first, uint32_t index_payload_mod,
-                          const uint32_t *key_stats, uint32_t key_recs, int pass_mode) {
+                          const uint32_t *key_stats, uint32_t key_recs, int pass_mode, const uint32_t *key_range,
+                          uint32_t *bucket_tab) {
     // pass_mode (FgsDims.sort_mode >> 1): 1 = the fused pass (one launch per pass, every block recounting its segment, 11-bit digits)
     // for any host-known segment length up to 64 K keys | 2 = the same with 8-bit digits | 3 = 8-bit digits with the hand-off (A/B runs,
     // agreement tests).  Measured (profiles/r05_ab_sort_passes.txt): at 16 x 8 192 keys the fused passes take 45.6 us (11-bit) / 55.5
@@ -785,6 +1085,9 @@ int fgs_launch_radix_sort(uint32_t *keys_in, uint32_t *vals_in, uint32_t *keys_a
     // Round 5, later: 0 = automatic now means the whole-segment LDS sort (k_sort_segment_lds: ONE launch for all passes) for
     // host-known segments of at most 8192 keys, the two-launch passes above that | 4 = the two-launch passes for any size | 5 = the LDS
     // sort where it applies (as automatic).  profiles/r05_ab_sort_lds.txt.
+    // Round 6: automatic (0, 5) above 8192 keys is the bucket sort (3 + 1 launches instead of 8) for the depth sort of full keys -- the
+    // caller hands k_project's key range records and the table; zone keys (key_stats) keep their compressed passes: a handful of
+    // distinct depths gives a handful of giant buckets.  profiles/r06_ab_bucket_sort.txt.
     const bool host_len = !seg_len_dev && seg_len == seg_capacity && key_bits >= 1u;
     if (host_len && seg_len <= (uint32_t)SL_CAP && (pass_mode == 0 || pass_mode == 5) && (vals_in || index_payload_mod)) {
         const bool compressed = key_stats != nullptr;
@@ -806,6 +1109,28 @@ int fgs_launch_radix_sort(uint32_t *keys_in, uint32_t *vals_in, uint32_t *keys_a
         FGS_LAUNCH_CHECK("k_sort_segment_lds");
         *keys_sorted = kdst;
         *vals_sorted = vdst;
+        return FGS_OK;
+    }
+    if (host_len && seg_len > (uint32_t)SL_CAP && (pass_mode == 0 || pass_mode == 5) && !key_stats && key_range && bucket_tab && keys_first &&
+        index_payload_mod && vals_final && key_recs && key_bits == 32u) {
+        uint32_t bps = fgs_radix_blocks_per_seg(seg_len, num_segs);
+        if (bps > 64u) bps = 64u;  // (the prefix over a segment's blocks is formed inside the scatter)
+        const dim3 grid(bps, num_segs);
+        hipLaunchKernelGGL((k_radix_upsweep<false, true>), grid, dim3(RS_THREADS), 0, st, keys_first, seg_len, (const uint32_t *)nullptr,
+                           seg_len, seg_stride, 0u, 0u, hist, key_range, key_recs, 0u, bucket_tab);
+        FGS_LAUNCH_CHECK("k_radix_upsweep");
+        hipLaunchKernelGGL((k_radix_downsweep<false, true>), grid, dim3(RS_THREADS), 0, st, keys_first, (const uint32_t *)nullptr, keys_in,
+                           vals_in, seg_len, (const uint32_t *)nullptr, seg_len, seg_stride, 0u, 0u, hist, (const uint32_t *)nullptr,
+                           index_payload_mod, key_range, key_recs, 0u, (uint32_t *)nullptr, bucket_tab);
+        FGS_LAUNCH_CHECK("k_radix_downsweep");
+        hipLaunchKernelGGL(k_bucket_sort, dim3(256, num_segs), dim3(RS_THREADS), 0, st, keys_in, vals_in, vals_final, seg_len, seg_stride,
+                           bucket_tab);
+        FGS_LAUNCH_CHECK("k_bucket_sort");
+        hipLaunchKernelGGL(k_bucket_sort_large, dim3(32, num_segs), dim3(SL_THREADS), 0, st, keys_in, vals_in, keys_alt, vals_alt, vals_final,
+                           seg_len, seg_stride, bucket_tab);
+        FGS_LAUNCH_CHECK("k_bucket_sort_large");
+        *keys_sorted = nullptr;  // (grouped by bucket only; the depth sort's caller reads `order`)
+        *vals_sorted = vals_final;
         return FGS_OK;
     }
     const bool fused = host_len && pass_mode >= 1 && pass_mode <= 3 && seg_len <= 65536u;
@@ -888,10 +1213,10 @@ int fgs_launch_radix_sort(uint32_t *keys_in, uint32_t *vals_in, uint32_t *keys_a
         const dim3 grid(bps, num_segs);
         if (compressed)
             hipLaunchKernelGGL(k_radix_upsweep<true>, grid, dim3(RS_THREADS), 0, st, kin, seg_len, seg_len_dev, seg_capacity,
-                               seg_stride, 0u, 0u, hist, key_stats, key_recs, p);
+                               seg_stride, 0u, 0u, hist, key_stats, key_recs, p, (uint32_t *)nullptr);
         else
             hipLaunchKernelGGL(k_radix_upsweep<false>, grid, dim3(RS_THREADS), 0, st, kin, seg_len, seg_len_dev, seg_capacity,
-                               seg_stride, p * width, dmask_of(p, width, key_bits), hist, (const uint32_t *)nullptr, 0u, p);
+                               seg_stride, p * width, dmask_of(p, width, key_bits), hist, (const uint32_t *)nullptr, 0u, p, (uint32_t *)nullptr);
         FGS_LAUNCH_CHECK("k_radix_upsweep");
         const uint32_t rows = num_segs * 256;
         if (!fused_scan) {
@@ -902,12 +1227,12 @@ int fgs_launch_radix_sort(uint32_t *keys_in, uint32_t *vals_in, uint32_t *keys_a
         if (compressed)
             hipLaunchKernelGGL(k_radix_downsweep<true>, grid, dim3(RS_THREADS), 0, st, kin, vsrc, kout, vdst, seg_len, seg_len_dev,
                                seg_capacity, seg_stride, 0u, 0u, hist, fused_scan ? (const uint32_t *)nullptr : dtot,
-                               index_payload_mod, key_stats, key_recs, p, vals_final);
+                               index_payload_mod, key_stats, key_recs, p, vals_final, (uint32_t *)nullptr);
         else
             hipLaunchKernelGGL(k_radix_downsweep<false>, grid, dim3(RS_THREADS), 0, st, kin, vsrc, kout, vdst, seg_len, seg_len_dev,
                                seg_capacity, seg_stride, p * width, dmask_of(p, width, key_bits), hist,
                                fused_scan ? (const uint32_t *)nullptr : dtot, index_payload_mod ? index_payload_mod : 1u,
-                               (const uint32_t *)nullptr, 0u, p, (uint32_t *)nullptr);
+                               (const uint32_t *)nullptr, 0u, p, (uint32_t *)nullptr, (uint32_t *)nullptr);
         FGS_LAUNCH_CHECK("k_radix_downsweep");
         // ping-pong: the buffer just read becomes the next output, except a read-only first-pass source
         uint32_t *next_out = (p == 0 && keys_first) ? kspare : const_cast<uint32_t *>(kin);

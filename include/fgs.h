@@ -99,7 +99,9 @@ typedef struct FgsDims {
                                depths look like is known on the device only (fgs_sort.hip).
                                Bits 1-3 (work split, never the result): 0 = automatic -- images of <= 8192 Gaussians are sorted by
                                ONE launch, all passes in the LDS of one compute unit per image (round 5); larger ones by the
-                               two-launch 8-bit passes of rounds 1-4 | 2 = one launch per pass, 11-bit digits, every block
+                               bucket sort (ONE pass over memory on a digit that spreads the image's visible keys between their
+                               minimum and maximum over 255 buckets, then every bucket sorted in LDS: 4 launches), or with
+                               bit 0 set by the two-launch 8-bit passes of rounds 1-4 on the compressed keys | 2 = one launch per pass, 11-bit digits, every block
                                recounting its image (<= 65 536 Gaussians) | 4 = the same with 8-bit digits | 6 = 8-bit digits,
                                the blocks' digit counts handed off between them instead of recounted (bounded wait) | 8 = the
                                two-launch passes for any size | 10 = as automatic.  Valid values: 0 ... 11.                 */
