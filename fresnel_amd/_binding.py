@@ -26,6 +26,7 @@ EXPORTED_SYMBOLS = [
     "fgs_ssim_workspace_bytes", "fgs_ssim_forward", "fgs_ssim_backward",
     "fgs_pixel_loss_workspace_bytes", "fgs_pixel_loss_stage1", "fgs_pixel_loss_stage2", "fgs_pixel_loss_stage3",
     "fgs_pixel_loss_forward", "fgs_pixel_loss_backward",
+    "fgs_head_workspace_bytes", "fgs_head_forward", "fgs_head_backward",
 ]
 
 STAGES = ["project", "depth_sort", "dup_emit", "tile_sort", "tile_ranges", "composite_fwd",
@@ -110,6 +111,12 @@ class FgsPixelLossDims(ctypes.Structure):
                 ("boundaries", ctypes.c_float * FGS_PIXEL_MAX_BOUNDARIES)]
 
 
+class FgsHeadDims(ctypes.Structure):
+    _fields_ = [("batch", ctypes.c_int32), ("points", ctypes.c_int32), ("k_full", ctypes.c_int32),
+                ("k_used", ctypes.c_int32), ("channels", ctypes.c_int32), ("xy_gain", ctypes.c_float),
+                ("edge_scale_factor", ctypes.c_float), ("edge_opacity_boost", ctypes.c_float)]
+
+
 class FgsError(RuntimeError):
     pass
 
@@ -183,6 +190,11 @@ def load():
     lib.fgs_pixel_loss_backward.argtypes = [pd] + [vp] * 12
     for fn in (lib.fgs_pixel_loss_workspace_bytes, lib.fgs_pixel_loss_stage1, lib.fgs_pixel_loss_stage2,
                lib.fgs_pixel_loss_stage3, lib.fgs_pixel_loss_forward, lib.fgs_pixel_loss_backward):
+        fn.restype = ctypes.c_int
+    lib.fgs_head_workspace_bytes.argtypes = [cp(FgsHeadDims), cp(ctypes.c_size_t)]
+    lib.fgs_head_forward.argtypes = [cp(FgsHeadDims)] + [vp] * 13
+    lib.fgs_head_backward.argtypes = [cp(FgsHeadDims)] + [vp] * 16
+    for fn in (lib.fgs_head_workspace_bytes, lib.fgs_head_forward, lib.fgs_head_backward):
         fn.restype = ctypes.c_int
     for fn in (lib.fgs_asm_propagate_workspace_bytes, lib.fgs_asm_propagate_forward, lib.fgs_asm_propagate_backward,
                lib.fgs_spectral_workspace_bytes, lib.fgs_spectral_loss_forward, lib.fgs_spectral_loss_backward,

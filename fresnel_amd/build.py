@@ -61,6 +61,8 @@ SOURCES = {
     # contraction (the forward's third stage and the backward form the normalised depths with the same roundings, so the
     # backward's sgn(u - v) is the one the forward summed)
     "fgs_pixel_loss.hip": ["-ffp-contract=off"],
+    # no FMA contraction: the backward recomputes the forward, and its clamp gates and quaternion branch must be the forward's
+    "fgs_head.hip": ["-ffp-contract=off"],
 }
 LINK_LIBS = ["-lhipfft"]
 

@@ -1,14 +1,26 @@
-"""Patch decoder that PRODUCES renderer inputs (not a kernel target).
+"""Patch decoders that PRODUCE renderer inputs.
 
-Own definition with the interface, shapes and ranges of the reference's DirectPatchDecoder
+`DirectPatchDecoder` and `FibonacciPatchDecoder` mirror the reference's classes of the same names
+(scripts/models/gaussian_decoder_models.py, "GDM": 622-948 and 1493-1747): constructor arguments, forward signature, returned dict
+and state_dict keys are the reference's, so its checkpoints load with strict=True.  Their MLP, convolutions and grid sampling
+are torch modules; the Gaussian-parameter head behind the MLP is `gaussian_head`: torch expressions (head_backend "torch", runs
+anywhere) or the fused HIP kernel pair of csrc/fgs_head.hip (head_backend "hip", CUDA/ROCm tensors only, no fallback).
+
+`PatchGaussianDecoder` is the older stand-in: own definition with the interface, shapes and ranges of the reference's DirectPatchDecoder
 (scripts/models/gaussian_decoder_models.py:622-948): a 37x37 DINOv2 patch grid, K Gaussians per
 patch -> dict{positions (B,N,3), scales (B,N,3) in [1e-6,2], rotations (B,N,4) unit wxyz,
 colors/opacities in [0,1] [, phases (B,N) in [0,1]]}, N = 37*37*K (K=4 -> 5476).  It is the
 module whose gradients the data-parallel step all-reduces (~0.63 M parameters at K=4).
 """
+import ctypes
+import math
+from typing import Dict, Optional, Tuple
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+
+from . import _binding as B
 
 
 def rotate_positions_for_pose(positions: torch.Tensor, elevation: torch.Tensor, azimuth: torch.Tensor) -> torch.Tensor:
@@ -111,3 +123,368 @@ class PatchGaussianDecoder(nn.Module):
         if self.use_phase_output:
             out["phases"] = torch.sigmoid(o[..., 15]).reshape(Bn, G * G * K)
         return out
+
+
+# =================================================================================================================================
+# The reference's decoders: DirectPatchDecoder (GDM:622-948), FibonacciPatchDecoder (GDM:1493-1747) and the head they share
+# =================================================================================================================================
+HEAD_BACKENDS = ("torch", "hip")
+HEAD_OUTPUTS = ("positions", "scales", "rotations", "colors", "opacities", "phases")
+
+
+def rotation_6d_to_quaternion(rot_6d: torch.Tensor) -> torch.Tensor:
+    """(..., 6) -> unit quaternion (..., 4) w,x,y,z, the reference's rotation_6d_to_quaternion (GDM:186-276): Gram-Schmidt of the
+    two 3-vectors with F.normalize(eps=1e-6), b3 = (0,0,1) where |b1 x b2| < 1e-6, matrix -> quaternion by the branch
+    trace > 0 | R00 largest | R11 > R22 | else, normalised.  One defined deviation: where the reference adds 1e-8 times a
+    RANDOM sign to b2 before normalising it (GDM:208), this adds +1e-8 -- one of the reference's own draws."""
+    a1, a2 = rot_6d[..., :3], rot_6d[..., 3:6]
+    b1 = F.normalize(a1, dim=-1, eps=1e-6)
+    b2 = F.normalize(a2 - (b1 * a2).sum(dim=-1, keepdim=True) * b1 + 1e-8, dim=-1, eps=1e-6)
+    b3 = torch.cross(b1, b2, dim=-1)
+    zero = torch.zeros_like(b3[..., 0])  # (0, 0, 1) formed on the device: no host copy, so the expression can be captured in a graph
+    b3 = torch.where(b3.norm(dim=-1, keepdim=True) < 1e-6, torch.stack([zero, zero, zero + 1.0], dim=-1), b3)
+    b3 = F.normalize(b3, dim=-1, eps=1e-6)
+    R00, R01, R02 = b1[..., 0], b2[..., 0], b3[..., 0]   # R = [b1 b2 b3], columns
+    R10, R11, R12 = b1[..., 1], b2[..., 1], b3[..., 1]
+    R20, R21, R22 = b1[..., 2], b2[..., 2], b3[..., 2]
+
+    def s_of(t):
+        return torch.sqrt(torch.clamp(t, min=1e-10)) * 2
+
+    s1, s2 = s_of(R00 + R11 + R22 + 1.0), s_of(1.0 + R00 - R11 - R22)
+    s3, s4 = s_of(1.0 + R11 - R00 - R22), s_of(1.0 + R22 - R00 - R11)
+    cases = (
+        (0.25 * s1, (R21 - R12) / s1, (R02 - R20) / s1, (R10 - R01) / s1),
+        ((R21 - R12) / s2, 0.25 * s2, (R01 + R10) / s2, (R02 + R20) / s2),
+        ((R02 - R20) / s3, (R01 + R10) / s3, 0.25 * s3, (R12 + R21) / s3),
+        ((R10 - R01) / s4, (R02 + R20) / s4, (R12 + R21) / s4, 0.25 * s4),
+    )
+    c1, c2, c3 = (R00 + R11 + R22) > 0, (R00 > R11) & (R00 > R22), R11 > R22
+    quat = torch.stack([torch.where(c1, cases[0][i], torch.where(c2, cases[1][i], torch.where(c3, cases[2][i], cases[3][i])))
+                        for i in range(4)], dim=-1)
+    return F.normalize(quat, dim=-1, eps=1e-6)
+
+
+def _head_torch(raw, base_xy, base_z, pose, opacity_mod, edge, K, xy_gain, edge_scale_factor, edge_opacity_boost):
+    """The head in torch ops, expression by expression as GDM:845-922: what head_backend "hip" is A/B'd against."""
+    Bn, P, _, C = raw.shape
+    o = raw[:, :, :K, :]
+    x = base_xy[:, 0].view(1, P, 1) + o[..., 0] * xy_gain
+    y = base_xy[:, 1].view(1, P, 1) + o[..., 1] * xy_gain
+    z = base_z.view(Bn, P, 1).expand(Bn, P, K)
+    if pose is not None:  # rotate_positions_for_pose, GDM:96-104
+        ca, sa, ce, se = (pose[:, i].view(Bn, 1, 1) for i in range(4))
+        xr, zr = x * ca + z * sa, -x * sa + z * ca
+        x, y, z = xr, y * ce - zr * se, y * se + zr * ce
+    positions = torch.stack([x, y, z], dim=-1)
+    scales = torch.clamp(F.softplus(torch.clamp(o[..., 3:6], min=-10, max=20) + 1.0) * 0.15, min=1e-6, max=2.0)
+    rotations = rotation_6d_to_quaternion(o[..., 6:12])
+    colors = torch.sigmoid(o[..., 12:15])
+    opacities = torch.sigmoid(o[..., 15])
+    if edge is not None:  # GDM:882-894
+        e = edge.view(Bn, P, 1)
+        scales = scales * (1.0 - edge_scale_factor * e.unsqueeze(-1))
+        opacities = torch.clamp(opacities + edge_opacity_boost * e, 0, 1)
+    if opacity_mod is not None:  # GDM:908-912
+        opacities = torch.clamp(opacities * opacity_mod.view(Bn, 1, 1), 0, 1)
+    N = P * K
+    out = [positions.reshape(Bn, N, 3), scales.reshape(Bn, N, 3), rotations.reshape(Bn, N, 4), colors.reshape(Bn, N, 3),
+           opacities.reshape(Bn, N)]
+    if C == 19:
+        out.append((torch.sigmoid(o[..., 16:19]) * (2 * math.pi)).reshape(Bn, N, 3))
+    return tuple(out)
+
+
+def _ptr(t):
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def _stream():
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _f32c(t):
+    return None if t is None else t.detach().contiguous().float()
+
+
+class _HeadHip(torch.autograd.Function):
+    """fgs_head_forward / fgs_head_backward.  Nothing but the inputs is saved: the backward recomputes from `raw`."""
+
+    @staticmethod
+    def forward(ctx, raw, base_xy, base_z, pose, opacity_mod, edge, K, xy_gain, edge_scale_factor, edge_opacity_boost):
+        if not raw.is_cuda:
+            raise B.FgsError("gaussian_head (backend 'hip') needs CUDA/ROCm tensors; there is no CPU fallback")
+        lib = B.load()
+        dev = raw.device
+        Bn, P, KF, C = raw.shape
+        d = B.FgsHeadDims(Bn, P, KF, int(K), C, float(xy_gain), float(edge_scale_factor), float(edge_opacity_boost))
+        raw_, xy_, z_, pose_, mod_, edge_ = (_f32c(t) for t in (raw, base_xy, base_z, pose, opacity_mod, edge))
+        N = P * int(K)
+        with torch.cuda.device(dev):
+            outs = [torch.empty((Bn, N, w) if w else (Bn, N), dtype=torch.float32, device=dev) for w in (3, 3, 4, 3, 0)]
+            if C == 19:
+                outs.append(torch.empty((Bn, N, 3), dtype=torch.float32, device=dev))
+            B.check(lib.fgs_head_forward(ctypes.byref(d), _ptr(raw_), _ptr(xy_), _ptr(z_), _ptr(pose_), _ptr(mod_), _ptr(edge_),
+                                         *[_ptr(t) for t in outs], *([None] if C != 19 else []), _stream()), "fgs_head_forward")
+        ctx.dims = d
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(raw_, pose_, mod_, edge_)
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *g_outs):
+        lib = B.load()
+        raw_, pose_, mod_, edge_ = ctx.saved_tensors
+        d = ctx.dims
+        need_z, need_mod, need_edge = ctx.needs_input_grad[2], ctx.needs_input_grad[4], ctx.needs_input_grad[5]
+        gs = [_f32c(g) for g in g_outs] + [None] * (6 - len(g_outs))
+        dev = raw_.device
+        with torch.cuda.device(dev):
+            g_raw = torch.empty_like(raw_)
+            g_z = torch.empty((d.batch, d.points), dtype=torch.float32, device=dev) if need_z else None
+            g_edge = torch.empty((d.batch, d.points), dtype=torch.float32, device=dev) if need_edge and edge_ is not None else None
+            g_mod = scratch = None
+            if need_mod and mod_ is not None:
+                nb = ctypes.c_size_t(0)
+                B.check(lib.fgs_head_workspace_bytes(ctypes.byref(d), ctypes.byref(nb)), "fgs_head_workspace_bytes")
+                g_mod = torch.empty((d.batch,), dtype=torch.float32, device=dev)
+                scratch = torch.empty(nb.value, dtype=torch.uint8, device=dev)
+            B.check(lib.fgs_head_backward(ctypes.byref(d), _ptr(raw_), _ptr(pose_), _ptr(mod_), _ptr(edge_), *[_ptr(g) for g in gs],
+                                          _ptr(g_raw), _ptr(g_z), _ptr(g_edge), _ptr(g_mod), _ptr(scratch), _stream()),
+                    "fgs_head_backward")
+        return (g_raw, None, g_z, None, g_mod, g_edge, None, None, None, None)
+
+
+def gaussian_head(raw: torch.Tensor, base_xy: torch.Tensor, base_z: torch.Tensor, pose: Optional[torch.Tensor] = None,
+                  opacity_mod: Optional[torch.Tensor] = None, edge: Optional[torch.Tensor] = None, *,
+                  num_gaussians: Optional[int] = None, xy_gain: float = 0.25, edge_scale_factor: float = 0.5,
+                  edge_opacity_boost: float = 0.2, backend: str = "torch") -> Dict[str, torch.Tensor]:
+    """The head shared by the reference's patch decoders (GDM:845-922): the MLP's raw (B, P, K_full, 16 | 19) output -> the
+    renderers' inputs, N = P x K with K = min(num_gaussians, K_full): positions (B,N,3), scales (B,N,3), rotations (B,N,4),
+    colors (B,N,3), opacities (B,N) and, with 19 channels, phases (B,N,3) in radians.
+
+    base_xy (P,2): grid / spiral coordinates; base_z (B,P): depth_offset - 2 depth; pose (B,4): cos az, sin az, cos el, sin el
+    (the positions are turned to face the camera); opacity_mod (B,): view-dependent opacity factor; edge (B,P): edge strength
+    (smaller, more opaque Gaussians at depth edges).  Gradients flow to raw, base_z, opacity_mod and edge.
+    backend "torch": torch expressions, any device.  backend "hip": csrc/fgs_head.hip, one launch forward and one backward,
+    bitwise repeatable; CUDA/ROCm tensors only."""
+    if backend not in HEAD_BACKENDS:
+        raise ValueError(f"unknown head backend {backend!r}: one of {HEAD_BACKENDS}")
+    if raw.dim() != 4 or raw.shape[-1] not in (16, 19):
+        raise ValueError(f"raw must be (B, P, K_full, 16 | 19), got {tuple(raw.shape)}")
+    Bn, P, KF, _ = raw.shape
+    K = KF if num_gaussians is None else max(1, min(int(num_gaussians), KF))
+    if tuple(base_xy.shape) != (P, 2) or tuple(base_z.shape) != (Bn, P):
+        raise ValueError(f"base_xy must be ({P}, 2) and base_z ({Bn}, {P}), got {tuple(base_xy.shape)} and {tuple(base_z.shape)}")
+    for name, t, shape in (("pose", pose, (Bn, 4)), ("opacity_mod", opacity_mod, (Bn,)), ("edge", edge, (Bn, P))):
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError(f"{name} must be {shape}, got {tuple(t.shape)}")
+    args = (raw, base_xy, base_z, pose, opacity_mod, edge, K, xy_gain, edge_scale_factor, edge_opacity_boost)
+    outs = _HeadHip.apply(*args) if backend == "hip" else _head_torch(*args)
+    return dict(zip(HEAD_OUTPUTS, outs))
+
+
+class _MLP(nn.Module):
+    """Linear / ReLU [/ Dropout] stack under the name `net` (GDM:279-302: the checkpoint keys are mlp.net.{0,3,6,...} with
+    dropout > 0, mlp.net.{0,2,4,...} without)."""
+
+    def __init__(self, input_dim: int, hidden_dims, output_dim: int, dropout: float = 0.0):
+        super().__init__()
+        layers, prev = [], input_dim
+        for h in hidden_dims:
+            layers += [nn.Linear(prev, h), nn.ReLU(inplace=True)]
+            if dropout > 0:
+                layers.append(nn.Dropout(dropout))
+            prev = h
+        layers.append(nn.Linear(prev, output_dim))
+        self.net = nn.Sequential(*layers)
+
+    def forward(self, x):
+        return self.net(x)
+
+
+class PoseEncoder(nn.Module):
+    """Sinusoidal encoding of (elevation, azimuth) at frequencies 2^0 ... 2^(F-1), then a two-layer MLP (GDM:305-367)."""
+
+    def __init__(self, embed_dim: int = 64, num_frequencies: int = 8):
+        super().__init__()
+        self.embed_dim, self.num_frequencies = embed_dim, num_frequencies
+        self.mlp = nn.Sequential(nn.Linear(num_frequencies * 4, embed_dim), nn.ReLU(inplace=True), nn.Linear(embed_dim, embed_dim))
+
+    def sinusoidal_encode(self, x: torch.Tensor) -> torch.Tensor:
+        xf = x.unsqueeze(-1) * (2.0 ** torch.arange(self.num_frequencies, device=x.device, dtype=x.dtype))
+        return torch.cat([torch.sin(xf), torch.cos(xf)], dim=-1)
+
+    def forward(self, elevation: torch.Tensor, azimuth: torch.Tensor) -> torch.Tensor:
+        return self.mlp(torch.cat([self.sinusoidal_encode(elevation), self.sinusoidal_encode(azimuth)], dim=-1))
+
+
+class DepthEncoder(nn.Module):
+    """Three 3x3 convolutions over the depth map, averaged down to the feature grid (GDM:577-615; the reference pools to its
+    fixed 37 x 37 grid, this pools to whatever grid the features have -- the same on the reference's grid)."""
+
+    def __init__(self, out_channels: int = 64):
+        super().__init__()
+        self.out_channels = out_channels
+        self.encoder = nn.Sequential(nn.Conv2d(1, 32, 3, padding=1), nn.ReLU(inplace=True),
+                                     nn.Conv2d(32, 64, 3, padding=1), nn.ReLU(inplace=True),
+                                     nn.Conv2d(64, out_channels, 3, padding=1), nn.ReLU(inplace=True))
+
+    def forward(self, depth: torch.Tensor, grid: Tuple[int, int] = (37, 37)) -> torch.Tensor:
+        return F.adaptive_avg_pool2d(self.encoder(depth), grid)
+
+
+class FresnelZoneTable(nn.Module):
+    """The decoder-side part of the reference's FresnelZones (scripts/utils/fresnel_zones.py:54-139): N equal zones over the depth
+    range, depths snapped to their zone's centre.  `boundary_emphasis` is the reference's learnable vector; the decoders never
+    read it, it exists so that checkpoints load."""
+
+    def __init__(self, num_zones: int = 8, depth_range: Tuple[float, float] = (0.0, 1.0)):
+        super().__init__()
+        self.num_zones, self.depth_range = num_zones, depth_range
+        bounds = torch.linspace(depth_range[0], depth_range[1], num_zones + 1)
+        self.register_buffer("zone_boundaries", bounds)
+        self.register_buffer("zone_centers", (bounds[:-1] + bounds[1:]) / 2)
+        self.register_buffer("zone_width", torch.tensor((depth_range[1] - depth_range[0]) / num_zones))
+        self.boundary_emphasis = nn.Parameter(torch.ones(num_zones + 1))
+
+    def get_zone_centers_for_depth(self, depth: torch.Tensor) -> torch.Tensor:
+        idx = torch.bucketize(torch.clamp(depth, self.depth_range[0], self.depth_range[1]), self.zone_boundaries[1:-1])
+        return self.zone_centers[idx.flatten()].view(idx.shape)
+
+
+def fibonacci_spiral_positions(n_points: int, device=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """n points of Vogel's golden-angle spiral in the unit disc (GDM:107-140): r = sqrt(i / n), theta = i pi (3 - sqrt 5)."""
+    i = torch.arange(n_points, device=device, dtype=torch.float32)
+    r, theta = torch.sqrt(i / n_points), i * (math.pi * (3 - math.sqrt(5)))
+    return r * torch.cos(theta), r * torch.sin(theta)
+
+
+def _pose_row(elevation, azimuth):
+    return torch.stack([torch.cos(azimuth), torch.sin(azimuth), torch.cos(elevation), torch.sin(elevation)], dim=-1).detach()
+
+
+def _check_backend(head_backend):
+    if head_backend not in HEAD_BACKENDS:
+        raise ValueError(f"unknown head_backend {head_backend!r}: one of {HEAD_BACKENDS}")
+    return head_backend
+
+
+class DirectPatchDecoder(nn.Module):
+    """The reference's DirectPatchDecoder (GDM:622-948): every cell of the (H, W) feature grid predicts `gaussians_per_patch`
+    Gaussians through a per-patch MLP.  Same constructor arguments and defaults, forward signature, returned dict and
+    state_dict keys.  `head_backend`: "torch" | "hip" (gaussian_head)."""
+
+    def __init__(self, feature_dim: int = 384, gaussians_per_patch: int = 8, hidden_dims=(512, 512, 256, 128),
+                 dropout: float = 0.1, use_fresnel_zones: bool = False, num_fresnel_zones: int = 8,
+                 use_edge_aware: bool = False, use_phase_output: bool = False, edge_scale_factor: float = 0.5,
+                 edge_opacity_boost: float = 0.2, use_pose_encoding: bool = False, pose_embed_dim: int = 64,
+                 use_depth_fusion: bool = False, depth_feature_dim: int = 64, head_backend: str = "torch"):
+        super().__init__()
+        self.feature_dim, self.gaussians_per_patch = feature_dim, gaussians_per_patch
+        self.use_fresnel_zones, self.use_edge_aware, self.use_phase_output = use_fresnel_zones, use_edge_aware, use_phase_output
+        self.edge_scale_factor, self.edge_opacity_boost = edge_scale_factor, edge_opacity_boost
+        self.use_pose_encoding, self.use_depth_fusion = use_pose_encoding, use_depth_fusion
+        self.head_backend = _check_backend(head_backend)
+        self.output_per_gaussian = 19 if use_phase_output else 16
+        self.depth_encoder = DepthEncoder(depth_feature_dim) if use_depth_fusion else None
+        self.mlp = _MLP(feature_dim + (depth_feature_dim if use_depth_fusion else 0), list(hidden_dims),
+                        gaussians_per_patch * self.output_per_gaussian, dropout)
+        self.depth_offset = nn.Parameter(torch.tensor(-2.0))
+        self.fresnel_zones = FresnelZoneTable(num_fresnel_zones, (0.0, 1.0)) if use_fresnel_zones else None
+        self.edge_detector = DepthEdgeDetector(16) if use_edge_aware else None
+        self.pose_encoder = PoseEncoder(pose_embed_dim) if use_pose_encoding else None
+        self.opacity_modulator = (nn.Sequential(nn.Linear(pose_embed_dim, 128), nn.ReLU(inplace=True), nn.Linear(128, 1),
+                                                nn.Sigmoid()) if use_pose_encoding else None)
+        self._grids = {}  # (H, W, device) -> (P, 2) grid coordinates
+
+    def _grid_xy(self, H, W, device):
+        key = (H, W, str(device))
+        if key not in self._grids:
+            ys, xs = torch.meshgrid(torch.linspace(-1, 1, H, device=device), torch.linspace(-1, 1, W, device=device), indexing="ij")
+            self._grids[key] = torch.stack([xs, ys], dim=-1).reshape(H * W, 2).contiguous()
+        return self._grids[key]
+
+    def forward(self, features: torch.Tensor, depth: Optional[torch.Tensor] = None, image_size: Tuple[int, int] = (518, 518),
+                num_gaussians: Optional[int] = None, elevation: Optional[torch.Tensor] = None,
+                azimuth: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        """features (B, C, H, W) channel-first; depth (B, 1, h, w) in [0, 1] or None; num_gaussians: progressive growing (the
+        full capacity is predicted, the first min(num_gaussians, K) Gaussians of every patch are used); elevation / azimuth
+        (B,) radians.  -> positions, scales, rotations, colors, opacities [, phases (B,N,3) radians] [, edge_strength (B,1,H,W)]."""
+        Bn, _, H, W = features.shape
+        if self.depth_encoder is not None and depth is not None:
+            features = torch.cat([features, self.depth_encoder(depth, (H, W))], dim=1)
+        raw = self.mlp(features.permute(0, 2, 3, 1).reshape(Bn * H * W, features.shape[1]))
+        raw = raw.reshape(Bn, H * W, self.gaussians_per_patch, self.output_per_gaussian)
+        edge_strength = None
+        if depth is not None:
+            depth_grid = F.interpolate(depth, (H, W), mode="bilinear", align_corners=False)
+            if self.edge_detector is not None:
+                edge_strength = self.edge_detector(depth_grid)
+            if self.fresnel_zones is not None:
+                depth_grid = self.fresnel_zones.get_zone_centers_for_depth(depth_grid)
+            base_z = self.depth_offset + depth_grid.reshape(Bn, H * W) * (-2)
+        else:  # (the reference reads the offset with .item() here: no gradient to it, and none here)
+            base_z = self.depth_offset.detach().reshape(1, 1).expand(Bn, H * W).contiguous()
+        posed = elevation is not None and azimuth is not None
+        opacity_mod = None
+        if self.pose_encoder is not None and posed:
+            opacity_mod = (0.5 + self.opacity_modulator(self.pose_encoder(elevation, azimuth))).reshape(Bn)
+        out = gaussian_head(raw, self._grid_xy(H, W, features.device), base_z,
+                            pose=_pose_row(elevation, azimuth) if posed else None, opacity_mod=opacity_mod,
+                            edge=edge_strength.reshape(Bn, H * W) if edge_strength is not None else None,
+                            num_gaussians=num_gaussians, xy_gain=0.25, edge_scale_factor=self.edge_scale_factor,
+                            edge_opacity_boost=self.edge_opacity_boost, backend=self.head_backend)
+        if edge_strength is not None:
+            out["edge_strength"] = edge_strength
+        return out
+
+
+class FibonacciPatchDecoder(nn.Module):
+    """The reference's FibonacciPatchDecoder (GDM:1493-1747): features and depth are sampled bilinearly at `n_spiral_points`
+    points of a golden-angle spiral, and a per-point MLP predicts `gaussians_per_point` Gaussians each.  Same constructor
+    arguments and defaults, forward signature (num_gaussians is accepted and ignored, as there), returned dict and state_dict keys."""
+
+    def __init__(self, feature_dim: int = 384, n_spiral_points: int = 377, gaussians_per_point: int = 1,
+                 hidden_dims=(512, 256, 128), dropout: float = 0.1, use_fresnel_zones: bool = False, num_fresnel_zones: int = 8,
+                 use_phase_output: bool = False, use_pose_encoding: bool = False, pose_embed_dim: int = 64,
+                 head_backend: str = "torch"):
+        super().__init__()
+        self.feature_dim, self.n_spiral_points, self.gaussians_per_point = feature_dim, n_spiral_points, gaussians_per_point
+        self.total_gaussians = n_spiral_points * gaussians_per_point
+        self.use_fresnel_zones, self.use_phase_output, self.use_pose_encoding = use_fresnel_zones, use_phase_output, use_pose_encoding
+        self.head_backend = _check_backend(head_backend)
+        self.output_per_gaussian = 19 if use_phase_output else 16
+        self.mlp = _MLP(feature_dim, list(hidden_dims), gaussians_per_point * self.output_per_gaussian, dropout)
+        self.depth_offset = nn.Parameter(torch.tensor(-2.0))
+        sx, sy = fibonacci_spiral_positions(n_spiral_points)
+        self.register_buffer("spiral_x", sx)
+        self.register_buffer("spiral_y", sy)
+        self.fresnel_zones = FresnelZoneTable(num_fresnel_zones, (0.0, 1.0)) if use_fresnel_zones else None
+        self.pose_encoder = PoseEncoder(pose_embed_dim) if use_pose_encoding else None
+        self.opacity_modulator = (nn.Sequential(nn.Linear(pose_embed_dim, 64), nn.ReLU(inplace=True), nn.Linear(64, 1),
+                                                nn.Sigmoid()) if use_pose_encoding else None)
+
+    def forward(self, features: torch.Tensor, depth: Optional[torch.Tensor] = None, image_size: Tuple[int, int] = (518, 518),
+                num_gaussians: Optional[int] = None, elevation: Optional[torch.Tensor] = None,
+                azimuth: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        Bn, C = features.shape[:2]
+        P = self.n_spiral_points
+        xy = torch.stack([self.spiral_x, self.spiral_y], dim=-1)                      # (P, 2)
+        coords = xy.view(1, 1, P, 2).expand(Bn, -1, -1, -1)
+        sampled = F.grid_sample(features, coords, mode="bilinear", padding_mode="border", align_corners=True)  # (B, C, 1, P)
+        raw = self.mlp(sampled.squeeze(2).permute(0, 2, 1).reshape(Bn * P, C))
+        raw = raw.reshape(Bn, P, self.gaussians_per_point, self.output_per_gaussian)
+        if depth is not None:
+            d = F.grid_sample(depth, coords, mode="bilinear", padding_mode="border", align_corners=True).reshape(Bn, P)
+            if self.fresnel_zones is not None:
+                d = self.fresnel_zones.get_zone_centers_for_depth(d)
+            base_z = self.depth_offset + d * (-2)
+        else:
+            base_z = self.depth_offset.detach().reshape(1, 1).expand(Bn, P).contiguous()
+        posed = elevation is not None and azimuth is not None
+        opacity_mod = None
+        if self.pose_encoder is not None and posed:
+            opacity_mod = (0.5 + self.opacity_modulator(self.pose_encoder(elevation, azimuth))).reshape(Bn)
+        return gaussian_head(raw, xy, base_z, pose=_pose_row(elevation, azimuth) if posed else None, opacity_mod=opacity_mod,
+                             xy_gain=0.15, backend=self.head_backend)

@@ -13,7 +13,11 @@ Kept from TGD (same flag names / defaults / behaviour):
                     synthetic stand-in data only when --data_dir holds no images
   hand-off          progressive Gaussians-per-patch, importance subsampling of K Gaussians, one orbit camera per
                     batch (fresnel_amd/handoff.py, TGD:1069-1207)
-  renderer choice   TileBasedRenderer(res, res, use_phase_blending, phase_amplitude)   TGD:1898-1907
+  decoder           --decoder standin (default: PatchGaussianDecoder, own head) | direct | fibonacci: mirrors of the reference's
+                    DirectPatchDecoder / FibonacciPatchDecoder (its keys: --resume takes its checkpoints), constructed as at
+                    TGD:1814-1840; --experiment 4 implies fibonacci; --head_backend hip runs their head as fused HIP kernels
+  renderer choice   TileBasedRenderer(res, res, use_phase_blending, phase_amplitude)   TGD:1898-1907;
+                    --experiment 4 --use_phase_blending: FourierGaussianRenderer(res, res, 0.65, 0.55, 0.45)  TGD:1877-1890
   camera            fx = fy = 0.8*res, cx = cy = res/2, view = I                       TGD:1910-1917
   step              decoder -> render -> stack -> L1 + normalised-depth L1 (SSIM / LPIPS only when
                     those packages exist, as TGD:53-65; --ssim_backend hip computes the SSIM term with this
@@ -64,7 +68,7 @@ from torch.optim.lr_scheduler import CosineAnnealingLR
 
 import numpy as np
 
-from .decoder import PatchGaussianDecoder
+from .decoder import HEAD_BACKENDS, DirectPatchDecoder, FibonacciPatchDecoder, PatchGaussianDecoder
 from .dist import DPContext
 from .handoff import HFTSConfig, camera_for_batch, importance_subsample, sample_training_pose
 
@@ -130,6 +134,11 @@ class TrainingConfig:  # subset of TGD:97-162 that this path uses; same names an
     hip_graph: bool = False   # replay the whole step (decoder, rasterizer, losses, backward, all-reduce, clip, AdamW) from
                               # ONE captured HIP graph: the library never allocates or synchronises and the step has no
                               # host decision left, so it is capturable; pays when the step is host-launch-bound
+    decoder: str = "standin"  # "standin": PatchGaussianDecoder (own head, shapes and ranges of the reference only) | "direct" |
+                              # "fibonacci": mirrors of the reference's DirectPatchDecoder / FibonacciPatchDecoder (fresnel_amd/
+                              # decoder.py: its state_dict keys, its head); --experiment 4 implies "fibonacci" (TGD:1829-1841)
+    head_backend: str = "torch"  # Gaussian-parameter head of "direct" / "fibonacci": torch expressions | "hip" (csrc/fgs_head.hip)
+    n_spiral_points: int = 377   # "fibonacci": points of the golden-angle spiral (TGD:1427)
     workspace: str = "worst"  # rasterizer workspaces: "worst" (sized for the radius cap) | "adaptive" (sized by the duplicates
                               # the previous steps needed, TileBasedRenderer(workspace="adaptive"); a step whose scene outgrew
                               # the capacity renders NaN and is dropped by the NaN/Inf skip, the next one has room)
@@ -376,7 +385,11 @@ def default_renderer_factory(cfg: TrainingConfig, device, res: Optional[int] = N
     resolution (HFTS --train_resolution / --fast_mode, TGD:1643, 1880-1887)."""
     from .renderer import Camera, TileBasedRenderer
     res = res or cfg.image_size
-    if cfg.use_wave_rendering:  # TGD:1891-1897
+    if cfg.experiment == 4 and cfg.use_phase_blending:  # TGD:1877-1890
+        from .renderer import FourierGaussianRenderer
+        renderer = FourierGaussianRenderer(res, res, wavelength_r=0.65, wavelength_g=0.55, wavelength_b=0.45,
+                                           learnable_wavelengths=True).to(device)
+    elif cfg.use_wave_rendering:  # TGD:1891-1897
         from .renderer import WaveFieldRenderer
         renderer = WaveFieldRenderer(res, res).to(device)
     else:                       # TGD:1898-1906
@@ -486,15 +499,19 @@ def train_step(model, renderer, camera, batch, optimizer, cfg: TrainingConfig, d
                                      cfg.pose_range_elevation, cfg.pose_range_azimuth, pose_rng)
     el_t = torch.full((feats.shape[0],), el, device=feats.device) if el is not None else None
     az_t = torch.full((feats.shape[0],), az, device=feats.device) if az is not None else None
-    out = model(feats, depth, num_gaussians=num_gaussians, elevation=el_t, azimuth=az_t)
+    mirror = cfg.decoder != "standin"  # the reference's decoders take channel-first features (TGD:1100) and emit (B,N,3) radians
+    out = model(feats.permute(0, 3, 1, 2) if mirror else feats, depth, num_gaussians=num_gaussians, elevation=el_t, azimuth=az_t)
+    out.pop("edge_strength", None)
     if not (cfg.use_phase_blending or cfg.use_wave_rendering):
         out.pop("phases", None)
     # stochastic Gaussian rendering: K Gaussians by opacity importance, gathered on the device (TGD:1154-1187)
     if hfts is not None:
         out, _ = importance_subsample(out, hfts.get_stochastic_k(out["positions"].shape[1]), generator=sample_gen)
     phases = out.get("phases")
-    if cfg.use_wave_rendering and phases is not None:
-        phases = phases * (2.0 * math.pi)  # wave renderers take radians (DR:772), the decoder emits [0,1]
+    if cfg.use_wave_rendering and phases is not None and not mirror:
+        phases = phases * (2.0 * math.pi)  # wave renderers take radians (DR:772), the stand-in decoder emits [0,1]
+    # (a mirror's (B,N,3) phases go on as they are: radians for the wave renderer, ignored by the Fourier renderer; on the
+    # TileBasedRenderer phase path the renderer's RuntimeError for (N,3) phases surfaces, as in the reference -- SURVEY section 0.4)
     render_camera = camera_for_batch(camera, el, az, res, cfg.multi_pose_augmentation)  # TGD:1196-1207
     # ONE batched call replaces the per-image loop of TGD:1209-1223
     rendered, rdepth = renderer(out["positions"], out["scales"], out["rotations"], out["colors"],
@@ -521,6 +538,55 @@ def train_step(model, renderer, camera, batch, optimizer, cfg: TrainingConfig, d
     elif not bool(skipped):  # non-fused optimizer: the skip is a host decision (one sync)
         optimizer.step()
     return StepResult(terms, skipped)
+
+
+DECODERS = ("standin", "direct", "fibonacci")
+
+
+def make_decoder(cfg: TrainingConfig):
+    """The step's decoder: the stand-in (default), or a mirror of the reference's class constructed as its training script
+    constructs it (TGD:1814-1828 experiment 2, TGD:1832-1840 experiment 4)."""
+    phase_out = cfg.use_phase_blending or cfg.use_wave_rendering
+    if cfg.decoder == "standin":
+        return PatchGaussianDecoder(cfg.feature_dim, cfg.gaussians_per_patch, grid=cfg.feature_size,
+                                    use_fresnel_zones=cfg.use_fresnel_zones,
+                                    num_fresnel_zones=cfg.num_fresnel_zones,
+                                    use_phase_output=phase_out,
+                                    use_edge_aware=cfg.use_edge_aware, edge_scale_factor=cfg.edge_scale_factor,
+                                    edge_opacity_boost=cfg.edge_opacity_boost)
+    if cfg.head_backend not in HEAD_BACKENDS:
+        raise ValueError(f"unknown head_backend {cfg.head_backend!r}: one of {HEAD_BACKENDS}")
+    if cfg.decoder == "direct":
+        return DirectPatchDecoder(feature_dim=cfg.feature_dim, gaussians_per_patch=cfg.gaussians_per_patch,
+                                  use_fresnel_zones=cfg.use_fresnel_zones, num_fresnel_zones=cfg.num_fresnel_zones,
+                                  use_edge_aware=cfg.use_edge_aware, use_phase_output=phase_out,
+                                  edge_scale_factor=cfg.edge_scale_factor, edge_opacity_boost=cfg.edge_opacity_boost,
+                                  use_pose_encoding=cfg.use_pose_encoding, head_backend=cfg.head_backend)
+    if cfg.decoder == "fibonacci":
+        return FibonacciPatchDecoder(feature_dim=cfg.feature_dim, n_spiral_points=cfg.n_spiral_points, gaussians_per_point=1,
+                                     use_fresnel_zones=cfg.use_fresnel_zones, num_fresnel_zones=cfg.num_fresnel_zones,
+                                     use_phase_output=phase_out, use_pose_encoding=cfg.use_pose_encoding,
+                                     head_backend=cfg.head_backend)
+    raise ValueError(f"unknown decoder {cfg.decoder!r}: one of {DECODERS}")
+
+
+def load_checkpoint(model, optimizer, ck, cfg: TrainingConfig) -> int:
+    """Restore model and optimizer from a checkpoint dict {epoch, model_state_dict, optimizer_state_dict} (TGD:1304-1310);
+    -> the epoch to start at.  A mirror decoder also takes the REFERENCE's checkpoints: the state dict loads strictly (same
+    keys), and of the optimizer only the per-parameter state and the learning rate are taken -- the parameters are registered
+    in the reference's order, so its AdamW moments land on the right tensors -- while this harness's own group options (the
+    fused step that takes the NaN/Inf skip flag) stay."""
+    model.load_state_dict(ck["model_state_dict"])
+    osd = ck["optimizer_state_dict"]
+    if cfg.decoder != "standin":
+        ours = optimizer.state_dict()
+        for g_ours, g_ck in zip(ours["param_groups"], osd["param_groups"]):
+            for k in ("lr", "initial_lr"):
+                if k in g_ck:
+                    g_ours[k] = g_ck[k]
+        osd = {"state": osd["state"], "param_groups": ours["param_groups"]}
+    optimizer.load_state_dict(osd)
+    return ck["epoch"] + 1
 
 
 def save_checkpoint(model, optimizer, epoch, losses, cfg: TrainingConfig):
@@ -603,12 +669,9 @@ def run_training(cfg: TrainingConfig, dp: Optional[DPContext] = None,
     if cfg.batch_size % dp.world != 0:  # fail fast, before any rank can stall in a collective (see DPContext.shard)
         raise ValueError(f"--batch_size {cfg.batch_size} is not a multiple of the {dp.world} ranks")
     torch.manual_seed(cfg.seed)
-    model = PatchGaussianDecoder(cfg.feature_dim, cfg.gaussians_per_patch, grid=cfg.feature_size,
-                                 use_fresnel_zones=cfg.use_fresnel_zones,
-                                 num_fresnel_zones=cfg.num_fresnel_zones,
-                                 use_phase_output=cfg.use_phase_blending or cfg.use_wave_rendering,
-                                 use_edge_aware=cfg.use_edge_aware, edge_scale_factor=cfg.edge_scale_factor,
-                                 edge_opacity_boost=cfg.edge_opacity_boost).to(device)
+    if cfg.decoder != "standin" and cfg.head_backend == "hip" and device.type != "cuda":
+        raise ValueError("head_backend 'hip' needs a GPU device: the HIP head kernels have no CPU fallback")
+    model = make_decoder(cfg).to(device)
     dp.broadcast_parameters(model)
     train_res = hfts.get_effective_train_resolution(cfg.image_size) if hfts is not None else cfg.image_size
     renderer, camera = _make_renderer(renderer_factory, cfg, device, train_res)
@@ -620,10 +683,7 @@ def run_training(cfg: TrainingConfig, dp: Optional[DPContext] = None,
     scheduler = CosineAnnealingLR(optimizer, T_max=cfg.epochs)
     start_epoch = 0
     if resume:
-        ck = torch.load(resume, map_location=device)
-        model.load_state_dict(ck["model_state_dict"])
-        optimizer.load_state_dict(ck["optimizer_state_dict"])
-        start_epoch = ck["epoch"] + 1
+        start_epoch = load_checkpoint(model, optimizer, torch.load(resume, map_location=device), cfg)
     data, n_items = make_dataset(cfg, log if dp.rank == 0 else (lambda *a: None))
     # metrics beyond the losses: composited Gaussian-pixels counted on the device by the renderer,
     # the rasterizer's stage timers sampled on the logged steps
@@ -772,7 +832,48 @@ def arg_parser() -> argparse.ArgumentParser:
                     help="SSIM term: pytorch_msssim when importable (default, as the reference) or this package's HIP kernels")
     ap.add_argument("--pixel_loss_backend", default=c.pixel_loss_backend, choices=list(PIXEL_LOSS_BACKENDS),
                     help="L1 / boundary / depth terms: torch expressions (default) or this package's fused HIP kernels")
+    ap.add_argument("--decoder", default=c.decoder, choices=list(DECODERS),
+                    help="the stand-in decoder (default) or a mirror of the reference's DirectPatchDecoder / FibonacciPatchDecoder "
+                         "(loads its checkpoints); --experiment 4 implies fibonacci")
+    ap.add_argument("--head_backend", default=c.head_backend, choices=list(HEAD_BACKENDS),
+                    help="Gaussian-parameter head of --decoder direct / fibonacci: torch expressions (default) or the fused HIP kernels")
+    ap.add_argument("--n_spiral_points", type=int, default=c.n_spiral_points, help="TGD:1427 (--decoder fibonacci)")
     return ap
+
+
+def config_from_args(a) -> TrainingConfig:
+    """The TrainingConfig of a parsed command line (no device yet).  --experiment 2 trains a patch-grid decoder, --experiment 4
+    the Fibonacci decoder (TGD:1829-1841), with --use_phase_blending through the Fourier renderer (TGD:1877-1890); the
+    reference's other experiments have no counterpart here."""
+    if a.experiment not in (2, 4):
+        raise SystemExit("only --experiment 2 (patch-grid decoder) and --experiment 4 (Fibonacci decoder) are on this repo's hot path")
+    decoder = a.decoder
+    if a.experiment == 4:
+        if decoder == "direct":
+            raise SystemExit("--experiment 4 trains the Fibonacci decoder: --decoder direct contradicts it")
+        decoder = "fibonacci"
+    elif decoder == "fibonacci":
+        raise SystemExit("--decoder fibonacci is --experiment 4")
+    return TrainingConfig(experiment=a.experiment, data_dir=a.data_dir, output_dir=a.output_dir,
+                          batch_size=a.batch_size, epochs=a.epochs, lr=a.lr, image_size=a.image_size,
+                          gaussians_per_patch=a.gaussians_per_patch, max_images=a.max_images,
+                          use_fresnel_zones=bool(a.use_fresnel_zones),
+                          num_fresnel_zones=a.use_fresnel_zones or a.num_fresnel_zones,
+                          use_phase_blending=a.use_phase_blending, phase_amplitude=a.phase_amplitude,
+                          use_edge_aware=a.use_edge_aware, edge_scale_factor=a.edge_scale_factor,
+                          multi_pose_augmentation=a.multi_pose_augmentation,
+                          pose_range_elevation=tuple(a.pose_range_elevation), pose_range_azimuth=tuple(a.pose_range_azimuth),
+                          frontal_prob=a.frontal_prob, use_pose_encoding=a.use_pose_encoding,
+                          use_wave_rendering=a.use_wave_rendering or a.use_qsr,
+                          wave_equation_weight=a.wave_equation_weight, wavelength=a.wavelength,
+                          use_phase_retrieval_loss=a.use_phase_retrieval_loss or a.use_qsr,
+                          phase_retrieval_weight=a.phase_retrieval_weight,
+                          use_frequency_loss=a.use_frequency_loss, frequency_loss_weight=a.frequency_loss_weight,
+                          seed=a.seed, hip_graph=a.hip_graph,
+                          ssim_backend=a.ssim_backend, boundary_weight=a.boundary_weight,
+                          use_vlm_guidance=a.use_vlm_guidance, vlm_weight=a.vlm_weight,
+                          pixel_loss_backend=a.pixel_loss_backend, workspace=a.workspace,
+                          decoder=decoder, head_backend=a.head_backend, n_spiral_points=a.n_spiral_points)
 
 
 def main(argv=None):
@@ -781,31 +882,12 @@ def main(argv=None):
         check_workspace_options(a.workspace, a.hip_graph)
     except ValueError as e:
         raise SystemExit(str(e))
-    if a.experiment != 2:
-        raise SystemExit("only --experiment 2 (direct patch decoder) is on this repo's hot path")
+    cfg = config_from_args(a)
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if not torch.cuda.is_available():
         raise SystemExit("fresnel_amd.train needs a GPU: the HIP rasterizer has no CPU fallback")
     torch.cuda.set_device(local_rank)
-    cfg = TrainingConfig(experiment=a.experiment, data_dir=a.data_dir, output_dir=a.output_dir,
-                         batch_size=a.batch_size, epochs=a.epochs, lr=a.lr, image_size=a.image_size,
-                         gaussians_per_patch=a.gaussians_per_patch, max_images=a.max_images,
-                         use_fresnel_zones=bool(a.use_fresnel_zones),
-                         num_fresnel_zones=a.use_fresnel_zones or a.num_fresnel_zones,
-                         use_phase_blending=a.use_phase_blending, phase_amplitude=a.phase_amplitude,
-                         use_edge_aware=a.use_edge_aware, edge_scale_factor=a.edge_scale_factor,
-                         multi_pose_augmentation=a.multi_pose_augmentation,
-                         pose_range_elevation=tuple(a.pose_range_elevation), pose_range_azimuth=tuple(a.pose_range_azimuth),
-                         frontal_prob=a.frontal_prob, use_pose_encoding=a.use_pose_encoding,
-                         use_wave_rendering=a.use_wave_rendering or a.use_qsr,
-                         wave_equation_weight=a.wave_equation_weight, wavelength=a.wavelength,
-                         use_phase_retrieval_loss=a.use_phase_retrieval_loss or a.use_qsr,
-                         phase_retrieval_weight=a.phase_retrieval_weight,
-                         use_frequency_loss=a.use_frequency_loss, frequency_loss_weight=a.frequency_loss_weight,
-                         device=f"cuda:{local_rank}", seed=a.seed, hip_graph=a.hip_graph,
-                         ssim_backend=a.ssim_backend, boundary_weight=a.boundary_weight,
-                         use_vlm_guidance=a.use_vlm_guidance, vlm_weight=a.vlm_weight,
-                         pixel_loss_backend=a.pixel_loss_backend, workspace=a.workspace)
+    cfg.device = f"cuda:{local_rank}"
     hfts = HFTSConfig(train_resolution=a.train_resolution, progressive_schedule=a.progressive_schedule,
                       stochastic_k=a.stochastic_k, fast_mode=a.fast_mode)
     dp = DPContext(device=torch.device(cfg.device))

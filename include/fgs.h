@@ -432,6 +432,42 @@ int fgs_pixel_loss_backward(const FgsPixelLossDims *dims, const float *rendered,
                             const void *stats, const float *g_rgb, const float *g_boundary, const float *g_depth,
                             float *g_rendered, float *g_rendered_depth, void *stream);
 
+/* Gaussian-parameter head of the reference's patch decoders (DirectPatchDecoder GDM:845-922, FibonacciPatchDecoder
+ * GDM:1674-1723, rotation_6d_to_quaternion GDM:186-276): the elementwise map from the decoder MLP's raw output to the
+ * renderers' inputs, and its derivative.  All tensors fp32, contiguous, DEVICE.
+ *   raw          (B, P, K_full, C)  C = 16: xyz offset 3 (z unused), scale 3, rotation-6D 6, colour 3, opacity 1; C = 19: + phase 3.
+ *                                   Only the first K = k_used Gaussians of every point are used; N = P x K
+ *   base_xy      (P, 2)             grid / spiral coordinates        base_z  (B, P)  depth_offset - 2 depth
+ *   pose         (B, 4) or NULL     cos az, sin az, cos el, sin el: positions turn about Y by az, then about X by el
+ *   opacity_mod  (B,)   or NULL     opacity = clamp(opacity x opacity_mod, 0, 1)
+ *   edge         (B, P) or NULL     scales x (1 - edge_scale_factor edge), opacity = clamp(opacity + edge_opacity_boost edge, 0, 1),
+ *                                   before opacity_mod
+ *   outputs      positions (B,N,3)  = (base_xy + xy_gain raw[0:2], base_z), turned by pose
+ *                scales    (B,N,3)  = clamp(softplus(clamp(raw, -10, 20) + 1) 0.15, 1e-6, 2)   (softplus linear above 20)
+ *                rotations (B,N,4)  unit w,x,y,z: Gram-Schmidt of the two 3-vectors (F.normalize eps 1e-6, b2 + 1e-8 before its
+ *                                   normalisation, b3 = (0,0,1) when |b1 x b2| < 1e-6), matrix -> quaternion by the branch
+ *                                   trace > 0 | R00 largest | R11 > R22 | else, normalised
+ *                colors (B,N,3), opacities (B,N) sigmoids;  phases (B,N,3) = 2 pi sigmoid, C = 19 only (else NULL)
+ * Backward: recomputes the forward from raw (nothing is saved); clamps pass the gradient on the closed interval; only the
+ * selected quaternion branch is differentiated.  Any upstream gradient may be NULL (= 0).  g_raw (B, P, K_full, C): every
+ * element written (zeros for channel 2 and for the K_full - K unused Gaussians).  g_base_z (B, P), g_edge (B, P; needs edge),
+ * g_opacity_mod (B,; needs opacity_mod and scratch of fgs_head_workspace_bytes): each may be NULL; sums in a fixed order, no
+ * atomics: results repeat bit for bit.  scratch is written, never read before it is written.  K_full <= 64, B <= 65535. */
+typedef struct FgsHeadDims {
+    int32_t batch, points, k_full, k_used;
+    int32_t channels;            /* 16 | 19 */
+    float xy_gain;               /* 0.25 grid decoder (GDM:848), 0.15 spiral decoder (GDM:1675) */
+    float edge_scale_factor, edge_opacity_boost;   /* used with edge */
+} FgsHeadDims;
+int fgs_head_workspace_bytes(const FgsHeadDims *dims, size_t *scratch_bytes);
+int fgs_head_forward(const FgsHeadDims *dims, const float *raw, const float *base_xy, const float *base_z, const float *pose,
+                     const float *opacity_mod, const float *edge, float *positions, float *scales, float *rotations,
+                     float *colors, float *opacities, float *phases, void *stream);
+int fgs_head_backward(const FgsHeadDims *dims, const float *raw, const float *pose, const float *opacity_mod, const float *edge,
+                      const float *g_positions, const float *g_scales, const float *g_rotations, const float *g_colors,
+                      const float *g_opacities, const float *g_phases, float *g_raw, float *g_base_z, float *g_edge,
+                      float *g_opacity_mod, void *scratch, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * Importance-subsampling hand-off between decoder and rasterizer (--stochastic_k; reference
  * scripts/training/train_gaussian_decoder.py:1160-1187): the n_out Gaussians whose indices torch.multinomial
