@@ -465,6 +465,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NSX == 2 ? 6
     // work unit = (tile, depth segment): blockIdx.x indexes the unit list built by k_tile_order; the grid is
     // sized from the capacity, surplus blocks leave at once
     constexpr int NS = 2 * NSX, PL = NS * 64, SLOT = 5 * PL;  // sub-tiles per tile, floats per checkpoint plane / slot
+    // geometric sums per sub-tile row, folded once per list entry (below).  32 x 16 tiles only: with at most four passes per
+    // entry the fold costs what the passes save, and 16 x 16 tiles measured 0.8 % SLOWER that way (DESIGN_LOG.md 15)
+    constexpr bool ROW_MOMENTS = NSX == 4;
     const uint32_t num_units = counters[2];
     if (blockIdx.x >= num_units) return;
     // units are listed tile by tile: an XCD gets a contiguous run of them, so neighbouring tiles -- which share
@@ -593,12 +596,19 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NSX == 2 ? 6
             asm("" : "+v"(bdya), "+v"(bdyb), "+v"(cyya), "+v"(cyyb));  // keep the row terms: do not recompute them per sub-tile
             // bbox membership: the lane's column / row bits of the staged pixel bits become all-ones / zero masks
             // (v_bfe_i32) and zero G with a bit-and -- no per-pixel compare / select (issue costs: DESIGN.md).
-            // per-lane partial sums over this lane's (up to four) pixels: moments of dL/dG about the Gaussian's mean, sum dG
+            // per-lane partial sums over this lane's (up to 2 NSX) pixels: moments of dL/dG about the Gaussian's mean, sum dG
             // {dx, dy, dx^2, dx dy, dy^2, 1}; the ln2 * opacity and K factors of the chain through m' = K m are
-            // applied once per Gaussian in k_project_bwd.  (Raw moments about the tile origin -- one FMA each with
-            // per-lane constants -- were 4 % faster but lose the second moments of sub-pixel Gaussians to
-            // cancellation in fp32: up to 4e-2 on dL/dscale in the randomized sweeps.)
+            // applied once per Gaussian in k_project_bwd.  ROW_MOMENTS (32 x 16 tiles): a lane's pixels lie on TWO values of dy
+            // (dya, dyb: one per sub-tile row), so a pass accumulates only the row's A_r = sum dG, B_r = sum dG dx, C_r = sum dG dx^2 (five
+            // ops instead of nine) and the dy factors are applied once per list entry, in the fold behind the passes:
+            //   {1, dx, dx^2} = A0 + A1, B0 + B1, C0 + C1;  dy = dya A0 + dyb A1;  dx dy = dya B0 + dyb B1;
+            //   dy^2 = dya (dya A0) + dyb (dyb A1).
+            // Still central moments, with the pass's own dx / dy: nothing is taken about a far origin.  (RAW moments
+            // about the tile origin -- one FMA each with per-lane constants -- were 4 % faster but lose the second
+            // moments of sub-pixel Gaussians to cancellation in fp32: up to 4e-2 on dL/dscale in the randomized sweeps.)
+            // An untouched row's sums stay zero and add exact zeros in the fold.
             float v_mx = 0, v_my = 0, v_ca = 0, v_cbc = 0, v_cd = 0, v_op = 0, v_r = 0, v_g = 0, v_b = 0, v_d = 0;
+            float mA[2] = {0.0f, 0.0f}, mB[2] = {0.0f, 0.0f}, mC[2] = {0.0f, 0.0f};  // per sub-tile row (ROW_MOMENTS)
             {   // ONE code path for every kind of entry; what differs is handled by a wave-uniform branch around two
                 // ops: `clamp` (flag bit 4 clear: opacity > 0.98 or a doubtful conic): the clamp-gradient select.
                 // (Four specialised instantiations of this loop body made the compiler carry T and S through eight
@@ -636,11 +646,24 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NSX == 2 ? 6
                     asm("" : "+s"(cf));  // an opaque scalar per use: one s_cmp + branch, nothing on the vector side
                     if (!cf) dalpha = select_lt(a1, 1.0f, dalpha);  // the clamp binds where G op / 0.99 reaches 1
                     const float dG = dalpha * G;
-                    v_op += dG;
-                    const float dmx = dG * dx, dmy = dG * dy;
-                    v_mx += dmx; v_my += dmy;
-                    v_ca += dmx * dx; v_cbc += dmx * dy; v_cd += dmy * dy;
+                    if constexpr (ROW_MOMENTS) {
+                        mA[row] += dG;
+                        const float dmx = dG * dx;
+                        mB[row] += dmx; mC[row] += dmx * dx;
+                    } else {
+                        v_op += dG;
+                        const float dmx = dG * dx, dmy = dG * dy;
+                        v_mx += dmx; v_my += dmy;
+                        v_ca += dmx * dx; v_cbc += dmx * dy; v_cd += dmy * dy;
+                    }
                     v_r += w * gr[s]; v_g += w * gg[s]; v_b += w * gb[s]; v_d += w * gd[s];
+                }
+                if constexpr (ROW_MOMENTS) {  // fold the rows: once per list entry, ten ops
+                    v_op = mA[0] + mA[1]; v_mx = mB[0] + mB[1]; v_ca = mC[0] + mC[1];
+                    const float t0 = dya * mA[0], t1 = dyb * mA[1];
+                    v_my = t0 + t1;
+                    v_cd = dya * t0 + dyb * t1;
+                    v_cbc = dya * mB[0] + dyb * mB[1];
                 }
             }
             // ---- reduce the ten sums over the 64 lanes (wave_sum10_addtid, fgs_wave.h) and store them straight
