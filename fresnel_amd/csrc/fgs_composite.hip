@@ -57,6 +57,17 @@ __device__ __forceinline__ float phase_sin(float x) {
 }
 constexpr int CH = 64;                                      // records per LDS chunk (one per lane)
 
+// The blend kernels' alpha (fgs_internal.h, "opacity fold"): every forward whose checkpoints k_composite_bwd restarts from,
+// and the backward itself, form a' = alpha / 0.99 with these two functions, so the backward recomputes the forward's T to the bit.
+// lop of a staged opacity >= 0: log2(op / 0.99); -inf for opacity 0 (a' = exp2(-inf) = 0: this unit is built with
+// -fno-finite-math-only and must stay so).  Negative and NaN opacities never reach a pass (stage_decode / stage_decode_w).
+__device__ __forceinline__ float blend_lop(float opacity) { return __builtin_log2f(opacity / ALPHA_MAX); }
+// a' = clamp01(exp2(e)) on the lanes of the mask, e = m' + lop: v_exp_f32 ... clamp (v_med3(x, 0, 1) of the v_exp's result
+// folds into its clamp modifier) and one v_and
+__device__ __forceinline__ float blend_alpha1(float e, uint32_t mask) {
+    return __uint_as_float(__float_as_uint(__builtin_amdgcn_fmed3f(__builtin_amdgcn_exp2f(e), 0.0f, 1.0f)) & mask);
+}
+
 struct TileCtx {
     uint32_t tile, b, tx, ty, X0, Y0, start, end;
 };
@@ -91,7 +102,7 @@ __device__ __forceinline__ TileCtx tile_ctx(uint32_t tiles, uint32_t tiles_x,
 //
 // Per-record work is decided once, at staging time, in parallel over the chunk: stage_decode (fgs_wave.h) leaves a flags
 // word (touched sub-tiles, ...) and 32 pixel bits; in the list loop a lane turns its column / row bit into an all-ones /
-// zero mask with v_bfe_i32 and and-s it onto G -- no per-pixel compare / select (issue costs: DESIGN.md section 4).
+// zero mask with v_bfe_i32 and and-s it onto a' = alpha / 0.99 -- no per-pixel compare / select (issue costs: DESIGN.md section 4).
 // SKIP: FgsDims.saturation_skip (separate instantiation).
 
 template <int FWD_WAVES, bool SKIP>
@@ -158,6 +169,9 @@ __global__ __launch_bounds__(64 * FWD_WAVES) void k_composite_fwd(
             uint32_t flags, bits;  // flags: touched sub-tiles (none when the opacity is negative); bits: pixel masks
             stage_decode(c.X0, c.Y0, bbx, bby, q1.y, flags, bits);
             q2.z = __uint_as_float(bits); q2.w = __uint_as_float(flags);
+            // the alpha of k_blend_fwd_parts and of the backward (see there): a' = alpha / 0.99 from the v_exp, colours x 0.99
+            q1.y = blend_lop(q1.y);
+            q1.z *= ALPHA_MAX; q1.w *= ALPHA_MAX; q2.x *= ALPHA_MAX; q2.y *= ALPHA_MAX;
             sh0[threadIdx.x] = q0; sh1[threadIdx.x] = q1; sh2[threadIdx.x] = q2;
         }
         __syncthreads();
@@ -166,7 +180,7 @@ __global__ __launch_bounds__(64 * FWD_WAVES) void k_composite_fwd(
             {
                 // Non-phase blend.  Most list entries touch only one or two of a wave's sub-tiles, so nothing is
                 // precomputed beyond the row terms; bbox membership = the lane's column / row bit of the staged
-                // pixel bits as an all-ones / zero mask (v_bfe_i32) and-ed onto G (no compare / select).
+                // pixel bits as an all-ones / zero mask (v_bfe_i32) and-ed onto a' (no compare / select).
                 const uint32_t msk = __builtin_amdgcn_readfirstlane(__float_as_uint(q2.w)) & (SKIP ? alive : 15u);
                 if (!(msk & (((1u << NS) - 1u) << (wave * NS)))) continue;
                 const uint32_t bits = __float_as_uint(q2.z);
@@ -174,7 +188,7 @@ __global__ __launch_bounds__(64 * FWD_WAVES) void k_composite_fwd(
                 for (int row = 0; row < NR; ++row) {
                     if (NS == 4 && !((msk >> (2 * row)) & 3u)) continue;
                     const float dy = (NS == 4 && row) ? fy0 + 8.0f - q0.y : fy0 - q0.y;
-                    const float bdy = q0.w * dy, cyy = (q1.x * dy) * dy;
+                    const float bdy = q0.w * dy, cyy = fmaf(q1.x * dy, dy, q1.y);  // lop included
                     const uint32_t my = (uint32_t)__builtin_amdgcn_sbfe((int)bits, shy + 8u * row, 1);
 #pragma unroll
                     for (int col = 0; col < NC; ++col) {
@@ -184,11 +198,10 @@ __global__ __launch_bounds__(64 * FWD_WAVES) void k_composite_fwd(
                         const float dx = (col ? fx1 : fx0) - q0.x;
                         const float t = q0.z * dx + bdy;
                         const uint32_t mk = my & (uint32_t)__builtin_amdgcn_sbfe((int)bits, shx + 8u * col, 1);
-                        const float G = __uint_as_float(__float_as_uint(__builtin_amdgcn_exp2f(t * dx + cyy)) & mk);
-                        const float alpha = fminf(G * q1.y, 0.99f);  // opacity >= 0 here: no lower clamp needed
-                        const float w = alpha * T[s];
+                        const float a1 = blend_alpha1(t * dx + cyy, mk);  // alpha / 0.99
+                        const float w = a1 * T[s];                       // (alpha T) / 0.99
                         Cr[s] += w * q1.z; Cg[s] += w * q1.w; Cb[s] += w * q2.x; Dm[s] += w * q2.y;
-                        T[s] -= w;
+                        T[s] = fmaf(w, -ALPHA_MAX, T[s]);
                     }
                 }
                 continue;
@@ -330,11 +343,12 @@ __global__ __launch_bounds__(64 * NP * (1 + WIDE)) __attribute__((amdgpu_waves_p
             const uint32_t slot = __builtin_amdgcn_mbcnt_hi((uint32_t)(tmask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)tmask, 0u));
             q0.z *= NEG_HALF_LOG2E; q0.w *= NEG_HALF_LOG2E; q1.x *= NEG_HALF_LOG2E;
             q2.z = __uint_as_float(cbits); q2.w = __uint_as_float(flags);
-            // alpha = min(G op, 0.99) = 0.99 clamp01(G op / 0.99): the list loop forms a' = clamp01(G op') with the
-            // FREE clamp modifier of v_mul instead of a v_min (4.3 issue cycles on gfx950), the 0.99 rides on the
-            // colours / depth (w c = (a' T)(0.99 c)) and on the transmittance update (T -= 0.99 a' T, one v_fmac with a
-            // literal): one instruction and ~10 % of the pass's issue cycles less
-            q1.y = q1.y / ALPHA_MAX;
+            // alpha = min(G op, 0.99) = 0.99 a', a' = clamp01(G op') with op' = op / 0.99, and G op' = exp2(m' + log2 op'):
+            // the list loop adds lop = log2 op' to the row term of the exponent (the FMA that forms it costs what the
+            // multiply did) and takes a' from the v_exp itself with the FREE clamp modifier -- no per-pixel multiply, no
+            // v_min (4.3 issue cycles on gfx950).  The 0.99 rides on the colours / depth (w c = (a' T)(0.99 c)) and on
+            // the transmittance update (T -= 0.99 a' T, one v_fmac with a literal).
+            q1.y = blend_lop(q1.y);
             q1.z *= ALPHA_MAX; q1.w *= ALPHA_MAX; q2.x *= ALPHA_MAX; q2.y *= ALPHA_MAX;
             sh0[wave][slot] = q0; sh1[wave][slot] = q1; sh2[wave][slot] = q2;
         }
@@ -356,7 +370,7 @@ __global__ __launch_bounds__(64 * NP * (1 + WIDE)) __attribute__((amdgpu_waves_p
             for (int row = 0; row < 2; ++row) {
                 if (!((msk >> (2 * row)) & 3u)) continue;
                 const float dy = row ? fy0 + 8.0f - q0.y : fy0 - q0.y;
-                const float bdy = q0.w * dy, cyy = (q1.x * dy) * dy;
+                const float bdy = q0.w * dy, cyy = fmaf(q1.x * dy, dy, q1.y);  // the row's part of the exponent, lop included
                 const uint32_t my = (uint32_t)__builtin_amdgcn_sbfe((int)rbits, shy + 8u * row, 1);
 #pragma unroll
                 for (int col = 0; col < 2; ++col) {
@@ -364,11 +378,8 @@ __global__ __launch_bounds__(64 * NP * (1 + WIDE)) __attribute__((amdgpu_waves_p
                     if (!((msk >> s) & 1u)) continue;  // scalar branch: sub-tile not touched
                     const float dx = dxc[col];
                     const float t = q0.z * dx + bdy;
-                    float G = __builtin_amdgcn_exp2f(t * dx + cyy);
                     const uint32_t mk = my & mxc[col];
-                    G = __uint_as_float(__float_as_uint(G) & mk);
-                    // alpha / 0.99 (opacity >= 0 here); v_med3(x, 0, 1) of a product folds into the product's clamp modifier
-                    const float a1 = __builtin_amdgcn_fmed3f(G * q1.y, 0.0f, 1.0f);
+                    const float a1 = blend_alpha1(t * dx + cyy, mk);  // alpha / 0.99, zero outside the bbox
                     const float w = a1 * T[s];  // (alpha T) / 0.99
                     Cr[s] += w * q1.z; Cg[s] += w * q1.w; Cb[s] += w * q2.x; Dm[s] += w * q2.y;
                     T[s] = fmaf(w, -ALPHA_MAX, T[s]);
@@ -576,10 +587,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NSX == 2 ? 6
             stage_decode_w<NSX>(c.X0, c.Y0, bbx, bby, q1.y, flags, cbits, conic_ok);
             q2.z = __uint_as_float(cbits); q2.w = __uint_as_float(flags);
             q0.z *= NEG_HALF_LOG2E; q0.w *= NEG_HALF_LOG2E; q1.x *= NEG_HALF_LOG2E;  // conic in exp2 units
-            // alpha = 0.99 a', a' = clamp01(G op / 0.99) (free clamp modifier instead of a v_min, as in the forward); the
-            // list loop works with w' = a' T = w / 0.99 and colours c' = 0.99 c, so that w q = w' q'; its sums come out
-            // as 0.99 x (moments, sum dG) and 1 / 0.99 x (colour, depth) and k_row_sum puts the factors back
-            q1.y = q1.y / ALPHA_MAX;
+            // alpha = 0.99 a', a' = clamp01(G op') = clamp01(exp2(m' + lop)), op' = op / 0.99, lop = log2 op' riding on the row
+            // terms of the exponent exactly as in the forward (blend_lop, blend_alpha1): the recomputed a', w and T are the
+            // forward's to the bit.  The list loop works with w' = a' T = w / 0.99 and colours c' = 0.99 c, so that w q = w' q',
+            // and its dalpha is 0.99 dL/dalpha.  The pass has a' where it had G, so it accumulates dG = dalpha a' = op dL/dalpha G.
+            // ROW CONTRACT with k_row_sum (fgs_project.hip), X = the sums of dL/dalpha G {dx, dy, dx^2, dx dy, dy^2, 1}:
+            //   moment rows and the sum-dG row = opacity X, colour / depth rows = 1 / 0.99 x theirs;
+            //   opacities below the floor of fgs_opacity_floored (fgs_internal.h; exactly 0 included, whose dL/dopacity is not
+            //   zero): the EXACT lop = -64 is folded instead of theirs, a' = 2^-64 G, and the rows are
+            //   0.99 2^-64 X and (2^-64 / op') / 0.99 x (colour, depth).
+            // A floored entry's a' is not the forward's (which folds the true lop, -inf for opacity 0): both are below
+            // 5.5e-20, where T (1 - 0.99 a') rounds to T and w q moves S by less than 1e-19 |q|.
+            q1.y = fgs_opacity_floored(q1.y) ? FGS_FOLD_FLOOR_LOG2 : blend_lop(q1.y);
             q1.z *= ALPHA_MAX; q1.w *= ALPHA_MAX; q2.x *= ALPHA_MAX; q2.y *= ALPHA_MAX;
             sh0[lane] = q0; sh1[lane] = q1; sh2[lane] = q2;
         }
@@ -589,16 +608,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NSX == 2 ? 6
             const uint32_t fl = __builtin_amdgcn_readfirstlane(__float_as_uint(q2.w));  // stage_decode_w flags
             const uint32_t msk = fl & alive;
             const uint32_t cbits = __float_as_uint(q2.z), rbits = __float_as_uint(q2.w);  // column bits; row bits at 16+
-            const float ca = q0.z, cbc = q0.w, cd = q1.x, op = q1.y;  // conic pre-multiplied by K = -log2(e)/2
-            // terms shared by the sub-tiles of a column / row, formed once per list entry
+            const float ca = q0.z, cbc = q0.w, cd = q1.x, lop = q1.y;  // conic pre-multiplied by K = -log2(e)/2; log2(opacity / 0.99)
+            // terms shared by the sub-tiles of a column / row, formed once per list entry; the row's term of the exponent carries lop
             const float dxa = fx0 - q0.x, dya = fy0 - q0.y, dyb = dya + 8.0f;
-            float bdya = cbc * dya, bdyb = cbc * dyb, cyya = (cd * dya) * dya, cyyb = (cd * dyb) * dyb;
+            float bdya = cbc * dya, bdyb = cbc * dyb, cyya = fmaf(cd * dya, dya, lop), cyyb = fmaf(cd * dyb, dyb, lop);
             asm("" : "+v"(bdya), "+v"(bdyb), "+v"(cyya), "+v"(cyyb));  // keep the row terms: do not recompute them per sub-tile
             // bbox membership: the lane's column / row bits of the staged pixel bits become all-ones / zero masks
             // (v_bfe_i32) and zero G with a bit-and -- no per-pixel compare / select (issue costs: DESIGN.md).
-            // per-lane partial sums over this lane's (up to 2 NSX) pixels: moments of dL/dG about the Gaussian's mean, sum dG
-            // {dx, dy, dx^2, dx dy, dy^2, 1}; the ln2 * opacity and K factors of the chain through m' = K m are
-            // applied once per Gaussian in k_project_bwd.  ROW_MOMENTS (32 x 16 tiles): a lane's pixels lie on TWO values of dy
+            // per-lane partial sums over this lane's (up to 2 NSX) pixels: moments of dG = dalpha a' about the Gaussian's mean, sum dG
+            // {dx, dy, dx^2, dx dy, dy^2, 1}; the ln2 and K factors of the chain through m' = K m and the factors of the
+            // row contract (at the staging above) are applied once per Gaussian in k_row_sum.  ROW_MOMENTS (32 x 16 tiles): a lane's pixels lie on TWO values of dy
             // (dya, dyb: one per sub-tile row), so a pass accumulates only the row's A_r = sum dG, B_r = sum dG dx, C_r = sum dG dx^2 (five
             // ops instead of nine) and the dy factors are applied once per list entry, in the fold behind the passes:
             //   {1, dx, dx^2} = A0 + A1, B0 + B1, C0 + C1;  dy = dya A0 + dyb A1;  dx dy = dya B0 + dyb B1;
@@ -610,7 +629,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NSX == 2 ? 6
             float v_mx = 0, v_my = 0, v_ca = 0, v_cbc = 0, v_cd = 0, v_op = 0, v_r = 0, v_g = 0, v_b = 0, v_d = 0;
             float mA[2] = {0.0f, 0.0f}, mB[2] = {0.0f, 0.0f}, mC[2] = {0.0f, 0.0f};  // per sub-tile row (ROW_MOMENTS)
             {   // ONE code path for every kind of entry; what differs is handled by a wave-uniform branch around two
-                // ops: `clamp` (flag bit 4 clear: opacity > 0.98 or a doubtful conic): the clamp-gradient select.
+                // ops: `clamp` (flag bit 8 clear: opacity > 0.98 or a doubtful conic): the clamp-gradient select.
                 // (Four specialised instantiations of this loop body made the compiler carry T and S through eight
                 // v_mov per list entry and were 5 % slower.)
                 uint32_t cflag = fl & 256u;  // clear: `clamp`.  Kept as a scalar and tested where it is used: as a bool the
@@ -628,14 +647,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NSX == 2 ? 6
 #pragma unroll
                 for (int s = 0; s < NS; ++s) {
                     if (!((msk >> s) & 1u)) continue;  // scalar branch: sub-tile not touched
-                    // G is zeroed outside the bbox: alpha, w and every gradient term below then vanish by themselves
+                    // a' is zeroed outside the bbox: w and every gradient term below then vanish by themselves
                     const int col = s % NSX, row = s / NSX;
                     const uint32_t mk = mxs[col] & (row ? my1 : my0);
                     const float dx = dxs[col], dy = row ? dyb : dya;
                     const float t = ca * dx + (row ? bdyb : bdya);
-                    const float Gu = __builtin_amdgcn_exp2f(t * dx + (row ? cyyb : cyya));
-                    const float G = __uint_as_float(__float_as_uint(Gu) & mk);
-                    const float a1 = __builtin_amdgcn_fmed3f(G * op, 0.0f, 1.0f);  // alpha / 0.99: v_mul ... clamp
+                    const float a1 = blend_alpha1(t * dx + (row ? cyyb : cyya), mk);  // alpha / 0.99: v_exp ... clamp, v_and
                     const float w = a1 * T[s];  // w / 0.99
                     const float q = gr[s] * q1.z + gg[s] * q1.w + gb[s] * q2.x + gd[s] * q2.y;  // 0.99 q
                     S[s] -= w * q;
@@ -645,7 +662,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NSX == 2 ? 6
                     uint32_t cf = cflag;
                     asm("" : "+s"(cf));  // an opaque scalar per use: one s_cmp + branch, nothing on the vector side
                     if (!cf) dalpha = select_lt(a1, 1.0f, dalpha);  // the clamp binds where G op / 0.99 reaches 1
-                    const float dG = dalpha * G;
+                    const float dG = dalpha * a1;  // op' x (0.99 dL/dalpha G): the opacity is already in the rows
                     if constexpr (ROW_MOMENTS) {
                         mA[row] += dG;
                         const float dmx = dG * dx;

@@ -113,6 +113,29 @@ __device__ __forceinline__ uint32_t fgs_xcd_remap(uint32_t bid, uint32_t nwg) {
     return (xcd < r ? xcd * (q + 1u) : r * (q + 1u) + (xcd - r) * q) + i;
 }
 
+// Opacity fold of the blend kernels (fgs_composite.hip) and the row contract that follows from it (k_row_sum, fgs_project.hip).
+// alpha / 0.99 = clamp01(G op'), op' = opacity / 0.99, is formed as clamp01(exp2(m' + log2 op')): the opacity rides on the
+// exponent's per-row term and the per-pixel multiply is gone.  The backward then accumulates dL/dalpha . a' = op' . dL/dalpha . G
+// where it had dL/dalpha . G: its moment rows already carry the opacity, and its sum-dG row (dL/dopacity) has to be DIVIDED by
+// the opacity -- impossible at opacity 0, whose dL/dopacity is not zero.  So the backward folds a FLOOR: for op' < 2^-64 it takes
+// lop = -64 exactly, a' = 2^-64 G, and k_row_sum takes the exact power of two out again and puts the true opacity where it belongs.
+// Why 2^-64, and no multiplier in the pass that would restore the true alpha of a floored entry:
+//  * alpha <= 0.99 x 2^-64 = 5.4e-20 is below every fp32 effect on the transmittance (T (1 - alpha) rounds to T from alpha <
+//    2^-25 on), so the backward may run with 2^-64 G where the forward ran with the smaller true alpha.  With a floor such as
+//    2^-16 the true alpha would have to be restored per pixel, and a second per-pixel value (alpha next to the factor of dG)
+//    live across the backward's wave-uniform clamp block costs the common class a v_mov per pass -- what the fold saves;
+//  * 2^-64 G, dalpha 2^-64 G and their moments stay normal fp32 numbers down to G = 2^-60, further than a bbox reaches;
+//  * the price is the rounding of the exponent m' + lop: half an ulp of a number below 2 |lop|, times ln 2, relative in alpha --
+//    1.3e-6 for op' >= 2^-16 (the size of the forward's parity with the oracle before the fold, 2e-6), at most 5.3e-6 for
+//    opacities down to the floor, whose alpha is below 1.6e-5 to begin with; the forward folds the true lop of any opacity anyway.
+// The test is on the fp32 opacity ITSELF against an exact constant, so that translation units with different floating-point
+// flags (fast-math reciprocals there, IEEE division here) cannot disagree about a Gaussian.  (Negative and NaN opacities count
+// as floored; they never reach a pass and their rows are zero.)
+constexpr float FGS_FOLD_FLOOR_LOG2 = -64.0f;
+constexpr float FGS_FOLD_FLOOR = 5.42101086242752217e-20f;            // 2^-64
+constexpr float FGS_FOLD_MIN_OPACITY = 0.99f * FGS_FOLD_FLOOR;        // exact: a power-of-two multiple of 0.99f
+__host__ __device__ __forceinline__ bool fgs_opacity_floored(float opacity) { return !(opacity >= FGS_FOLD_MIN_OPACITY); }
+
 // order-preserving map float -> uint32 (ascending), -0.0 folded into +0.0
 __device__ __forceinline__ uint32_t fgs_float_key(float f) {
     f = f + 0.0f;

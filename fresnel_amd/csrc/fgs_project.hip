@@ -237,7 +237,8 @@ __global__ __launch_bounds__(256) void k_fourier_project(
 // DEPTH-RANK order (rows are laid out in emission order, so neighbouring lanes read neighbouring rows), lane `sub`
 // takes rows sub, sub + 4, ..., two rows in flight per lane; moments in double; two quad shuffles combine the partial
 // sums.  The totals get the factors of the chain through m' = K m, G = exp2(m'), alpha = G opacity (first moments x
-// ln2 opacity, second moments x K ln2 opacity) and go to sums[input index][12].  Streaming kernel: ~40 VGPRs, full occupancy.
+// ln2 opacity, second moments x K ln2 opacity; the opacity is already IN the rows of a Gaussian whose opacity the blend
+// kernels fold into the exponent, see below) and go to sums[input index][12].  Streaming kernel: ~40 VGPRs, full occupancy.
 __global__ __launch_bounds__(256) void k_row_sum(int32_t total, int32_t N, uint32_t dcap,
                                                  const uint32_t *__restrict__ order,
                                                  const uint32_t *__restrict__ dup_off,
@@ -292,13 +293,24 @@ __global__ __launch_bounds__(256) void k_row_sum(int32_t total, int32_t N, uint3
             acc[6] += dq.x; acc[7] += dq.y; acc[8] += eq.x; acc[9] += eq.y;
         }
 #endif
-        // k_composite_bwd works with alpha / 0.99 and 0.99 x colours: its moment and sum-dG rows carry a factor 0.99, its
-        // colour / depth rows 1 / 0.99
-        const double ia = 1.0 / (double)0.99f;
-        const double hp = 0.69314718055994530942 * (double)rec[(size_t)idx * FGS_REC_FLOATS + R_OP] * ia;
+        // k_composite_bwd works with a' = alpha / 0.99 = clamp01(exp2(m' + log2(opacity / 0.99))) and 0.99 x colours, and accumulates
+        // dalpha a' (row contract: fgs_composite.hip, at the backward's staging; fgs_internal.h, "opacity fold").  With X = the sums
+        // of dL/dalpha G {dx, ..., 1}, its moment and sum-dG rows are opacity X and its colour / depth rows 1 / 0.99 x theirs:
+        //   first moments x ln2, second x K ln2 (the opacity of the chain is in the rows), sum dG x 1 / opacity, colours x 0.99.
+        // Floored opacities (0 included) were folded as 0.99 x 2^-64: rows 0.99 2^-64 X, colour / depth rows 2^-64 / op' too
+        // large -- the power of two comes out exactly and the true opacity goes in.
+        const float opacity = rec[(size_t)idx * FGS_REC_FLOATS + R_OP];
+        const bool floored = fgs_opacity_floored(opacity);
+        const double unfloor = 1.0 / ((double)0.99f * (double)FGS_FOLD_FLOOR);  // 2^64 / 0.99
+        const double hp = 0.69314718055994530942 * (floored ? (double)opacity * unfloor : 1.0);
         acc[0] = (float)(hp * m[0]); acc[1] = (float)(hp * m[1]);
         acc[2] = (float)(-0.72134752044448170368 * hp * m[2]); acc[3] = (float)(-0.72134752044448170368 * hp * m[3]);
-        acc[4] = (float)(-0.72134752044448170368 * hp * m[4]); acc[5] = (float)(m[5] * ia);
+        acc[4] = (float)(-0.72134752044448170368 * hp * m[4]);
+        acc[5] = (float)(m[5] * (floored ? unfloor : 1.0 / (double)opacity));
+        if (floored) {  // w of the pass was (2^-64 / op') x the true one
+            const float back = (float)((double)opacity * unfloor);
+            acc[6] *= back; acc[7] *= back; acc[8] *= back; acc[9] *= back;
+        }
         acc[6] *= 0.99f; acc[7] *= 0.99f; acc[8] *= 0.99f; acc[9] *= 0.99f;
     }
 #pragma unroll

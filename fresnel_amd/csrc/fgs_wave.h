@@ -35,7 +35,10 @@ __device__ __forceinline__ void stage_decode(uint32_t X0, uint32_t Y0, uint32_t 
 
 // The same for a tile of NSX x 2 sub-tiles (16 or 32 pixels wide), depth-split forward and blend backward:
 //   flags  bits 0 .. 2 NSX - 1: sub-tile s = row * NSX + col touched (none when the opacity is negative);
-//          bit 8: the alpha clamp cannot bind (opacity <= 0.98 and `conic_ok`); bits 16-31: pixel row Y0 + i in [y0, y1);
+//          bit 8: the alpha clamp cannot bind (opacity <= 0.98 and `conic_ok`): G op / 0.99 = exp2(m' + log2(opacity / 0.99)), as
+//                 the blend kernels form it (the opacity folded into the exponent, fgs_internal.h), stays below 1 whatever the
+//                 pixel, so the clamp modifier of the v_exp is idle and the backward needs no clamp-gradient select;
+//          bits 16-31: pixel row Y0 + i in [y0, y1);
 //   cbits  bit i (i < 8 NSX): pixel column X0 + i lies in [x0, x1).
 template <int NSX>
 __device__ __forceinline__ void stage_decode_w(uint32_t X0, uint32_t Y0, uint32_t bbx, uint32_t bby, float op,
