@@ -570,7 +570,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NSX == 2 ? 6
     float fx0 = (float)(c.X0 + lx), fy0 = (float)(c.Y0 + ly);
     asm("" : "+v"(fx0), "+v"(fy0));  // hoisted for good: no v_cvt in the list loop
     for (uint32_t base = c.start; base < c.end; base += CH) {
-        const uint32_t n = min((uint32_t)CH, c.end - base);
+        // the list loop's trip count, pinned to an SGPR: left to itself the compiler keeps it in a VGPR (it is compared with `lane`
+        // here) and counts the list loop down with a v_add_u32 / v_cmp_eq_u32 pair per entry
+        const uint32_t n = __builtin_amdgcn_readfirstlane(min((uint32_t)CH, c.end - base));
         if (lane < n) {
             const uint32_t gid = dup_ids[base + lane];
             const float4 *r = reinterpret_cast<const float4 *>(rec + (size_t)gid * FGS_REC_FLOATS);
@@ -644,12 +646,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NSX == 2 ? 6
                     dxs[col] = dxa + 8.0f * col;
                 }
                 const uint32_t my0 = (uint32_t)__builtin_amdgcn_sbfe((int)rbits, shy, 1), my1 = (uint32_t)__builtin_amdgcn_sbfe((int)rbits, shy + 8u, 1);
-#pragma unroll
-                for (int s = 0; s < NS; ++s) {
-                    if (!((msk >> s) & 1u)) continue;  // scalar branch: sub-tile not touched
+                // One sub-tile pass.  A lambda called from the unrolled sub-tile loop, not the loop's body: the same arithmetic, but
+                // the compiler then updates the sums in place (v_fmac where it had v_fma into a copy) and spills one dword of
+                // k_composite_bwd<4> instead of five -- 2.9 fewer VALU instructions per list entry (DESIGN_LOG.md 17)
+                auto pass = [&](const int s, const uint32_t mk) {
                     // a' is zeroed outside the bbox: w and every gradient term below then vanish by themselves
                     const int col = s % NSX, row = s / NSX;
-                    const uint32_t mk = mxs[col] & (row ? my1 : my0);
                     const float dx = dxs[col], dy = row ? dyb : dya;
                     const float t = ca * dx + (row ? bdyb : bdya);
                     const float a1 = blend_alpha1(t * dx + (row ? cyyb : cyya), mk);  // alpha / 0.99: v_exp ... clamp, v_and
@@ -674,6 +676,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NSX == 2 ? 6
                         v_ca += dmx * dx; v_cbc += dmx * dy; v_cd += dmy * dy;
                     }
                     v_r += w * gr[s]; v_g += w * gg[s]; v_b += w * gb[s]; v_d += w * gd[s];
+                };
+#pragma unroll
+                for (int s = 0; s < NS; ++s) {
+                    if (!((msk >> s) & 1u)) continue;  // scalar branch: sub-tile not touched
+                    pass(s, mxs[s % NSX] & (s / NSX ? my1 : my0));
                 }
                 if constexpr (ROW_MOMENTS) {  // fold the rows: once per list entry, ten ops
                     v_op = mA[0] + mA[1]; v_mx = mB[0] + mB[1]; v_ca = mC[0] + mC[1];
