@@ -569,6 +569,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NSX == 2 ? 6
     }
     float fx0 = (float)(c.X0 + lx), fy0 = (float)(c.Y0 + ly);
     asm("" : "+v"(fx0), "+v"(fy0));  // hoisted for good: no v_cvt in the list loop
+    // The reduction of a list entry's ten sums is DEFERRED by one entry: the passes of entry j end with the sums parked in `red`
+    // (addtid_park10), and the read-back, the adds and the row store happen at the top of entry j + 1, where their LDS reads travel
+    // together with that entry's record reads -- one exposed LDS round trip per entry instead of three (record; parked sums; row
+    // index).  One wave's LDS instructions execute in order, so the read-back of entry j is served before entry j + 1 parks its own
+    // sums in the same cells.  e_prev: row of the entry whose sums are parked (none yet: no row passes e < dcap).
+    uint32_t e_prev = ~0u;
+    auto reduce_parked = [&]() {
+        const float tot = wave_sum_addtid_finish(red, lane, 10u);
+        // (16-float rows: all sixteen quads' last lanes store, lanes >= 40 a zero -- one whole 64-byte line)
+        if ((lane & 3u) == 3u && lane < 4u * FGS_BLEND_ROW_FLOATS && e_prev < dcap) grad_rows[(size_t)e_prev * FGS_BLEND_ROW_FLOATS + (lane >> 2)] = tot;
+    };
     for (uint32_t base = c.start; base < c.end; base += CH) {
         // the list loop's trip count, pinned to an SGPR: left to itself the compiler keeps it in a VGPR (it is compared with `lane`
         // here) and counts the list loop down with a v_add_u32 / v_cmp_eq_u32 pair per entry
@@ -607,6 +618,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NSX == 2 ? 6
         __syncthreads();
         for (uint32_t j = 0; j < n; ++j) {
             const float4 q0 = sh0[j], q1 = sh1[j], q2 = sh2[j];
+            uint32_t e = __builtin_amdgcn_readfirstlane(she[j]);
+            reduce_parked();  // the previous entry's sums
+            asm volatile("" : "+s"(e));  // taken here, with the record: left to the end of the entry it waits for the parking stores
+            e_prev = e;
             const uint32_t fl = __builtin_amdgcn_readfirstlane(__float_as_uint(q2.w));  // stage_decode_w flags
             const uint32_t msk = fl & alive;
             const uint32_t cbits = __float_as_uint(q2.z), rbits = __float_as_uint(q2.w);  // column bits; row bits at 16+
@@ -690,18 +705,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NSX == 2 ? 6
                     v_cbc = dya * mB[0] + dyb * mB[1];
                 }
             }
-            // ---- reduce the ten sums over the 64 lanes (wave_sum10_addtid, fgs_wave.h) and store them straight
-            // into this duplicate's gradient row: no atomics, fixed order, bitwise reproducible ----
+            // ---- park the ten sums (fgs_wave.h); the next entry, or the end of the unit, adds them up over the 64 lanes in a fixed
+            // order and stores them straight into this duplicate's gradient row: no atomics, bitwise reproducible ----
             {
                 const float vals[10] = {v_mx, v_my, v_ca, v_cbc, v_cd, v_op, v_r, v_g, v_b, v_d};
-                const float tot = wave_sum10_addtid(red, vals, lane);
-                const uint32_t kk = lane >> 2, e = she[j];
-                // (16-float rows: all sixteen quads' last lanes store, lanes >= 40 a zero -- one whole 64-byte line)
-                if ((lane & 3u) == 3u && lane < 4u * FGS_BLEND_ROW_FLOATS && e < dcap) grad_rows[(size_t)e * FGS_BLEND_ROW_FLOATS + kk] = tot;
+                addtid_park10((uint32_t)(uintptr_t)(fgs_lds_float *)red, vals);
             }
         }
         __syncthreads();
     }
+    reduce_parked();  // the unit's last entry
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
