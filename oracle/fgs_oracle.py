@@ -167,8 +167,10 @@ class Rendered:
 
 
 def render(pos, scale, quat, color, opacity, cam, bg=(0.0, 0.0, 0.0), max_radius=64.0,
-           phases=None, phase_amp=0.25, keep_pairs=True):
-    """Oracle forward for ONE image: returns Rendered with .image (3,H,W), .depth (H,W)."""
+           phases=None, phase_amp=0.25, keep_pairs=True, proj=None):
+    """Oracle forward for ONE image: returns Rendered with .image (3,H,W), .depth (H,W).
+    proj: composite THIS projection (a dict as project() returns, e.g. an earlier run's with a bbox moved) instead of projecting
+    the Gaussians; the depth order is taken from its depths and visibility.  Default: project here, as always."""
     global _REAL, _CREAL
     r = Rendered()
     r.pos, r.scale, r.quat = _f32(pos), _f32(scale), _f32(quat)
@@ -177,8 +179,9 @@ def render(pos, scale, quat, color, opacity, cam, bg=(0.0, 0.0, 0.0), max_radius
     r.phases = None if phases is None else _f32(phases)
     r.phase_amp = float(phase_amp)
     W, H = cam.width, cam.height
-    r.proj = project(r.pos, r.scale, r.quat, cam, max_radius)
-    if _REAL is np.float64:
+    r.proj = project(r.pos, r.scale, r.quat, cam, max_radius) if proj is None else {
+        k: np.ascontiguousarray(v, dtype=v.dtype if k in ("visible", "bbox") else _REAL) for k, v in proj.items()}
+    if proj is None and _REAL is np.float64:
         # the fp64 REFEREE keeps the fp32 run's INTEGER stages (visibility, bboxes, depth order) -- like the reference-derived fp64 runs
         # of the K1 / K2 fixtures (tests/golden/make_goldens.py phase_restatement) -- so that it differs from the fp32 run by arithmetic
         # precision alone, not by a bbox edge that lands on the other side of a pixel
