@@ -60,7 +60,7 @@ constexpr int CH = 64;                                      // records per LDS c
 // The blend kernels' alpha (fgs_internal.h, "opacity fold"): every forward whose checkpoints k_composite_bwd restarts from,
 // and the backward itself, form a' = alpha / 0.99 with these two functions, so the backward recomputes the forward's T to the bit.
 // lop of a staged opacity >= 0: log2(op / 0.99); -inf for opacity 0 (a' = exp2(-inf) = 0: this unit is built with
-// -fno-finite-math-only and must stay so).  Negative and NaN opacities never reach a pass (stage_decode / stage_decode_w).
+// -fno-finite-math-only and must stay so).  Negative and NaN opacities never reach a pass (stage_decode_w).
 __device__ __forceinline__ float blend_lop(float opacity) { return __builtin_log2f(opacity / ALPHA_MAX); }
 // a' = clamp01(exp2(e)) on the lanes of the mask, e = m' + lop: v_exp_f32 ... clamp (v_med3(x, 0, 1) of the v_exp's result
 // folds into its clamp modifier) and one v_and
@@ -93,6 +93,87 @@ __device__ __forceinline__ TileCtx tile_ctx(uint32_t tiles, uint32_t tiles_x,
     return tile_ctx_of(tile_order ? tile_order[blockIdx.x] : blockIdx.x, tiles, tiles_x, ranges, tile_w);
 }
 
+// Checkpoints are a write-once / read-once stream (307 MB per config-3 step against 12.6 MB of records).  Non-temporal
+// stores / loads for them (FGS_CKPT_NT=1) were measured in round 3 and are OFF: WRITE_SIZE of the forward ROSE from 450
+// to 547 MB per launch (the nt stores reach the fabric as more, smaller writes), the backward got 1 % slower, and what
+// actually evicted `rec` from L2 was the launch order, not the checkpoint stream (see order_groups in k_blend_fwd_parts: FETCH_SIZE
+// 330 -> 62 MB).
+#ifndef FGS_CKPT_NT
+#define FGS_CKPT_NT 0
+#endif
+__device__ __forceinline__ void nt_store(float *p, float v) {
+#if FGS_CKPT_NT
+    __builtin_nontemporal_store(v, p);
+#else
+    *p = v;
+#endif
+}
+__device__ __forceinline__ float nt_load(const float *p) {
+#if FGS_CKPT_NT
+    return __builtin_nontemporal_load(p);
+#else
+    return *p;
+#endif
+}
+
+// The staged record of a list entry, as ALL THREE blend kernels park it in LDS (k_composite_fwd, k_blend_fwd_parts, k_composite_bwd):
+// the backward's recomputed a', w and T are the forward's to the bit because the three stage through this one function.
+//   q0 = (u, v, K a, K (b + c)), q1 = (K d, lop, 0.99 r, 0.99 g), q2 = (0.99 b, 0.99 depth, cbits, flags)   (stage_decode_w, fgs_wave.h)
+// with the conic in exp2 units (K = -log2(e) / 2) and lop passed in: blend_lop(opacity) by the forwards; by the backward
+// FGS_FOLD_FLOOR_LOG2 for the opacities fgs_opacity_floored names, blend_lop(opacity) for the rest.
+// alpha = min(G op, 0.99) = 0.99 a', a' = clamp01(G op') with op' = op / 0.99, and G op' = exp2(m' + log2 op'): the list loop adds
+// lop = log2 op' to the row term of the exponent (the FMA that forms it costs what the multiply did) and takes a' from the v_exp
+// itself with the FREE clamp modifier -- no per-pixel multiply, no v_min (4.3 issue cycles on gfx950).  The 0.99 rides on the
+// colours / depth (w c = (a' T)(0.99 c)) and on the transmittance update (T -= 0.99 a' T, one v_fmac with a literal).
+// The backward's list loop works with w' = a' T = w / 0.99 and colours c' = 0.99 c, so that w q = w' q', and its dalpha is
+// 0.99 dL/dalpha.  The pass has a' where it had G, so it accumulates dG = dalpha a' = op dL/dalpha G.
+// ROW CONTRACT with k_row_sum (fgs_project.hip), X = the sums of dL/dalpha G {dx, dy, dx^2, dx dy, dy^2, 1}:
+//   moment rows and the sum-dG row = opacity X, colour / depth rows = 1 / 0.99 x theirs;
+//   opacities below the floor of fgs_opacity_floored (fgs_internal.h; exactly 0 included, whose dL/dopacity is not
+//   zero): the EXACT lop = -64 is folded instead of theirs, a' = 2^-64 G, and the rows are
+//   0.99 2^-64 X and (2^-64 / op') / 0.99 x (colour, depth).
+// A floored entry's a' is not the forward's (which folds the true lop, -inf for opacity 0): both are below
+// 5.5e-20, where T (1 - 0.99 a') rounds to T and w q moves S by less than 1e-19 |q|.
+__device__ __forceinline__ void blend_stage_fold(float4 &q0, float4 &q1, float4 &q2, uint32_t flags, uint32_t cbits, float lop) {
+    q0.z *= NEG_HALF_LOG2E; q0.w *= NEG_HALF_LOG2E; q1.x *= NEG_HALF_LOG2E;
+    q1.y = lop;
+    q1.z *= ALPHA_MAX; q1.w *= ALPHA_MAX; q2.x *= ALPHA_MAX; q2.y *= ALPHA_MAX;
+    q2.z = __uint_as_float(cbits); q2.w = __uint_as_float(flags);
+}
+
+// Per-pixel epilogue of the three forwards (k_composite_fwd, k_blend_fwd_parts, k_phase_fwd), pixel at offset o = y W + x of image b:
+// the saved state (planes C_r, C_g, C_b, A, D of pix_state; plane 5, Phi, belongs to the phase path, whose forward adds it: nobody
+// reads it on the blend path), the clamped image and the depth.  A and T = 1 - A are the caller's: each forward rounds them its way.
+__device__ __forceinline__ void pixel_store(float *__restrict__ pix_state, float *__restrict__ out_rgb, float *__restrict__ out_depth,
+                                            uint32_t b, size_t HW, size_t o, float bg0, float bg1, float bg2, float Cr, float Cg,
+                                            float Cb, float A, float T, float D) {
+    float *ps = pix_state + (size_t)b * 6 * HW + o;
+    nt_store(ps, Cr); nt_store(ps + HW, Cg); nt_store(ps + 2 * HW, Cb); nt_store(ps + 3 * HW, A); nt_store(ps + 4 * HW, D);
+    float *img = out_rgb + (size_t)b * 3 * HW + o;
+    nt_store(img, fminf(fmaxf(Cr + T * bg0, 0.0f), 1.0f));
+    nt_store(img + HW, fminf(fmaxf(Cg + T * bg1, 0.0f), 1.0f));
+    nt_store(img + 2 * HW, fminf(fmaxf(Cb + T * bg2, 0.0f), 1.0f));
+    nt_store(out_depth + (size_t)b * HW + o, D);
+}
+
+// Per-pixel prologue of the two backwards (k_composite_bwd, k_phase_bwd): the forward's saved state and the upstream gradients of the
+// pixel at offset o of image b.  The image's clamp passes its gradient on the CLOSED interval [0, 1] of the unclamped value, which is
+// re-formed from the saved state as pixel_store formed it.  Each kernel builds its own S / Abar from these.
+struct PixelGrad { float gr, gg, gb, gd, Cr, Cg, Cb, Tf, D; };
+__device__ __forceinline__ PixelGrad pixel_grad_load(const float *__restrict__ pix_state, const float *__restrict__ g_rgb,
+                                                     const float *__restrict__ g_depth, uint32_t b, size_t HW, size_t o, float bg0,
+                                                     float bg1, float bg2) {
+    const float *ps = pix_state + (size_t)b * 6 * HW + o;
+    PixelGrad g;
+    g.Cr = ps[0]; g.Cg = ps[HW]; g.Cb = ps[2 * HW]; g.Tf = 1.0f - ps[3 * HW]; g.D = ps[4 * HW];
+    const float pr = g.Cr + g.Tf * bg0, pg = g.Cg + g.Tf * bg1, pb = g.Cb + g.Tf * bg2;
+    const float *gi = g_rgb + (size_t)b * 3 * HW + o;
+    g.gr = (pr >= 0.0f && pr <= 1.0f) ? gi[0] : 0.0f;  // clamp backward, closed interval
+    g.gg = (pg >= 0.0f && pg <= 1.0f) ? gi[HW] : 0.0f;
+    g.gb = (pb >= 0.0f && pb <= 1.0f) ? gi[2 * HW] : 0.0f;
+    g.gd = g_depth[(size_t)b * HW + o];
+    return g;
+}
 
 // Row-split forward of the blend path (FgsDims.saturation_skip and fwd_variant < 0; the default is the depth-split
 // k_blend_fwd_parts below, the phase path has its own kernels, k_phase_fwd / k_phase_bwd).  FWD_WAVES waves per tile: with 2,
@@ -100,8 +181,8 @@ __device__ __forceinline__ TileCtx tile_ctx(uint32_t tiles, uint32_t tiles_x,
 // split is free and halves the serial length of the longest lists); 1 when the launch has enough tiles to fill the chip
 // several times over.  All waves of a block share the LDS-staged chunk of the list.
 //
-// Per-record work is decided once, at staging time, in parallel over the chunk: stage_decode (fgs_wave.h) leaves a flags
-// word (touched sub-tiles, ...) and 32 pixel bits; in the list loop a lane turns its column / row bit into an all-ones /
+// Per-record work is decided once, at staging time, in parallel over the chunk: stage_decode_w (fgs_wave.h) leaves a flags
+// word (touched sub-tiles, row bits) and the column bits; in the list loop a lane turns its column / row bit into an all-ones /
 // zero mask with v_bfe_i32 and and-s it onto a' = alpha / 0.99 -- no per-pixel compare / select (issue costs: DESIGN.md section 4).
 // SKIP: FgsDims.saturation_skip (separate instantiation).
 
@@ -128,7 +209,7 @@ __global__ __launch_bounds__(64 * FWD_WAVES) void k_composite_fwd(
     // sub-tile rows / columns per wave: 4 sub-tiles = 2 x 2, 2 = one row of two, 1 = a single sub-tile
     constexpr int NR = NS == 4 ? 2 : 1, NC = NS == 1 ? 1 : 2;
     const uint32_t row0 = NS == 4 ? 0u : (NS == 2 ? wave : wave >> 1), col0 = NS == 1 ? (wave & 1u) : 0u;
-    // this lane's column / row bit in the staged pixel bits
+    // this lane's column bit in the staged column bits / row bit in the flags
     const uint32_t shx = lx + 8u * col0, shy = 16u + ly + 8u * row0;
     uint32_t alive = 15u;  // sub-tiles still being composited (saturation_skip)
     uint32_t live_segments = (c.end - c.start + FGS_SEG - 1) / FGS_SEG;
@@ -164,14 +245,9 @@ __global__ __launch_bounds__(64 * FWD_WAVES) void k_composite_fwd(
             const uint32_t gid = dup_ids[base + threadIdx.x];
             const float4 *r = reinterpret_cast<const float4 *>(rec + (size_t)gid * FGS_REC_FLOATS);
             float4 q0 = r[0], q1 = r[1], q2 = r[2];
-            q0.z *= NEG_HALF_LOG2E; q0.w *= NEG_HALF_LOG2E; q1.x *= NEG_HALF_LOG2E;
-            const uint32_t bbx = __float_as_uint(q2.z), bby = __float_as_uint(q2.w);
-            uint32_t flags, bits;  // flags: touched sub-tiles (none when the opacity is negative); bits: pixel masks
-            stage_decode(c.X0, c.Y0, bbx, bby, q1.y, flags, bits);
-            q2.z = __uint_as_float(bits); q2.w = __uint_as_float(flags);
-            // the alpha of k_blend_fwd_parts and of the backward (see there): a' = alpha / 0.99 from the v_exp, colours x 0.99
-            q1.y = blend_lop(q1.y);
-            q1.z *= ALPHA_MAX; q1.w *= ALPHA_MAX; q2.x *= ALPHA_MAX; q2.y *= ALPHA_MAX;
+            uint32_t flags, cbits;  // flags: touched sub-tiles (none when the opacity is negative), row bits; cbits: column bits
+            stage_decode_w<2>(c.X0, c.Y0, __float_as_uint(q2.z), __float_as_uint(q2.w), q1.y, flags, cbits);
+            blend_stage_fold(q0, q1, q2, flags, cbits, blend_lop(q1.y));
             sh0[threadIdx.x] = q0; sh1[threadIdx.x] = q1; sh2[threadIdx.x] = q2;
         }
         __syncthreads();
@@ -180,16 +256,16 @@ __global__ __launch_bounds__(64 * FWD_WAVES) void k_composite_fwd(
             {
                 // Non-phase blend.  Most list entries touch only one or two of a wave's sub-tiles, so nothing is
                 // precomputed beyond the row terms; bbox membership = the lane's column / row bit of the staged
-                // pixel bits as an all-ones / zero mask (v_bfe_i32) and-ed onto a' (no compare / select).
+                // column bits / flags as an all-ones / zero mask (v_bfe_i32) and-ed onto a' (no compare / select).
                 const uint32_t msk = __builtin_amdgcn_readfirstlane(__float_as_uint(q2.w)) & (SKIP ? alive : 15u);
                 if (!(msk & (((1u << NS) - 1u) << (wave * NS)))) continue;
-                const uint32_t bits = __float_as_uint(q2.z);
+                const uint32_t cbits = __float_as_uint(q2.z), rbits = __float_as_uint(q2.w);
 #pragma unroll
                 for (int row = 0; row < NR; ++row) {
                     if (NS == 4 && !((msk >> (2 * row)) & 3u)) continue;
                     const float dy = (NS == 4 && row) ? fy0 + 8.0f - q0.y : fy0 - q0.y;
                     const float bdy = q0.w * dy, cyy = fmaf(q1.x * dy, dy, q1.y);  // lop included
-                    const uint32_t my = (uint32_t)__builtin_amdgcn_sbfe((int)bits, shy + 8u * row, 1);
+                    const uint32_t my = (uint32_t)__builtin_amdgcn_sbfe((int)rbits, shy + 8u * row, 1);
 #pragma unroll
                     for (int col = 0; col < NC; ++col) {
                         const int s = NC * row + col;  // index into this wave's state
@@ -197,7 +273,7 @@ __global__ __launch_bounds__(64 * FWD_WAVES) void k_composite_fwd(
                         if (NS > 1 && !((msk >> sg) & 1u)) continue;  // scalar branch: sub-tile not touched
                         const float dx = (col ? fx1 : fx0) - q0.x;
                         const float t = q0.z * dx + bdy;
-                        const uint32_t mk = my & (uint32_t)__builtin_amdgcn_sbfe((int)bits, shx + 8u * col, 1);
+                        const uint32_t mk = my & (uint32_t)__builtin_amdgcn_sbfe((int)cbits, shx + 8u * col, 1);
                         const float a1 = blend_alpha1(t * dx + cyy, mk);  // alpha / 0.99
                         const float w = a1 * T[s];                       // (alpha T) / 0.99
                         Cr[s] += w * q1.z; Cg[s] += w * q1.w; Cb[s] += w * q2.x; Dm[s] += w * q2.y;
@@ -218,16 +294,9 @@ __global__ __launch_bounds__(64 * FWD_WAVES) void k_composite_fwd(
         const uint32_t sg = wave * NS + s;
         const uint32_t px = c.X0 + 8u * (sg & 1) + lx, py = c.Y0 + 8u * (sg >> 1) + ly;
         if (px < W && py < H) {
-            const size_t o = (size_t)py * W + px;
-            float *ps = pix_state + (size_t)c.b * 6 * HW + o;
             const float Af = 1.0f - T[s];
-            ps[0] = Cr[s]; ps[HW] = Cg[s]; ps[2 * HW] = Cb[s]; ps[3 * HW] = Af; ps[4 * HW] = Dm[s];
-            const float T = 1.0f - Af;  // (as the backward will see it)
-            float *img = out_rgb + (size_t)c.b * 3 * HW + o;
-            img[0] = fminf(fmaxf(Cr[s] + T * bg0, 0.0f), 1.0f);
-            img[HW] = fminf(fmaxf(Cg[s] + T * bg1, 0.0f), 1.0f);
-            img[2 * HW] = fminf(fmaxf(Cb[s] + T * bg2, 0.0f), 1.0f);
-            out_depth[(size_t)c.b * HW + o] = Dm[s];
+            pixel_store(pix_state, out_rgb, out_depth, c.b, HW, (size_t)py * W + px, bg0, bg1, bg2, Cr[s], Cg[s], Cb[s], Af,
+                        1.0f - Af /* T as the backward will see it */, Dm[s]);
         }
     }
 }
@@ -249,28 +318,6 @@ __device__ __forceinline__ BlendState compose(const BlendState &a, const BlendSt
     return {a.Cr + a.T * b.Cr, a.Cg + a.T * b.Cg, a.Cb + a.T * b.Cb, a.T * b.T, a.D + a.T * b.D};
 }
 // [5][NS][64] slot (NS = 4 sub-tiles of a 16 x 16 tile, 8 of a 32 x 16 tile), this lane's cell; PL = NS * 64
-// Checkpoints are a write-once / read-once stream (307 MB per config-3 step against 12.6 MB of records).  Non-temporal
-// stores / loads for them (FGS_CKPT_NT=1) were measured in round 3 and are OFF: WRITE_SIZE of the forward ROSE from 450
-// to 547 MB per launch (the nt stores reach the fabric as more, smaller writes), the backward got 1 % slower, and what
-// actually evicted `rec` from L2 was the launch order, not the checkpoint stream (see order_groups above: FETCH_SIZE
-// 330 -> 62 MB).
-#ifndef FGS_CKPT_NT
-#define FGS_CKPT_NT 0
-#endif
-__device__ __forceinline__ void nt_store(float *p, float v) {
-#if FGS_CKPT_NT
-    __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
-}
-__device__ __forceinline__ float nt_load(const float *p) {
-#if FGS_CKPT_NT
-    return __builtin_nontemporal_load(p);
-#else
-    return *p;
-#endif
-}
 template <int PL = 256>
 __device__ __forceinline__ void ckpt_store(float *ck, const BlendState &v) {
     nt_store(ck, v.Cr); nt_store(ck + PL, v.Cg); nt_store(ck + 2 * PL, v.Cb); nt_store(ck + 3 * PL, 1.0f - v.T); nt_store(ck + 4 * PL, v.D);
@@ -341,15 +388,7 @@ __global__ __launch_bounds__(64 * NP * (1 + WIDE)) __attribute__((amdgpu_waves_p
         const uint32_t nt = (uint32_t)__popcll(tmask);
         if (flags & 15u) {
             const uint32_t slot = __builtin_amdgcn_mbcnt_hi((uint32_t)(tmask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)tmask, 0u));
-            q0.z *= NEG_HALF_LOG2E; q0.w *= NEG_HALF_LOG2E; q1.x *= NEG_HALF_LOG2E;
-            q2.z = __uint_as_float(cbits); q2.w = __uint_as_float(flags);
-            // alpha = min(G op, 0.99) = 0.99 a', a' = clamp01(G op') with op' = op / 0.99, and G op' = exp2(m' + log2 op'):
-            // the list loop adds lop = log2 op' to the row term of the exponent (the FMA that forms it costs what the
-            // multiply did) and takes a' from the v_exp itself with the FREE clamp modifier -- no per-pixel multiply, no
-            // v_min (4.3 issue cycles on gfx950).  The 0.99 rides on the colours / depth (w c = (a' T)(0.99 c)) and on
-            // the transmittance update (T -= 0.99 a' T, one v_fmac with a literal).
-            q1.y = blend_lop(q1.y);
-            q1.z *= ALPHA_MAX; q1.w *= ALPHA_MAX; q2.x *= ALPHA_MAX; q2.y *= ALPHA_MAX;
+            blend_stage_fold(q0, q1, q2, flags, cbits, blend_lop(q1.y));
             sh0[wave][slot] = q0; sh1[wave][slot] = q1; sh2[wave][slot] = q2;
         }
         __builtin_amdgcn_wave_barrier();  // wave-private LDS: one wave's LDS instructions execute in order
@@ -422,18 +461,9 @@ __global__ __launch_bounds__(64 * NP * (1 + WIDE)) __attribute__((amdgpu_waves_p
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
         const uint32_t px = X0 + 8u * (s & 1) + lx, py = c.Y0 + 8u * (s >> 1) + ly;
-        if (px < W && py < H) {
-            const size_t o = (size_t)py * W + px;
-            float *ps = pix_state + (size_t)c.b * 6 * HW + o;
-            const float Tf = T[s];
-            nt_store(ps, Cr[s]); nt_store(ps + HW, Cg[s]); nt_store(ps + 2 * HW, Cb[s]); nt_store(ps + 3 * HW, 1.0f - Tf);
-            nt_store(ps + 4 * HW, Dm[s]);  // (plane 5, Phi, belongs to the phase path: nobody reads it on this one)
-            float *img = out_rgb + (size_t)c.b * 3 * HW + o;
-            nt_store(img, fminf(fmaxf(Cr[s] + Tf * bg0, 0.0f), 1.0f));
-            nt_store(img + HW, fminf(fmaxf(Cg[s] + Tf * bg1, 0.0f), 1.0f));
-            nt_store(img + 2 * HW, fminf(fmaxf(Cb[s] + Tf * bg2, 0.0f), 1.0f));
-            nt_store(out_depth + (size_t)c.b * HW + o, Dm[s]);
-        }
+        if (px < W && py < H)
+            pixel_store(pix_state, out_rgb, out_depth, c.b, HW, (size_t)py * W + px, bg0, bg1, bg2, Cr[s], Cg[s], Cb[s], 1.0f - T[s],
+                        T[s], Dm[s]);
     }
 }
 
@@ -446,7 +476,7 @@ __global__ __launch_bounds__(64 * NP * (1 + WIDE)) __attribute__((amdgpu_waves_p
 //
 // Gradient accumulation is atomic-free and deterministic: each lane sums its (up to four)
 // pixels' contributions to the ten per-Gaussian sums, the wave adds them up through LDS in a fixed
-// order (wave_sum10_addtid, fgs_wave.h) and ten lanes store ONE 48-byte row at the duplicate's
+// order (addtid_park + wave_sum_addtid_finish, fgs_wave.h) and ten lanes store ONE 48-byte row at the duplicate's
 // emission slot (dup_off[gaussian] + index of this tile inside the Gaussian's tile rectangle).  A
 // Gaussian's rows are contiguous and k_project_bwd sums them in a fixed order.
 //
@@ -510,10 +540,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NSX == 2 ? 6
             for (uint32_t i = c.start + lane; i < c.end; i += 64) {
                 const uint32_t gid = dup_ids[i];
                 const float4 q2 = reinterpret_cast<const float4 *>(rec + (size_t)gid * FGS_REC_FLOATS)[2];
-                const uint32_t bbx = __float_as_uint(q2.z), bby = __float_as_uint(q2.w);
-                const uint32_t tx0 = (bbx & 0xFFFFu) / (8u * NSX), tx1 = ((bbx >> 16) - 1) / (8u * NSX);
-                const uint32_t ty0 = (bby & 0xFFFFu) / FGS_TILE;
-                const uint32_t e = dup_off[gid] + (c.ty - ty0) * (tx1 - tx0 + 1) + (c.tx - tx0);
+                const uint32_t e = fgs_emission_slot<8 * NSX>(c.tx, c.ty, gid, __float_as_uint(q2.z), __float_as_uint(q2.w), dup_off);
                 if (e < dcap) {
                     float2 *row = reinterpret_cast<float2 *>(grad_rows + (size_t)e * FGS_BLEND_ROW_FLOATS);
 #pragma unroll
@@ -532,18 +559,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NSX == 2 ? 6
         gr[s] = gg[s] = gb[s] = gd[s] = S[s] = 0.0f;
         T[s] = 1.0f;
         if (px < W && py < H) {
-            const size_t o = (size_t)py * W + px;
-            const float *ps = pix_state + (size_t)c.b * 6 * HW + o;
-            const float Cr = ps[0], Cg = ps[HW], Cb = ps[2 * HW], Af = ps[3 * HW];
-            const float Tf = 1.0f - Af;
-            const float pr = Cr + Tf * bg0, pg = Cg + Tf * bg1, pb = Cb + Tf * bg2;
-            const float *gi = g_rgb + (size_t)c.b * 3 * HW + o;
-            gr[s] = (pr >= 0.0f && pr <= 1.0f) ? gi[0] : 0.0f;  // clamp backward, closed interval
-            gg[s] = (pg >= 0.0f && pg <= 1.0f) ? gi[HW] : 0.0f;
-            gb[s] = (pb >= 0.0f && pb <= 1.0f) ? gi[2 * HW] : 0.0f;
-            gd[s] = g_depth[(size_t)c.b * HW + o];
-            S[s] = Tf * (gr[s] * bg0 + gg[s] * bg1 + gb[s] * bg2) + (gr[s] * Cr + gg[s] * Cg + gb[s] * Cb) +
-                   gd[s] * ps[4 * HW];
+            const PixelGrad g = pixel_grad_load(pix_state, g_rgb, g_depth, c.b, HW, (size_t)py * W + px, bg0, bg1, bg2);
+            gr[s] = g.gr; gg[s] = g.gg; gb[s] = g.gb; gd[s] = g.gd;
+            S[s] = g.Tf * (gr[s] * bg0 + gg[s] * bg1 + gb[s] * bg2) + (gr[s] * g.Cr + gg[s] * g.Cg + gb[s] * g.Cb) + gd[s] * g.D;
         }
         if (seg) {
             // restart from the forward's state in front of this segment: T, and S minus the part of Total that
@@ -570,7 +588,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NSX == 2 ? 6
     float fx0 = (float)(c.X0 + lx), fy0 = (float)(c.Y0 + ly);
     asm("" : "+v"(fx0), "+v"(fy0));  // hoisted for good: no v_cvt in the list loop
     // The reduction of a list entry's ten sums is DEFERRED by one entry: the passes of entry j end with the sums parked in `red`
-    // (addtid_park10), and the read-back, the adds and the row store happen at the top of entry j + 1, where their LDS reads travel
+    // (addtid_park), and the read-back, the adds and the row store happen at the top of entry j + 1, where their LDS reads travel
     // together with that entry's record reads -- one exposed LDS round trip per entry instead of three (record; parked sums; row
     // index).  One wave's LDS instructions execute in order, so the read-back of entry j is served before entry j + 1 parks its own
     // sums in the same cells.  e_prev: row of the entry whose sums are parked (none yet: no row passes e < dcap).
@@ -589,30 +607,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NSX == 2 ? 6
             const float4 *r = reinterpret_cast<const float4 *>(rec + (size_t)gid * FGS_REC_FLOATS);
             float4 q2 = r[2];
             const uint32_t bbx = __float_as_uint(q2.z), bby = __float_as_uint(q2.w);
-            const uint32_t bx0 = bbx & 0xFFFFu, bx1 = bbx >> 16, by0 = bby & 0xFFFFu;
-            const uint32_t tx0 = bx0 / (8u * NSX), tx1 = (bx1 - 1) / (8u * NSX), ty0 = by0 / FGS_TILE;
-            she[lane] = dup_off[gid] + (c.ty - ty0) * (tx1 - tx0 + 1) + (c.tx - tx0);
+            she[lane] = fgs_emission_slot<8 * NSX>(c.tx, c.ty, gid, bbx, bby, dup_off);
             float4 q0 = r[0], q1 = r[1];
             // m = a dx^2 + (b+c) dx dy + d dy^2 >= 0 everywhere (so G <= 1): positive definite, with a margin
             // that covers the fp32 rounding of m
             const bool conic_ok = q0.z > 0.0f && q1.x > 0.0f && 3.996f * q0.z * q1.x > q0.w * q0.w;
             uint32_t flags, cbits;
             stage_decode_w<NSX>(c.X0, c.Y0, bbx, bby, q1.y, flags, cbits, conic_ok);
-            q2.z = __uint_as_float(cbits); q2.w = __uint_as_float(flags);
-            q0.z *= NEG_HALF_LOG2E; q0.w *= NEG_HALF_LOG2E; q1.x *= NEG_HALF_LOG2E;  // conic in exp2 units
-            // alpha = 0.99 a', a' = clamp01(G op') = clamp01(exp2(m' + lop)), op' = op / 0.99, lop = log2 op' riding on the row
-            // terms of the exponent exactly as in the forward (blend_lop, blend_alpha1): the recomputed a', w and T are the
-            // forward's to the bit.  The list loop works with w' = a' T = w / 0.99 and colours c' = 0.99 c, so that w q = w' q',
-            // and its dalpha is 0.99 dL/dalpha.  The pass has a' where it had G, so it accumulates dG = dalpha a' = op dL/dalpha G.
-            // ROW CONTRACT with k_row_sum (fgs_project.hip), X = the sums of dL/dalpha G {dx, dy, dx^2, dx dy, dy^2, 1}:
-            //   moment rows and the sum-dG row = opacity X, colour / depth rows = 1 / 0.99 x theirs;
-            //   opacities below the floor of fgs_opacity_floored (fgs_internal.h; exactly 0 included, whose dL/dopacity is not
-            //   zero): the EXACT lop = -64 is folded instead of theirs, a' = 2^-64 G, and the rows are
-            //   0.99 2^-64 X and (2^-64 / op') / 0.99 x (colour, depth).
-            // A floored entry's a' is not the forward's (which folds the true lop, -inf for opacity 0): both are below
-            // 5.5e-20, where T (1 - 0.99 a') rounds to T and w q moves S by less than 1e-19 |q|.
-            q1.y = fgs_opacity_floored(q1.y) ? FGS_FOLD_FLOOR_LOG2 : blend_lop(q1.y);
-            q1.z *= ALPHA_MAX; q1.w *= ALPHA_MAX; q2.x *= ALPHA_MAX; q2.y *= ALPHA_MAX;
+            // (blend_stage_fold: the forward's record, but for the floored opacities' lop -- see there, with the row contract)
+            blend_stage_fold(q0, q1, q2, flags, cbits, fgs_opacity_floored(q1.y) ? FGS_FOLD_FLOOR_LOG2 : blend_lop(q1.y));
             sh0[lane] = q0; sh1[lane] = q1; sh2[lane] = q2;
         }
         __syncthreads();
@@ -634,7 +637,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NSX == 2 ? 6
             // (v_bfe_i32) and zero G with a bit-and -- no per-pixel compare / select (issue costs: DESIGN.md).
             // per-lane partial sums over this lane's (up to 2 NSX) pixels: moments of dG = dalpha a' about the Gaussian's mean, sum dG
             // {dx, dy, dx^2, dx dy, dy^2, 1}; the ln2 and K factors of the chain through m' = K m and the factors of the
-            // row contract (at the staging above) are applied once per Gaussian in k_row_sum.  ROW_MOMENTS (32 x 16 tiles): a lane's pixels lie on TWO values of dy
+            // row contract (blend_stage_fold) are applied once per Gaussian in k_row_sum.  ROW_MOMENTS (32 x 16 tiles): a lane's pixels lie on TWO values of dy
             // (dya, dyb: one per sub-tile row), so a pass accumulates only the row's A_r = sum dG, B_r = sum dG dx, C_r = sum dG dx^2 (five
             // ops instead of nine) and the dy factors are applied once per list entry, in the fold behind the passes:
             //   {1, dx, dx^2} = A0 + A1, B0 + B1, C0 + C1;  dy = dya A0 + dyb A1;  dx dy = dya B0 + dyb B1;
@@ -709,7 +712,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NSX == 2 ? 6
             // order and stores them straight into this duplicate's gradient row: no atomics, bitwise reproducible ----
             {
                 const float vals[10] = {v_mx, v_my, v_ca, v_cbc, v_cd, v_op, v_r, v_g, v_b, v_d};
-                addtid_park10((uint32_t)(uintptr_t)(fgs_lds_float *)red, vals);
+                addtid_park(red, vals);
             }
         }
         __syncthreads();
@@ -772,10 +775,8 @@ __device__ __forceinline__ unsigned long long phase_scan(PhaseRec &st, uint32_t 
         const uint32_t cm = lx1 > lx0 ? ((1u << (lx1 - lx0)) - 1u) << lx0 : 0u;
         const uint32_t rm = ly1 > ly0 ? ((1u << (ly1 - ly0)) - 1u) << ly0 : 0u;
         bits = (cm && rm) ? (cm | (rm << 8)) : 0u;
-        if (!FWD) {  // this duplicate's emission slot: its four gradient rows (one per sub-tile wave) are 4 e .. 4 e + 3 (k_project_bwd)
-            const uint32_t tx0 = (uint32_t)x0 / FGS_TILE, tx1 = (uint32_t)(x1 - 1) / FGS_TILE, ty0 = (uint32_t)y0 / FGS_TILE;
-            e = dup_off[gid] + (c.ty - ty0) * (tx1 - tx0 + 1) + (c.tx - tx0);
-        }
+        // this duplicate's emission slot: its four gradient rows (one per sub-tile wave) are 4 e .. 4 e + 3 (k_project_bwd)
+        if (!FWD) e = fgs_emission_slot<FGS_TILE>(c.tx, c.ty, gid, bbx, bby, dup_off);
     }
     const unsigned long long touched = __ballot(bits != 0u);
     if (bits) {
@@ -789,6 +790,33 @@ __device__ __forceinline__ unsigned long long phase_scan(PhaseRec &st, uint32_t 
     }
     __builtin_amdgcn_wave_barrier();  // wave-private LDS: one wave's LDS instructions execute in order
     return touched;
+}
+
+// One step of the phase recurrence (DR:629-667) at this lane's pixel (fpx, fpy) = sub-tile pixel (lx, ly), for the parked entry
+// (q0, q1, q2) of a PhaseRec: advances (A, Ph) and returns w = alpha (1 - A_{i-1}).  Called by the forward AND by the re-run loop of
+// the backward, whose adjoint is exact only because its re-run reproduces the forward's (A_{i-1}, Phi_{i-1}) to the bit.  (The
+// backward's reverse sweep keeps its own code: it needs the intermediates.)
+// One source is necessary for that, NOT sufficient: this unit is built with -ffast-math, and the order in which the compiler sums the
+// three terms of mm follows the order of the loads around the call.  Both callers therefore read the record into locals first and pass
+// those; called on the LDS references directly, the re-run rounded c dy before (b + c) dx, the forward the other way round, and the
+// gradients moved by an ulp or two (DESIGN_LOG.md 19).  After a change here, compare both kernels' exponent code or their outputs.
+__device__ __forceinline__ float phase_step(const float4 &q0, const float4 &q1, const float4 &q2, uint32_t lx, uint32_t ly, float fpx,
+                                            float fpy, float base_amp, float amp, float &A, float &Ph) {
+    const uint32_t bits = __float_as_uint(q2.w);
+    const uint32_t mk = (uint32_t)__builtin_amdgcn_sbfe((int)bits, lx, 1) & (uint32_t)__builtin_amdgcn_sbfe((int)bits, 8u + ly, 1);
+    const float dx = fpx - q0.x, dy = fpy - q0.y;
+    const float mm = (q0.z * dx) * dx + (q0.w * dx) * dy + (q1.x * dy) * dy;  // conic staged in exp2 units
+    float alpha = __builtin_amdgcn_exp2f(mm) * q1.y;
+    float pd = fabsf(q2.z - Ph);
+    pd = fminf(pd, 1.0f - pd);
+    alpha *= base_amp + amp * phase_cos(pd * PHASE_KAPPA);
+    alpha = __builtin_amdgcn_fmed3f(alpha, 0.0f, ALPHA_MAX);
+    alpha = __uint_as_float(__float_as_uint(alpha) & mk);   // zero outside the bbox: w = pc = 0, nothing moves
+    const float w = alpha * (1.0f - A);
+    A += w;
+    const float pc = w / fmaxf(A, 1e-6f);
+    Ph = Ph * (1.0f - pc) + q2.z * pc;
+    return w;
 }
 
 __global__ __launch_bounds__(FGS_PHASE_WAVE_BLOCKS ? 64 : 256) void k_phase_fwd(
@@ -833,21 +861,8 @@ __global__ __launch_bounds__(FGS_PHASE_WAVE_BLOCKS ? 64 : 256) void k_phase_fwd(
             for (int k = 0; k < PCK; ++k) {
                 if (k >= (int)m) break;  // wave-uniform
                 const float4 q0 = st.a[j0 + k], q1 = st.b[j0 + k], q2 = st.c[j0 + k];
-                const uint32_t bits = __float_as_uint(q2.w);
-                const uint32_t mk = (uint32_t)__builtin_amdgcn_sbfe((int)bits, lx, 1) & (uint32_t)__builtin_amdgcn_sbfe((int)bits, 8u + ly, 1);
-                const float dx = fpx - q0.x, dy = fpy - q0.y;
-                const float mm = (q0.z * dx) * dx + (q0.w * dx) * dy + (q1.x * dy) * dy;  // conic in exp2 units
-                float alpha = __builtin_amdgcn_exp2f(mm) * q1.y;
-                float pd = fabsf(q2.z - Ph);
-                pd = fminf(pd, 1.0f - pd);
-                alpha *= base_amp + amp * phase_cos(pd * PHASE_KAPPA);
-                alpha = __builtin_amdgcn_fmed3f(alpha, 0.0f, ALPHA_MAX);
-                alpha = __uint_as_float(__float_as_uint(alpha) & mk);   // zero outside the bbox: w = pc = 0, nothing moves
-                const float w = alpha * (1.0f - A);
+                const float w = phase_step(q0, q1, q2, lx, ly, fpx, fpy, base_amp, amp, A, Ph);
                 Cr += w * q1.z; Cg += w * q1.w; Cb += w * q2.x; Dm += w * q2.y;
-                A += w;
-                const float pc = w / fmaxf(A, 1e-6f);
-                Ph = Ph * (1.0f - pc) + q2.z * pc;
             }
         }
         __builtin_amdgcn_wave_barrier();  // the next scan block overwrites the parked records
@@ -855,14 +870,8 @@ __global__ __launch_bounds__(FGS_PHASE_WAVE_BLOCKS ? 64 : 256) void k_phase_fwd(
     const uint32_t px = sx + lx, py = sy + ly;
     if (px < W && py < H) {
         const size_t HW = (size_t)W * H, o = (size_t)py * W + px;
-        float *ps = pix_state + (size_t)c.b * 6 * HW + o;
-        ps[0] = Cr; ps[HW] = Cg; ps[2 * HW] = Cb; ps[3 * HW] = A; ps[4 * HW] = Dm; ps[5 * HW] = Ph;
-        const float T = 1.0f - A;
-        float *img = out_rgb + (size_t)c.b * 3 * HW + o;
-        img[0] = fminf(fmaxf(Cr + T * bg0, 0.0f), 1.0f);
-        img[HW] = fminf(fmaxf(Cg + T * bg1, 0.0f), 1.0f);
-        img[2 * HW] = fminf(fmaxf(Cb + T * bg2, 0.0f), 1.0f);
-        out_depth[(size_t)c.b * HW + o] = Dm;
+        pixel_store(pix_state, out_rgb, out_depth, c.b, HW, o, bg0, bg1, bg2, Cr, Cg, Cb, A, 1.0f - A, Dm);
+        nt_store(pix_state + (size_t)c.b * 6 * HW + o + 5 * HW, Ph);
     }
 }
 
@@ -911,15 +920,8 @@ __global__ __launch_bounds__(FGS_PHASE_WAVE_BLOCKS ? 64 : 256) void k_phase_bwd(
     asm("" : "+v"(fpx), "+v"(fpy));
     float gr = 0.0f, gg = 0.0f, gb = 0.0f, gd = 0.0f, Abar = 0.0f, Pbar = 0.0f;
     if (px < W && py < H) {
-        const size_t o = (size_t)py * W + px;
-        const float *ps = pix_state + (size_t)c.b * 6 * HW + o;
-        const float Tf = 1.0f - ps[3 * HW];
-        const float pr = ps[0] + Tf * bg0, pg = ps[HW] + Tf * bg1, pb = ps[2 * HW] + Tf * bg2;
-        const float *gi = g_rgb + (size_t)c.b * 3 * HW + o;
-        gr = (pr >= 0.0f && pr <= 1.0f) ? gi[0] : 0.0f;  // clamp backward, closed interval
-        gg = (pg >= 0.0f && pg <= 1.0f) ? gi[HW] : 0.0f;
-        gb = (pb >= 0.0f && pb <= 1.0f) ? gi[2 * HW] : 0.0f;
-        gd = g_depth[(size_t)c.b * HW + o];
+        const PixelGrad g = pixel_grad_load(pix_state, g_rgb, g_depth, c.b, HW, (size_t)py * W + px, bg0, bg1, bg2);
+        gr = g.gr; gg = g.gg; gb = g.gb; gd = g.gd;
         Abar = -(gr * bg0 + gg * bg1 + gb * bg2);  // d/dA of (1 - A) * bg
     }
     const float base_amp = 1.0f - amp, neg_amp_kappa = -(amp * PHASE_KAPPA);
@@ -952,21 +954,8 @@ __global__ __launch_bounds__(FGS_PHASE_WAVE_BLOCKS ? 64 : 256) void k_phase_bwd(
                 sA[k] = 0.0f; sP[k] = 0.0f;
                 if (k >= (int)m) continue;  // wave-uniform
                 const float4 q0 = st.a[j0 + k], q1 = st.b[j0 + k], q2 = st.c[j0 + k];
-                const uint32_t bits = __float_as_uint(q2.w);
-                const uint32_t mk = (uint32_t)__builtin_amdgcn_sbfe((int)bits, lx, 1) & (uint32_t)__builtin_amdgcn_sbfe((int)bits, 8u + ly, 1);
                 sA[k] = Af; sP[k] = Pf;
-                const float dx = fpx - q0.x, dy = fpy - q0.y;
-                const float mm = (q0.z * dx) * dx + (q0.w * dx) * dy + (q1.x * dy) * dy;
-                float alpha = __builtin_amdgcn_exp2f(mm) * q1.y;  // (conic staged in exp2 units)
-                float pd = fabsf(q2.z - Pf);
-                pd = fminf(pd, 1.0f - pd);
-                alpha *= base_amp + amp * phase_cos(pd * PHASE_KAPPA);
-                alpha = __builtin_amdgcn_fmed3f(alpha, 0.0f, ALPHA_MAX);
-                alpha = __uint_as_float(__float_as_uint(alpha) & mk);
-                const float w = alpha * (1.0f - Af);
-                Af += w;
-                const float pc = w / fmaxf(Af, 1e-6f);
-                Pf = Pf * (1.0f - pc) + q2.z * pc;
+                phase_step(q0, q1, q2, lx, ly, fpx, fpy, base_amp, amp, Af, Pf);
             }
             // ---- reverse sweep of the group ----
 #pragma unroll
@@ -1027,7 +1016,7 @@ __global__ __launch_bounds__(FGS_PHASE_WAVE_BLOCKS ? 64 : 256) void k_phase_bwd(
                 // blend path's convention: x 1 / K = -2 ln2, once per Gaussian since round 5) and forms dL/d(u, v) = -K conic_sym (moments)
                 // in double (the same chain as the blend backward's rows)
                 const float vals[11] = {dmx, dmy, dmx * dx, dmx * dy, dmy * dy, v_op, v_r, v_g, v_b, v_d, v_ph};  // (slots 0-4: moments of -2 dL/dm, rescaled in k_project_bwd)
-                const float tot = wave_sum11_addtid(red, vals, lane);
+                const float tot = wave_sum_addtid<11>(red, vals, lane);
                 if ((lane & 3u) == 3u && lane < 44u && e < dcap)
                     grad_rows[((size_t)e * 4 + wave) * FGS_GROW_FLOATS + (lane >> 2)] = tot;
             }
@@ -1040,33 +1029,36 @@ __global__ __launch_bounds__(FGS_PHASE_WAVE_BLOCKS ? 64 : 256) void k_phase_bwd(
 
 // Kernel variants are template instantiations selected by the plan (fgs_make_plan: FgsPlan.fwd_parts / fwd_waves,
 // a pure function of the FgsDims; FgsDims.fwd_variant overrides for A/B runs and the variant-agreement tests).
+// typed pointer at a byte offset of a workspace (FgsSavedLayout offsets into `saved`, FgsPlan.s_* into `scratch`)
+template <typename T>
+static T *fgs_at(const char *base, size_t offset) {
+    return reinterpret_cast<T *>(const_cast<char *>(base) + offset);
+}
+
 int fgs_launch_composite_fwd(const FgsPlan &p, const float *phase, char *saved, float *out_rgb,
                              float *out_depth, hipStream_t st) {
     const uint32_t grid = (uint32_t)p.d.batch * p.tiles;
-    const uint32_t *ranges = reinterpret_cast<const uint32_t *>(saved + p.L.ranges);
-    const uint32_t *dup_ids = reinterpret_cast<const uint32_t *>(saved + p.L.dup_ids);
-    const uint32_t *tile_order = reinterpret_cast<const uint32_t *>(saved + p.L.tile_order);
-    const float *rec = reinterpret_cast<const float *>(saved + p.L.rec);
-    float *pix = reinterpret_cast<float *>(saved + p.L.pix_state);
-    const uint32_t *seg_off = reinterpret_cast<const uint32_t *>(saved + p.L.seg_off);
-    float *seg_ckpt = reinterpret_cast<float *>(saved + p.L.seg_ckpt);
+    const uint32_t tiles = (uint32_t)p.tiles, tiles_x = (uint32_t)p.L.tiles_x, W = (uint32_t)p.d.width, H = (uint32_t)p.d.height;
+    const float bg0 = p.d.background[0], bg1 = p.d.background[1], bg2 = p.d.background[2];
+    const uint32_t *ranges = fgs_at<const uint32_t>(saved, p.L.ranges), *dup_ids = fgs_at<const uint32_t>(saved, p.L.dup_ids);
+    const uint32_t *tile_order = fgs_at<const uint32_t>(saved, p.L.tile_order), *seg_off = fgs_at<const uint32_t>(saved, p.L.seg_off);
+    const float *rec = fgs_at<const float>(saved, p.L.rec);
+    float *pix = fgs_at<float>(saved, p.L.pix_state), *seg_ckpt = fgs_at<float>(saved, p.L.seg_ckpt);
     if (p.d.use_phase) {  // one wave per 8 x 8 sub-tile, four per block
+        float *phase_ckpt = fgs_at<float>(saved, p.L.phase_ckpt);
         hipLaunchKernelGGL(k_phase_fwd, dim3(FGS_PHASE_WAVE_BLOCKS ? (grid + 7u) / 8u * 32u : grid), dim3(FGS_PHASE_WAVE_BLOCKS ? 64 : 256), 0, st,
-                           (uint32_t)p.tiles, (uint32_t)p.L.tiles_x, (uint32_t)p.d.width,
-                           (uint32_t)p.d.height, p.d.background[0], p.d.background[1], p.d.background[2], p.d.phase_amplitude,
-                           tile_order, ranges, dup_ids, rec, phase, pix, reinterpret_cast<float *>(saved + p.L.phase_ckpt), out_rgb,
-                           out_depth, grid);
+                           tiles, tiles_x, W, H, bg0, bg1, bg2, p.d.phase_amplitude, tile_order, ranges, dup_ids, rec, phase, pix,
+                           phase_ckpt, out_rgb, out_depth, grid);
         FGS_LAUNCH_CHECK("k_phase_fwd");
         return FGS_OK;
     }
     const float t_eps = p.d.saturation_skip ? FGS_SATURATION_EPS : 0.0f;
     const int fw = p.fwd_waves;
     if (const int np = p.fwd_parts) {
-#define FGS_PARTS_LAUNCH(NP, WD)                                                                              \
-    hipLaunchKernelGGL((k_blend_fwd_parts<NP, WD>), dim3(grid), dim3(64 * NP * (1 + WD)), 0, st, (uint32_t)p.tiles, \
-                       (uint32_t)p.L.tiles_x, (uint32_t)p.d.width, (uint32_t)p.d.height, p.d.background[0],  \
-                       p.d.background[1], p.d.background[2], tile_order, ranges, dup_ids, rec, pix, out_rgb,  \
-                       out_depth, seg_off, seg_ckpt, (uint32_t)p.L.seg_len, (uint32_t)p.order_groups)
+        const uint32_t seg_len = (uint32_t)p.L.seg_len, order_groups = (uint32_t)p.order_groups;
+#define FGS_PARTS_LAUNCH(NP, WD)                                                                                          \
+    hipLaunchKernelGGL((k_blend_fwd_parts<NP, WD>), dim3(grid), dim3(64 * NP * (1 + WD)), 0, st, tiles, tiles_x, W, H, bg0, bg1, \
+                       bg2, tile_order, ranges, dup_ids, rec, pix, out_rgb, out_depth, seg_off, seg_ckpt, seg_len, order_groups)
         if (p.tile_w == 32) {
             if (np == 1) FGS_PARTS_LAUNCH(1, 1); else if (np == 2) FGS_PARTS_LAUNCH(2, 1); else if (np == 4) FGS_PARTS_LAUNCH(4, 1);
             else FGS_PARTS_LAUNCH(8, 1);
@@ -1078,11 +1070,9 @@ int fgs_launch_composite_fwd(const FgsPlan &p, const float *phase, char *saved, 
         FGS_LAUNCH_CHECK("k_blend_fwd_parts");
         return FGS_OK;
     }
-#define FGS_FWD_LAUNCH(FW, SK)                                                                                \
-    hipLaunchKernelGGL((k_composite_fwd<FW, SK>), dim3(grid), dim3(64 * FW), 0, st, (uint32_t)p.tiles,       \
-                       (uint32_t)p.L.tiles_x, (uint32_t)p.d.width, (uint32_t)p.d.height, p.d.background[0],  \
-                       p.d.background[1], p.d.background[2], tile_order, ranges, dup_ids, rec, pix, out_rgb,  \
-                       out_depth, seg_off, seg_ckpt, t_eps)
+#define FGS_FWD_LAUNCH(FW, SK)                                                                                            \
+    hipLaunchKernelGGL((k_composite_fwd<FW, SK>), dim3(grid), dim3(64 * FW), 0, st, tiles, tiles_x, W, H, bg0, bg1, bg2, tile_order, \
+                       ranges, dup_ids, rec, pix, out_rgb, out_depth, seg_off, seg_ckpt, t_eps)
     if (t_eps > 0.0f) {  // FgsDims.saturation_skip: separate instantiation, the default path carries no trace of it
         if (fw == 1) FGS_FWD_LAUNCH(1, true); else if (fw == 4) FGS_FWD_LAUNCH(4, true); else FGS_FWD_LAUNCH(2, true);
     } else {
@@ -1097,37 +1087,30 @@ int fgs_launch_composite_bwd(const FgsPlan &p, const float *phase, const char *s
                              const float *g_rgb, const float *g_depth, float *g_phase, hipStream_t st) {
     (void)g_phase;  // dL/dphase travels in the gradient rows and is written by k_project_bwd
     const uint32_t grid = (uint32_t)p.d.batch * p.tiles;
+    const uint32_t tiles = (uint32_t)p.tiles, tiles_x = (uint32_t)p.L.tiles_x, W = (uint32_t)p.d.width, H = (uint32_t)p.d.height;
+    const uint32_t dcap = (uint32_t)p.L.dup_capacity;
+    const float bg0 = p.d.background[0], bg1 = p.d.background[1], bg2 = p.d.background[2];
+    const uint32_t *ranges = fgs_at<const uint32_t>(saved, p.L.ranges), *dup_ids = fgs_at<const uint32_t>(saved, p.L.dup_ids);
+    const uint32_t *dup_off = fgs_at<const uint32_t>(saved, p.L.dup_off);
+    const float *rec = fgs_at<const float>(saved, p.L.rec), *pix = fgs_at<const float>(saved, p.L.pix_state);
+    float *grad_rows = fgs_at<float>(scratch, p.s_grows);
     if (p.d.use_phase) {
-        hipLaunchKernelGGL(k_phase_bwd, dim3(FGS_PHASE_WAVE_BLOCKS ? (grid + 7u) / 8u * 32u : grid), dim3(FGS_PHASE_WAVE_BLOCKS ? 64 : 256), 0, st, (uint32_t)p.tiles,
-                           (uint32_t)p.L.tiles_x, (uint32_t)p.d.width, (uint32_t)p.d.height, p.d.background[0],
-                           p.d.background[1], p.d.background[2], p.d.phase_amplitude, (uint32_t)p.L.dup_capacity,
-                           reinterpret_cast<const uint32_t *>(saved + p.L.tile_order),
-                           reinterpret_cast<const uint32_t *>(saved + p.L.ranges),
-                           reinterpret_cast<const uint32_t *>(saved + p.L.dup_ids),
-                           reinterpret_cast<const float *>(saved + p.L.rec), phase,
-                           reinterpret_cast<const uint32_t *>(saved + p.L.dup_off),
-                           reinterpret_cast<const float *>(saved + p.L.pix_state),
-                           reinterpret_cast<const float *>(saved + p.L.phase_ckpt), g_rgb, g_depth,
-                           reinterpret_cast<float *>(scratch + p.s_grows), grid);
+        const uint32_t *tile_order = fgs_at<const uint32_t>(saved, p.L.tile_order);
+        const float *phase_ckpt = fgs_at<const float>(saved, p.L.phase_ckpt);
+        hipLaunchKernelGGL(k_phase_bwd, dim3(FGS_PHASE_WAVE_BLOCKS ? (grid + 7u) / 8u * 32u : grid), dim3(FGS_PHASE_WAVE_BLOCKS ? 64 : 256), 0, st,
+                           tiles, tiles_x, W, H, bg0, bg1, bg2, p.d.phase_amplitude, dcap, tile_order, ranges, dup_ids, rec, phase,
+                           dup_off, pix, phase_ckpt, g_rgb, g_depth, grad_rows, grid);
         FGS_LAUNCH_CHECK("k_phase_bwd");
         return FGS_OK;
     }
     const uint32_t ugrid = (uint32_t)p.L.seg_capacity;  // surplus blocks exit at once (measured: free)
-#define FGS_BWD_LAUNCH(NSXV)                                                                                  \
-    hipLaunchKernelGGL(k_composite_bwd<NSXV>, dim3(ugrid), dim3(64), FGS_BWD_DYN_LDS, st, (uint32_t)p.tiles, (uint32_t)p.L.tiles_x, \
-                       (uint32_t)p.d.width, (uint32_t)p.d.height, p.d.background[0], p.d.background[1], \
-                       p.d.background[2], (uint32_t)p.L.dup_capacity, \
-                       reinterpret_cast<const uint32_t *>(saved + p.L.counters), \
-                       reinterpret_cast<const uint32_t *>(saved + p.L.seg_off), \
-                       reinterpret_cast<const uint32_t *>(saved + p.L.seg_tile), \
-                       reinterpret_cast<const float *>(saved + p.L.seg_ckpt), \
-                       reinterpret_cast<const uint32_t *>(saved + p.L.ranges), \
-                       reinterpret_cast<const uint32_t *>(saved + p.L.dup_ids), \
-                       reinterpret_cast<const float *>(saved + p.L.rec), \
-                       reinterpret_cast<const uint32_t *>(saved + p.L.dup_off), \
-                       reinterpret_cast<const float *>(saved + p.L.pix_state), g_rgb, g_depth, \
-                       reinterpret_cast<float *>(scratch + p.s_grows), \
-                       p.d.saturation_skip ? FGS_SATURATION_EPS : 0.0f)
+    const uint32_t *counters = fgs_at<const uint32_t>(saved, p.L.counters), *seg_off = fgs_at<const uint32_t>(saved, p.L.seg_off);
+    const uint32_t *seg_tile = fgs_at<const uint32_t>(saved, p.L.seg_tile);
+    const float *seg_ckpt = fgs_at<const float>(saved, p.L.seg_ckpt);
+    const float t_eps = p.d.saturation_skip ? FGS_SATURATION_EPS : 0.0f;
+#define FGS_BWD_LAUNCH(NSXV)                                                                                              \
+    hipLaunchKernelGGL(k_composite_bwd<NSXV>, dim3(ugrid), dim3(64), FGS_BWD_DYN_LDS, st, tiles, tiles_x, W, H, bg0, bg1, bg2, dcap, \
+                       counters, seg_off, seg_tile, seg_ckpt, ranges, dup_ids, rec, dup_off, pix, g_rgb, g_depth, grad_rows, t_eps)
     if (p.tile_w == 32) FGS_BWD_LAUNCH(4); else FGS_BWD_LAUNCH(2);
 #undef FGS_BWD_LAUNCH
     FGS_LAUNCH_CHECK("k_composite_bwd");

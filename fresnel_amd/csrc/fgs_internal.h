@@ -136,6 +136,19 @@ constexpr float FGS_FOLD_FLOOR = 5.42101086242752217e-20f;            // 2^-64
 constexpr float FGS_FOLD_MIN_OPACITY = 0.99f * FGS_FOLD_FLOOR;        // exact: a power-of-two multiple of 0.99f
 __host__ __device__ __forceinline__ bool fgs_opacity_floored(float opacity) { return !(opacity >= FGS_FOLD_MIN_OPACITY); }
 
+// Emission slot of a duplicate = where its gradient row(s) go: a Gaussian's duplicates occupy the slots dup_off[gid] ... in
+// row-major order of the tiles of its bbox's tile rectangle (tiles TW pixels wide, FGS_TILE high; bbx = x0 | x1 << 16, bby likewise,
+// the record's integer bbox [x0, x1) x [y0, y1)).  ASSIGNED by the binning (k_dup_emit, k_mask_emit* of fgs_bin.hip: dup_off and the
+// emission order); USED by the backwards, which write the row of tile (tx, ty) there (k_composite_bwd with TW = 8 NSX, k_phase_bwd
+// through phase_scan -- rows 4 e ... 4 e + 3, one per sub-tile wave -- and k_asm_splat<BWD> with TW = FGS_TILE); CONSUMED by
+// k_project_bwd / k_row_sum (fgs_project.hip), which sum a Gaussian's contiguous rows in a fixed order.
+template <int TW>
+__device__ __forceinline__ uint32_t fgs_emission_slot(uint32_t tx, uint32_t ty, uint32_t gid, uint32_t bbx, uint32_t bby,
+                                                      const uint32_t *__restrict__ dup_off) {
+    const uint32_t tx0 = (bbx & 0xFFFFu) / TW, tx1 = ((bbx >> 16) - 1) / TW, ty0 = (bby & 0xFFFFu) / FGS_TILE;
+    return dup_off[gid] + (ty - ty0) * (tx1 - tx0 + 1) + (tx - tx0);
+}
+
 // order-preserving map float -> uint32 (ascending), -0.0 folded into +0.0
 __device__ __forceinline__ uint32_t fgs_float_key(float f) {
     f = f + 0.0f;

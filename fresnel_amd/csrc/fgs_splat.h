@@ -156,13 +156,11 @@ __global__ __launch_bounds__(64 * NP) void k_asm_splat(
             // touched sub-tiles + the pixel bits of the tile (bit i: column X0 + i inside the bbox, bit 16 + i: row Y0 + i): in the
             // list loop a lane turns its column / row bits into all-ones / zero masks (v_bfe_i32) and and-s them onto G -- no
             // per-pixel compare / select, as on the blend path (issue costs: DESIGN.md section 4)
-            uint32_t sflags, pbits;
-            stage_decode(X0, Y0, bbx, bby, 1.0f, sflags, pbits);
+            uint32_t sflags, cbits;
+            stage_decode_w<2>(X0, Y0, bbx, bby, 1.0f, sflags, cbits);
+            const uint32_t pbits = cbits | (sflags & 0xFFFF0000u);
             shm[wofs + lane] = sflags & 15u;
-            if (BWD) {
-                const uint32_t tx0 = (bbx & 0xFFFFu) / FGS_TILE, tx1 = ((bbx >> 16) - 1) / FGS_TILE, ty0 = (bby & 0xFFFFu) / FGS_TILE;
-                she[lane] = dup_off[gid] + (ty - ty0) * (tx1 - tx0 + 1) + (tx - tx0);
-            }
+            if (BWD) she[lane] = fgs_emission_slot<FGS_TILE>(tx, ty, gid, bbx, bby, dup_off);
             const float4 *pz = reinterpret_cast<const float4 *>(ccs + (size_t)gid * 8);
             const float4 z0 = pz[0], z1 = pz[1];  // cc[0..2], cs[0] | cs[1..2]
             // conic pre-multiplied by K = -log2(e) / 2: G = exp2(K m) without a multiply per pixel (the backward's

@@ -1,45 +1,20 @@
 // Wave64 cross-lane reductions and list-staging helpers for gfx950, shared by the composite and ASM kernels.
 #pragma once
 
-// Staging-time (per lane, parallel over the chunk) decode of a record's bbox against a 16x16 tile
-// at (X0, Y0): bit s = sub-tile s (8x8, s = 2*row + col) intersects the bbox [x0,x1) x [y0,y1).
-__device__ __forceinline__ uint32_t subtile_mask(uint32_t X0, uint32_t Y0, uint32_t x0, uint32_t x1, uint32_t y0,
-                                                 uint32_t y1) {
-    const uint32_t cx0 = (x1 > X0 && x0 < X0 + 8u) ? 1u : 0u, cx1 = (x1 > X0 + 8u && x0 < X0 + 16u) ? 1u : 0u;
-    const uint32_t ry0 = (y1 > Y0 && y0 < Y0 + 8u) ? 1u : 0u, ry1 = (y1 > Y0 + 8u && y0 < Y0 + 16u) ? 1u : 0u;
-    return (cx0 & ry0) | ((cx1 & ry0) << 1) | ((cx0 & ry1) << 2) | ((cx1 & ry1) << 3);
-}
-
-// Staging-time decode (per lane, parallel over the chunk) of a record against the 16x16 tile at (X0, Y0), for the
-// non-phase composite kernels:
-//   flags  bits 0-3: sub-tile s (8x8, s = 2*row + col) intersects the bbox -- all clear when the opacity is
-//                    negative (alpha clamps to 0 with zero gradient, DR:646: the record contributes nothing);
-//          bit 4:    opacity <= 0.98 and `conic_ok` (the caller's check that the quadratic form is positive
-//                    definite with a margin), so alpha = min(G op, 0.99) cannot bind: G <= 1 up to rounding.
-//                    For a regularised inverse covariance that came out indefinite in fp32 (needles, edge-on
-//                    discs) G can exceed 1.0102 and the clamp of DR:647 does bind -- those keep the clamped path;
-//          bit 5:    the bbox covers the whole tile (no per-pixel membership test needed)
-//   bits   bit i (i < 16): pixel column X0 + i lies in [x0, x1);  bit 16 + i: pixel row Y0 + i lies in [y0, y1).
-// In the list loop a lane turns its column / row bit into an all-ones / zero mask with one v_bfe_i32.
-__device__ __forceinline__ void stage_decode(uint32_t X0, uint32_t Y0, uint32_t bbx, uint32_t bby, float op,
-                                             uint32_t &flags, uint32_t &bits, bool conic_ok = true) {
-    const uint32_t x0 = bbx & 0xFFFFu, x1 = bbx >> 16, y0 = bby & 0xFFFFu, y1 = bby >> 16;
-    flags = (op >= 0.0f ? subtile_mask(X0, Y0, x0, x1, y0, y1) : 0u) | ((op <= 0.98f && conic_ok) ? 16u : 0u) |
-            ((x0 <= X0 && x1 >= X0 + 16u && y0 <= Y0 && y1 >= Y0 + 16u) ? 32u : 0u);
-    const int lx0 = max((int)x0 - (int)X0, 0), lx1 = min((int)x1 - (int)X0, 16);
-    const int ly0 = max((int)y0 - (int)Y0, 0), ly1 = min((int)y1 - (int)Y0, 16);
-    const uint32_t xm = lx1 > lx0 ? ((1u << (lx1 - lx0)) - 1u) << lx0 : 0u;
-    const uint32_t ym = ly1 > ly0 ? ((1u << (ly1 - ly0)) - 1u) << ly0 : 0u;
-    bits = xm | (ym << 16);
-}
-
-// The same for a tile of NSX x 2 sub-tiles (16 or 32 pixels wide), depth-split forward and blend backward:
-//   flags  bits 0 .. 2 NSX - 1: sub-tile s = row * NSX + col touched (none when the opacity is negative);
-//          bit 8: the alpha clamp cannot bind (opacity <= 0.98 and `conic_ok`): G op / 0.99 = exp2(m' + log2(opacity / 0.99)), as
-//                 the blend kernels form it (the opacity folded into the exponent, fgs_internal.h), stays below 1 whatever the
-//                 pixel, so the clamp modifier of the v_exp is idle and the backward needs no clamp-gradient select;
-//          bits 16-31: pixel row Y0 + i in [y0, y1);
+// Staging-time decode (per lane, parallel over the chunk) of a record's bbox against the tile of NSX x 2 sub-tiles (8x8 each; 16 or 32
+// pixels wide) at (X0, Y0) -- the ONE decoder of the blend kernels (k_composite_fwd, k_blend_fwd_parts, k_composite_bwd) and of the
+// splat (k_asm_splat, which passes opacity 1 and uses the touched bits and the pixel bits only):
+//   flags  bits 0 .. 2 NSX - 1: sub-tile s = row * NSX + col intersects the bbox [x0, x1) x [y0, y1) -- all clear when the opacity is
+//                 negative (alpha clamps to 0 with zero gradient, DR:646: the record contributes nothing);
+//          bit 8: the alpha clamp cannot bind (opacity <= 0.98 and `conic_ok`, the caller's check that the quadratic form is positive
+//                 definite with a margin): G op / 0.99 = exp2(m' + log2(opacity / 0.99)), as the blend kernels form it (the opacity
+//                 folded into the exponent, fgs_internal.h), stays below 1 whatever the pixel, so the clamp modifier of the v_exp is
+//                 idle and the backward needs no clamp-gradient select.  For a regularised inverse covariance that came out
+//                 indefinite in fp32 (needles, edge-on discs) G can exceed 1.0102 and the clamp of DR:647 does bind -- those keep
+//                 the clamped path;
+//          bits 16-31: pixel row Y0 + i lies in [y0, y1);
 //   cbits  bit i (i < 8 NSX): pixel column X0 + i lies in [x0, x1).
+// In the list loop a lane turns its column / row bit into an all-ones / zero mask with one v_bfe_i32.
 template <int NSX>
 __device__ __forceinline__ void stage_decode_w(uint32_t X0, uint32_t Y0, uint32_t bbx, uint32_t bby, float op,
                                                uint32_t &flags, uint32_t &cbits, bool conic_ok = true) {
@@ -101,67 +76,38 @@ __device__ __forceinline__ void quad_sum1(float &a) {
 // conflict-free (the [80]-pitch layout above cost 29 % of the LDS cycles in conflicts).  M0 is saved and restored.
 typedef __attribute__((address_space(3))) float fgs_lds_float;
 #define FGS_RED_PITCH 68
-__device__ __forceinline__ void addtid_park10(uint32_t lds_base, const float (&v)[10]) {
-    uint32_t m0_save;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %11\n\ts_nop 0\n\t"
-                 "ds_write_addtid_b32 %1 offset:0\n\tds_write_addtid_b32 %2 offset:272\n\t"
-                 "ds_write_addtid_b32 %3 offset:544\n\tds_write_addtid_b32 %4 offset:816\n\t"
-                 "ds_write_addtid_b32 %5 offset:1088\n\tds_write_addtid_b32 %6 offset:1360\n\t"
-                 "ds_write_addtid_b32 %7 offset:1632\n\tds_write_addtid_b32 %8 offset:1904\n\t"
-                 "ds_write_addtid_b32 %9 offset:2176\n\tds_write_addtid_b32 %10 offset:2448\n\t"
-                 "s_mov_b32 m0, %0"
-                 : "=&s"(m0_save)
-                 : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]), "v"(v[6]), "v"(v[7]), "v"(v[8]),
-                   "v"(v[9]), "s"(lds_base)
-                 : "memory");
-}
+// Parking of NV = 10 ... 13 values (10: blend backward, 11: phase backward, 12 / 13: ASM / wave splat backward), one overload per NV
+// from one macro.  ALL stores of a call and the M0 save / restore sit in ONE asm block: M0 must not be live across
+// compiler-scheduled code (every DS instruction reads it).  `red` = FGS_RED_PITCH * NV floats of LDS private to the calling wave.
+#define FGS_PARK_ST(k, off) "ds_write_addtid_b32 %[v" #k "] offset:" #off "\n\t"
+#define FGS_PARK_OP(k) [v##k] "v"(v[k])
+#define FGS_PARK_ST10                                                                                              \
+    FGS_PARK_ST(0, 0) FGS_PARK_ST(1, 272) FGS_PARK_ST(2, 544) FGS_PARK_ST(3, 816) FGS_PARK_ST(4, 1088)             \
+    FGS_PARK_ST(5, 1360) FGS_PARK_ST(6, 1632) FGS_PARK_ST(7, 1904) FGS_PARK_ST(8, 2176) FGS_PARK_ST(9, 2448)
+#define FGS_PARK_OP10                                                                                              \
+    FGS_PARK_OP(0), FGS_PARK_OP(1), FGS_PARK_OP(2), FGS_PARK_OP(3), FGS_PARK_OP(4), FGS_PARK_OP(5), FGS_PARK_OP(6), \
+    FGS_PARK_OP(7), FGS_PARK_OP(8), FGS_PARK_OP(9)
+#define FGS_DEFINE_PARK(NV, STORES, ...)                                                                           \
+    __device__ __forceinline__ void addtid_park(float *red, const float (&v)[NV]) {                                \
+        uint32_t m0_save;                                                                                          \
+        asm volatile("s_mov_b32 %[save], m0\n\ts_mov_b32 m0, %[base]\n\ts_nop 0\n\t" STORES "s_mov_b32 m0, %[save]"  \
+                     : [save] "=&s"(m0_save)                                                                       \
+                     : __VA_ARGS__, [base] "s"((uint32_t)(uintptr_t)(fgs_lds_float *)red)                          \
+                     : "memory");                                                                                  \
+    }
+FGS_DEFINE_PARK(10, FGS_PARK_ST10, FGS_PARK_OP10)
+FGS_DEFINE_PARK(11, FGS_PARK_ST10 FGS_PARK_ST(10, 2720), FGS_PARK_OP10, FGS_PARK_OP(10))
+FGS_DEFINE_PARK(12, FGS_PARK_ST10 FGS_PARK_ST(10, 2720) FGS_PARK_ST(11, 2992), FGS_PARK_OP10, FGS_PARK_OP(10), FGS_PARK_OP(11))
+FGS_DEFINE_PARK(13, FGS_PARK_ST10 FGS_PARK_ST(10, 2720) FGS_PARK_ST(11, 2992) FGS_PARK_ST(12, 3264), FGS_PARK_OP10, FGS_PARK_OP(10),
+                FGS_PARK_OP(11), FGS_PARK_OP(12))
+#undef FGS_DEFINE_PARK
+#undef FGS_PARK_OP10
+#undef FGS_PARK_ST10
+#undef FGS_PARK_OP
+#undef FGS_PARK_ST
 
-__device__ __forceinline__ void addtid_park11(uint32_t lds_base, const float (&v)[11]) {
-    uint32_t m0_save;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %12\n\ts_nop 0\n\t"
-                 "ds_write_addtid_b32 %1 offset:0\n\tds_write_addtid_b32 %2 offset:272\n\t"
-                 "ds_write_addtid_b32 %3 offset:544\n\tds_write_addtid_b32 %4 offset:816\n\t"
-                 "ds_write_addtid_b32 %5 offset:1088\n\tds_write_addtid_b32 %6 offset:1360\n\t"
-                 "ds_write_addtid_b32 %7 offset:1632\n\tds_write_addtid_b32 %8 offset:1904\n\t"
-                 "ds_write_addtid_b32 %9 offset:2176\n\tds_write_addtid_b32 %10 offset:2448\n\t"
-                 "ds_write_addtid_b32 %11 offset:2720\n\t"
-                 "s_mov_b32 m0, %0"
-                 : "=&s"(m0_save)
-                 : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]), "v"(v[6]), "v"(v[7]), "v"(v[8]),
-                   "v"(v[9]), "v"(v[10]), "s"(lds_base)
-                 : "memory");
-}
-
-// twelve / thirteen values (ASM / wave splat backward).  ONE asm block per variant: M0 must not be live across
-// compiler-scheduled code (every DS instruction reads it).
-#define FGS_PARK12_BODY                                                                              \
-    "ds_write_addtid_b32 %1 offset:0\n\tds_write_addtid_b32 %2 offset:272\n\t"                       \
-    "ds_write_addtid_b32 %3 offset:544\n\tds_write_addtid_b32 %4 offset:816\n\t"                     \
-    "ds_write_addtid_b32 %5 offset:1088\n\tds_write_addtid_b32 %6 offset:1360\n\t"                   \
-    "ds_write_addtid_b32 %7 offset:1632\n\tds_write_addtid_b32 %8 offset:1904\n\t"                   \
-    "ds_write_addtid_b32 %9 offset:2176\n\tds_write_addtid_b32 %10 offset:2448\n\t"                  \
-    "ds_write_addtid_b32 %11 offset:2720\n\tds_write_addtid_b32 %12 offset:2992\n\t"
-__device__ __forceinline__ void addtid_park12(uint32_t lds_base, const float (&v)[12]) {
-    uint32_t m0_save;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %13\n\ts_nop 0\n\t" FGS_PARK12_BODY "s_mov_b32 m0, %0"
-                 : "=&s"(m0_save)
-                 : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]), "v"(v[6]), "v"(v[7]), "v"(v[8]),
-                   "v"(v[9]), "v"(v[10]), "v"(v[11]), "s"(lds_base)
-                 : "memory");
-}
-__device__ __forceinline__ void addtid_park13(uint32_t lds_base, const float (&v)[13]) {
-    uint32_t m0_save;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %14\n\ts_nop 0\n\t" FGS_PARK12_BODY
-                 "ds_write_addtid_b32 %13 offset:3264\n\ts_mov_b32 m0, %0"
-                 : "=&s"(m0_save)
-                 : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]), "v"(v[6]), "v"(v[7]), "v"(v[8]),
-                   "v"(v[9]), "v"(v[10]), "v"(v[11]), "v"(v[12]), "s"(lds_base)
-                 : "memory");
-}
-#undef FGS_PARK12_BODY
-
-// Sum ten per-lane values over the wave; returns, in lanes with (lane & 3) == 3 and lane < 40, the total of value
-// lane >> 2 (other lanes: junk).  `red` = FGS_RED_PITCH * 10 floats of LDS private to the calling wave, 16-B aligned.
+// Second half of the sum: adds the parked values up; returns, in lanes with (lane & 3) == 3 and lane < 4 nv, the total of value
+// lane >> 2 (other lanes: junk).  `red` is 16-B aligned.
 __device__ __forceinline__ float wave_sum_addtid_finish(const float *red, uint32_t lane, uint32_t nv) {
     __builtin_amdgcn_wave_barrier();
     float tot = 0.0f;
@@ -175,20 +121,9 @@ __device__ __forceinline__ float wave_sum_addtid_finish(const float *red, uint32
     __builtin_amdgcn_wave_barrier();
     return tot;
 }
-__device__ __forceinline__ float wave_sum10_addtid(float *red, const float (&v)[10], uint32_t lane) {
-    addtid_park10((uint32_t)(uintptr_t)(fgs_lds_float *)red, v);
-    return wave_sum_addtid_finish(red, lane, 10u);
-}
-// NV = 12 | 13 values (ASM / wave splat backward); `red` = FGS_RED_PITCH * NV floats
+// Sum NV per-lane values over the wave: park and finish in one call (the blend backward calls the two halves an entry apart)
 template <int NV>
 __device__ __forceinline__ float wave_sum_addtid(float *red, const float (&v)[NV], uint32_t lane) {
-    static_assert(NV == 12 || NV == 13, "park helpers written for 12 / 13 values");
-    if constexpr (NV == 12) addtid_park12((uint32_t)(uintptr_t)(fgs_lds_float *)red, v);
-    else addtid_park13((uint32_t)(uintptr_t)(fgs_lds_float *)red, v);
+    addtid_park(red, v);
     return wave_sum_addtid_finish(red, lane, (uint32_t)NV);
-}
-// eleven values (phase backward); `red` = FGS_RED_PITCH * 11 floats
-__device__ __forceinline__ float wave_sum11_addtid(float *red, const float (&v)[11], uint32_t lane) {
-    addtid_park11((uint32_t)(uintptr_t)(fgs_lds_float *)red, v);
-    return wave_sum_addtid_finish(red, lane, 11u);
 }
