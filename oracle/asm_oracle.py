@@ -49,6 +49,15 @@ def _zero_visible(N, H, W, bg, phases, proj, need, wavelengths, depth=False):
     return out
 
 
+def _regime(rendered, tasq):
+    """Which side of its two kinks the output stage is on: M = max(peak, 1) and the clamp of the summed amplitude at 1."""
+    r = rendered.detach()
+    peak = r.max()
+    below = r[r < peak]
+    return dict(peak=float(peak), peak_count=int((r == peak).sum()), runner_up=float(below.max()) if below.numel() else 0.0,
+                tasq=tasq.detach().double().numpy())
+
+
 def _project_bwd(pos, scale, quat, cam, proj, mean, conic, dep, f64):
     """Chain dL/d(mean2d, conic, depth) (autograd of the restatement) through the C oracle's projection adjoint."""
     import ctypes
@@ -85,12 +94,17 @@ def propagate(field, z, wl, pixel_pitch=1.0 / 256.0):
 
 def render(pos, scale, quat, color, opacity, phases, wavelengths, cam, bg=(0.0, 0.0, 0.0), max_radius=64.0,
            num_planes=16, depth_range=(0.1, 2.0), focal_depth=0.5, pixel_pitch=1.0 / 256.0,
-           dtype=torch.float32, grad_out=None, project_f64=False):
+           dtype=torch.float32, grad_out=None, project_f64=False, bbox=None, plane_idx=None):
     """ASM forward for one image; with grad_out (3,H,W) also returns gradients of sum(img*grad_out)
     w.r.t. mean2d/conic/opacity/colour/phase/wavelengths chained through the C oracle's projection
-    backward to positions/scales/rotations."""
+    backward to positions/scales/rotations.  `bbox` (N,4) / `plane_idx` (N,) replace the run's own bboxes / plane assignment
+    (tests/test_splat_seams.py: what one seam error does to the result); the result also carries the normalisation's
+    regime: `peak` = max sqrt(I + 1e-8), `peak_count` = elements equal to it, `runner_up` = the largest element below it,
+    `tasq` = the per-pixel summed amplitude in front of its clamp to [0, 1]."""
     with _prec(project_f64):  # (project_f64: the projection and its adjoint on the fp64 referee build too -- the sweeps' referee)
         proj = orc.project(pos, scale, quat, cam, max_radius)
+    if bbox is not None:
+        proj = dict(proj, bbox=np.ascontiguousarray(bbox, np.int32))
     W, H = cam.width, cam.height
     vis = proj["visible"].astype(bool)
     N = len(vis)
@@ -108,7 +122,10 @@ def render(pos, scale, quat, color, opacity, phases, wavelengths, cam, bg=(0.0, 
     # sat 1.7e-5 ... 2e-4 (dL/dlambda) from the reference's own fp64 run on K6: z rounded to fp32 under a phase of ~200 rad)
     planes = torch.linspace(depth_range[0], depth_range[1], num_planes, dtype=dtype)
     depth_t = torch.tensor(proj["depth"], dtype=dtype)
-    plane_idx = (depth_t.unsqueeze(1) - planes.unsqueeze(0)).abs().argmin(dim=1)  # DR:1147-1148
+    if plane_idx is None:
+        plane_idx = (depth_t.unsqueeze(1) - planes.unsqueeze(0)).abs().argmin(dim=1)  # DR:1147-1148
+    else:
+        plane_idx = torch.as_tensor(np.asarray(plane_idx), dtype=torch.int64)
     fields = [[torch.zeros(H, W, dtype=dtype), torch.zeros(H, W, dtype=dtype)] for _ in range(num_planes * 3)]
     for i in range(N):  # DR:1238-1283 (order-independent accumulation)
         if not vis[i]:
@@ -137,11 +154,12 @@ def render(pos, scale, quat, color, opacity, phases, wavelengths, cam, bg=(0.0, 
             total[c] = total[c] + _ifft2(_fft2(fc[c]) * Htf)
     tf = torch.stack(total, dim=-1)                                   # (H,W,3) complex
     rendered = _sqrt(tf.real ** 2 + tf.imag ** 2 + 1e-8)               # DR:1316-1319
+    regime = _regime(rendered, tf.abs().sum(dim=-1))
     rendered = torch.clamp(rendered / rendered.max().clamp(min=1.0), 0, 1)
     total_amp = tf.abs().sum(dim=-1, keepdim=True).clamp(0, 1)         # DR:1327
     rendered = rendered + torch.tensor(bg, dtype=dtype).view(1, 1, 3) * (1 - total_amp)
     img = torch.clamp(rendered.permute(2, 0, 1), 0, 1)
-    out = dict(image=img.detach().float().numpy(), plane_idx=plane_idx.numpy(), proj=proj)
+    out = dict(image=img.detach().float().numpy(), plane_idx=plane_idx.numpy(), proj=proj, **regime)
     if need:
         loss = (img * torch.tensor(grad_out, dtype=dtype)).sum()
         if loss.requires_grad:  # (no visible Gaussian: the image is a constant, every gradient is zero)
@@ -154,12 +172,16 @@ def render(pos, scale, quat, color, opacity, phases, wavelengths, cam, bg=(0.0, 
 
 
 def render_wave(pos, scale, quat, color, opacity, phases, cam, bg=(0.0, 0.0, 0.0), max_radius=64.0,
-                dtype=torch.float32, grad_out=None, grad_depth=None, project_f64=False):
+                dtype=torch.float32, grad_out=None, grad_depth=None, project_f64=False, bbox=None, max_to_first=False):
     """WaveFieldRenderer (DR:747-926) for one image: order-independent complex accumulation, intensity,
     max normalisation, background, amplitude-weighted depth map.  Gradients by autograd of this
-    restatement, chained through the C oracle's projection backward."""
+    restatement, chained through the C oracle's projection backward.  `bbox` and the regime entries of the result: as in
+    render(), `tasq` = sqrt(sum_c I_c + 1e-8); max_to_first: the gradient of the maximum goes to ONE of the elements equal to
+    it instead of being shared among them (what a wrong tie rule does; the forward is unchanged)."""
     with _prec(project_f64):  # (project_f64: the projection and its adjoint on the fp64 referee build too -- the sweeps' referee)
         proj = orc.project(pos, scale, quat, cam, max_radius)
+    if bbox is not None:
+        proj = dict(proj, bbox=np.ascontiguousarray(bbox, np.int32))
     W, H = cam.width, cam.height
     vis = proj["visible"].astype(bool)
     N = len(vis)
@@ -191,12 +213,14 @@ def render_wave(pos, scale, quat, color, opacity, phases, cam, bg=(0.0, 0.0, 0.0
         wt = wt + torch.nn.functional.pad(amp, pad)
     wr, wi = torch.stack(re, -1), torch.stack(im, -1)
     rendered = torch.sqrt(wr ** 2 + wi ** 2 + 1e-8)
-    rendered = torch.clamp(rendered / rendered.max().clamp(min=1.0), 0, 1)
+    regime = _regime(rendered, torch.sqrt((wr ** 2 + wi ** 2).sum(dim=-1) + 1e-8))
+    peak = rendered.flatten()[rendered.argmax()] if max_to_first else rendered.max()
+    rendered = torch.clamp(rendered / peak.clamp(min=1.0), 0, 1)
     ta = torch.sqrt((wr ** 2 + wi ** 2).sum(dim=-1, keepdim=True) + 1e-8).clamp(0, 1)
     rendered = rendered + torch.tensor(bg, dtype=dtype).view(1, 1, 3) * (1 - ta)
     img = torch.clamp(rendered.permute(2, 0, 1), 0, 1)
     dmap = ad / (wt + 1e-8)
-    out = dict(image=img.detach().float().numpy(), depth=dmap.detach().float().numpy(), proj=proj)
+    out = dict(image=img.detach().float().numpy(), depth=dmap.detach().float().numpy(), proj=proj, **regime)
     if need:
         loss = (img * torch.tensor(grad_out, dtype=dtype)).sum()
         if grad_depth is not None:
