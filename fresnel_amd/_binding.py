@@ -27,6 +27,8 @@ EXPORTED_SYMBOLS = [
     "fgs_pixel_loss_workspace_bytes", "fgs_pixel_loss_stage1", "fgs_pixel_loss_stage2", "fgs_pixel_loss_stage3",
     "fgs_pixel_loss_forward", "fgs_pixel_loss_backward",
     "fgs_head_workspace_bytes", "fgs_head_forward", "fgs_head_backward",
+    "fgs_nca_workspace_bytes", "fgs_nca_perceive_forward", "fgs_nca_perceive_backward", "fgs_nca_update_forward",
+    "fgs_nca_update_backward",
 ]
 
 STAGES = ["project", "depth_sort", "dup_emit", "tile_sort", "tile_ranges", "composite_fwd",
@@ -117,6 +119,10 @@ class FgsHeadDims(ctypes.Structure):
                 ("edge_scale_factor", ctypes.c_float), ("edge_opacity_boost", ctypes.c_float)]
 
 
+class FgsNcaDims(ctypes.Structure):
+    _fields_ = [("batch", ctypes.c_int32), ("points", ctypes.c_int32), ("state_dim", ctypes.c_int32), ("k", ctypes.c_int32)]
+
+
 class FgsError(RuntimeError):
     pass
 
@@ -195,6 +201,15 @@ def load():
     lib.fgs_head_forward.argtypes = [cp(FgsHeadDims)] + [vp] * 13
     lib.fgs_head_backward.argtypes = [cp(FgsHeadDims)] + [vp] * 16
     for fn in (lib.fgs_head_workspace_bytes, lib.fgs_head_forward, lib.fgs_head_backward):
+        fn.restype = ctypes.c_int
+    nd = cp(FgsNcaDims)
+    lib.fgs_nca_workspace_bytes.argtypes = [nd, cp(ctypes.c_size_t)]
+    lib.fgs_nca_perceive_forward.argtypes = [nd] + [vp] * 4
+    lib.fgs_nca_perceive_backward.argtypes = [nd] + [vp] * 4
+    lib.fgs_nca_update_forward.argtypes = [nd] + [vp] * 4 + [f32, vp, vp]
+    lib.fgs_nca_update_backward.argtypes = [nd] + [vp] * 3 + [f32] + [vp] * 5
+    for fn in (lib.fgs_nca_workspace_bytes, lib.fgs_nca_perceive_forward, lib.fgs_nca_perceive_backward,
+               lib.fgs_nca_update_forward, lib.fgs_nca_update_backward):
         fn.restype = ctypes.c_int
     for fn in (lib.fgs_asm_propagate_workspace_bytes, lib.fgs_asm_propagate_forward, lib.fgs_asm_propagate_backward,
                lib.fgs_spectral_workspace_bytes, lib.fgs_spectral_loss_forward, lib.fgs_spectral_loss_backward,

@@ -63,6 +63,9 @@ SOURCES = {
     "fgs_pixel_loss.hip": ["-ffp-contract=off"],
     # no FMA contraction: the backward recomputes the forward, and its clamp gates and quaternion branch must be the forward's
     "fgs_head.hip": ["-ffp-contract=off"],
+    # no FMA contraction: the neighbour distance d2 = (dx dx + dy dy) + dz dz and the update state + step (delta mask) are
+    # DEFINED with every operation rounded on its own (include/fgs.h); tests compare them bit for bit with torch expressions
+    "fgs_nca.hip": ["-ffp-contract=off"],
 }
 LINK_LIBS = ["-lhipfft"]
 

@@ -6,6 +6,10 @@ and state_dict keys are the reference's, so its checkpoints load with strict=Tru
 are torch modules; the Gaussian-parameter head behind the MLP is `gaussian_head`: torch expressions (head_backend "torch", runs
 anywhere) or the fused HIP kernel pair of csrc/fgs_head.hip (head_backend "hip", CUDA/ROCm tensors only, no fallback).
 
+`NCAGaussianDecoder` mirrors the reference's class of that name (scripts/models/nca_gaussian_decoder.py, "NCA"; --experiment 5) the
+same way; the two parts of its step that are not GEMMs are `nca_perceive` and `nca_update`: the reference's torch expressions
+(nca_backend "torch") or the HIP kernels of csrc/fgs_nca.hip (nca_backend "hip", CUDA/ROCm tensors only, no fallback).
+
 `PatchGaussianDecoder` is the older stand-in: own definition with the interface, shapes and ranges of the reference's DirectPatchDecoder
 (scripts/models/gaussian_decoder_models.py:622-948): a 37x37 DINOv2 patch grid, K Gaussians per
 patch -> dict{positions (B,N,3), scales (B,N,3) in [1e-6,2], rotations (B,N,4) unit wxyz,
@@ -488,3 +492,218 @@ class FibonacciPatchDecoder(nn.Module):
             opacity_mod = (0.5 + self.opacity_modulator(self.pose_encoder(elevation, azimuth))).reshape(Bn)
         return gaussian_head(raw, xy, base_z, pose=_pose_row(elevation, azimuth) if posed else None, opacity_mod=opacity_mod,
                              xy_gain=0.15, backend=self.head_backend)
+
+
+# =================================================================================================================================
+# The reference's NCAGaussianDecoder (scripts/models/nca_gaussian_decoder.py, "NCA") and the two pieces of its step that are not GEMMs
+# =================================================================================================================================
+NCA_BACKENDS = ("torch", "hip")
+
+
+def _check_nca_backend(backend):
+    if backend not in NCA_BACKENDS:
+        raise ValueError(f"unknown nca_backend {backend!r}: one of {NCA_BACKENDS}")
+    return backend
+
+
+def _nca_dims(state, k):
+    Bn, N, D = state.shape
+    return B.FgsNcaDims(Bn, N, D, int(k))
+
+
+class _NcaPerceiveHip(torch.autograd.Function):
+    """fgs_nca_perceive_forward / _backward.  Saved: the neighbour table alone."""
+
+    @staticmethod
+    def forward(ctx, state, k):
+        if not state.is_cuda:
+            raise B.FgsError("nca_perceive (backend 'hip') needs CUDA/ROCm tensors; there is no CPU fallback")
+        lib = B.load()
+        state_ = _f32c(state)
+        d = _nca_dims(state_, k)
+        dev = state_.device
+        with torch.cuda.device(dev):
+            perception = torch.empty((d.batch, d.points, (d.k + 1) * d.state_dim), dtype=torch.float32, device=dev)
+            neighbors = torch.empty((d.batch, d.points, d.k), dtype=torch.int32, device=dev)
+            B.check(lib.fgs_nca_perceive_forward(ctypes.byref(d), _ptr(state_), _ptr(perception), _ptr(neighbors), _stream()),
+                    "fgs_nca_perceive_forward")
+        ctx.dims = d
+        ctx.save_for_backward(neighbors)
+        ctx.mark_non_differentiable(neighbors)
+        return perception, neighbors
+
+    @staticmethod
+    def backward(ctx, g_perception, _g_neighbors):
+        lib = B.load()
+        neighbors, = ctx.saved_tensors
+        d = ctx.dims
+        g_ = _f32c(g_perception)
+        with torch.cuda.device(g_.device):
+            g_state = torch.empty((d.batch, d.points, d.state_dim), dtype=torch.float32, device=g_.device)
+            B.check(lib.fgs_nca_perceive_backward(ctypes.byref(d), _ptr(neighbors), _ptr(g_), _ptr(g_state), _stream()),
+                    "fgs_nca_perceive_backward")
+        return g_state, None
+
+
+def _nca_perceive_torch(state, k):
+    """NCA:247-264 as written there: cdist, topk of k + 1 smallest with the first (self, at distance 0) dropped, gather over the
+    (B, N, N, D) expanded view, cat."""
+    Bn, N, D = state.shape
+    positions = state[..., :3]
+    dists = torch.cdist(positions, positions)
+    _, neighbor_idx = dists.topk(k + 1, dim=-1, largest=False)
+    neighbor_idx = neighbor_idx[..., 1:]
+    idx_expanded = neighbor_idx.unsqueeze(-1).expand(-1, -1, -1, D)
+    neighbors = torch.gather(state.unsqueeze(1).expand(-1, N, -1, -1), dim=2, index=idx_expanded)
+    return torch.cat([state, neighbors.reshape(Bn, N, k * D)], dim=-1), neighbor_idx
+
+
+def nca_perceive(state: torch.Tensor, k: int, backend: str = "torch") -> Tuple[torch.Tensor, torch.Tensor]:
+    """The perception input of one NCA step (NCA:247-264): state (B, N, D), channels 0..2 the position -> (perception
+    (B, N, (k+1) D): every point's own row followed by the rows of its k nearest neighbours; neighbors (B, N, k), not
+    differentiable).  Gradients flow to the gathered rows only, never through the choice of neighbours.
+    backend "torch": the reference's cdist + topk + gather, any device; neighbors int64, ties and near-ties in topk's order.
+    backend "hip": csrc/fgs_nca.hip, one launch each way, the CANONICAL neighbours of include/fgs.h (k smallest (d2, j), d2 in
+    exactly rounded fp32 differences), int32; CUDA/ROCm tensors only; 1 <= k <= 16, k + 1 <= N <= 4096, 3 <= D <= 64."""
+    _check_nca_backend(backend)
+    if state.dim() != 3 or state.shape[-1] < 3:
+        raise ValueError(f"state must be (B, N, D >= 3), got {tuple(state.shape)}")
+    if not 1 <= int(k) < state.shape[1]:
+        raise ValueError(f"k must be in [1, N - 1] = [1, {state.shape[1] - 1}], got {k}")
+    return _NcaPerceiveHip.apply(state, int(k)) if backend == "hip" else _nca_perceive_torch(state, int(k))
+
+
+class _NcaUpdateHip(torch.autograd.Function):
+    """fgs_nca_update_forward / _backward.  dL/dstate is the upstream gradient itself: the same tensor is returned, no copy."""
+
+    @staticmethod
+    def forward(ctx, state, delta, step_size, uniform, update_prob):
+        if not state.is_cuda:
+            raise B.FgsError("nca_update (backend 'hip') needs CUDA/ROCm tensors; there is no CPU fallback")
+        lib = B.load()
+        state_, delta_, step_, uni_ = _f32c(state), _f32c(delta), _f32c(step_size), _f32c(uniform)
+        d = _nca_dims(state_, 1)
+        with torch.cuda.device(state_.device):
+            new_state = torch.empty_like(state_)
+            B.check(lib.fgs_nca_update_forward(ctypes.byref(d), _ptr(state_), _ptr(delta_), _ptr(step_), _ptr(uni_),
+                                               float(update_prob), _ptr(new_state), _stream()), "fgs_nca_update_forward")
+        ctx.dims, ctx.update_prob = d, float(update_prob)
+        ctx.save_for_backward(delta_, step_, uni_)
+        return new_state
+
+    @staticmethod
+    def backward(ctx, g_new_state):
+        lib = B.load()
+        delta_, step_, uni_ = ctx.saved_tensors
+        d = ctx.dims
+        g_ = _f32c(g_new_state)
+        dev = g_.device
+        with torch.cuda.device(dev):
+            nb = ctypes.c_size_t(0)
+            B.check(lib.fgs_nca_workspace_bytes(ctypes.byref(d), ctypes.byref(nb)), "fgs_nca_workspace_bytes")
+            g_delta = torch.empty_like(delta_)
+            g_step = torch.empty((), dtype=torch.float32, device=dev)
+            scratch = torch.empty(nb.value, dtype=torch.uint8, device=dev)
+            B.check(lib.fgs_nca_update_backward(ctypes.byref(d), _ptr(delta_), _ptr(step_), _ptr(uni_), ctx.update_prob, _ptr(g_),
+                                                _ptr(g_delta), _ptr(g_step), _ptr(scratch), _stream()), "fgs_nca_update_backward")
+        return g_new_state, g_delta, g_step, None, None
+
+
+def nca_update(state: torch.Tensor, delta: torch.Tensor, step_size: torch.Tensor, uniform: Optional[torch.Tensor] = None,
+               update_prob: float = 0.5, backend: str = "torch") -> torch.Tensor:
+    """The tail of one NCA step (NCA:276-284): state + step_size x (delta x mask) with mask = (uniform < update_prob) per point.
+    state, delta (B, N, D); step_size a 0-dim tensor (the learnable step); uniform (B, N) | (B, N, 1) draws of U[0, 1), or None:
+    eval mode, no mask.  Gradients flow to state, delta and step_size.
+    backend "torch": the reference's expressions, any device.  backend "hip": csrc/fgs_nca.hip, one launch forward (the same
+    roundings: bit-equal), two backward (dL/dstep_size by a fixed-order sum in double: repeats bit for bit); CUDA/ROCm only."""
+    _check_nca_backend(backend)
+    if state.dim() != 3 or delta.shape != state.shape:
+        raise ValueError(f"state and delta must share one (B, N, D) shape, got {tuple(state.shape)} and {tuple(delta.shape)}")
+    if uniform is not None:
+        if tuple(uniform.shape) not in (tuple(state.shape[:2]), tuple(state.shape[:2]) + (1,)):
+            raise ValueError(f"uniform must be (B, N) or (B, N, 1), got {tuple(uniform.shape)}")
+        uniform = uniform.reshape(state.shape[0], state.shape[1], 1)
+    if backend == "hip":
+        return _NcaUpdateHip.apply(state, delta, step_size.reshape(()), uniform, update_prob)
+    if uniform is not None:
+        delta = delta * (uniform < update_prob).float()
+    return state + step_size * delta
+
+
+def _nca_uniform(batch: int, points: int, device) -> torch.Tensor:
+    """The step's draws (NCA:278): one torch.rand(B, N, 1) per step from the global generator, so the stream is the reference's."""
+    return torch.rand(batch, points, 1, device=device)
+
+
+class NCAGaussianDecoder(nn.Module):
+    """The reference's NCAGaussianDecoder (NCA:39-365, --experiment 5): Gaussians are cells of a cellular automaton.  Features
+    sampled at `n_points` spiral points give an initial (B, N, 16) state [pos 3, scale 3, rot6d 6, colour 3, opacity 1] with x, y on
+    the spiral and z locked to the depth; `n_steps` times every point perceives itself and its `k_neighbors` nearest neighbours,
+    two small MLPs turn that into a delta, and a random half of the points (training) take a step of the learnable `step_size`.
+    Same constructor arguments and defaults, forward signature, returned dict, state_dict keys and registration order.
+    `nca_backend`: neighbour perception and update, "torch" (the reference's cdist / topk / gather) | "hip" (nca_perceive,
+    nca_update); `head_backend`: the final state -> Gaussian parameters, which is gaussian_head with a zero grid and gain 1."""
+
+    def __init__(self, feature_dim: int = 384, n_points: int = 377, n_steps: int = 16, k_neighbors: int = 6, hidden_dim: int = 128,
+                 update_prob: float = 0.5, state_dim: int = 16, *, nca_backend: str = "torch", head_backend: str = "torch"):
+        super().__init__()
+        self.feature_dim, self.n_points, self.n_steps, self.k_neighbors = feature_dim, n_points, n_steps, k_neighbors
+        self.hidden_dim, self.update_prob, self.state_dim = hidden_dim, update_prob, state_dim
+        self.nca_backend, self.head_backend = _check_nca_backend(nca_backend), _check_backend(head_backend)
+        sx, sy = fibonacci_spiral_positions(n_points)
+        self.register_buffer("spiral_x", sx)
+        self.register_buffer("spiral_y", sy)
+        self.depth_offset = nn.Parameter(torch.tensor(-2.0))
+        self.init_state_net = nn.Sequential(nn.Linear(feature_dim, hidden_dim * 2), nn.ReLU(inplace=True),
+                                            nn.Linear(hidden_dim * 2, hidden_dim), nn.ReLU(inplace=True),
+                                            nn.Linear(hidden_dim, state_dim))
+        self.perception = nn.Sequential(nn.Linear(state_dim * (k_neighbors + 1), hidden_dim * 2), nn.ReLU(inplace=True),
+                                        nn.Linear(hidden_dim * 2, hidden_dim), nn.ReLU(inplace=True))
+        self.update_rule = nn.Sequential(nn.Linear(hidden_dim, hidden_dim), nn.ReLU(inplace=True), nn.Linear(hidden_dim, state_dim))
+        nn.init.zeros_(self.update_rule[-1].weight)  # residual learning: the automaton starts as the identity (NCA:131-132)
+        nn.init.zeros_(self.update_rule[-1].bias)
+        self.step_size = nn.Parameter(torch.tensor(0.1))
+        # the head's grid term: the state carries absolute x, y (not part of checkpoints)
+        self.register_buffer("zero_xy", torch.zeros(n_points, 2), persistent=False)
+
+    def forward(self, features: torch.Tensor, depth: Optional[torch.Tensor] = None, image_size: Tuple[int, int] = (518, 518),
+                num_gaussians: Optional[int] = None, elevation: Optional[torch.Tensor] = None,
+                azimuth: Optional[torch.Tensor] = None, n_steps: Optional[int] = None,
+                return_trajectory: bool = False) -> Dict[str, torch.Tensor]:
+        """features (B, C, H, W); depth (B, 1, h, w) or None; num_gaussians, elevation, azimuth: accepted and ignored, as there.
+        -> positions, scales, rotations, colors, opacities [, trajectory: the n_steps + 1 detached states]."""
+        n_steps = n_steps if n_steps is not None else self.n_steps
+        Bn, C = features.shape[:2]
+        N = self.n_points
+        coords = torch.stack([self.spiral_x, self.spiral_y], dim=-1).view(1, 1, N, 2).expand(Bn, -1, -1, -1)
+        sampled = F.grid_sample(features, coords, mode="bilinear", padding_mode="border", align_corners=True)  # (B, C, 1, N)
+        if depth is not None:
+            d = F.grid_sample(depth, coords, mode="bilinear", padding_mode="border", align_corners=True).reshape(Bn, N)
+        else:
+            d = torch.zeros(Bn, N, device=features.device)
+        init = self.init_state_net(sampled.squeeze(2).permute(0, 2, 1).reshape(Bn * N, C)).reshape(Bn, N, self.state_dim)
+        # x, y: the spiral plus a small detached offset; z locked to the depth (NCA:199-210)
+        x = self.spiral_x.view(1, N) + init[..., 0].detach() * 0.15
+        y = self.spiral_y.view(1, N) + init[..., 1].detach() * 0.15
+        z = self.depth_offset + d * (-2)
+        state = torch.cat([torch.stack([x, y, z], dim=-1), init[..., 3:]], dim=-1)
+        trajectory = [state.detach().clone()] if return_trajectory else None
+        for _ in range(n_steps):
+            state = self._nca_step(state)
+            if return_trajectory:
+                trajectory.append(state.detach().clone())
+        result = self._parse_state(state)
+        if return_trajectory:
+            result["trajectory"] = trajectory
+        return result
+
+    def _nca_step(self, state: torch.Tensor) -> torch.Tensor:
+        Bn, N, D = state.shape
+        perception, _ = nca_perceive(state, self.k_neighbors, backend=self.nca_backend)
+        delta = self.update_rule(self.perception(perception.reshape(Bn * N, -1))).reshape(Bn, N, D)
+        uniform = _nca_uniform(Bn, N, state.device) if self.training else None
+        return nca_update(state, delta, self.step_size, uniform, self.update_prob, backend=self.nca_backend)
+
+    def _parse_state(self, state: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """NCA:324-365 through the shared head: base_xy = 0 and xy_gain = 1 leave x, y as they are, z rides as base_z."""
+        return gaussian_head(state.unsqueeze(2), self.zero_xy, state[..., 2], xy_gain=1.0, backend=self.head_backend)

@@ -15,7 +15,9 @@ Kept from TGD (same flag names / defaults / behaviour):
                     batch (fresnel_amd/handoff.py, TGD:1069-1207)
   decoder           --decoder standin (default: PatchGaussianDecoder, own head) | direct | fibonacci: mirrors of the reference's
                     DirectPatchDecoder / FibonacciPatchDecoder (its keys: --resume takes its checkpoints), constructed as at
-                    TGD:1814-1840; --experiment 4 implies fibonacci; --head_backend hip runs their head as fused HIP kernels
+                    TGD:1814-1840; --experiment 4 implies fibonacci; --head_backend hip runs their head as fused HIP kernels;
+                    --experiment 5 implies nca: NCAGaussianDecoder (TGD:1841-1849; --nca_steps, --nca_neighbors, --nca_step_size),
+                    --nca_backend hip runs its neighbour perception and update as HIP kernels (csrc/fgs_nca.hip)
   renderer choice   TileBasedRenderer(res, res, use_phase_blending, phase_amplitude)   TGD:1898-1907;
                     --experiment 4 --use_phase_blending: FourierGaussianRenderer(res, res, 0.65, 0.55, 0.45)  TGD:1877-1890
   camera            fx = fy = 0.8*res, cx = cy = res/2, view = I                       TGD:1910-1917
@@ -68,7 +70,8 @@ from torch.optim.lr_scheduler import CosineAnnealingLR
 
 import numpy as np
 
-from .decoder import HEAD_BACKENDS, DirectPatchDecoder, FibonacciPatchDecoder, PatchGaussianDecoder
+from .decoder import (HEAD_BACKENDS, NCA_BACKENDS, DirectPatchDecoder, FibonacciPatchDecoder, NCAGaussianDecoder,
+                      PatchGaussianDecoder)
 from .dist import DPContext
 from .handoff import HFTSConfig, camera_for_batch, importance_subsample, sample_training_pose
 
@@ -138,7 +141,14 @@ class TrainingConfig:  # subset of TGD:97-162 that this path uses; same names an
                               # "fibonacci": mirrors of the reference's DirectPatchDecoder / FibonacciPatchDecoder (fresnel_amd/
                               # decoder.py: its state_dict keys, its head); --experiment 4 implies "fibonacci" (TGD:1829-1841)
     head_backend: str = "torch"  # Gaussian-parameter head of "direct" / "fibonacci": torch expressions | "hip" (csrc/fgs_head.hip)
-    n_spiral_points: int = 377   # "fibonacci": points of the golden-angle spiral (TGD:1427)
+    n_spiral_points: int = 377   # "fibonacci" / "nca": points of the golden-angle spiral (TGD:1427)
+    # "nca" (--experiment 5, TGD:1842-1849): steps and neighbours of the automaton (TGD:1435-1440), the backend of its neighbour
+    # perception and update (torch: cdist / topk / gather | hip: csrc/fgs_nca.hip), and the INITIAL value of the learnable step
+    # size -- the reference parses --nca_step_size and never passes it on (TGD:1844-1849); the default is the class's own 0.1
+    nca_steps: int = 16
+    nca_neighbors: int = 6
+    nca_backend: str = "torch"
+    nca_step_size: float = 0.1
     workspace: str = "worst"  # rasterizer workspaces: "worst" (sized for the radius cap) | "adaptive" (sized by the duplicates
                               # the previous steps needed, TileBasedRenderer(workspace="adaptive"); a step whose scene outgrew
                               # the capacity renders NaN and is dropped by the NaN/Inf skip, the next one has room)
@@ -540,12 +550,12 @@ def train_step(model, renderer, camera, batch, optimizer, cfg: TrainingConfig, d
     return StepResult(terms, skipped)
 
 
-DECODERS = ("standin", "direct", "fibonacci")
+DECODERS = ("standin", "direct", "fibonacci", "nca")
 
 
 def make_decoder(cfg: TrainingConfig):
     """The step's decoder: the stand-in (default), or a mirror of the reference's class constructed as its training script
-    constructs it (TGD:1814-1828 experiment 2, TGD:1832-1840 experiment 4)."""
+    constructs it (TGD:1814-1828 experiment 2, TGD:1832-1840 experiment 4, TGD:1842-1849 experiment 5)."""
     phase_out = cfg.use_phase_blending or cfg.use_wave_rendering
     if cfg.decoder == "standin":
         return PatchGaussianDecoder(cfg.feature_dim, cfg.gaussians_per_patch, grid=cfg.feature_size,
@@ -567,6 +577,12 @@ def make_decoder(cfg: TrainingConfig):
                                      use_fresnel_zones=cfg.use_fresnel_zones, num_fresnel_zones=cfg.num_fresnel_zones,
                                      use_phase_output=phase_out, use_pose_encoding=cfg.use_pose_encoding,
                                      head_backend=cfg.head_backend)
+    if cfg.decoder == "nca":  # TGD:1842-1849
+        model = NCAGaussianDecoder(feature_dim=cfg.feature_dim, n_points=cfg.n_spiral_points, n_steps=cfg.nca_steps,
+                                   k_neighbors=cfg.nca_neighbors, nca_backend=cfg.nca_backend, head_backend=cfg.head_backend)
+        with torch.no_grad():
+            model.step_size.fill_(cfg.nca_step_size)
+        return model
     raise ValueError(f"unknown decoder {cfg.decoder!r}: one of {DECODERS}")
 
 
@@ -671,6 +687,8 @@ def run_training(cfg: TrainingConfig, dp: Optional[DPContext] = None,
     torch.manual_seed(cfg.seed)
     if cfg.decoder != "standin" and cfg.head_backend == "hip" and device.type != "cuda":
         raise ValueError("head_backend 'hip' needs a GPU device: the HIP head kernels have no CPU fallback")
+    if cfg.decoder == "nca" and cfg.nca_backend == "hip" and device.type != "cuda":
+        raise ValueError("nca_backend 'hip' needs a GPU device: the HIP perception / update kernels have no CPU fallback")
     model = make_decoder(cfg).to(device)
     dp.broadcast_parameters(model)
     train_res = hfts.get_effective_train_resolution(cfg.image_size) if hfts is not None else cfg.image_size
@@ -837,23 +855,36 @@ def arg_parser() -> argparse.ArgumentParser:
                          "(loads its checkpoints); --experiment 4 implies fibonacci")
     ap.add_argument("--head_backend", default=c.head_backend, choices=list(HEAD_BACKENDS),
                     help="Gaussian-parameter head of --decoder direct / fibonacci: torch expressions (default) or the fused HIP kernels")
-    ap.add_argument("--n_spiral_points", type=int, default=c.n_spiral_points, help="TGD:1427 (--decoder fibonacci)")
+    ap.add_argument("--n_spiral_points", type=int, default=c.n_spiral_points, help="TGD:1427 (--decoder fibonacci / nca)")
+    ap.add_argument("--nca_steps", type=int, default=c.nca_steps, help="NCA iterations (TGD:1435; --experiment 5)")
+    ap.add_argument("--nca_neighbors", type=int, default=c.nca_neighbors, help="k nearest neighbours every point perceives (TGD:1437)")
+    ap.add_argument("--nca_step_size", type=float, default=c.nca_step_size,
+                    help="initial value of the learnable step size (the reference parses this flag, TGD:1439, and never uses it)")
+    ap.add_argument("--nca_backend", default=c.nca_backend, choices=list(NCA_BACKENDS),
+                    help="neighbour perception and update of --experiment 5: the reference's torch ops (default) or the fused HIP kernels")
     return ap
 
 
 def config_from_args(a) -> TrainingConfig:
     """The TrainingConfig of a parsed command line (no device yet).  --experiment 2 trains a patch-grid decoder, --experiment 4
-    the Fibonacci decoder (TGD:1829-1841), with --use_phase_blending through the Fourier renderer (TGD:1877-1890); the
-    reference's other experiments have no counterpart here."""
-    if a.experiment not in (2, 4):
-        raise SystemExit("only --experiment 2 (patch-grid decoder) and --experiment 4 (Fibonacci decoder) are on this repo's hot path")
+    the Fibonacci decoder (TGD:1829-1841), with --use_phase_blending through the Fourier renderer (TGD:1877-1890), --experiment 5
+    the NCA decoder (TGD:1841-1849) through the TileBasedRenderer; the reference's other experiments have no counterpart here."""
+    if a.experiment not in (2, 4, 5):
+        raise SystemExit("only --experiment 2 (patch-grid decoder), --experiment 4 (Fibonacci decoder) and --experiment 5 (NCA "
+                         "decoder) are on this repo's hot path")
     decoder = a.decoder
     if a.experiment == 4:
-        if decoder == "direct":
-            raise SystemExit("--experiment 4 trains the Fibonacci decoder: --decoder direct contradicts it")
+        if decoder in ("direct", "nca"):
+            raise SystemExit(f"--experiment 4 trains the Fibonacci decoder: --decoder {decoder} contradicts it")
         decoder = "fibonacci"
+    elif a.experiment == 5:
+        if decoder in ("direct", "fibonacci"):
+            raise SystemExit(f"--experiment 5 trains the NCA decoder: --decoder {decoder} contradicts it")
+        decoder = "nca"
     elif decoder == "fibonacci":
         raise SystemExit("--decoder fibonacci is --experiment 4")
+    elif decoder == "nca":
+        raise SystemExit("--decoder nca is --experiment 5")
     return TrainingConfig(experiment=a.experiment, data_dir=a.data_dir, output_dir=a.output_dir,
                           batch_size=a.batch_size, epochs=a.epochs, lr=a.lr, image_size=a.image_size,
                           gaussians_per_patch=a.gaussians_per_patch, max_images=a.max_images,
@@ -873,7 +904,9 @@ def config_from_args(a) -> TrainingConfig:
                           ssim_backend=a.ssim_backend, boundary_weight=a.boundary_weight,
                           use_vlm_guidance=a.use_vlm_guidance, vlm_weight=a.vlm_weight,
                           pixel_loss_backend=a.pixel_loss_backend, workspace=a.workspace,
-                          decoder=decoder, head_backend=a.head_backend, n_spiral_points=a.n_spiral_points)
+                          decoder=decoder, head_backend=a.head_backend, n_spiral_points=a.n_spiral_points,
+                          nca_steps=a.nca_steps, nca_neighbors=a.nca_neighbors, nca_backend=a.nca_backend,
+                          nca_step_size=a.nca_step_size)
 
 
 def main(argv=None):

@@ -469,6 +469,43 @@ int fgs_head_backward(const FgsHeadDims *dims, const float *raw, const float *po
                       float *g_opacity_mod, void *scratch, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Neighbour perception and state update of the reference's NCAGaussianDecoder (scripts/models/nca_gaussian_decoder.py,
+ * "NCA": _nca_step 232-286).  state (B, N, D) fp32, channels 0..2 the position.
+ *
+ * Canonical neighbours (this library's definition; torch.topk leaves the order of ties open and cdist changes its arithmetic
+ * with the point count): d2(i, j) = (dx dx + dy dy) + dz dz of the coordinate differences, every operation rounded to fp32; a
+ * NaN d2 counts as +inf; the neighbours of i are the k points j != i with the smallest (d2, j), in ascending (d2, j) order.
+ * Self is excluded by index.  For ANY input, NaN and Inf included, the k indices written for a point are in [0, N), distinct
+ * and different from the point's own.
+ *
+ * fgs_nca_perceive_forward:  perception (B, N, (k+1) D) = the point's own row, then its k neighbours' rows (the input of the
+ *     reference's `perception` network, NCA:247-264); neighbors (B, N, k) int32 -- all that the backward needs (`saved`).
+ * fgs_nca_perceive_backward: g_state[b, j, :] = g_perception[b, j, 0:D] + sum of g_perception[b, i, (s+1) D : (s+2) D] over all
+ *     (i, s) with neighbors[b, i, s] = j, added in ascending (i, s) order after the self term.  No float atomics: two calls
+ *     agree to the bit.  Any in-degree 0 ... N - 1.  Nothing flows through the indices (the reference discards topk's values).
+ *     The inverted index is built in LDS: the call needs no scratch.  Entries of `neighbors` outside [0, N) are ignored.
+ * fgs_nca_update_forward:    new_state = state + step_size (delta mask), mask = (uniform < update_prob) per point; rounded as
+ *     torch's expression (three roundings, no FMA).  uniform (B, N) or NULL = eval mode: no mask (NCA:276-284).  step_size: one
+ *     DEVICE float.
+ * fgs_nca_update_backward:   g_delta = (g_new_state step_size) mask;  *g_step_size = sum of g_new_state (delta mask), exact
+ *     products added in double in a fixed order (fixed grid, fixed-shape block tree, block partials in block order in `scratch`
+ *     of fgs_nca_workspace_bytes), rounded to fp32 once: repeats bit for bit.  dL/dstate is g_new_state itself: not written.
+ * Shapes: 1 <= k <= 16, k + 1 <= N <= 4096, 3 <= D <= 64, B <= 65535, B N (k+1) D < 2^31; otherwise FGS_EINVAL (bad dims, null
+ * pointers) / FGS_EUNSUPPORTED before anything touches the device. */
+typedef struct FgsNcaDims {
+    int32_t batch, points, state_dim, k;
+} FgsNcaDims;
+int fgs_nca_workspace_bytes(const FgsNcaDims *dims, size_t *scratch_bytes);
+int fgs_nca_perceive_forward(const FgsNcaDims *dims, const float *state, float *perception, int32_t *neighbors, void *stream);
+int fgs_nca_perceive_backward(const FgsNcaDims *dims, const int32_t *neighbors, const float *g_perception, float *g_state,
+                              void *stream);
+int fgs_nca_update_forward(const FgsNcaDims *dims, const float *state, const float *delta, const float *step_size,
+                           const float *uniform, float update_prob, float *new_state, void *stream);
+int fgs_nca_update_backward(const FgsNcaDims *dims, const float *delta, const float *step_size, const float *uniform,
+                            float update_prob, const float *g_new_state, float *g_delta, float *g_step_size, void *scratch,
+                            void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Importance-subsampling hand-off between decoder and rasterizer (--stochastic_k; reference
  * scripts/training/train_gaussian_decoder.py:1160-1187): the n_out Gaussians whose indices torch.multinomial
  * drew (DEVICE int64 (n_out,), unique, shared by the batch) are gathered out of every (B, n_in, .) tensor into
