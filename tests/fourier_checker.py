@@ -2,7 +2,7 @@
 formulas in plain torch, in DENSE form -- every Gaussian evaluated on every pixel, exp(-((x-u)^2 + (y-v)^2)/s), no factoring
 into rows and columns -- in the dtype of its inputs (fp32 or fp64), differentiated by autograd.  Test infrastructure only.
 
-    render(pos, scale, quat, color, opacity, view, intr, W, H, bg) -> image (3,H,W), raw (3,H,W)
+    render(pos, scale, quat, color, opacity, view, intr, W, H, bg, tie=None) -> image (3,H,W), raw (3,H,W)
 
 `raw` is the un-normalised accumulation (its two largest elements decide where the gradient through the maximum lands:
 argmax_gap).  tests/test_fourier_checker.py checks this file against fixtures the reference's own class produced.
@@ -29,9 +29,11 @@ def project(pos, scale, quat, view, fx, fy, cx, cy):
     return cov2, torch.stack([fx * xc / (-zs) + cx, fy * (-yc) / (-zs) + cy], 1), -zc
 
 
-def render(pos, scale, quat, color, opacity, view, intr, W, H, bg=(0.0, 0.0, 0.0), chunk=None):
+def render(pos, scale, quat, color, opacity, view, intr, W, H, bg=(0.0, 0.0, 0.0), chunk=None, tie=None):
     """One image.  view (4,4) world -> camera, intr = (fx, fy, cx, cy, near, far).  `chunk`: Gaussians evaluated at a time
-    (None = all at once; the sums are the same, only the peak memory differs)."""
+    (None = all at once; the sums are the same, only the peak memory differs).  `tie`: where the gradient through the maximum
+    lands when several elements of `raw` hold it -- None: torch's raw.max(), an even split among them (the reference's);
+    "lowest": all of it on the element with the lowest flat index in (3, H, W), the library's rule (include/fgs.h)."""
     dt, dev = pos.dtype, pos.device
     view = torch.as_tensor(view, dtype=dt, device=dev)
     fx, fy, cx, cy, near, far = [float(v) for v in intr]
@@ -53,7 +55,15 @@ def render(pos, scale, quat, color, opacity, view, intr, W, H, bg=(0.0, 0.0, 0.0
         d2 = (X - mean[j, 0].view(-1, 1, 1)) ** 2 + (Y - mean[j, 1].view(-1, 1, 1)) ** 2
         g = torch.exp(-d2 / s[j].view(-1, 1, 1)) * opacity[j].view(-1, 1, 1)
         raw = raw + torch.einsum("nc,nhw->chw", color[j], g)
-    m = raw.max()
+    if tie is None:
+        m = raw.max()
+    elif tie == "lowest":
+        flat = raw.reshape(-1)
+        with torch.no_grad():  # the index is found outside the graph, the value gathered through it
+            first = int(torch.nonzero(flat == flat.max())[0])
+        m = flat[first]
+    else:
+        raise ValueError(f"tie must be None or 'lowest', got {tie!r}")
     img = raw / m if bool(m > 1e-8) else raw
     bgw = torch.clamp(1.0 - img.sum(0, keepdim=True), 0, 1)
     return torch.clamp(img + bgt * bgw, 0, 1), raw
@@ -66,10 +76,10 @@ def argmax_gap(raw):
     return float((top[0] - top[1]) / top[0].abs().clamp_min(1e-300))
 
 
-def render_with_grads(arrs, view, intr, W, H, bg, gI, dtype=torch.float32, device="cpu", chunk=None):
+def render_with_grads(arrs, view, intr, W, H, bg, gI, dtype=torch.float32, device="cpu", chunk=None, tie=None):
     """numpy in, numpy out: image, raw, the five gradients of sum(image * gI)."""
     leaves = [torch.tensor(a, dtype=dtype, device=device, requires_grad=True) for a in arrs]
-    img, raw = render(*leaves, view, intr, W, H, bg, chunk=chunk)
+    img, raw = render(*leaves, view, intr, W, H, bg, chunk=chunk, tie=tie)
     (img * torch.as_tensor(gI, dtype=dtype, device=device)).sum().backward()
     grads = [(t.grad if t.grad is not None else torch.zeros_like(t)).cpu().numpy() for t in leaves]
     return img.detach().cpu().numpy(), raw.detach().cpu().numpy(), grads
