@@ -971,20 +971,26 @@ int fgs_launch_binning(const FgsPlan &p, char *saved, char *scratch, hipStream_t
         if (layered_direct) {
             uint32_t pbits = 0;
             while ((1u << pbits) < (uint32_t)p.layers) ++pbits;
-            uint32_t *vs2;
-            if ((rc = fgs_launch_radix_sort(keys0, vals0, keys1, vals1, order, &plane_keys, &vs2, N, nullptr, N, N, B, pbits, hist, st,
-                                            reinterpret_cast<const uint32_t *>(saved + p.s_layer), N, nullptr, 0, p.d.sort_mode >> 1)))
-                return rc;
+            FgsRadixSort by_plane = {.keys_in = keys0, .vals_in = vals0, .keys_alt = keys1, .vals_alt = vals1, .vals_final = order,
+                                     .seg_len = N, .seg_capacity = N, .seg_stride = N, .num_segs = B, .key_bits = pbits, .hist = hist,
+                                     .st = st, .keys_first = reinterpret_cast<const uint32_t *>(saved + p.s_layer),
+                                     .index_payload_mod = N, .pass_mode = p.d.sort_mode >> 1};
+            if ((rc = fgs_launch_radix_sort(by_plane))) return rc;
+            plane_keys = by_plane.keys_sorted;
         } else {
             hipLaunchKernelGGL(k_index_order, dim3(nblk), dim3(256), 0, st, total, N, order);
             FGS_LAUNCH_CHECK("k_index_order");
         }
-    } else if ((rc = fgs_launch_radix_sort(keys0, vals0, keys1, vals1, layered_direct ? nullptr : order, &ks, &vs, N, nullptr, N, N,
-                                           B, 32, hist, st, depth_key, N,
-                                           (layered_direct || !(p.d.sort_mode & 1)) ? nullptr : reinterpret_cast<const uint32_t *>(saved + p.s_keybits),
-                                           (N + 255u) / 256u, p.d.sort_mode >> 1, reinterpret_cast<const uint32_t *>(saved + p.s_keybits),
-                                           reinterpret_cast<uint32_t *>(scratch + p.s_bucket)))) {
-        return rc;
+    } else {
+        const uint32_t *vis_keys = reinterpret_cast<const uint32_t *>(saved + p.s_keybits);  // k_project's records of the visible keys
+        FgsRadixSort by_depth = {.keys_in = keys0, .vals_in = vals0, .keys_alt = keys1, .vals_alt = vals1,
+                                 .vals_final = layered_direct ? nullptr : order, .seg_len = N, .seg_capacity = N, .seg_stride = N,
+                                 .num_segs = B, .key_bits = 32, .hist = hist, .st = st, .keys_first = depth_key, .index_payload_mod = N,
+                                 .key_stats = (layered_direct || !(p.d.sort_mode & 1)) ? nullptr : vis_keys,
+                                 .key_recs = (N + 255u) / 256u, .pass_mode = p.d.sort_mode >> 1, .key_range = vis_keys,
+                                 .bucket_tab = reinterpret_cast<uint32_t *>(scratch + p.s_bucket)};
+        if ((rc = fgs_launch_radix_sort(by_depth))) return rc;
+        ks = by_depth.keys_sorted; vs = by_depth.vals_sorted;
     }
     if (p.depth_ordered && layered_direct) {
         // group the depth order by layer (depth plane) with ONE more stable pass over the plane ids: `order` then lists
@@ -995,11 +1001,11 @@ int fgs_launch_binning(const FgsPlan &p, char *saved, char *scratch, hipStream_t
         FGS_LAUNCH_CHECK("k_plane_keys");
         uint32_t pbits = 0;
         while ((1u << pbits) < (uint32_t)p.layers) ++pbits;
-        uint32_t *ks2, *vs2;
-        if ((rc = fgs_launch_radix_sort(kfree, vs, ks, vfree, order, &ks2, &vs2, N, nullptr, N, N, B, pbits, hist, st, nullptr, 0,
-                                        nullptr, 0, p.d.sort_mode >> 1)))
-            return rc;
-        plane_keys = ks2;
+        FgsRadixSort by_plane = {.keys_in = kfree, .vals_in = vs, .keys_alt = ks, .vals_alt = vfree, .vals_final = order, .seg_len = N,
+                                 .seg_capacity = N, .seg_stride = N, .num_segs = B, .key_bits = pbits, .hist = hist, .st = st,
+                                 .pass_mode = p.d.sort_mode >> 1};
+        if ((rc = fgs_launch_radix_sort(by_plane))) return rc;
+        plane_keys = by_plane.keys_sorted;
     }
     fgs_stage_end(ST_DEPTH_SORT, st);
     const uint32_t ntiles_all = B * (uint32_t)p.layers * (uint32_t)p.tiles;
@@ -1080,9 +1086,11 @@ int fgs_launch_binning(const FgsPlan &p, char *saved, char *scratch, hipStream_t
     fgs_stage_end(ST_DUP_EMIT, st);
     fgs_stage_begin(ST_TILE_SORT, st);
     // (4) stable sort by tile key only
-    rc = fgs_launch_radix_sort(keys0, vals0, keys1, vals1, dup_ids, &ks, &vs, 0, counters, dcap, 0, 1,
-                               p.tile_key_bits, hist, st);
-    if (rc) return rc;
+    FgsRadixSort by_tile = {.keys_in = keys0, .vals_in = vals0, .keys_alt = keys1, .vals_alt = vals1, .vals_final = dup_ids,
+                            .seg_len_dev = counters, .seg_capacity = dcap, .num_segs = 1, .key_bits = p.tile_key_bits, .hist = hist,
+                            .st = st};
+    if ((rc = fgs_launch_radix_sort(by_tile))) return rc;
+    ks = by_tile.keys_sorted; vs = by_tile.vals_sorted;
     fgs_stage_end(ST_TILE_SORT, st);
     fgs_stage_begin(ST_TILE_RANGES, st);
     // (5) per-tile [start,end)

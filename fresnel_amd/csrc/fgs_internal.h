@@ -55,28 +55,34 @@ int fgs_launch_fourier_project_bwd(int32_t B, int32_t N, int32_t num_cameras, co
 // Stable LSD radix sort of (key,val) uint32 pairs over `num_segs` independent segments.
 // Segment s covers elements [s*seg_stride, s*seg_stride + len) with len = seg_len (host) or
 // *seg_len_dev (device, single segment).  Sorts bits [0, key_bits).  The sorted result is
-// left in (keys_out, vals_out); in/alt buffers are clobbered.
-int fgs_launch_radix_sort(uint32_t *keys_in, uint32_t *vals_in, uint32_t *keys_alt, uint32_t *vals_alt,
-                          uint32_t *vals_final /*nullable: where the last pass writes vals*/,
-                          uint32_t **keys_sorted /*out: which buffer holds sorted keys*/,
-                          uint32_t **vals_sorted, uint32_t seg_len, const uint32_t *seg_len_dev,
-                          uint32_t seg_capacity, uint32_t seg_stride, uint32_t num_segs, uint32_t key_bits,
-                          uint32_t *hist, hipStream_t st, const uint32_t *keys_first = nullptr,
-                          uint32_t index_payload_mod = 0,
-                          const uint32_t *key_stats = nullptr /* depth sort: k_project's per-block OR / AND of the visible keys:
-                                                                 sort by the bits that vary, skip the passes nobody needs */,
-                          uint32_t key_recs = 0 /* records per segment */,
-                          int pass_mode = 0 /* FgsDims.sort_mode >> 1.  0 = automatic: host-known segments of <= 8192 keys by ONE launch,
-                                               all passes in LDS; larger ones with `key_range` by the bucket sort (one bucket pass
-                                               over memory, then every bucket in LDS), else by the two-launch 8-bit passes | 1 = fused
-                                               passes (one launch each), 11-bit digits, up to 64 K keys | 2 = fused passes, 8-bit
-                                               digits | 3 = fused passes, 8-bit digits, per-block histograms HANDED OFF between the
-                                               blocks through `hist` (which the caller cleared beforehand: fgs_sort.hip) | 4 = the
-                                               two-launch passes at any size | 5 = as automatic */,
-                          const uint32_t *key_range = nullptr /* depth sort: k_project's records again (smallest visible key in the
-                                                                 fourth word, the largest behind the records), `key_recs` per segment:
-                                                                 what the bucket sort takes its digit from */,
-                          uint32_t *bucket_tab = nullptr /* scratch of num_segs * FGS_SORT_BUCKET_WORDS words for the bucket sort */);
+// left in (keys_sorted, vals_sorted); in/alt buffers are clobbered.
+struct FgsRadixSort {
+    uint32_t *keys_in, *vals_in, *keys_alt, *vals_alt;
+    uint32_t *vals_final;            // nullable: where the last pass writes vals
+    uint32_t seg_len;
+    const uint32_t *seg_len_dev;
+    uint32_t seg_capacity, seg_stride, num_segs, key_bits;
+    uint32_t *hist;
+    hipStream_t st;
+    const uint32_t *keys_first;      // nullable: the first pass reads its keys from there (read-only) instead of keys_in
+    uint32_t index_payload_mod;      // != 0: the first pass generates the payload (element index modulo it) instead of reading vals_in
+    const uint32_t *key_stats;       // depth sort: k_project's per-block OR / AND of the visible keys: sort by the bits that vary,
+                                     // skip the passes nobody needs
+    uint32_t key_recs;               // records per segment
+    int pass_mode;                   // FgsDims.sort_mode >> 1.  0 = automatic: host-known segments of <= 8192 keys by ONE launch,
+                                     // all passes in LDS; larger ones with `key_range` by the bucket sort (one bucket pass over
+                                     // memory, then every bucket in LDS), else by the two-launch 8-bit passes | 1 = fused passes (one
+                                     // launch each), 11-bit digits, up to 64 K keys | 2 = fused passes, 8-bit digits | 3 = fused
+                                     // passes, 8-bit digits, per-block histograms HANDED OFF between the blocks through `hist` (which
+                                     // the caller cleared beforehand: fgs_sort.hip) | 4 = the two-launch passes at any size | 5 = as
+                                     // automatic
+    const uint32_t *key_range;       // depth sort: k_project's records again (smallest visible key in the fourth word, the largest
+                                     // behind the records), `key_recs` per segment: what the bucket sort takes its digit from
+    uint32_t *bucket_tab;            // scratch of num_segs * FGS_SORT_BUCKET_WORDS words for the bucket sort
+    uint32_t *keys_sorted;           // out: which buffer holds the sorted keys (nullptr: none does -- fgs_sort.hip)
+    uint32_t *vals_sorted;           // out: ... the sorted payload
+};
+int fgs_launch_radix_sort(FgsRadixSort &s);
 
 int fgs_launch_binning(const FgsPlan &p, char *saved, char *scratch, hipStream_t st);
 

@@ -80,19 +80,73 @@ __device__ __forceinline__ void match_rank(uint32_t digit, bool valid, uint32_t 
     count = (uint32_t)__popc(mlo) + (uint32_t)__popc(mhi);
 }
 
+// Inclusive sum over the wave's lanes 0 ... own.
+__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t s) {
+    const uint32_t lane = threadIdx.x & 63u;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t t = __shfl_up(s, o, 64);
+        if ((int)lane >= o) s += t;
+    }
+    return s;
+}
+
+// Stable rank of a key among the keys of digit `digit` that its wave has ranked so far, this chunk of 64 included: ranking against
+// the wave's OWN running digit counters in LDS, `wcnt_row` (a wave's LDS operations execute in program order, so
+// read-count-then-bump needs no barrier); the lowest lane of every digit bumps the counter by the chunk's count.
+template <int BITS>
+__device__ __forceinline__ void rank_against_counters(uint32_t digit, bool valid, uint32_t *wcnt_row, uint32_t &lrank) {
+    uint32_t rank, count;
+    match_rank<BITS>(digit, valid, rank, count);
+    const uint32_t prev = valid ? wcnt_row[digit] : 0u;
+    lrank = prev + rank;
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    if (valid && rank == 0) wcnt_row[digit] = prev + count;
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+}
+
+// The 256 digits' counts per wave, `wcnt`, -> each wave's output base per digit, written back over the counts: the exclusive prefix
+// over the waves + the digit's exclusive prefix over the digits, so the scatter reads ONE word per key (its wave's base for its
+// digit).  Two halves with a block barrier between them, both run by the threads 0 ... 255 (thread = digit): the first leaves the
+// digit's total in `acc` and the four digit waves' sums in wtot[0 ... 3].
+template <int WAVES>
+__device__ __forceinline__ void wave_digit_bases_scan(uint32_t (*wcnt)[256], uint32_t *wtot, uint32_t (&cw)[WAVES], uint32_t &acc,
+                                                      uint32_t &sc) {
+    const uint32_t tid = threadIdx.x;
+    acc = 0u; sc = 0u;
+    if (tid < 256u) {
+#pragma unroll
+        for (int w = 0; w < WAVES; ++w) cw[w] = wcnt[w][tid];
+#pragma unroll
+        for (int w = 0; w < WAVES; ++w) { const uint32_t x = cw[w]; cw[w] = acc; acc += x; }
+        sc = wave_incl_scan(acc);
+        if ((tid & 63u) == 63u) wtot[tid >> 6] = sc;
+    }
+}
+
+template <int WAVES>
+__device__ __forceinline__ void wave_digit_bases_write(uint32_t (*wcnt)[256], const uint32_t *wtot, const uint32_t (&cw)[WAVES],
+                                                       uint32_t acc, uint32_t sc) {
+    const uint32_t tid = threadIdx.x, wave = tid >> 6;
+    if (tid < 256u) {
+        uint32_t base = sc - acc;
+#pragma unroll
+        for (int w = 0; w < 3; ++w) base += (w < (int)wave) ? wtot[w] : 0u;
+#pragma unroll
+        for (int w = 0; w < WAVES; ++w) wcnt[w][tid] = base + cw[w];
+    }
+}
+
 // ---- key compression (see the header) ------------------------------------------------------------------------------------
-struct KeyPlan {
-    uint32_t live;      // passes this segment needs (>= 1)
-    uint32_t sh[8];     // source bit of digit bit i of the current pass
-    uint32_t vmask;     // digit bits that exist in this pass
-    uint32_t cull;      // digit of a culled key in this pass
+struct KeyRecords {
+    uint32_t vor, vand, flags;  // OR and AND of the segment's visible keys; flags: 1 = some key is culled, 2 = some key is visible
 };
 
-// every thread of the block returns the plan of (segment, pass); `kb` = 12 + 12 words of LDS
-__device__ __forceinline__ KeyPlan key_plan(const uint32_t *__restrict__ bits, uint32_t nrec, uint32_t seg, uint32_t pass,
-                                            uint32_t *kb) {
+// every thread of the block returns the fold of k_project's records of segment `seg`; `kb` = 3 words of LDS per wave
+template <int THREADS>
+__device__ __forceinline__ KeyRecords fold_key_records(const uint32_t *__restrict__ bits, uint32_t nrec, uint32_t seg, uint32_t *kb) {
     uint32_t vor = 0u, vand = 0xFFFFFFFFu, fl = 0u;
-    for (uint32_t i = threadIdx.x; i < nrec; i += RS_THREADS) {
+    for (uint32_t i = threadIdx.x; i < nrec; i += THREADS) {
         const uint4 r = reinterpret_cast<const uint4 *>(bits)[(size_t)seg * nrec + i];
         vor |= r.x; vand &= r.y; fl |= r.z;
     }
@@ -101,29 +155,50 @@ __device__ __forceinline__ KeyPlan key_plan(const uint32_t *__restrict__ bits, u
     const uint32_t wave = threadIdx.x >> 6;
     if ((threadIdx.x & 63u) == 0) { kb[3 * wave] = vor; kb[3 * wave + 1] = vand; kb[3 * wave + 2] = fl; }
     __syncthreads();
-    if (threadIdx.x < 8) {
-        uint32_t o = 0u, a = 0xFFFFFFFFu, f = 0u;
+    KeyRecords r = {0u, 0xFFFFFFFFu, 0u};
 #pragma unroll
-        for (int w = 0; w < RS_WAVES; ++w) { o |= kb[3 * w]; a &= kb[3 * w + 1]; f |= kb[3 * w + 2]; }
-        const uint32_t m = (f & 2u) ? (o ^ a) : 0u;  // no visible key: nothing varies
-        const uint32_t nbits = (uint32_t)__popc(m), cull = f & 1u;
-        const uint32_t idx = 8u * pass + threadIdx.x;
+    for (int w = 0; w < THREADS / 64; ++w) { r.vor |= kb[3 * w]; r.vand &= kb[3 * w + 1]; r.flags |= kb[3 * w + 2]; }
+    return r;
+}
+
+// The plan of (segment, pass) for BITS-bit digits: 8 in the two-launch passes, 8 or 11 in the fused ones.
+template <int BITS>
+struct KeyPlanW {
+    uint32_t live;        // passes this segment needs (>= 1)
+    uint32_t sh[BITS];    // source bit of digit bit i of the current pass
+    uint32_t vmask;       // digit bits that exist in this pass
+    uint32_t cull;        // digit of a culled key in this pass
+    bool plain;           // the compressed key needs as many passes as the plain one has: the key's own digits then (key_digit_w)
+};
+constexpr int key_plan_words(int bits) { return 12 + bits + 2; }
+
+// every thread of the block returns the plan; `kb` = key_plan_words(BITS) words of LDS
+template <int BITS>
+__device__ __forceinline__ KeyPlanW<BITS> key_plan_w(const uint32_t *__restrict__ bits, uint32_t nrec, uint32_t seg, uint32_t pass,
+                                                     uint32_t *kb) {
+    constexpr uint32_t MAXP = (32u + BITS - 1u) / BITS;
+    const KeyRecords r = fold_key_records<RS_THREADS>(bits, nrec, seg, kb);
+    if (threadIdx.x < (uint32_t)BITS) {
+        const uint32_t m = (r.flags & 2u) ? (r.vor ^ r.vand) : 0u;  // no visible key: nothing varies
+        const uint32_t nbits = (uint32_t)__popc(m), cull = r.flags & 1u;
+        const uint32_t idx = (uint32_t)BITS * pass + threadIdx.x;
         uint32_t mm = m;
         for (uint32_t j = 0; j < idx && mm; ++j) mm &= mm - 1u;
         kb[12 + threadIdx.x] = (idx < nbits) ? (uint32_t)__ffs((int)mm) - 1u : 32u;
         if (threadIdx.x == 0) {
-            const uint32_t need = (nbits + cull + 7u) / 8u;
-            kb[20] = need < 1u ? 1u : (need > 4u ? 4u : need);  // (33 bits -- every key bit varies and some keys are culled -- is the full key: key_digit)
-            kb[21] = (cull && nbits >= 8u * pass && nbits < 8u * pass + 8u) ? 1u << (nbits - 8u * pass) : 0u;
+            const uint32_t need = (nbits + cull + BITS - 1u) / BITS;
+            kb[12 + BITS] = need < 1u ? 1u : (need > MAXP ? MAXP : need);
+            kb[13 + BITS] = (cull && nbits >= BITS * pass && nbits < BITS * pass + BITS) ? 1u << (nbits - BITS * pass) : 0u;
         }
     }
     __syncthreads();
-    KeyPlan kp;
-    kp.live = kb[20];
-    kp.cull = kb[21];
+    KeyPlanW<BITS> kp;
+    kp.live = kb[12 + BITS];
+    kp.cull = kb[13 + BITS];
+    kp.plain = kp.live >= MAXP;  // need >= MAXP
     kp.vmask = 0u;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
+    for (int i = 0; i < BITS; ++i) {
         const uint32_t p = kb[12 + i];
         kp.sh[i] = p & 31u;
         kp.vmask |= (p < 32u ? 1u : 0u) << i;
@@ -131,12 +206,15 @@ __device__ __forceinline__ KeyPlan key_plan(const uint32_t *__restrict__ bits, u
     return kp;
 }
 
-// (a segment whose keys vary in more than 24 bits needs four passes either way: the key's own bytes then, same permutation)
-__device__ __forceinline__ uint32_t key_digit(const KeyPlan &kp, uint32_t key, uint32_t pass) {
-    if (kp.live >= 4u) return (key >> (8u * pass)) & 0xFFu;  // block-uniform
+// `plain`: a segment whose compressed key needs MAXP passes -- 8-bit digits: its keys vary in more than 24 bits, up to 33 (every key
+// bit varies and some keys are culled) -- needs them either way: the key's own digits then.  Same permutation: the bits that the
+// compressed key drops are equal in all visible keys, and a culled key is all ones, the largest digit of every pass.
+template <int BITS>
+__device__ __forceinline__ uint32_t key_digit_w(const KeyPlanW<BITS> &kp, uint32_t key, uint32_t pass) {
+    if (kp.plain) return (key >> (BITS * pass)) & ((1u << BITS) - 1u);  // block-uniform
     uint32_t d = 0u;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) d |= ((key >> kp.sh[i]) & 1u) << i;
+    for (int i = 0; i < BITS; ++i) d |= ((key >> kp.sh[i]) & 1u) << i;
     return key == 0xFFFFFFFFu ? kp.cull : (d & kp.vmask);
 }
 
@@ -182,10 +260,10 @@ __global__ __launch_bounds__(RS_THREADS) void k_radix_upsweep(
     uint32_t seg_capacity, uint32_t seg_stride, uint32_t shift, uint32_t dmask, uint32_t *__restrict__ hist,
     const uint32_t *__restrict__ key_bits, uint32_t key_recs, uint32_t pass, uint32_t *__restrict__ bucket_tab) {
     __shared__ uint32_t h[256];
-    __shared__ uint32_t kb[24];
-    KeyPlan kp;
+    __shared__ uint32_t kb[key_plan_words(8)];
+    KeyPlanW<8> kp;
     if (COMPRESSED) {
-        kp = key_plan(key_bits, key_recs, blockIdx.y, pass, kb);
+        kp = key_plan_w<8>(key_bits, key_recs, blockIdx.y, pass, kb);
         if (pass >= kp.live) return;  // this segment is sorted already
     }
     uint32_t kmin = 0u;
@@ -206,7 +284,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_radix_upsweep(
 #pragma unroll
         for (int u = 0; u < 4; ++u)
             if (i + u * RS_THREADS < r.end)
-                atomicAdd(&h[BUCKET ? bucket_digit(k[u], kmin, shift) : COMPRESSED ? key_digit(kp, k[u], pass) : (k[u] >> shift) & dmask], 1u);
+                atomicAdd(&h[BUCKET ? bucket_digit(k[u], kmin, shift) : COMPRESSED ? key_digit_w<8>(kp, k[u], pass) : (k[u] >> shift) & dmask], 1u);
     }
     __syncthreads();
     // layout: hist[(seg*256 + digit) * bps + blk]
@@ -226,16 +304,105 @@ __global__ __launch_bounds__(256) void k_radix_scan(uint32_t *__restrict__ hist,
     for (uint32_t base = 0; base < bps; base += 64) {
         const uint32_t i = base + lane;
         const uint32_t v = i < bps ? p[i] : 0u;
-        uint32_t s = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t t = __shfl_up(s, o, 64);
-            if ((int)lane >= o) s += t;
-        }
+        const uint32_t s = wave_incl_scan(v);
         if (i < bps) p[i] = carry + s - v;
         carry += __shfl(s, 63, 64);
     }
     if (lane == 0) dtot[row] = carry;
+}
+
+// ---- the scatter rounds of a pass (k_radix_downsweep, k_radix_fused) -----------------------------------------------------------
+// Rounds of 1024 keys: wave w owns the contiguous 256 keys [base + 256 w, +256) and walks them in four 64-key sub-rounds.
+constexpr uint32_t RS_ROUND = RS_THREADS * 4;
+
+struct Round {
+    uint32_t key[4], val[4];
+    bool valid[4];
+};
+
+// vals_in == nullptr: the payload is the element's index modulo idx_mod
+__device__ __forceinline__ void load_round(Round &q, const uint32_t *keys_in, const uint32_t *vals_in, uint32_t idx_mod,
+                                           uint32_t base, uint32_t end) {
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int it = 0; it < 4; ++it) {
+        const uint32_t i = base + wave * 256u + it * 64u + lane;
+        q.valid[it] = i < end;
+        q.key[it] = q.valid[it] ? keys_in[i] : 0u;
+        q.val[it] = q.valid[it] ? (vals_in ? vals_in[i] : i % idx_mod) : 0u;
+    }
+}
+
+// The block scatters its range `r` over NB digits, digit_of(key): `run_off` holds the output position of the block's first key of
+// every digit (then the running one), `wcnt` the four waves' rank counters of a round (zero on entry), `q` the first round's keys
+// (load_round -- which the caller requests BEFORE it forms the prefix, so the two memory round trips overlap).  One block barrier
+// per round turns the four waves' counts into global positions; the next round's keys travel under the counters' fold.
+template <uint32_t NB, class DigitOf>
+__device__ __forceinline__ void scatter_rounds(Round &q, const uint32_t *keys_in, const uint32_t *vals_in, uint32_t *keys_out,
+                                               uint32_t *vals_out, uint32_t idx_mod, SegInfo r, uint32_t *run_off,
+                                               uint32_t (*wcnt)[NB], DigitOf digit_of) {
+    const uint32_t tid = threadIdx.x, wave = tid >> 6;
+    for (uint32_t base = r.begin; base < r.end; base += RS_ROUND) {
+        uint32_t lrank[4], dig[4];
+#pragma unroll
+        for (int it = 0; it < 4; ++it) {
+            dig[it] = digit_of(q.key[it]);
+            rank_against_counters<__builtin_ctz(NB)>(dig[it], q.valid[it], wcnt[wave], lrank[it]);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int it = 0; it < 4; ++it) {
+            if (q.valid[it]) {
+                const uint32_t digit = dig[it];
+                uint32_t pre = 0;
+#pragma unroll
+                for (int w = 0; w < RS_WAVES; ++w) { const uint32_t c = wcnt[w][digit]; pre += (w < (int)wave) ? c : 0u; }
+                const uint32_t dst = run_off[digit] + pre + lrank[it];
+                keys_out[dst] = q.key[it];
+                vals_out[dst] = q.val[it];
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (uint32_t k = 0; k < NB / RS_THREADS; ++k) {
+            const uint32_t d = tid + k * RS_THREADS;
+            uint32_t tot = 0;
+#pragma unroll
+            for (int w = 0; w < RS_WAVES; ++w) { tot += wcnt[w][d]; wcnt[w][d] = 0; }
+            run_off[d] += tot;
+        }
+        if (base + RS_ROUND < r.end) load_round(q, keys_in, vals_in, idx_mod, base + RS_ROUND, r.end);
+        __syncthreads();
+    }
+}
+
+// One count per key of [begin, end), walked in rounds of 1024 from `begin`, at digit_of(key) of the histogram hist_of(index of the
+// wave instruction's first key) -- a wave-uniform choice: ONE LDS atomic per key, and a wave whose 64 keys share a digit (quantised
+// depths) adds once.
+template <class DigitOf, class HistOf>
+__device__ __forceinline__ void count_digits(const uint32_t *keys_in, uint32_t begin, uint32_t end, DigitOf digit_of,
+                                             HistOf hist_of) {
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    for (uint32_t i0 = begin + tid; i0 - tid < end; i0 += RS_ROUND) {
+        uint32_t k4[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) k4[u] = i0 + u * RS_THREADS < end ? keys_in[i0 + u * RS_THREADS] : 0u;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const uint32_t i = i0 + u * RS_THREADS;
+            const bool v = i < end;
+            const uint32_t d = digit_of(k4[u]);
+            const unsigned long long act = __ballot(v);
+            if (act == 0ull) continue;  // wave-uniform
+            uint32_t *h = hist_of(__builtin_amdgcn_readfirstlane(i));
+            const uint32_t d0 = __builtin_amdgcn_readfirstlane(d);  // (lane 0 of the wave: valid whenever any lane is)
+            if (__ballot(v && d == d0) == act) {
+                if (lane == 0) atomicAdd(&h[d0], (uint32_t)__popcll(act));  // the wave's 64 keys share one digit
+            } else if (v) {
+                atomicAdd(&h[d], 1u);
+            }
+        }
+    }
 }
 
 template <bool COMPRESSED, bool BUCKET = false>
@@ -259,10 +426,10 @@ __global__ __launch_bounds__(RS_THREADS) void k_radix_downsweep(
     __shared__ uint32_t wcnt[RS_WAVES][256];
     __shared__ uint32_t wtot[RS_WAVES];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    __shared__ uint32_t kb[24];
-    KeyPlan kp;
+    __shared__ uint32_t kb[key_plan_words(8)];
+    KeyPlanW<8> kp;
     if (COMPRESSED) {
-        kp = key_plan(key_bits, key_recs, blockIdx.y, pass, kb);
+        kp = key_plan_w<8>(key_bits, key_recs, blockIdx.y, pass, kb);
         if (pass >= kp.live) return;                        // this segment is sorted already
         if (pass + 1u == kp.live) vals_out = vals_final;    // its last live pass: the payload goes to its final place
     }
@@ -273,22 +440,8 @@ __global__ __launch_bounds__(RS_THREADS) void k_radix_downsweep(
     }
     const SegInfo r = block_range(seg_len, seg_len_dev, seg_capacity, seg_stride);
     const uint32_t seg0 = blockIdx.y * seg_stride;
-    constexpr uint32_t ROUND = RS_THREADS * 4;
-    uint32_t key[4], val[4];
-    bool valid[4];
-    // Rounds of 1024 keys: wave w owns the contiguous 256 keys [base + 256 w, +256) and walks them
-    // in four 64-key sub-rounds.  The first round's keys are requested BEFORE the prefix below is formed, so the
-    // two memory round trips overlap.
-    auto load_round = [&](uint32_t base) {
-#pragma unroll
-        for (int it = 0; it < 4; ++it) {
-            const uint32_t i = base + wave * 256u + it * 64u + lane;
-            valid[it] = i < r.end;
-            key[it] = valid[it] ? keys_in[i] : 0u;
-            val[it] = valid[it] ? (vals_in ? vals_in[i] : i % idx_mod) : 0u;
-        }
-    };
-    load_round(r.begin);
+    Round q;
+    load_round(q, keys_in, vals_in, idx_mod, r.begin, r.end);  // (travels under the prefix below)
     // exclusive scan of the 256 digit totals of this segment: wave scans + the four wave totals
     {
         uint32_t t, mine;
@@ -331,12 +484,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_radix_downsweep(
                 }
             }
         }
-        uint32_t s = t;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t v = __shfl_up(s, o, 64);
-            if ((int)lane >= o) s += v;
-        }
+        const uint32_t s = wave_incl_scan(t);
         if (lane == 63) wtot[wave] = s;
 #pragma unroll
         for (int w = 0; w < RS_WAVES; ++w) wcnt[w][tid] = 0;
@@ -352,46 +500,9 @@ __global__ __launch_bounds__(RS_THREADS) void k_radix_downsweep(
         }
     }
     __syncthreads();
-    // Ranking against the wave's OWN running digit counters in LDS (a wave's LDS operations execute in program
-    // order, so read-count-then-bump needs no barrier); one block barrier per round then turns the four waves'
-    // counts into global positions.
-    for (uint32_t base = r.begin; base < r.end; base += ROUND) {
-        uint32_t lrank[4], dig[4];
-#pragma unroll
-        for (int it = 0; it < 4; ++it) {
-            const uint32_t digit = BUCKET ? bucket_digit(key[it], kmin, shift) : COMPRESSED ? key_digit(kp, key[it], pass) : (key[it] >> shift) & dmask;
-            dig[it] = digit;
-            uint32_t rank, count;
-            match_rank<8>(digit, valid[it], rank, count);
-            const uint32_t prev = valid[it] ? wcnt[wave][digit] : 0u;
-            lrank[it] = prev + rank;
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            if (valid[it] && rank == 0) wcnt[wave][digit] = prev + count;
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        }
-        __syncthreads();
-#pragma unroll
-        for (int it = 0; it < 4; ++it) {
-            if (valid[it]) {
-                const uint32_t digit = dig[it];
-                uint32_t pre = 0;
-#pragma unroll
-                for (int w = 0; w < RS_WAVES; ++w) pre += (w < (int)wave) ? wcnt[w][digit] : 0u;
-                const uint32_t dst = run_off[digit] + pre + lrank[it];
-                keys_out[dst] = key[it];
-                vals_out[dst] = val[it];
-            }
-        }
-        __syncthreads();
-        {
-            uint32_t tot = 0;
-#pragma unroll
-            for (int w = 0; w < RS_WAVES; ++w) { tot += wcnt[w][tid]; wcnt[w][tid] = 0; }
-            run_off[tid] += tot;
-        }
-        if (base + ROUND < r.end) load_round(base + ROUND);
-        __syncthreads();
-    }
+    scatter_rounds<256>(q, keys_in, vals_in, keys_out, vals_out, idx_mod, r, run_off, wcnt, [&](uint32_t key) -> uint32_t {
+        return BUCKET ? bucket_digit(key, kmin, shift) : COMPRESSED ? key_digit_w<8>(kp, key, pass) : (key >> shift) & dmask;
+    });
 }
 
 // ---- FUSED PASS (round 5): one launch per radix pass, no histogram hand-off between blocks -------------------------------------
@@ -404,69 +515,6 @@ __global__ __launch_bounds__(RS_THREADS) void k_radix_downsweep(
 // passes over 32-bit keys instead of four (2048 bins: `pre`, `rest` / running offsets and the four waves' rank counters = 48 KB of
 // LDS).  Ranking and scatter are k_radix_downsweep's (wave64 ballots, stable, no atomics in the scatter).
 // Depth sort: 8 launches -> 3; with key compression a dead pass is one launch of blocks that read ~100 words and leave.
-template <int BITS>
-struct KeyPlanW {
-    uint32_t live;        // passes this segment needs (>= 1)
-    uint32_t sh[BITS];    // source bit of digit bit i of the current pass
-    uint32_t vmask;       // digit bits that exist in this pass
-    uint32_t cull;        // digit of a culled key in this pass
-    uint32_t plain;       // != 0: the compressed key would need more passes than the plain one has: the key's own bits then
-};
-
-template <int BITS>
-__device__ __forceinline__ KeyPlanW<BITS> key_plan_w(const uint32_t *__restrict__ bits, uint32_t nrec, uint32_t seg, uint32_t pass,
-                                                     uint32_t *kb /* 12 + BITS + 3 words */) {
-    constexpr uint32_t MAXP = (32u + BITS - 1u) / BITS;
-    uint32_t vor = 0u, vand = 0xFFFFFFFFu, fl = 0u;
-    for (uint32_t i = threadIdx.x; i < nrec; i += RS_THREADS) {
-        const uint4 r = reinterpret_cast<const uint4 *>(bits)[(size_t)seg * nrec + i];
-        vor |= r.x; vand &= r.y; fl |= r.z;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { vor |= __shfl_xor(vor, o, 64); vand &= __shfl_xor(vand, o, 64); fl |= __shfl_xor(fl, o, 64); }
-    const uint32_t wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63u) == 0) { kb[3 * wave] = vor; kb[3 * wave + 1] = vand; kb[3 * wave + 2] = fl; }
-    __syncthreads();
-    if (threadIdx.x < (uint32_t)BITS) {
-        uint32_t o = 0u, a = 0xFFFFFFFFu, f = 0u;
-#pragma unroll
-        for (int w = 0; w < RS_WAVES; ++w) { o |= kb[3 * w]; a &= kb[3 * w + 1]; f |= kb[3 * w + 2]; }
-        const uint32_t m = (f & 2u) ? (o ^ a) : 0u;  // no visible key: nothing varies
-        const uint32_t nbits = (uint32_t)__popc(m), cull = f & 1u;
-        const uint32_t idx = (uint32_t)BITS * pass + threadIdx.x;
-        uint32_t mm = m;
-        for (uint32_t j = 0; j < idx && mm; ++j) mm &= mm - 1u;
-        kb[12 + threadIdx.x] = (idx < nbits) ? (uint32_t)__ffs((int)mm) - 1u : 32u;
-        if (threadIdx.x == 0) {
-            const uint32_t need = (nbits + cull + BITS - 1u) / BITS;
-            kb[12 + BITS] = need < 1u ? 1u : (need > MAXP ? MAXP : need);
-            kb[13 + BITS] = (cull && nbits >= BITS * pass && nbits < BITS * pass + BITS) ? 1u << (nbits - BITS * pass) : 0u;
-            kb[14 + BITS] = need > MAXP ? 1u : 0u;  // (8-bit digits: 33 bits -- every key bit varies and some keys are culled)
-        }
-    }
-    __syncthreads();
-    KeyPlanW<BITS> kp;
-    kp.live = kb[12 + BITS];
-    kp.cull = kb[13 + BITS];
-    kp.plain = kb[14 + BITS];
-    kp.vmask = 0u;
-#pragma unroll
-    for (int i = 0; i < BITS; ++i) {
-        const uint32_t p = kb[12 + i];
-        kp.sh[i] = p & 31u;
-        kp.vmask |= (p < 32u ? 1u : 0u) << i;
-    }
-    return kp;
-}
-
-template <int BITS>
-__device__ __forceinline__ uint32_t key_digit_w(const KeyPlanW<BITS> &kp, uint32_t key, uint32_t pass) {
-    if (kp.plain) return (key >> (BITS * pass)) & ((1u << BITS) - 1u);  // block-uniform
-    uint32_t d = 0u;
-#pragma unroll
-    for (int i = 0; i < BITS; ++i) d |= ((key >> kp.sh[i]) & 1u) << i;
-    return key == 0xFFFFFFFFu ? kp.cull : (d & kp.vmask);
-}
 
 // HANDOFF (sort_mode bits 1-2 = 3; VERDICT r4 item 4c, "the look-back pass actually built and timed"): instead of counting the whole
 // segment, a block counts its OWN keys, publishes the NB counts (count + 1 per word, write-through agent-scope stores into this pass's
@@ -489,7 +537,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_radix_fused(
     __shared__ uint32_t rest[NB];              // ... from this block's range on; then the running output offset per digit
     __shared__ uint32_t wcnt[RS_WAVES][NB];    // the four waves' running digit counters of a round
     __shared__ uint32_t wtot[RS_WAVES];
-    __shared__ uint32_t kb[12 + BITS + 3];
+    __shared__ uint32_t kb[key_plan_words(BITS)];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     KeyPlanW<BITS> kp;
     if (COMPRESSED) {
@@ -503,18 +551,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_radix_fused(
     };
     const SegInfo r = block_range(seg_len, nullptr, seg_len, seg_stride);
     const uint32_t seg0 = blockIdx.y * seg_stride, seg_end = seg0 + seg_len;
-    constexpr uint32_t ROUND = RS_THREADS * 4;
-    uint32_t key[4], val[4];
-    bool valid[4];
-    auto load_round = [&](uint32_t base) {
-#pragma unroll
-        for (int it = 0; it < 4; ++it) {
-            const uint32_t i = base + wave * 256u + it * 64u + lane;
-            valid[it] = i < r.end;
-            key[it] = valid[it] ? keys_in[i] : 0u;
-            val[it] = valid[it] ? (vals_in ? vals_in[i] : i % idx_mod) : 0u;
-        }
-    };
+    Round q;
 #pragma unroll
     for (uint32_t k = 0; k < DPT; ++k) {
         pre[tid + k * RS_THREADS] = 0u; rest[tid + k * RS_THREADS] = 0u;
@@ -527,24 +564,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_radix_fused(
         __shared__ volatile uint32_t gave_up;
         if (tid == 0) gave_up = 0u;
         // (1) this block's own digit counts -> `rest`
-        for (uint32_t i0 = r.begin + tid; i0 - tid < r.end; i0 += ROUND) {
-            uint32_t k4[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) k4[u] = i0 + u * RS_THREADS < r.end ? keys_in[i0 + u * RS_THREADS] : 0u;
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const bool v = i0 + u * RS_THREADS < r.end;
-                const uint32_t d = digit_of(k4[u]);
-                const unsigned long long act = __ballot(v);
-                if (act == 0ull) continue;
-                const uint32_t d0 = __builtin_amdgcn_readfirstlane(d);
-                if (__ballot(v && d == d0) == act) {
-                    if (lane == 0) atomicAdd(&rest[d0], (uint32_t)__popcll(act));
-                } else if (v) {
-                    atomicAdd(&rest[d], 1u);
-                }
-            }
-        }
+        count_digits(keys_in, r.begin, r.end, digit_of, [&](uint32_t) { return rest; });
         __syncthreads();
         // (2) publish them, (3) collect the other blocks': every thread owns DPT digits
         uint32_t *mine = handoff + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * NB;
@@ -588,39 +608,15 @@ __global__ __launch_bounds__(RS_THREADS) void k_radix_fused(
     }
     // ---- the segment's digit histogram, split at this block's first key (r.begin is a multiple of 1024: a wave instruction's
     // 64 consecutive keys lie on one side) ----
-    for (uint32_t i0 = seg0 + tid; !counted && i0 - tid < seg_end; i0 += ROUND) {
-        uint32_t k4[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) k4[u] = i0 + u * RS_THREADS < seg_end ? keys_in[i0 + u * RS_THREADS] : 0u;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const uint32_t i = i0 + u * RS_THREADS;
-            const bool v = i < seg_end;
-            const uint32_t d = digit_of(k4[u]);
-            const unsigned long long act = __ballot(v);
-            if (act == 0ull) continue;  // wave-uniform
-            uint32_t *h = (__builtin_amdgcn_readfirstlane(i) < r.begin) ? pre : rest;
-            const uint32_t d0 = __builtin_amdgcn_readfirstlane(d);  // (lane 0 of the wave: valid whenever any lane is)
-            if (__ballot(v && d == d0) == act) {
-                if (lane == 0) atomicAdd(&h[d0], (uint32_t)__popcll(act));  // the wave's 64 keys share one digit (quantised depths)
-            } else if (v) {
-                atomicAdd(&h[d], 1u);
-            }
-        }
-    }
-    load_round(r.begin);  // (this block's first keys travel under the scan below)
+    if (!counted) count_digits(keys_in, seg0, seg_end, digit_of, [&](uint32_t i) { return i < r.begin ? pre : rest; });
+    load_round(q, keys_in, vals_in, idx_mod, r.begin, r.end);  // (this block's first keys travel under the scan below)
     __syncthreads();
     // ---- exclusive scan over the NB digit totals; running output offset of every digit for THIS block ----
     {
         uint32_t t[DPT], p[DPT], loc = 0;
 #pragma unroll
         for (uint32_t k = 0; k < DPT; ++k) { p[k] = pre[tid * DPT + k]; t[k] = p[k] + rest[tid * DPT + k]; loc += t[k]; }
-        uint32_t sc = loc;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t v = __shfl_up(sc, o, 64);
-            if ((int)lane >= o) sc += v;
-        }
+        const uint32_t sc = wave_incl_scan(loc);
         if (lane == 63) wtot[wave] = sc;
         __syncthreads();  // (every thread has read its bins of `rest`)
         uint32_t run = seg0 + (sc - loc);
@@ -630,46 +626,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_radix_fused(
         for (uint32_t k = 0; k < DPT; ++k) { rest[tid * DPT + k] = run + p[k]; run += t[k]; }
     }
     __syncthreads();
-    uint32_t *run_off = rest;
-    for (uint32_t base = r.begin; base < r.end; base += ROUND) {
-        uint32_t lrank[4], dig[4];
-#pragma unroll
-        for (int it = 0; it < 4; ++it) {
-            const uint32_t digit = digit_of(key[it]);
-            dig[it] = digit;
-            uint32_t rank, count;
-            match_rank<BITS>(digit, valid[it], rank, count);
-            const uint32_t prev = valid[it] ? wcnt[wave][digit] : 0u;
-            lrank[it] = prev + rank;
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            if (valid[it] && rank == 0) wcnt[wave][digit] = prev + count;
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        }
-        __syncthreads();
-#pragma unroll
-        for (int it = 0; it < 4; ++it) {
-            if (valid[it]) {
-                const uint32_t digit = dig[it];
-                uint32_t pr = 0;
-#pragma unroll
-                for (int w = 0; w < RS_WAVES; ++w) pr += (w < (int)wave) ? wcnt[w][digit] : 0u;
-                const uint32_t dst = run_off[digit] + pr + lrank[it];
-                keys_out[dst] = key[it];
-                vals_out[dst] = val[it];
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (uint32_t k = 0; k < DPT; ++k) {
-            const uint32_t d = tid + k * RS_THREADS;
-            uint32_t tot = 0;
-#pragma unroll
-            for (int w = 0; w < RS_WAVES; ++w) { tot += wcnt[w][d]; wcnt[w][d] = 0; }
-            run_off[d] += tot;
-        }
-        if (base + ROUND < r.end) load_round(base + ROUND);
-        __syncthreads();
-    }
+    scatter_rounds<NB>(q, keys_in, vals_in, keys_out, vals_out, idx_mod, r, rest, wcnt, digit_of);
 }
 
 // ---- WHOLE SEGMENT IN LDS (round 5) ---------------------------------------------------------------------------------------------
@@ -708,23 +665,12 @@ __global__ __launch_bounds__(SL_THREADS) void k_sort_segment_lds(
         val[c] = valid[c] ? (vals_in ? vals_in[seg0 + i] : (idx_mod == seg_stride ? i : (seg0 + i) % idx_mod)) : 0u;
     }
     if (COMPRESSED) {
-        uint32_t vor = 0u, vand = 0xFFFFFFFFu, fl = 0u;
-        for (uint32_t i = tid; i < key_recs; i += SL_THREADS) {
-            const uint4 r = reinterpret_cast<const uint4 *>(key_bits)[(size_t)blockIdx.x * key_recs + i];
-            vor |= r.x; vand &= r.y; fl |= r.z;
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { vor |= __shfl_xor(vor, o, 64); vand &= __shfl_xor(vand, o, 64); fl |= __shfl_xor(fl, o, 64); }
-        if (lane == 0) { kb[3 * wave] = vor; kb[3 * wave + 1] = vand; kb[3 * wave + 2] = fl; }
-        __syncthreads();
-        uint32_t o = 0u, a = 0xFFFFFFFFu, f = 0u;
-#pragma unroll
-        for (int w = 0; w < SL_WAVES; ++w) { o |= kb[3 * w]; a &= kb[3 * w + 1]; f |= kb[3 * w + 2]; }
-        const uint32_t m = (f & 2u) ? (o ^ a) : 0u;  // no visible key: nothing varies
-        const uint32_t nbits = (uint32_t)__popc(m), cull = f & 1u;
+        const KeyRecords r = fold_key_records<SL_THREADS>(key_bits, key_recs, blockIdx.x, kb);
+        const uint32_t m = (r.flags & 2u) ? (r.vor ^ r.vand) : 0u;  // no visible key: nothing varies
+        const uint32_t nbits = (uint32_t)__popc(m), cull = r.flags & 1u;
         const uint32_t need = (nbits + cull + 7u) / 8u;
         passes = need < 1u ? 1u : (need > 4u ? 4u : need);
-        if (need <= 4u) {  // (33 bits -- every key bit varies and some keys are culled -- is the key itself, as in key_digit)
+        if (need <= 4u) {  // (33 bits -- every key bit varies and some keys are culled -- is the key itself, as in key_digit_w)
             uint32_t d[SL_CH];
 #pragma unroll
             for (int c = 0; c < SL_CH; ++c) d[c] = 0u;
@@ -749,41 +695,14 @@ __global__ __launch_bounds__(SL_THREADS) void k_sort_segment_lds(
 #pragma unroll
         for (int c = 0; c < SL_CH; ++c) {
             if ((uint32_t)c >= nch) continue;  // block-uniform
-            const uint32_t digit = (key[c] >> shift) & 0xFFu;
-            dig[c] = digit;
-            uint32_t rank, count;
-            match_rank<8>(digit, valid[c], rank, count);
-            const uint32_t prev = valid[c] ? wcnt[wave][digit] : 0u;
-            lrank[c] = prev + rank;
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            if (valid[c] && rank == 0) wcnt[wave][digit] = prev + count;
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            dig[c] = (key[c] >> shift) & 0xFFu;
+            rank_against_counters<8>(dig[c], valid[c], wcnt[wave], lrank[c]);
         }
         __syncthreads();
-        // digit `tid` (threads 0 ... 255): the waves' counts -> their exclusive prefix over the waves + the digit's exclusive prefix over the
-        // digits, written back over the counts: the scatter then reads ONE word per key (its wave's base for its digit)
-        uint32_t cw[SL_WAVES], acc = 0u, sc = 0u;
-        if (tid < 256u) {
-#pragma unroll
-            for (int w = 0; w < SL_WAVES; ++w) cw[w] = wcnt[w][tid];
-#pragma unroll
-            for (int w = 0; w < SL_WAVES; ++w) { const uint32_t x = cw[w]; cw[w] = acc; acc += x; }
-            sc = acc;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const uint32_t v = __shfl_up(sc, o, 64);
-                if ((int)lane >= o) sc += v;
-            }
-            if (lane == 63u) wtot[wave] = sc;
-        }
+        uint32_t cw[SL_WAVES], acc, sc;
+        wave_digit_bases_scan<SL_WAVES>(wcnt, wtot, cw, acc, sc);
         __syncthreads();
-        if (tid < 256u) {
-            uint32_t base = sc - acc;
-#pragma unroll
-            for (int w = 0; w < 3; ++w) base += (w < (int)wave) ? wtot[w] : 0u;
-#pragma unroll
-            for (int w = 0; w < SL_WAVES; ++w) wcnt[w][tid] = base + cw[w];
-        }
+        wave_digit_bases_write<SL_WAVES>(wcnt, wtot, cw, acc, sc);
         __syncthreads();
         const bool last = p + 1u == passes;
         uint32_t *kd = ks[p & 1u], *vd = vs[p & 1u];
@@ -859,32 +778,13 @@ __device__ __forceinline__ void bucket_sort_lds(const uint32_t *__restrict__ kin
 #pragma unroll
         for (int c = 0; c < CH; ++c) {
             if ((uint32_t)c >= nch) continue;  // block-uniform
-            const uint32_t digit = (key[c] >> shift) & 0xFFu;
-            dig[c] = digit;
-            uint32_t rank, count;
-            match_rank<8>(digit, valid[c], rank, count);
-            const uint32_t prev = valid[c] ? wcnt[wave][digit] : 0u;
-            lrank[c] = prev + rank;
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            if (valid[c] && rank == 0) wcnt[wave][digit] = prev + count;
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            dig[c] = (key[c] >> shift) & 0xFFu;
+            rank_against_counters<8>(dig[c], valid[c], wcnt[wave], lrank[c]);
         }
         __syncthreads();
-        uint32_t cw[WAVES], acc = 0u, sc = 0u;
-        if (tid < 256u) {
-#pragma unroll
-            for (int w = 0; w < WAVES; ++w) cw[w] = wcnt[w][tid];
-#pragma unroll
-            for (int w = 0; w < WAVES; ++w) { const uint32_t x = cw[w]; cw[w] = acc; acc += x; }
-            sc = acc;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const uint32_t v = __shfl_up(sc, o, 64);
-                if ((int)lane >= o) sc += v;
-            }
-            if (lane == 63u) wtot[wave] = sc;
-            if (acc == cnt) wtot[4u + p] = 1u;
-        }
+        uint32_t cw[WAVES], acc, sc;
+        wave_digit_bases_scan<WAVES>(wcnt, wtot, cw, acc, sc);
+        if (tid < 256u && acc == cnt) wtot[4u + p] = 1u;
         __syncthreads();
         if (wtot[4u + p]) {  // block-uniform: all keys share this digit, the pass would move nothing
             if (last) {
@@ -897,13 +797,7 @@ __device__ __forceinline__ void bucket_sort_lds(const uint32_t *__restrict__ kin
             for (int k = 0; k < 4; ++k) wcnt[wave][lane + 64u * k] = 0u;  // (the wave's own row; the others' reads of it are behind the barrier)
             continue;
         }
-        if (tid < 256u) {
-            uint32_t base = sc - acc;
-#pragma unroll
-            for (int w = 0; w < 3; ++w) base += (w < (int)wave) ? wtot[w] : 0u;
-#pragma unroll
-            for (int w = 0; w < WAVES; ++w) wcnt[w][tid] = base + cw[w];
-        }
+        wave_digit_bases_write<WAVES>(wcnt, wtot, cw, acc, sc);
         __syncthreads();
 #pragma unroll
         for (int c = 0; c < CH; ++c) {
@@ -981,12 +875,7 @@ __device__ __forceinline__ void bucket_sort_global(uint32_t *ka, uint32_t *va, u
         uint32_t t = 0u, sc = 0u;
         if (tid < 256u) {
             t = h[tid];
-            sc = t;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const uint32_t v = __shfl_up(sc, o, 64);
-                if ((int)lane >= o) sc += v;
-            }
+            sc = wave_incl_scan(t);
             if (lane == 63u) wtot[wave] = sc;
             if (t == cnt) wtot[4] = 1u;
         }
@@ -1067,15 +956,158 @@ uint32_t dmask_of(uint32_t p, uint32_t width, uint32_t key_bits) {
     return (1u << (left < width ? left : width)) - 1u;
 }
 
+// key compression (depth sort): full 32-bit keys read from keys_first, the index as payload, a final place for the payload
+bool compression_ok(const FgsRadixSort &s) {
+    if (!s.key_stats || (s.keys_first && s.index_payload_mod && s.vals_final && s.key_recs && !s.seg_len_dev && s.key_bits == 32u)) return true;
+    fgs_set_error("radix sort: key compression needs 32-bit keys in keys_first, an index payload and vals_final");
+    return false;
+}
+
+// The buffers of pass p of the pass loops (fused and two-launch).  keys_first: the first pass reads its keys from there (read-only)
+// instead of keys_in; index_payload_mod != 0: the first pass generates the payload (element index modulo it) instead of reading vals_in.
+struct PassBuffers {
+    const FgsRadixSort &s;
+    const uint32_t *kin;           // keys the pass reads
+    uint32_t *kout, *vin;          // keys it writes; the payload of the pass before it
+    const uint32_t *vsrc = nullptr;  // payload it reads (nullptr: generated) and writes
+    uint32_t *vdst = nullptr;
+
+    explicit PassBuffers(const FgsRadixSort &sort)
+        : s(sort), kin(sort.keys_first ? sort.keys_first : sort.keys_in), kout(sort.keys_first ? sort.keys_in : sort.keys_alt), vin(sort.vals_in) {}
+    void begin(uint32_t p, uint32_t passes) {
+        vdst = (p == passes - 1 && s.vals_final) ? s.vals_final : (vin == s.vals_in ? s.vals_alt : s.vals_in);
+        if (p == 0 && s.index_payload_mod && !(passes == 1 && s.vals_final)) vdst = s.vals_in;  // vals_in is free: nothing to read
+        vsrc = (p == 0 && s.index_payload_mod) ? nullptr : vin;
+    }
+    // ping-pong: the buffer just read becomes the next output, except a read-only first-pass source
+    void end(uint32_t p) {
+        uint32_t *next_out = (p == 0 && s.keys_first) ? s.keys_alt : const_cast<uint32_t *>(kin);
+        kin = kout; kout = next_out;
+        vin = vdst;
+    }
+    // Key compression: a segment stops after its own number of live passes, so NO buffer holds every segment's sorted keys
+    // (the pass-4 buffer has stale data for segments that needed fewer) and the payload is in vals_final: hand back no key
+    // pointer rather than one that looks valid (ADVICE r4; the depth sort's caller reads `order` only).
+    void hand_back(FgsRadixSort &out) const {
+        out.keys_sorted = s.key_stats ? nullptr : const_cast<uint32_t *>(kin);
+        out.vals_sorted = s.key_stats ? s.vals_final : vin;
+    }
+};
+
+// host-known segments of at most SL_CAP keys: k_sort_segment_lds, ONE launch for all passes
+int sort_segments_lds(FgsRadixSort &s) {
+    const bool compressed = s.key_stats != nullptr;
+    const uint32_t *kin = s.keys_first ? s.keys_first : s.keys_in;
+    uint32_t *kdst = compressed ? nullptr : (s.keys_first ? s.keys_in : s.keys_alt);
+    uint32_t *vdst = s.vals_final ? s.vals_final : s.vals_alt;
+    const uint32_t *vsrc = s.index_payload_mod ? nullptr : s.vals_in;
+    const uint32_t passes = (s.key_bits + 7u) / 8u, imod = s.index_payload_mod ? s.index_payload_mod : 1u;
+    hipLaunchKernelGGL(compressed ? k_sort_segment_lds<true> : k_sort_segment_lds<false>, dim3(s.num_segs), dim3(SL_THREADS), 0, s.st, kin,
+                       vsrc, kdst, vdst, s.seg_len, s.seg_stride, passes, imod, s.key_stats, s.key_recs);
+    FGS_LAUNCH_CHECK("k_sort_segment_lds");
+    s.keys_sorted = kdst;
+    s.vals_sorted = vdst;
+    return FGS_OK;
+}
+
+// the bucket sort: one bucket pass over memory, then every bucket in LDS (see BUCKET SORT above)
+int sort_buckets(FgsRadixSort &s) {
+    uint32_t bps = fgs_radix_blocks_per_seg(s.seg_len, s.num_segs);
+    if (bps > 64u) bps = 64u;  // (the prefix over a segment's blocks is formed inside the scatter)
+    const dim3 grid(bps, s.num_segs);
+    hipLaunchKernelGGL((k_radix_upsweep<false, true>), grid, dim3(RS_THREADS), 0, s.st, s.keys_first, s.seg_len, (const uint32_t *)nullptr,
+                       s.seg_len, s.seg_stride, 0u, 0u, s.hist, s.key_range, s.key_recs, 0u, s.bucket_tab);
+    FGS_LAUNCH_CHECK("k_radix_upsweep");
+    hipLaunchKernelGGL((k_radix_downsweep<false, true>), grid, dim3(RS_THREADS), 0, s.st, s.keys_first, (const uint32_t *)nullptr, s.keys_in,
+                       s.vals_in, s.seg_len, (const uint32_t *)nullptr, s.seg_len, s.seg_stride, 0u, 0u, s.hist, (const uint32_t *)nullptr,
+                       s.index_payload_mod, s.key_range, s.key_recs, 0u, (uint32_t *)nullptr, s.bucket_tab);
+    FGS_LAUNCH_CHECK("k_radix_downsweep");
+    hipLaunchKernelGGL(k_bucket_sort, dim3(256, s.num_segs), dim3(RS_THREADS), 0, s.st, s.keys_in, s.vals_in, s.vals_final, s.seg_len,
+                       s.seg_stride, s.bucket_tab);
+    FGS_LAUNCH_CHECK("k_bucket_sort");
+    hipLaunchKernelGGL(k_bucket_sort_large, dim3(32, s.num_segs), dim3(SL_THREADS), 0, s.st, s.keys_in, s.vals_in, s.keys_alt, s.vals_alt,
+                       s.vals_final, s.seg_len, s.seg_stride, s.bucket_tab);
+    FGS_LAUNCH_CHECK("k_bucket_sort_large");
+    s.keys_sorted = nullptr;  // (grouped by bucket only; the depth sort's caller reads `order`)
+    s.vals_sorted = s.vals_final;
+    return FGS_OK;
+}
+
+// the fused passes, one launch each (k_radix_fused): host-known segments of up to 64 K keys
+// (pass_mode 3, the hand-off form: a compressed segment that leaves a pass early publishes nothing for it, and nobody of that
+//  segment waits either -- all its blocks leave together; region p belongs to pass p alone, so no word is ever reused in a call)
+int sort_fused_passes(FgsRadixSort &s) {
+    const bool compressed = s.key_stats != nullptr;
+    const uint32_t bits = (s.pass_mode >= 2 || s.key_bits <= 8u) ? 8u : 11u;  // (plane ids, <= 5 bits: the small histogram)
+    // hand-off form: the depth sort of a forward whose projection cleared `hist` (fgs_api.hip); needs its four pass regions
+    const bool handoff = s.pass_mode == 3 && s.hist != nullptr && s.key_bits == 32u && s.keys_first != nullptr;
+    const uint32_t passes = (s.key_bits + bits - 1u) / bits, width = (s.key_bits + passes - 1u) / passes;
+    const uint32_t imod = s.index_payload_mod ? s.index_payload_mod : 1u;
+    const dim3 grid(fused_blocks_per_seg(s.seg_len, s.num_segs), s.num_segs);
+    const auto kernel = handoff      ? (compressed ? k_radix_fused<8, true, true> : k_radix_fused<8, false, true>)
+                        : bits == 8u ? (compressed ? k_radix_fused<8, true> : k_radix_fused<8, false>)
+                                     : (compressed ? k_radix_fused<11, true> : k_radix_fused<11, false>);
+    PassBuffers b(s);
+    for (uint32_t p = 0; p < passes; ++p) {
+        b.begin(p, passes);
+        uint32_t *region = handoff ? s.hist + (size_t)p * s.num_segs * 16u * 256u : nullptr;
+        hipLaunchKernelGGL(kernel, grid, dim3(RS_THREADS), 0, s.st, b.kin, b.vsrc, b.kout, b.vdst, s.seg_len, s.seg_stride, p * width,
+                           dmask_of(p, width, s.key_bits), imod, s.key_stats, s.key_recs, p, s.vals_final, region);
+        FGS_LAUNCH_CHECK("k_radix_fused");
+        b.end(p);
+    }
+    b.hand_back(s);
+    return FGS_OK;
+}
+
+// the two-launch passes (k_radix_upsweep, k_radix_downsweep; k_radix_scan between them above 64 blocks per segment): any length
+int sort_two_launch_passes(FgsRadixSort &s) {
+    const bool compressed = s.key_stats != nullptr;
+    const uint32_t bps = fgs_radix_blocks_per_seg(s.seg_capacity, s.num_segs);
+    uint32_t *dtot = s.hist + (size_t)s.num_segs * 256 * bps;
+    const uint32_t passes = (s.key_bits + 7) / 8;
+    // equal digit widths over the passes (13 key bits -> 7 + 6, not 8 + 5): fewer bins per pass means longer
+    // runs of neighbouring destinations in the scatter
+    const uint32_t width = passes ? (s.key_bits + passes - 1) / passes : 8;
+    const uint32_t imod = s.index_payload_mod ? s.index_payload_mod : 1u;
+    const bool fused_scan = bps <= 64;
+    PassBuffers b(s);
+    if (passes == 0) {
+        if (s.vals_final && s.vals_final != s.vals_in) {
+            // single possible key: already sorted; move the payload where the caller wants it
+            hipError_t e = hipMemcpyAsync(s.vals_final, s.vals_in, (size_t)s.seg_stride * (s.num_segs - 1) * 4 + (size_t)s.seg_capacity * 4,
+                                          hipMemcpyDeviceToDevice, s.st);
+            if (e != hipSuccess) { fgs_set_error("radix copy: %s", hipGetErrorString(e)); return FGS_ELAUNCH; }
+            b.vin = s.vals_final;
+        }
+        s.keys_sorted = const_cast<uint32_t *>(b.kin); s.vals_sorted = b.vin;
+        return FGS_OK;
+    }
+    const dim3 grid(bps, s.num_segs);
+    const uint32_t rows = s.num_segs * 256;
+    for (uint32_t p = 0; p < passes; ++p) {
+        b.begin(p, passes);
+        const uint32_t shift = p * width, dmask = dmask_of(p, width, s.key_bits);  // (the compressed kernels take their digits from the plan)
+        hipLaunchKernelGGL(compressed ? k_radix_upsweep<true> : k_radix_upsweep<false>, grid, dim3(RS_THREADS), 0, s.st, b.kin, s.seg_len,
+                           s.seg_len_dev, s.seg_capacity, s.seg_stride, shift, dmask, s.hist, s.key_stats, s.key_recs, p, (uint32_t *)nullptr);
+        FGS_LAUNCH_CHECK("k_radix_upsweep");
+        if (!fused_scan) {
+            hipLaunchKernelGGL(k_radix_scan, dim3((rows + 3) / 4), dim3(256), 0, s.st, s.hist, dtot, bps, rows);
+            FGS_LAUNCH_CHECK("k_radix_scan");
+        }
+        hipLaunchKernelGGL(compressed ? k_radix_downsweep<true> : k_radix_downsweep<false>, grid, dim3(RS_THREADS), 0, s.st, b.kin, b.vsrc,
+                           b.kout, b.vdst, s.seg_len, s.seg_len_dev, s.seg_capacity, s.seg_stride, shift, dmask, s.hist,
+                           fused_scan ? (const uint32_t *)nullptr : dtot, imod, s.key_stats, s.key_recs, p, s.vals_final, (uint32_t *)nullptr);
+        FGS_LAUNCH_CHECK("k_radix_downsweep");
+        b.end(p);
+    }
+    b.hand_back(s);
+    return FGS_OK;
+}
+
 }  // namespace
 
-int fgs_launch_radix_sort(uint32_t *keys_in, uint32_t *vals_in, uint32_t *keys_alt, uint32_t *vals_alt,
-                          uint32_t *vals_final, uint32_t **keys_sorted, uint32_t **vals_sorted,
-                          uint32_t seg_len, const uint32_t *seg_len_dev, uint32_t seg_capacity,
-                          uint32_t seg_stride, uint32_t num_segs, uint32_t key_bits, uint32_t *hist,
-                          hipStream_t st, const uint32_t *keys_first, uint32_t index_payload_mod,
-                          const uint32_t *key_stats, uint32_t key_recs, int pass_mode, const uint32_t *key_range,
-                          uint32_t *bucket_tab) {
+int fgs_launch_radix_sort(FgsRadixSort &s) {
     // pass_mode (FgsDims.sort_mode >> 1): 1 = the fused pass (one launch per pass, every block recounting its segment, 11-bit digits)
     // for any host-known segment length up to 64 K keys | 2 = the same with 8-bit digits | 3 = 8-bit digits with the hand-off (A/B runs,
     // agreement tests).  Measured (profiles/r05_ab_sort_passes.txt): at 16 x 8 192 keys the fused passes take 45.6 us (11-bit) / 55.5
@@ -1088,162 +1120,12 @@ int fgs_launch_radix_sort(uint32_t *keys_in, uint32_t *vals_in, uint32_t *keys_a
     // Round 6: automatic (0, 5) above 8192 keys is the bucket sort (3 + 1 launches instead of 8) for the depth sort of full keys -- the
     // caller hands k_project's key range records and the table; zone keys (key_stats) keep their compressed passes: a handful of
     // distinct depths gives a handful of giant buckets.  profiles/r06_ab_bucket_sort.txt.
-    const bool host_len = !seg_len_dev && seg_len == seg_capacity && key_bits >= 1u;
-    if (host_len && seg_len <= (uint32_t)SL_CAP && (pass_mode == 0 || pass_mode == 5) && (vals_in || index_payload_mod)) {
-        const bool compressed = key_stats != nullptr;
-        if (compressed && !(keys_first && index_payload_mod && vals_final && key_recs && key_bits == 32u)) {
-            fgs_set_error("radix sort: key compression needs 32-bit keys in keys_first, an index payload and vals_final");
-            return FGS_EINVAL;
-        }
-        const uint32_t *kin = keys_first ? keys_first : keys_in;
-        uint32_t *kdst = compressed ? nullptr : (keys_first ? keys_in : keys_alt);
-        uint32_t *vdst = vals_final ? vals_final : vals_alt;
-        const uint32_t *vsrc = index_payload_mod ? nullptr : vals_in;
-        const uint32_t passes = (key_bits + 7u) / 8u, imod = index_payload_mod ? index_payload_mod : 1u;
-        if (compressed)
-            hipLaunchKernelGGL(k_sort_segment_lds<true>, dim3(num_segs), dim3(SL_THREADS), 0, st, kin, vsrc, kdst, vdst, seg_len, seg_stride,
-                               passes, imod, key_stats, key_recs);
-        else
-            hipLaunchKernelGGL(k_sort_segment_lds<false>, dim3(num_segs), dim3(SL_THREADS), 0, st, kin, vsrc, kdst, vdst, seg_len, seg_stride,
-                               passes, imod, (const uint32_t *)nullptr, 0u);
-        FGS_LAUNCH_CHECK("k_sort_segment_lds");
-        *keys_sorted = kdst;
-        *vals_sorted = vdst;
-        return FGS_OK;
-    }
-    if (host_len && seg_len > (uint32_t)SL_CAP && (pass_mode == 0 || pass_mode == 5) && !key_stats && key_range && bucket_tab && keys_first &&
-        index_payload_mod && vals_final && key_recs && key_bits == 32u) {
-        uint32_t bps = fgs_radix_blocks_per_seg(seg_len, num_segs);
-        if (bps > 64u) bps = 64u;  // (the prefix over a segment's blocks is formed inside the scatter)
-        const dim3 grid(bps, num_segs);
-        hipLaunchKernelGGL((k_radix_upsweep<false, true>), grid, dim3(RS_THREADS), 0, st, keys_first, seg_len, (const uint32_t *)nullptr,
-                           seg_len, seg_stride, 0u, 0u, hist, key_range, key_recs, 0u, bucket_tab);
-        FGS_LAUNCH_CHECK("k_radix_upsweep");
-        hipLaunchKernelGGL((k_radix_downsweep<false, true>), grid, dim3(RS_THREADS), 0, st, keys_first, (const uint32_t *)nullptr, keys_in,
-                           vals_in, seg_len, (const uint32_t *)nullptr, seg_len, seg_stride, 0u, 0u, hist, (const uint32_t *)nullptr,
-                           index_payload_mod, key_range, key_recs, 0u, (uint32_t *)nullptr, bucket_tab);
-        FGS_LAUNCH_CHECK("k_radix_downsweep");
-        hipLaunchKernelGGL(k_bucket_sort, dim3(256, num_segs), dim3(RS_THREADS), 0, st, keys_in, vals_in, vals_final, seg_len, seg_stride,
-                           bucket_tab);
-        FGS_LAUNCH_CHECK("k_bucket_sort");
-        hipLaunchKernelGGL(k_bucket_sort_large, dim3(32, num_segs), dim3(SL_THREADS), 0, st, keys_in, vals_in, keys_alt, vals_alt, vals_final,
-                           seg_len, seg_stride, bucket_tab);
-        FGS_LAUNCH_CHECK("k_bucket_sort_large");
-        *keys_sorted = nullptr;  // (grouped by bucket only; the depth sort's caller reads `order`)
-        *vals_sorted = vals_final;
-        return FGS_OK;
-    }
-    const bool fused = host_len && pass_mode >= 1 && pass_mode <= 3 && seg_len <= 65536u;
-    // (pass_mode 3, the hand-off form: a compressed segment that leaves a pass early publishes nothing for it, and nobody of that
-    //  segment waits either -- all its blocks leave together; region p belongs to pass p alone, so no word is ever reused in a call)
-    if (fused) {
-        const bool compressed = key_stats != nullptr;
-        if (compressed && !(keys_first && index_payload_mod && vals_final && key_recs && key_bits == 32u)) {
-            fgs_set_error("radix sort: key compression needs 32-bit keys in keys_first, an index payload and vals_final");
-            return FGS_EINVAL;
-        }
-        const uint32_t bits = (pass_mode >= 2 || key_bits <= 8u) ? 8u : 11u;  // (plane ids, <= 5 bits: the small histogram)
-        // hand-off form: the depth sort of a forward whose projection cleared `hist` (fgs_api.hip); needs its four pass regions
-        const bool handoff = pass_mode == 3 && hist != nullptr && key_bits == 32u && keys_first != nullptr;
-        const uint32_t passes = (key_bits + bits - 1u) / bits, width = (key_bits + passes - 1u) / passes;
-        const dim3 grid(fused_blocks_per_seg(seg_len, num_segs), num_segs);
-        const uint32_t *kin = keys_first ? keys_first : keys_in;
-        uint32_t *vin = vals_in, *kout = keys_first ? keys_in : keys_alt, *kspare = keys_alt;
-        for (uint32_t p = 0; p < passes; ++p) {
-            uint32_t *vdst = (p == passes - 1 && vals_final) ? vals_final : (vin == vals_in ? vals_alt : vals_in);
-            if (p == 0 && index_payload_mod && !(passes == 1 && vals_final)) vdst = vals_in;  // vals_in is free: nothing to read
-            const uint32_t *vsrc = (p == 0 && index_payload_mod) ? nullptr : vin;
-            const uint32_t shift = p * width, dmask = dmask_of(p, width, key_bits), imod = index_payload_mod ? index_payload_mod : 1u;
-#define FGS_FUSED_LAUNCH(B_, C_)                                                                                             \
-    hipLaunchKernelGGL((k_radix_fused<B_, C_>), grid, dim3(RS_THREADS), 0, st, kin, vsrc, kout, vdst, seg_len, seg_stride, shift, \
-                       dmask, imod, key_stats, key_recs, p, vals_final)
-            if (handoff) {
-                uint32_t *region = hist + (size_t)p * num_segs * 16u * 256u;
-                if (compressed)
-                    hipLaunchKernelGGL((k_radix_fused<8, true, true>), grid, dim3(RS_THREADS), 0, st, kin, vsrc, kout, vdst, seg_len, seg_stride,
-                                       shift, dmask, imod, key_stats, key_recs, p, vals_final, region);
-                else
-                    hipLaunchKernelGGL((k_radix_fused<8, false, true>), grid, dim3(RS_THREADS), 0, st, kin, vsrc, kout, vdst, seg_len, seg_stride,
-                                       shift, dmask, imod, key_stats, key_recs, p, vals_final, region);
-            } else if (bits == 8u) { if (compressed) FGS_FUSED_LAUNCH(8, true); else FGS_FUSED_LAUNCH(8, false); }
-            else            { if (compressed) FGS_FUSED_LAUNCH(11, true); else FGS_FUSED_LAUNCH(11, false); }
-#undef FGS_FUSED_LAUNCH
-            FGS_LAUNCH_CHECK("k_radix_fused");
-            uint32_t *next_out = (p == 0 && keys_first) ? kspare : const_cast<uint32_t *>(kin);
-            kin = kout; kout = next_out;
-            vin = vdst;
-        }
-        *keys_sorted = compressed ? nullptr : const_cast<uint32_t *>(kin);  // (compressed: see the end of this function)
-        *vals_sorted = compressed ? vals_final : vin;
-        return FGS_OK;
-    }
-    const uint32_t bps = fgs_radix_blocks_per_seg(seg_capacity, num_segs);
-    // key compression (depth sort): full 32-bit keys read from keys_first, the index as payload, a final place for the payload
-    const bool compressed = key_stats != nullptr;
-    if (compressed && !(keys_first && index_payload_mod && vals_final && key_recs && !seg_len_dev && key_bits == 32u)) {
-        fgs_set_error("radix sort: key compression needs 32-bit keys in keys_first, an index payload and vals_final");
-        return FGS_EINVAL;
-    }
-    uint32_t *dtot = hist + (size_t)num_segs * 256 * bps;
-    const uint32_t passes = (key_bits + 7) / 8;
-    // equal digit widths over the passes (13 key bits -> 7 + 6, not 8 + 5): fewer bins per pass means longer
-    // runs of neighbouring destinations in the scatter
-    const uint32_t width = passes ? (key_bits + passes - 1) / passes : 8;
-    // keys_first: the first pass reads its keys from there (read-only) instead of keys_in; index_payload_mod != 0:
-    // the first pass generates the payload (element index modulo it) instead of reading vals_in
-    const uint32_t *kin = keys_first ? keys_first : keys_in;
-    uint32_t *vin = vals_in, *kout = keys_first ? keys_in : keys_alt, *vout = vals_alt;
-    uint32_t *kspare = keys_alt;
-    const bool fused_scan = bps <= 64;
-    if (passes == 0) {
-        if (vals_final && vals_final != vals_in) {
-            // single possible key: already sorted; move the payload where the caller wants it
-            hipError_t e = hipMemcpyAsync(vals_final, vals_in, (size_t)seg_stride * (num_segs - 1) * 4 + (size_t)seg_capacity * 4,
-                                          hipMemcpyDeviceToDevice, st);
-            if (e != hipSuccess) { fgs_set_error("radix copy: %s", hipGetErrorString(e)); return FGS_ELAUNCH; }
-            vin = vals_final;
-        }
-        *keys_sorted = const_cast<uint32_t *>(kin); *vals_sorted = vin;
-        return FGS_OK;
-    }
-    (void)vout;
-    for (uint32_t p = 0; p < passes; ++p) {
-        uint32_t *vdst = (p == passes - 1 && vals_final) ? vals_final : (vin == vals_in ? vals_alt : vals_in);
-        if (p == 0 && index_payload_mod && !(passes == 1 && vals_final)) vdst = vals_in;  // vals_in is free: nothing to read
-        const dim3 grid(bps, num_segs);
-        if (compressed)
-            hipLaunchKernelGGL(k_radix_upsweep<true>, grid, dim3(RS_THREADS), 0, st, kin, seg_len, seg_len_dev, seg_capacity,
-                               seg_stride, 0u, 0u, hist, key_stats, key_recs, p, (uint32_t *)nullptr);
-        else
-            hipLaunchKernelGGL(k_radix_upsweep<false>, grid, dim3(RS_THREADS), 0, st, kin, seg_len, seg_len_dev, seg_capacity,
-                               seg_stride, p * width, dmask_of(p, width, key_bits), hist, (const uint32_t *)nullptr, 0u, p, (uint32_t *)nullptr);
-        FGS_LAUNCH_CHECK("k_radix_upsweep");
-        const uint32_t rows = num_segs * 256;
-        if (!fused_scan) {
-            hipLaunchKernelGGL(k_radix_scan, dim3((rows + 3) / 4), dim3(256), 0, st, hist, dtot, bps, rows);
-            FGS_LAUNCH_CHECK("k_radix_scan");
-        }
-        const uint32_t *vsrc = (p == 0 && index_payload_mod) ? nullptr : vin;
-        if (compressed)
-            hipLaunchKernelGGL(k_radix_downsweep<true>, grid, dim3(RS_THREADS), 0, st, kin, vsrc, kout, vdst, seg_len, seg_len_dev,
-                               seg_capacity, seg_stride, 0u, 0u, hist, fused_scan ? (const uint32_t *)nullptr : dtot,
-                               index_payload_mod, key_stats, key_recs, p, vals_final, (uint32_t *)nullptr);
-        else
-            hipLaunchKernelGGL(k_radix_downsweep<false>, grid, dim3(RS_THREADS), 0, st, kin, vsrc, kout, vdst, seg_len, seg_len_dev,
-                               seg_capacity, seg_stride, p * width, dmask_of(p, width, key_bits), hist,
-                               fused_scan ? (const uint32_t *)nullptr : dtot, index_payload_mod ? index_payload_mod : 1u,
-                               (const uint32_t *)nullptr, 0u, p, (uint32_t *)nullptr, (uint32_t *)nullptr);
-        FGS_LAUNCH_CHECK("k_radix_downsweep");
-        // ping-pong: the buffer just read becomes the next output, except a read-only first-pass source
-        uint32_t *next_out = (p == 0 && keys_first) ? kspare : const_cast<uint32_t *>(kin);
-        kin = kout; kout = next_out;
-        vin = vdst;
-    }
-    // Key compression: a segment stops after its own number of live passes, so NO buffer holds every segment's sorted keys
-    // (the pass-4 buffer has stale data for segments that needed fewer) and the payload is in vals_final: hand back no key
-    // pointer rather than one that looks valid (ADVICE r4; the depth sort's caller reads `order` only).
-    *keys_sorted = compressed ? nullptr : const_cast<uint32_t *>(kin);
-    *vals_sorted = compressed ? vals_final : vin;
-    return FGS_OK;
+    if (!compression_ok(s)) return FGS_EINVAL;
+    const bool host_len = !s.seg_len_dev && s.seg_len == s.seg_capacity && s.key_bits >= 1u;
+    const bool automatic = host_len && (s.pass_mode == 0 || s.pass_mode == 5);
+    const bool depth_keys = s.keys_first && s.index_payload_mod && s.vals_final && s.key_recs && s.key_bits == 32u;
+    if (automatic && s.seg_len <= (uint32_t)SL_CAP && (s.vals_in || s.index_payload_mod)) return sort_segments_lds(s);
+    if (automatic && s.seg_len > (uint32_t)SL_CAP && !s.key_stats && s.key_range && s.bucket_tab && depth_keys) return sort_buckets(s);
+    if (host_len && s.pass_mode >= 1 && s.pass_mode <= 3 && s.seg_len <= 65536u) return sort_fused_passes(s);
+    return sort_two_launch_passes(s);
 }
-
