@@ -29,6 +29,7 @@ EXPORTED_SYMBOLS = [
     "fgs_head_workspace_bytes", "fgs_head_forward", "fgs_head_backward",
     "fgs_nca_workspace_bytes", "fgs_nca_perceive_forward", "fgs_nca_perceive_backward", "fgs_nca_update_forward",
     "fgs_nca_update_backward",
+    "fgs_saag_workspace_bytes", "fgs_saag_inputs_forward", "fgs_saag_refine_forward", "fgs_saag_refine_backward",
 ]
 
 STAGES = ["project", "depth_sort", "dup_emit", "tile_sort", "tile_ranges", "composite_fwd",
@@ -123,6 +124,13 @@ class FgsNcaDims(ctypes.Structure):
     _fields_ = [("batch", ctypes.c_int32), ("points", ctypes.c_int32), ("state_dim", ctypes.c_int32), ("k", ctypes.c_int32)]
 
 
+class FgsSaagDims(ctypes.Structure):
+    _fields_ = [("batch", ctypes.c_int32), ("points", ctypes.c_int32), ("channels", ctypes.c_int32),
+                ("grid_h", ctypes.c_int32), ("grid_w", ctypes.c_int32),
+                ("feat_stride_batch", ctypes.c_int64), ("feat_stride_channel", ctypes.c_int64),
+                ("feat_stride_row", ctypes.c_int64), ("residual_scale", ctypes.c_float)]
+
+
 class FgsError(RuntimeError):
     pass
 
@@ -210,6 +218,14 @@ def load():
     lib.fgs_nca_update_backward.argtypes = [nd] + [vp] * 3 + [f32] + [vp] * 5
     for fn in (lib.fgs_nca_workspace_bytes, lib.fgs_nca_perceive_forward, lib.fgs_nca_perceive_backward,
                lib.fgs_nca_update_forward, lib.fgs_nca_update_backward):
+        fn.restype = ctypes.c_int
+    sd = cp(FgsSaagDims)
+    lib.fgs_saag_workspace_bytes.argtypes = [sd, cp(ctypes.c_size_t)]
+    lib.fgs_saag_inputs_forward.argtypes = [sd] + [vp] * 8
+    lib.fgs_saag_refine_forward.argtypes = [sd] + [vp] * 17
+    lib.fgs_saag_refine_backward.argtypes = [sd] + [vp] * 19
+    for fn in (lib.fgs_saag_workspace_bytes, lib.fgs_saag_inputs_forward, lib.fgs_saag_refine_forward,
+               lib.fgs_saag_refine_backward):
         fn.restype = ctypes.c_int
     for fn in (lib.fgs_asm_propagate_workspace_bytes, lib.fgs_asm_propagate_forward, lib.fgs_asm_propagate_backward,
                lib.fgs_spectral_workspace_bytes, lib.fgs_spectral_loss_forward, lib.fgs_spectral_loss_backward,

@@ -66,6 +66,9 @@ SOURCES = {
     # no FMA contraction: the neighbour distance d2 = (dx dx + dy dy) + dz dz and the update state + step (delta mask) are
     # DEFINED with every operation rounded on its own (include/fgs.h); tests compare them bit for bit with torch expressions
     "fgs_nca.hip": ["-ffp-contract=off"],
+    # as the head: the backward recomputes the forward (clamp gates, quaternion branch), and the deltas are DEFINED as
+    # (raw gain) residual_scale with both products rounded (include/fgs.h)
+    "fgs_saag.hip": ["-ffp-contract=off"],
 }
 LINK_LIBS = ["-lhipfft"]
 

@@ -20,14 +20,32 @@ import torch
 from . import io as fio
 
 
+def collate_host_items(items, saag_tensors: int = 0):
+    """Stack the per-item tuples of `host_item` into one batch tuple.  The last `saag_tensors` (5, or 0) entries of every item are
+    its SAAG cloud, empty (0 Gaussians) where the image has no `_saag.bin`: they join the batch only when EVERY item has a cloud
+    and all clouds have the same count; otherwise they are left out and the step draws the dummy cloud (train_step).  (The
+    reference stacks whatever the items hold in its default collate, TGD:1760-1767, and would crash there on unequal counts;
+    it falls back to the dummy cloud only when the stacked clouds are empty, TGD:1046-1056.)"""
+    cols = list(zip(*items))
+    step, saag = (cols[:-saag_tensors], cols[-saag_tensors:]) if saag_tensors else (cols, [])
+    batch = [torch.stack(t) for t in step]
+    if saag:
+        counts = {int(t.shape[0]) for t in saag[0]}
+        if len(counts) == 1 and counts != {0}:
+            batch += [torch.stack(t) for t in saag]
+    return tuple(batch)
+
+
 class ImageDataset:
     def __init__(self, data_dir: str, image_size: int = 256, feature_cache_dir: Optional[str] = None,
-                 max_images: Optional[int] = None, feature_dim: int = 384, load_vlm_density: bool = False):
+                 max_images: Optional[int] = None, feature_dim: int = 384, load_vlm_density: bool = False,
+                 load_saag: bool = False):
         self.data_dir = Path(data_dir)
         self.image_size = image_size
         self.feature_cache_dir = Path(feature_cache_dir) if feature_cache_dir else self.data_dir / "features"
         self.feature_dim = feature_dim
         self.load_vlm_density = load_vlm_density
+        self.saag_tensors = 5 if load_saag else 0  # host_item appends the SAAG cloud (--experiment 1); 0: it returns what it returned
         self.feature_suffix = fio.feature_cache_suffix(feature_dim)
         paths: List[Path] = []
         for ext in ["*.jpg", "*.jpeg", "*.png", "*.webp"]:
@@ -74,17 +92,21 @@ class ImageDataset:
                 pass
         return torch.ones(1, S, S), False
 
-    def __getitem__(self, idx: int) -> Dict[str, torch.Tensor]:
-        name, image, features, depth = self._step_tensors(idx)
+    def saag_cloud(self, name: str):
+        """(has_saag, {saag_positions (N,3), saag_scales (N,3), saag_rotations (N,4), saag_colors (N,3), saag_opacities (N,)}) of
+        image `name`: the `{name}_saag.bin` cache, or empty tensors (N = 0) when there is none (TGD:632-647)."""
         spath = self.feature_cache_dir / f"{name}_saag.bin"
-        item = {"image": image, "features": features, "depth": depth, "has_saag": spath.exists(), "name": name}
         if spath.exists():
             saag = fio.load_gaussians_from_binary(str(spath))
-            for k in ("positions", "scales", "rotations", "colors", "opacities"):
-                item["saag_" + k] = saag[k].float()
-        else:
-            item.update(saag_positions=torch.zeros(0, 3), saag_scales=torch.zeros(0, 3), saag_rotations=torch.zeros(0, 4),
-                        saag_colors=torch.zeros(0, 3), saag_opacities=torch.zeros(0))
+            return True, {"saag_" + k: saag[k].float() for k in ("positions", "scales", "rotations", "colors", "opacities")}
+        return False, dict(saag_positions=torch.zeros(0, 3), saag_scales=torch.zeros(0, 3), saag_rotations=torch.zeros(0, 4),
+                           saag_colors=torch.zeros(0, 3), saag_opacities=torch.zeros(0))
+
+    def __getitem__(self, idx: int) -> Dict[str, torch.Tensor]:
+        name, image, features, depth = self._step_tensors(idx)
+        has_saag, cloud = self.saag_cloud(name)
+        item = {"image": image, "features": features, "depth": depth, "has_saag": has_saag, "name": name}
+        item.update(cloud)
         if self.load_vlm_density:
             item["vlm_density"], item["has_vlm_density"] = self.vlm_density(name)
         return item
@@ -92,13 +114,20 @@ class ImageDataset:
     def host_item(self, idx: int):
         """(image (3,S,S), features (37,37,C) patch-major as the decoder takes them, depth (1,S,S)[, density (1,S,S)]) on the host: what the
         training loop's prefetch threads load ahead of the step (fresnel_amd/train.py BatchPrefetcher)."""
-        name, image, features, depth = self._step_tensors(idx)  # (not self[idx]: the SAAG binaries are not part of a step)
+        name, image, features, depth = self._step_tensors(idx)  # (not self[idx]: the SAAG binaries are part of an --experiment 1 step only)
+        item = (image, features.permute(1, 2, 0).contiguous(), depth)
         if self.load_vlm_density:  # the fourth tensor of a --use_vlm_guidance step
-            return image, features.permute(1, 2, 0).contiguous(), depth, self.vlm_density(name)[0]
-        return image, features.permute(1, 2, 0).contiguous(), depth
+            item += (self.vlm_density(name)[0],)
+        if self.saag_tensors:  # load_saag: the five SAAG tensors behind them, empty where the image has no cloud
+            cloud = self.saag_cloud(name)[1]
+            item += tuple(cloud["saag_" + k] for k in ("positions", "scales", "rotations", "colors", "opacities"))
+        return item
 
     def batch(self, indices, device):
-        """(images (B,3,S,S), features (B,37,37,C) patch-major as the decoder takes them, depth (B,1,S,S)[, density (B,1,S,S)])."""
+        """(images (B,3,S,S), features (B,37,37,C) patch-major as the decoder takes them, depth (B,1,S,S)[, density (B,1,S,S)])
+        [, the five SAAG tensors: with load_saag, when every item has a cloud and all clouds have the same count]."""
+        if self.saag_tensors:
+            return tuple(t.to(device) for t in collate_host_items([self.host_item(i) for i in indices], self.saag_tensors))
         items = [self[i] for i in indices]
         images = torch.stack([it["image"] for it in items]).to(device)
         feats = torch.stack([it["features"].permute(1, 2, 0) for it in items]).to(device)

@@ -10,6 +10,10 @@ anywhere) or the fused HIP kernel pair of csrc/fgs_head.hip (head_backend "hip",
 same way; the two parts of its step that are not GEMMs are `nca_perceive` and `nca_update`: the reference's torch expressions
 (nca_backend "torch") or the HIP kernels of csrc/fgs_nca.hip (nca_backend "hip", CUDA/ROCm tensors only, no fallback).
 
+`SAAGRefinementNet` mirrors the reference's class of that name (GDM:424-570; --experiment 1) the same way; the two stages around
+its MLP are `saag_mlp_inputs` and `saag_refine_head`: the reference's torch expressions (backend "torch") or the HIP kernels of
+csrc/fgs_saag.hip (backend "hip", CUDA/ROCm tensors only, no fallback).
+
 `PatchGaussianDecoder` is the older stand-in: own definition with the interface, shapes and ranges of the reference's DirectPatchDecoder
 (scripts/models/gaussian_decoder_models.py:622-948): a 37x37 DINOv2 patch grid, K Gaussians per
 patch -> dict{positions (B,N,3), scales (B,N,3) in [1e-6,2], rotations (B,N,4) unit wxyz,
@@ -707,3 +711,211 @@ class NCAGaussianDecoder(nn.Module):
     def _parse_state(self, state: torch.Tensor) -> Dict[str, torch.Tensor]:
         """NCA:324-365 through the shared head: base_xy = 0 and xy_gain = 1 leave x, y as they are, z rides as base_z."""
         return gaussian_head(state.unsqueeze(2), self.zero_xy, state[..., 2], xy_gain=1.0, backend=self.head_backend)
+
+
+# =================================================================================================================================
+# The reference's SAAGRefinementNet (GDM:424-570, --experiment 1) and the two stages of it that are not GEMMs
+# =================================================================================================================================
+SAAG_BACKENDS = ("torch", "hip")
+SAAG_OUTPUTS = ("positions", "scales", "rotations", "colors", "opacities", "pos_delta", "scale_delta", "color_delta", "opacity_delta")
+_SAAG_NAMES = ("positions", "scales", "rotations", "colors", "opacities")
+
+
+def _check_saag_backend(backend):
+    if backend not in SAAG_BACKENDS:
+        raise ValueError(f"unknown saag backend {backend!r}: one of {SAAG_BACKENDS}")
+    return backend
+
+
+def _check_saag_cloud(positions, scales, rotations, colors, opacities):
+    if positions.dim() != 3 or positions.shape[-1] != 3:
+        raise ValueError(f"positions must be (B, N, 3), got {tuple(positions.shape)}")
+    Bn, N = positions.shape[:2]
+    for name, t, shape in (("scales", scales, (Bn, N, 3)), ("rotations", rotations, (Bn, N, 4)), ("colors", colors, (Bn, N, 3)),
+                           ("opacities", opacities, (Bn, N))):
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name} must be {shape}, got {tuple(t.shape)}")
+    return Bn, N
+
+
+def _refuse_grad(backend_of, tensors):
+    for name, t in tensors:
+        if t.requires_grad:
+            raise ValueError(f"{backend_of} (backend 'hip') produces no gradient for {name} (dataset data in the reference's "
+                             "training); use backend 'torch' to differentiate with respect to it")
+
+
+def _saag_quaternion_multiply(q1, q2):
+    """q1 (x) q2, (w, x, y, z) (GDM:555-570)."""
+    w1, x1, y1, z1 = q1[..., 0], q1[..., 1], q1[..., 2], q1[..., 3]
+    w2, x2, y2, z2 = q2[..., 0], q2[..., 1], q2[..., 2], q2[..., 3]
+    return torch.stack([w1 * w2 - x1 * x2 - y1 * y2 - z1 * z2, w1 * x2 + x1 * w2 + y1 * z2 - z1 * y2,
+                        w1 * y2 - x1 * z2 + y1 * w2 + z1 * x2, w1 * z2 + x1 * y2 - y1 * x2 + z1 * w2], dim=-1)
+
+
+def _saag_mlp_inputs_torch(features, positions, scales, rotations, colors, opacities):
+    """GDM:491-509 with FeatureInterpolator (GDM:396-417) as written there."""
+    pos_2d = positions[..., :2] / positions[..., 2:3].clamp(min=0.1)
+    pos_2d_norm = ((pos_2d + 2) / 4).clamp(0, 1)
+    grid = (pos_2d_norm * 2 - 1).unsqueeze(2)
+    sampled = F.grid_sample(features, grid, mode="bilinear", padding_mode="border", align_corners=False)  # (B, C, N, 1)
+    sampled = sampled.squeeze(-1).permute(0, 2, 1)
+    return torch.cat([sampled, positions, scales, rotations, colors, opacities.unsqueeze(-1)], dim=-1)
+
+
+def _saag_dims(Bn, N, C=1, H=1, W=1, strides=(1, 1, 1), residual_scale=0.0):
+    return B.FgsSaagDims(Bn, N, C, H, W, int(strides[0]), int(strides[1]), int(strides[2]), float(residual_scale))
+
+
+def _saag_mlp_inputs_hip(features, positions, scales, rotations, colors, opacities):
+    if not (features.is_cuda and positions.is_cuda):
+        raise B.FgsError("saag_mlp_inputs (backend 'hip') needs CUDA/ROCm tensors; there is no CPU fallback")
+    _refuse_grad("saag_mlp_inputs", (("features", features),) + tuple(zip(_SAAG_NAMES, (positions, scales, rotations, colors, opacities))))
+    lib = B.load()
+    Bn, C, H, W = features.shape
+    N = positions.shape[1]
+    feats = features.detach().float()
+    # the two layouts the kernel samples in place; strides come from the shape (torch leaves those of size-1 dimensions open)
+    if feats.permute(0, 2, 3, 1).is_contiguous():    # the training loop's (B, h, w, C) tensor seen channel-first
+        strides = (H * W * C, 1, W * C)
+    else:
+        feats = feats.contiguous()                   # (a no-op for a contiguous channel-first tensor)
+        strides = (C * H * W, H * W, W)
+    cloud = [_f32c(t) for t in (positions, scales, rotations, colors, opacities)]
+    d = _saag_dims(Bn, N, C, H, W, strides)
+    with torch.cuda.device(feats.device):
+        out = torch.empty((Bn, N, C + 14), dtype=torch.float32, device=feats.device)
+        B.check(lib.fgs_saag_inputs_forward(ctypes.byref(d), _ptr(feats), *[_ptr(t) for t in cloud], _ptr(out), _stream()),
+                "fgs_saag_inputs_forward")
+    return out
+
+
+def saag_mlp_inputs(features: torch.Tensor, positions: torch.Tensor, scales: torch.Tensor, rotations: torch.Tensor,
+                    colors: torch.Tensor, opacities: torch.Tensor, backend: str = "torch") -> torch.Tensor:
+    """The input of SAAGRefinementNet's MLP (GDM:489-509): features (B, C, H, W) sampled bilinearly at every SAAG Gaussian's
+    projected position, concatenated with the Gaussian's 14 parameters -> (B, N, C + 14), row = [C features | position 3 | scale 3 |
+    rotation 4 | colour 3 | opacity 1].  positions (B,N,3), scales (B,N,3), rotations (B,N,4), colors (B,N,3), opacities (B,N).
+    backend "torch": the reference's projection, grid_sample, permute and cat, any device, differentiable.  backend "hip":
+    csrc/fgs_saag.hip, one launch that writes the result once; CUDA/ROCm tensors only; a channel-last `features` view (the
+    training loop's (B, h, w, C) tensor permuted) and a contiguous channel-first tensor are sampled in place; forward only -- an
+    input that requires grad is refused (every input is dataset data in the reference's training)."""
+    _check_saag_backend(backend)
+    if features.dim() != 4:
+        raise ValueError(f"features must be (B, C, H, W), got {tuple(features.shape)}")
+    Bn, _ = _check_saag_cloud(positions, scales, rotations, colors, opacities)
+    if features.shape[0] != Bn:
+        raise ValueError(f"features hold {features.shape[0]} images, the SAAG cloud {Bn}")
+    args = (features, positions, scales, rotations, colors, opacities)
+    return _saag_mlp_inputs_hip(*args) if backend == "hip" else _saag_mlp_inputs_torch(*args)
+
+
+def _saag_refine_torch(raw, positions, scales, rotations, colors, opacities, gains, residual_scale):
+    """GDM:515-553 as written there; gains = (pos_scale, scale_scale, color_scale, opacity_scale)."""
+    pos_delta = raw[..., 0:3] * gains[0] * residual_scale
+    scale_delta = raw[..., 3:6] * gains[1] * residual_scale
+    color_delta = raw[..., 12:15] * gains[2] * residual_scale
+    opacity_delta = raw[..., 15:16] * gains[3] * residual_scale
+    rot = F.normalize(_saag_quaternion_multiply(rotation_6d_to_quaternion(raw[..., 6:12]), rotations), dim=-1)
+    return (positions + pos_delta, scales * torch.exp(scale_delta), rot, torch.clamp(colors + color_delta, 0, 1),
+            torch.clamp(opacities + opacity_delta.squeeze(-1), 0, 1), pos_delta, scale_delta, color_delta, opacity_delta)
+
+
+class _SaagRefineHip(torch.autograd.Function):
+    """fgs_saag_refine_forward / _backward.  Nothing but the inputs is saved: the backward recomputes from `raw`."""
+
+    @staticmethod
+    def forward(ctx, raw, gains, positions, scales, rotations, colors, opacities, residual_scale):
+        if not (raw.is_cuda and gains.is_cuda and positions.is_cuda):
+            raise B.FgsError("saag_refine_head (backend 'hip') needs CUDA/ROCm tensors; there is no CPU fallback")
+        lib = B.load()
+        dev = raw.device
+        Bn, N, _ = raw.shape
+        raw_, gains_ = _f32c(raw), _f32c(gains)
+        cloud = [_f32c(t) for t in (positions, scales, rotations, colors, opacities)]
+        d = _saag_dims(Bn, N, residual_scale=residual_scale)
+        with torch.cuda.device(dev):
+            outs = [torch.empty(s, dtype=torch.float32, device=dev) for s in
+                    ((Bn, N, 3), (Bn, N, 3), (Bn, N, 4), (Bn, N, 3), (Bn, N), (Bn, N, 3), (Bn, N, 3), (Bn, N, 3), (Bn, N, 1))]
+            B.check(lib.fgs_saag_refine_forward(ctypes.byref(d), _ptr(raw_), *[_ptr(t) for t in cloud], _ptr(gains_),
+                                                *[_ptr(t) for t in outs], _stream()), "fgs_saag_refine_forward")
+        ctx.dims = d
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(raw_, gains_, *cloud[1:])
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *g_outs):
+        lib = B.load()
+        raw_, gains_, scales_, rot_, colors_, opa_ = ctx.saved_tensors
+        d = ctx.dims
+        gs = [_f32c(g) for g in g_outs]
+        dev = raw_.device
+        with torch.cuda.device(dev):
+            nb = ctypes.c_size_t(0)
+            B.check(lib.fgs_saag_workspace_bytes(ctypes.byref(d), ctypes.byref(nb)), "fgs_saag_workspace_bytes")
+            g_raw = torch.empty_like(raw_)
+            g_gains = torch.empty((4,), dtype=torch.float32, device=dev)
+            scratch = torch.empty(nb.value, dtype=torch.uint8, device=dev)
+            B.check(lib.fgs_saag_refine_backward(ctypes.byref(d), _ptr(raw_), _ptr(scales_), _ptr(rot_), _ptr(colors_), _ptr(opa_),
+                                                 _ptr(gains_), *[_ptr(g) for g in gs], _ptr(g_raw), _ptr(g_gains), _ptr(scratch),
+                                                 _stream()), "fgs_saag_refine_backward")
+        return (g_raw, g_gains, None, None, None, None, None, None)
+
+
+def saag_refine_head(raw: torch.Tensor, positions: torch.Tensor, scales: torch.Tensor, rotations: torch.Tensor,
+                     colors: torch.Tensor, opacities: torch.Tensor, gains: torch.Tensor, residual_scale: float = 0.1,
+                     backend: str = "torch") -> Dict[str, torch.Tensor]:
+    """The residual head of SAAGRefinementNet (GDM:515-553): the MLP's raw (B, N, 16) output [position 3 | scale 3 | rotation-6D 6 |
+    colour 3 | opacity 1] and the SAAG cloud -> the reference's nine-entry dict: positions = saag + pos_delta, scales = saag x
+    exp(scale_delta), rotations = normalize(q_delta (x) q_saag), colors / opacities = clamp(saag + delta, 0, 1), and the four
+    deltas = raw x gain x residual_scale that the loss regularises (opacity_delta is (B, N, 1)).  gains: 4 floats (pos_scale,
+    scale_scale, color_scale, opacity_scale) on raw's device.  Gradients flow to raw and gains.
+    backend "torch": the reference's expressions, any device (and differentiable in the SAAG tensors).  backend "hip":
+    csrc/fgs_saag.hip, one launch forward and two backward, bitwise repeatable, nothing read on the host; CUDA/ROCm tensors
+    only; a SAAG tensor that requires grad is refused."""
+    _check_saag_backend(backend)
+    if raw.dim() != 3 or raw.shape[-1] != 16:
+        raise ValueError(f"raw must be (B, N, 16), got {tuple(raw.shape)}")
+    if tuple(_check_saag_cloud(positions, scales, rotations, colors, opacities)) != tuple(raw.shape[:2]):
+        raise ValueError(f"raw is {tuple(raw.shape)}, the SAAG cloud {tuple(positions.shape[:2])}")
+    if tuple(gains.shape) != (4,):
+        raise ValueError(f"gains must be (4,): pos, scale, colour, opacity; got {tuple(gains.shape)}")
+    cloud = (positions, scales, rotations, colors, opacities)
+    if backend == "hip":
+        if not (raw.is_cuda and gains.is_cuda and positions.is_cuda):
+            raise B.FgsError("saag_refine_head (backend 'hip') needs CUDA/ROCm tensors; there is no CPU fallback")
+        _refuse_grad("saag_refine_head", tuple(zip(_SAAG_NAMES, cloud)))
+        outs = _SaagRefineHip.apply(raw, gains, *cloud, float(residual_scale))
+    else:
+        outs = _saag_refine_torch(raw, *cloud, gains, residual_scale)
+    return dict(zip(SAAG_OUTPUTS, outs))
+
+
+class SAAGRefinementNet(nn.Module):
+    """The reference's SAAGRefinementNet (GDM:424-570, --experiment 1): features sampled at every SAAG Gaussian and the Gaussian's
+    own parameters go through an MLP that predicts residuals; the output is SAAG plus the residuals, scaled by four learnable
+    gains and `residual_scale`.  Same constructor arguments and defaults, forward signature (image_size and intrinsics are
+    accepted and unused, as there), returned dict, state_dict keys (mlp.net.{0,3,6}.*, pos_scale, scale_scale, color_scale,
+    opacity_scale) and registration order.  `backend`: "torch" | "hip" for saag_mlp_inputs and saag_refine_head."""
+
+    def __init__(self, feature_dim: int = 384, hidden_dims=(256, 128), residual_scale: float = 0.1, dropout: float = 0.1,
+                 backend: str = "torch"):
+        super().__init__()
+        self.feature_dim, self.residual_scale = feature_dim, residual_scale
+        self.backend = _check_saag_backend(backend)
+        self.mlp = _MLP(feature_dim + 14, list(hidden_dims), 16, dropout)
+        self.pos_scale = nn.Parameter(torch.tensor(0.05))
+        self.scale_scale = nn.Parameter(torch.tensor(0.1))
+        self.color_scale = nn.Parameter(torch.tensor(0.1))
+        self.opacity_scale = nn.Parameter(torch.tensor(0.1))
+
+    def forward(self, features: torch.Tensor, saag_positions: torch.Tensor, saag_scales: torch.Tensor,
+                saag_rotations: torch.Tensor, saag_colors: torch.Tensor, saag_opacities: torch.Tensor,
+                image_size: Tuple[int, int] = (518, 518), intrinsics: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        cloud = (saag_positions, saag_scales, saag_rotations, saag_colors, saag_opacities)
+        inputs = saag_mlp_inputs(features, *cloud, backend=self.backend)
+        Bn, N, D = inputs.shape
+        raw = self.mlp(inputs.reshape(Bn * N, D)).reshape(Bn, N, 16)
+        # the four scalars as one device vector: the hip head reads them there, nothing goes through the host
+        gains = torch.stack([self.pos_scale, self.scale_scale, self.color_scale, self.opacity_scale])
+        return saag_refine_head(raw, *cloud, gains, residual_scale=self.residual_scale, backend=self.backend)

@@ -17,7 +17,11 @@ Kept from TGD (same flag names / defaults / behaviour):
                     DirectPatchDecoder / FibonacciPatchDecoder (its keys: --resume takes its checkpoints), constructed as at
                     TGD:1814-1840; --experiment 4 implies fibonacci; --head_backend hip runs their head as fused HIP kernels;
                     --experiment 5 implies nca: NCAGaussianDecoder (TGD:1841-1849; --nca_steps, --nca_neighbors, --nca_step_size),
-                    --nca_backend hip runs its neighbour perception and update as HIP kernels (csrc/fgs_nca.hip)
+                    --nca_backend hip runs its neighbour perception and update as HIP kernels (csrc/fgs_nca.hip);
+                    --experiment 1 implies saag: SAAGRefinementNet refines the dataset's SAAG clouds (`{name}_saag.bin`; a dummy
+                    cloud of 1000 Gaussians where a batch has none, TGD:1043-1067), the residual regulariser --residual_weight
+                    (TGD:932-939) joins the loss, --saag_backend hip runs its input gather and residual head as HIP kernels
+                    (csrc/fgs_saag.hip)
   renderer choice   TileBasedRenderer(res, res, use_phase_blending, phase_amplitude)   TGD:1898-1907;
                     --experiment 4 --use_phase_blending: FourierGaussianRenderer(res, res, 0.65, 0.55, 0.45)  TGD:1877-1890
   camera            fx = fy = 0.8*res, cx = cy = res/2, view = I                       TGD:1910-1917
@@ -70,8 +74,9 @@ from torch.optim.lr_scheduler import CosineAnnealingLR
 
 import numpy as np
 
-from .decoder import (HEAD_BACKENDS, NCA_BACKENDS, DirectPatchDecoder, FibonacciPatchDecoder, NCAGaussianDecoder,
-                      PatchGaussianDecoder)
+from .decoder import (HEAD_BACKENDS, NCA_BACKENDS, SAAG_BACKENDS, DirectPatchDecoder, FibonacciPatchDecoder, NCAGaussianDecoder,
+                      PatchGaussianDecoder, SAAGRefinementNet)
+from .data import collate_host_items
 from .dist import DPContext
 from .handoff import HFTSConfig, camera_for_batch, importance_subsample, sample_training_pose
 
@@ -149,6 +154,10 @@ class TrainingConfig:  # subset of TGD:97-162 that this path uses; same names an
     nca_neighbors: int = 6
     nca_backend: str = "torch"
     nca_step_size: float = 0.1
+    # "saag" (--experiment 1, TGD:1043-1067): backend of SAAGRefinementNet's input gather and residual head (torch: the
+    # reference's ops | hip: csrc/fgs_saag.hip) and the weight of the residual regulariser (TGD:120, 932-939)
+    saag_backend: str = "torch"
+    residual_weight: float = 0.01
     workspace: str = "worst"  # rasterizer workspaces: "worst" (sized for the radius cap) | "adaptive" (sized by the duplicates
                               # the previous steps needed, TileBasedRenderer(workspace="adaptive"); a step whose scene outgrew
                               # the capacity renders NaN and is dropped by the NaN/Inf skip, the next one has room)
@@ -234,7 +243,7 @@ class BatchPrefetcher:
                     if self.stop.is_set():
                         return
                     items = list(pool.map(self.data.host_item, idx))
-                    batch = tuple(torch.stack(t) for t in zip(*items))
+                    batch = collate_host_items(items, getattr(self.data, "saag_tensors", 0))
                     if self.pin:
                         batch = tuple(t.pin_memory() for t in batch)
                     if not self._put(batch):
@@ -299,7 +308,25 @@ def _ssim_term_fn(cfg: TrainingConfig):
     raise ValueError(f"unknown ssim_backend {cfg.ssim_backend!r}: one of {SSIM_BACKENDS}")
 
 
-def compute_losses(rendered, target, rendered_depth, target_depth, cfg: TrainingConfig, dp=None, vlm_density=None):
+RESIDUAL_KEYS = ("pos_delta", "scale_delta", "color_delta", "opacity_delta")
+SAAG_NAMES = ("positions", "scales", "rotations", "colors", "opacities")
+DUMMY_SAAG_POINTS = 1000
+
+
+def create_dummy_saag(batch_size: int, num_gaussians: int, device, generator: Optional[torch.Generator] = None):
+    """The stand-in cloud of the reference's training script (TGD:760-778) for a batch without SAAG binaries: positions
+    N(0, 0.5) with z moved to -2, scales 0.05, identity quaternions, uniform colours, opacity 0.8 -- drawn on `device` from
+    `generator` (the step's), in the reference's order (positions, then colours).  -> the five tensors in SAAG_NAMES order."""
+    positions = torch.randn(batch_size, num_gaussians, 3, device=device, generator=generator) * 0.5
+    positions[..., 2] -= 2
+    rotations = torch.zeros(batch_size, num_gaussians, 4, device=device)
+    rotations[..., 0] = 1
+    colors = torch.rand(batch_size, num_gaussians, 3, device=device, generator=generator)
+    return (positions, torch.full((batch_size, num_gaussians, 3), 0.05, device=device), rotations, colors,
+            torch.full((batch_size, num_gaussians), 0.8, device=device))
+
+
+def compute_losses(rendered, target, rendered_depth, target_depth, cfg: TrainingConfig, dp=None, vlm_density=None, residuals=None):
     """L1 + SSIM term + normalised depth L1 + zone-boundary term (TGD:875-953).  The SSIM term, cfg.ssim_weight * (1 - SSIM(clamp(rendered,
     0, 1), target)), comes from pytorch_msssim when that package is importable and is left out otherwise
     (cfg.ssim_backend "msssim", TGD:53-65), or from fresnel_amd.losses.ssim's HIP kernels (cfg.ssim_backend "hip", CUDA/ROCm
@@ -310,7 +337,9 @@ def compute_losses(rendered, target, rendered_depth, target_depth, cfg: Training
     L1, boundary and depth terms from fresnel_amd.losses.pixel_losses (CUDA/ROCm tensors only; under data parallelism two or
     three small sum all-reduces forward and none backward), "torch" from the expressions below.  Returns (total, terms):
     `terms` holds the individual losses as DETACHED 0-d DEVICE tensors -- nothing here
-    synchronises with the host (the reference's `.item()` per term, TGD:891-1001, would cost a device round trip each)."""
+    synchronises with the host (the reference's `.item()` per term, TGD:891-1001, would cost a device round trip each).
+    residuals (--experiment 1; None for every other step): the decoder's pos_delta / scale_delta / color_delta / opacity_delta;
+    cfg.residual_weight * sum_k mean|residuals[k]| is added and reported as terms["residual"] (TGD:932-939)."""
     d: Dict[str, torch.Tensor] = {}
     if cfg.pixel_loss_backend not in PIXEL_LOSS_BACKENDS:
         raise ValueError(f"unknown pixel_loss_backend {cfg.pixel_loss_backend!r}: one of {PIXEL_LOSS_BACKENDS}")
@@ -353,6 +382,10 @@ def compute_losses(rendered, target, rendered_depth, target_depth, cfg: Training
                        (target_depth - td_mean) / torch.clamp(td_std, min=1e-4))
         d["depth"] = dl.detach()
         total = total + cfg.depth_weight * dl
+    if residuals is not None:  # TGD:932-939
+        reg = sum(residuals[k].abs().mean() for k in RESIDUAL_KEYS if k in residuals)
+        d["residual"] = reg.detach()
+        total = total + cfg.residual_weight * reg
     if use_boundary:  # TGD:943-953
         if px is not None:
             bl = px["boundary"]
@@ -498,6 +531,10 @@ def train_step(model, renderer, camera, batch, optimizer, cfg: TrainingConfig, d
                hfts: Optional[HFTSConfig] = None, epoch: int = 0, train_res: Optional[int] = None,
                pose_rng: Optional[np.random.RandomState] = None, sample_gen: Optional[torch.Generator] = None):
     """One optimizer step on this rank's image shard, without a host synchronisation.  Returns a StepResult."""
+    saag = None
+    if cfg.decoder == "saag":  # the batch's SAAG clouds ride behind the step's tensors when every image has one (collate_host_items)
+        n_step = 4 if cfg.use_vlm_guidance else 3
+        batch, saag = batch[:n_step], (tuple(batch[n_step:]) if len(batch) == n_step + len(SAAG_NAMES) else None)
     if cfg.use_vlm_guidance:
         images, feats, depth, density = batch
     else:
@@ -510,7 +547,15 @@ def train_step(model, renderer, camera, batch, optimizer, cfg: TrainingConfig, d
     el_t = torch.full((feats.shape[0],), el, device=feats.device) if el is not None else None
     az_t = torch.full((feats.shape[0],), az, device=feats.device) if az is not None else None
     mirror = cfg.decoder != "standin"  # the reference's decoders take channel-first features (TGD:1100) and emit (B,N,3) radians
-    out = model(feats.permute(0, 3, 1, 2) if mirror else feats, depth, num_gaussians=num_gaussians, elevation=el_t, azimuth=az_t)
+    residuals = None
+    if cfg.decoder == "saag":  # TGD:1043-1067: frontal camera, no progressive K, no pose arguments
+        el = az = None
+        if saag is None:
+            saag = create_dummy_saag(feats.shape[0], DUMMY_SAAG_POINTS, feats.device, generator=sample_gen)
+        out = model(feats.permute(0, 3, 1, 2), *saag)  # (a view: the hip backend samples the patch-major tensor in place)
+        residuals = {k: out.pop(k) for k in RESIDUAL_KEYS}  # taken before any subsampling (TGD:1067 against :1154)
+    else:
+        out = model(feats.permute(0, 3, 1, 2) if mirror else feats, depth, num_gaussians=num_gaussians, elevation=el_t, azimuth=az_t)
     out.pop("edge_strength", None)
     if not (cfg.use_phase_blending or cfg.use_wave_rendering):
         out.pop("phases", None)
@@ -528,7 +573,7 @@ def train_step(model, renderer, camera, batch, optimizer, cfg: TrainingConfig, d
                                 out["opacities"], render_camera, return_depth=True, phases=phases)
     target = F.interpolate(images, size=(res, res), mode="bilinear", align_corners=False)
     tdepth = F.interpolate(depth, size=(res, res), mode="bilinear", align_corners=False).squeeze(1)
-    loss, terms = compute_losses(rendered, target, rdepth, tdepth, cfg, dp, vlm_density=density)
+    loss, terms = compute_losses(rendered, target, rdepth, tdepth, cfg, dp, vlm_density=density, residuals=residuals)
     # NaN/Inf batch skip (TGD:1255-1258), decided on the device and by ALL ranks together: the flag and the loss ride
     # behind the gradients in the one all-reduce of the step
     bad = (~torch.isfinite(loss.detach())).float()
@@ -550,12 +595,12 @@ def train_step(model, renderer, camera, batch, optimizer, cfg: TrainingConfig, d
     return StepResult(terms, skipped)
 
 
-DECODERS = ("standin", "direct", "fibonacci", "nca")
+DECODERS = ("standin", "direct", "fibonacci", "nca", "saag")
 
 
 def make_decoder(cfg: TrainingConfig):
     """The step's decoder: the stand-in (default), or a mirror of the reference's class constructed as its training script
-    constructs it (TGD:1814-1828 experiment 2, TGD:1832-1840 experiment 4, TGD:1842-1849 experiment 5)."""
+    constructs it (TGD:1814-1828 experiment 2, TGD:1832-1840 experiment 4, TGD:1842-1849 experiment 5, TGD:1786 experiment 1)."""
     phase_out = cfg.use_phase_blending or cfg.use_wave_rendering
     if cfg.decoder == "standin":
         return PatchGaussianDecoder(cfg.feature_dim, cfg.gaussians_per_patch, grid=cfg.feature_size,
@@ -564,6 +609,10 @@ def make_decoder(cfg: TrainingConfig):
                                     use_phase_output=phase_out,
                                     use_edge_aware=cfg.use_edge_aware, edge_scale_factor=cfg.edge_scale_factor,
                                     edge_opacity_boost=cfg.edge_opacity_boost)
+    if cfg.decoder == "saag":
+        if cfg.saag_backend not in SAAG_BACKENDS:
+            raise ValueError(f"unknown saag_backend {cfg.saag_backend!r}: one of {SAAG_BACKENDS}")
+        return SAAGRefinementNet(feature_dim=cfg.feature_dim, backend=cfg.saag_backend)  # (the class's defaults, as TGD:1786)
     if cfg.head_backend not in HEAD_BACKENDS:
         raise ValueError(f"unknown head_backend {cfg.head_backend!r}: one of {HEAD_BACKENDS}")
     if cfg.decoder == "direct":
@@ -620,7 +669,7 @@ def make_dataset(cfg: TrainingConfig, log=print):
     if cfg.data_dir and os.path.isdir(cfg.data_dir):
         from .data import ImageDataset
         ds = ImageDataset(cfg.data_dir, cfg.image_size, max_images=cfg.max_images, feature_dim=cfg.feature_dim,
-                          load_vlm_density=cfg.use_vlm_guidance)
+                          load_vlm_density=cfg.use_vlm_guidance, load_saag=cfg.decoder == "saag")
         if len(ds) > 0:
             if ds[0]["features"].shape[-1] != cfg.feature_size:
                 raise ValueError(f"feature caches are 37x37 patch grids; got feature_size={cfg.feature_size}")
@@ -689,6 +738,11 @@ def run_training(cfg: TrainingConfig, dp: Optional[DPContext] = None,
         raise ValueError("head_backend 'hip' needs a GPU device: the HIP head kernels have no CPU fallback")
     if cfg.decoder == "nca" and cfg.nca_backend == "hip" and device.type != "cuda":
         raise ValueError("nca_backend 'hip' needs a GPU device: the HIP perception / update kernels have no CPU fallback")
+    if cfg.decoder == "saag" and cfg.saag_backend == "hip" and device.type != "cuda":
+        raise ValueError("saag_backend 'hip' needs a GPU device: the HIP input / refinement kernels have no CPU fallback")
+    if cfg.decoder == "saag" and cfg.hip_graph:
+        raise ValueError("--experiment 1 cannot be combined with --hip_graph: the size of the SAAG cloud follows the files, so "
+                         "the step's shapes change from batch to batch")
     model = make_decoder(cfg).to(device)
     dp.broadcast_parameters(model)
     train_res = hfts.get_effective_train_resolution(cfg.image_size) if hfts is not None else cfg.image_size
@@ -860,20 +914,34 @@ def arg_parser() -> argparse.ArgumentParser:
     ap.add_argument("--nca_neighbors", type=int, default=c.nca_neighbors, help="k nearest neighbours every point perceives (TGD:1437)")
     ap.add_argument("--nca_step_size", type=float, default=c.nca_step_size,
                     help="initial value of the learnable step size (the reference parses this flag, TGD:1439, and never uses it)")
+    ap.add_argument("--saag_backend", default=c.saag_backend, choices=list(SAAG_BACKENDS),
+                    help="input gather and residual head of --experiment 1: the reference's torch ops (default) or the fused HIP kernels")
+    ap.add_argument("--residual_weight", type=float, default=c.residual_weight,
+                    help="weight of the residual regulariser of --experiment 1 (TGD:120)")
     ap.add_argument("--nca_backend", default=c.nca_backend, choices=list(NCA_BACKENDS),
                     help="neighbour perception and update of --experiment 5: the reference's torch ops (default) or the fused HIP kernels")
     return ap
 
 
 def config_from_args(a) -> TrainingConfig:
-    """The TrainingConfig of a parsed command line (no device yet).  --experiment 2 trains a patch-grid decoder, --experiment 4
-    the Fibonacci decoder (TGD:1829-1841), with --use_phase_blending through the Fourier renderer (TGD:1877-1890), --experiment 5
-    the NCA decoder (TGD:1841-1849) through the TileBasedRenderer; the reference's other experiments have no counterpart here."""
-    if a.experiment not in (2, 4, 5):
-        raise SystemExit("only --experiment 2 (patch-grid decoder), --experiment 4 (Fibonacci decoder) and --experiment 5 (NCA "
-                         "decoder) are on this repo's hot path")
+    """The TrainingConfig of a parsed command line (no device yet).  --experiment 1 trains the SAAG refinement net
+    (TGD:1043-1067), --experiment 2 a patch-grid decoder, --experiment 4 the Fibonacci decoder (TGD:1829-1841), with
+    --use_phase_blending through the Fourier renderer (TGD:1877-1890), --experiment 5 the NCA decoder (TGD:1841-1849) through the
+    TileBasedRenderer; the reference's experiment 3 has no counterpart here."""
+    if a.experiment not in (1, 2, 4, 5):
+        raise SystemExit("only --experiment 1 (SAAG refinement), --experiment 2 (patch-grid decoder), --experiment 4 (Fibonacci "
+                         "decoder) and --experiment 5 (NCA decoder) are on this repo's hot path")
     decoder = a.decoder
-    if a.experiment == 4:
+    if a.experiment == 1:
+        if decoder in ("direct", "fibonacci", "nca"):
+            raise SystemExit(f"--experiment 1 trains the SAAG refinement net: --decoder {decoder} contradicts it")
+        if a.hip_graph:
+            raise SystemExit("--experiment 1 cannot be combined with --hip_graph: the size of the SAAG cloud follows the files, "
+                             "so the step's shapes change from batch to batch")
+        decoder = "saag"
+    elif decoder == "saag":
+        raise SystemExit("--decoder saag is --experiment 1")
+    elif a.experiment == 4:
         if decoder in ("direct", "nca"):
             raise SystemExit(f"--experiment 4 trains the Fibonacci decoder: --decoder {decoder} contradicts it")
         decoder = "fibonacci"
@@ -906,7 +974,7 @@ def config_from_args(a) -> TrainingConfig:
                           pixel_loss_backend=a.pixel_loss_backend, workspace=a.workspace,
                           decoder=decoder, head_backend=a.head_backend, n_spiral_points=a.n_spiral_points,
                           nca_steps=a.nca_steps, nca_neighbors=a.nca_neighbors, nca_backend=a.nca_backend,
-                          nca_step_size=a.nca_step_size)
+                          nca_step_size=a.nca_step_size, saag_backend=a.saag_backend, residual_weight=a.residual_weight)
 
 
 def main(argv=None):
@@ -925,7 +993,7 @@ def main(argv=None):
                       stochastic_k=a.stochastic_k, fast_mode=a.fast_mode)
     dp = DPContext(device=torch.device(cfg.device))
     try:
-        run_training(cfg, dp, resume=a.resume, hfts=hfts if hfts.enabled else None)
+        return run_training(cfg, dp, resume=a.resume, hfts=hfts if hfts.enabled else None)  # (model, per-epoch losses)
     finally:
         dp.shutdown()
 

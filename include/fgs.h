@@ -506,6 +506,54 @@ int fgs_nca_update_backward(const FgsNcaDims *dims, const float *delta, const fl
                             void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The two stages of the reference's SAAGRefinementNet (scripts/models/gaussian_decoder_models.py, GDM:424-570; --experiment 1)
+ * that are not GEMMs.  All tensors fp32, DEVICE; everything but `features` contiguous.
+ *   SAAG cloud   positions (B,N,3), scales (B,N,3), rotations (B,N,4) w,x,y,z (not necessarily unit), colors (B,N,3),
+ *                opacities (B,N)
+ *   features     (B, C, grid_h, grid_w) addressed by element strides: feat_stride_batch, feat_stride_channel, feat_stride_row; the
+ *                column stride is C when feat_stride_channel = 1 (channel-last memory, the (B, h, w, C) tensor of the training loop
+ *                seen through permute(0, 3, 1, 2): sampled in place, no copy) and 1 otherwise (channel-first memory: the same
+ *                kernel with these strides -- 4-byte gathers a plane apart instead of coalesced rows, no workspace, bit-equal
+ *                results).  Rows, planes and images may be padded, not overlapping.
+ * fgs_saag_inputs_forward:  mlp_inputs (B, N, C + 14), row = [C sampled features | position 3 | scale 3 | rotation 4 | colour 3 |
+ *     opacity 1].  Sampling (GDM:491-496 + F.grid_sample(bilinear, padding_mode='border', align_corners=False)):
+ *     u = clamp((x / max(z, 0.1) + 2) / 4, 0, 1), v likewise from y; ix = clip(u grid_w - 0.5, 0, grid_w - 1), iy likewise with
+ *     grid_h; x0 = floor(ix), weights (x0 + 1 - ix, ix - x0) x (y0 + 1 - iy, iy - y0), summed in the order (x0,y0), (x0+1,y0),
+ *     (x0,y0+1), (x0+1,y0+1).  A corner outside the grid (index grid_w or grid_h, reached at ix = grid_w - 1) contributes nothing
+ *     and is NOT READ.  Forward only: every input is dataset data.
+ * fgs_saag_refine_forward:  raw (B,N,16) = [position 3 | scale 3 | rotation-6D 6 | colour 3 | opacity 1], gains = 4 DEVICE floats
+ *     (pos, scale, colour, opacity: nothing is read on the host, the call is capturable), rs = residual_scale (GDM:515-540):
+ *       pos_delta = raw gain rs, positions = saag + pos_delta;     scale_delta likewise, scales = saag exp(scale_delta)
+ *       rotations = normalize(q_delta (x) q_saag), q_delta = the head's rotation_6d_to_quaternion (with its +1e-8), (x) the
+ *                   Hamilton product (GDM:555-570), normalize = p / max(|p|, 1e-12)
+ *       color_delta likewise, colors = clamp(saag + color_delta, 0, 1);   opacity_delta (B,N,1), opacities (B,N) likewise
+ * fgs_saag_refine_backward: recomputes the forward from raw (nothing is saved); the clamps pass the gradient on the closed
+ *     interval [0, 1]; only the selected quaternion branch is differentiated.  Each of the nine upstream gradients may be NULL
+ *     (= 0).  g_raw (B,N,16): every element written.  g_gains[4] = sums over B N 3 (or B N) products of two floats, exact in
+ *     double, added in a fixed order (fixed grid, fixed-shape block tree, block partials in block order from `scratch` of
+ *     fgs_saag_workspace_bytes), times rs, rounded to fp32 once.  No atomics: two calls agree to the bit.  scratch is written,
+ *     never read before it is written.  No gradient for the SAAG tensors.
+ * Shapes: B, N, C, grid_h, grid_w >= 1, B <= 65535, B N (C + 14) < 2^31; otherwise FGS_EINVAL (bad dims or strides, null
+ * pointers) / FGS_EUNSUPPORTED before anything touches the device.  The refine entries ignore C's grid and strides. */
+typedef struct FgsSaagDims {
+    int32_t batch, points, channels, grid_h, grid_w;
+    int64_t feat_stride_batch, feat_stride_channel, feat_stride_row;   /* in elements */
+    float residual_scale;
+} FgsSaagDims;
+int fgs_saag_workspace_bytes(const FgsSaagDims *dims, size_t *scratch_bytes);
+int fgs_saag_inputs_forward(const FgsSaagDims *dims, const float *features, const float *positions, const float *scales,
+                            const float *rotations, const float *colors, const float *opacities, float *mlp_inputs, void *stream);
+int fgs_saag_refine_forward(const FgsSaagDims *dims, const float *raw, const float *positions, const float *scales,
+                            const float *rotations, const float *colors, const float *opacities, const float *gains,
+                            float *o_positions, float *o_scales, float *o_rotations, float *o_colors, float *o_opacities,
+                            float *pos_delta, float *scale_delta, float *color_delta, float *opacity_delta, void *stream);
+int fgs_saag_refine_backward(const FgsSaagDims *dims, const float *raw, const float *scales, const float *rotations,
+                             const float *colors, const float *opacities, const float *gains, const float *g_positions,
+                             const float *g_scales, const float *g_rotations, const float *g_colors, const float *g_opacities,
+                             const float *g_pos_delta, const float *g_scale_delta, const float *g_color_delta,
+                             const float *g_opacity_delta, float *g_raw, float *g_gains, void *scratch, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Importance-subsampling hand-off between decoder and rasterizer (--stochastic_k; reference
  * scripts/training/train_gaussian_decoder.py:1160-1187): the n_out Gaussians whose indices torch.multinomial
  * drew (DEVICE int64 (n_out,), unique, shared by the batch) are gathered out of every (B, n_in, .) tensor into
