@@ -30,6 +30,7 @@ EXPORTED_SYMBOLS = [
     "fgs_nca_workspace_bytes", "fgs_nca_perceive_forward", "fgs_nca_perceive_backward", "fgs_nca_update_forward",
     "fgs_nca_update_backward",
     "fgs_saag_workspace_bytes", "fgs_saag_inputs_forward", "fgs_saag_refine_forward", "fgs_saag_refine_backward",
+    "fgs_physics_workspace_bytes", "fgs_physics_forward", "fgs_physics_backward",
 ]
 
 STAGES = ["project", "depth_sort", "dup_emit", "tile_sort", "tile_ranges", "composite_fwd",
@@ -131,6 +132,15 @@ class FgsSaagDims(ctypes.Structure):
                 ("feat_stride_row", ctypes.c_int64), ("residual_scale", ctypes.c_float)]
 
 
+class FgsPhysicsDims(ctypes.Structure):
+    _fields_ = [("batch", ctypes.c_int32), ("points", ctypes.c_int32), ("k_full", ctypes.c_int32), ("k_used", ctypes.c_int32),
+                ("xy_gain", ctypes.c_float), ("focal_depth", ctypes.c_float),
+                ("wavelength_min", ctypes.c_float), ("wavelength_max", ctypes.c_float)]
+
+
+FGS_PHYSICS_RANGE_BYTES = 16  # float z_min, z_max; int32 n_min, n_max (include/fgs.h)
+
+
 class FgsError(RuntimeError):
     pass
 
@@ -226,6 +236,12 @@ def load():
     lib.fgs_saag_refine_backward.argtypes = [sd] + [vp] * 19
     for fn in (lib.fgs_saag_workspace_bytes, lib.fgs_saag_inputs_forward, lib.fgs_saag_refine_forward,
                lib.fgs_saag_refine_backward):
+        fn.restype = ctypes.c_int
+    phd = cp(FgsPhysicsDims)
+    lib.fgs_physics_workspace_bytes.argtypes = [phd, cp(ctypes.c_size_t)]
+    lib.fgs_physics_forward.argtypes = [phd] + [vp] * 13
+    lib.fgs_physics_backward.argtypes = [phd] + [vp] * 15
+    for fn in (lib.fgs_physics_workspace_bytes, lib.fgs_physics_forward, lib.fgs_physics_backward):
         fn.restype = ctypes.c_int
     for fn in (lib.fgs_asm_propagate_workspace_bytes, lib.fgs_asm_propagate_forward, lib.fgs_asm_propagate_backward,
                lib.fgs_spectral_workspace_bytes, lib.fgs_spectral_loss_forward, lib.fgs_spectral_loss_backward,

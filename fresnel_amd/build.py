@@ -69,6 +69,9 @@ SOURCES = {
     # as the head: the backward recomputes the forward (clamp gates, quaternion branch), and the deltas are DEFINED as
     # (raw gain) residual_scale with both products rounded (include/fgs.h)
     "fgs_saag.hip": ["-ffp-contract=off"],
+    # as the head (the backward recomputes the forward); and the z_norm / phase chain is DEFINED with every operation rounded on its
+    # own and an IEEE divide (include/fgs.h): the wrapped phase of an unwrapped value up to 314 is torch's fp32 result bit for bit
+    "fgs_physics.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
 }
 LINK_LIBS = ["-lhipfft"]
 

@@ -14,6 +14,10 @@ same way; the two parts of its step that are not GEMMs are `nca_perceive` and `n
 its MLP are `saag_mlp_inputs` and `saag_refine_head`: the reference's torch expressions (backend "torch") or the HIP kernels of
 csrc/fgs_saag.hip (backend "hip", CUDA/ROCm tensors only, no fallback).
 
+`PhysicsDirectPatchDecoder` mirrors the reference's class of that name (GDM:955-1147; --use_wave_rendering without --use_qsr) the
+same way, with `PhysicsFresnelZones` (scripts/utils/fresnel_zones.py:400-614) beside it; its head is `physics_head`: the reference's
+torch expressions (backend "torch") or the HIP kernels of csrc/fgs_physics.hip (backend "hip", CUDA/ROCm tensors only, no fallback).
+
 `PatchGaussianDecoder` is the older stand-in: own definition with the interface, shapes and ranges of the reference's DirectPatchDecoder
 (scripts/models/gaussian_decoder_models.py:622-948): a 37x37 DINOv2 patch grid, K Gaussians per
 patch -> dict{positions (B,N,3), scales (B,N,3) in [1e-6,2], rotations (B,N,4) unit wxyz,
@@ -919,3 +923,211 @@ class SAAGRefinementNet(nn.Module):
         # the four scalars as one device vector: the hip head reads them there, nothing goes through the host
         gains = torch.stack([self.pos_scale, self.scale_scale, self.color_scale, self.opacity_scale])
         return saag_refine_head(raw, *cloud, gains, residual_scale=self.residual_scale, backend=self.backend)
+
+
+# =================================================================================================================================
+# The reference's PhysicsDirectPatchDecoder (GDM:955-1147) with PhysicsFresnelZones (scripts/utils/fresnel_zones.py, "FZ": 400-614)
+# =================================================================================================================================
+class PhysicsFresnelZones(nn.Module):
+    """The reference's PhysicsFresnelZones (FZ:400-614): phase from the optical path difference, phi = (2 pi / lambda) |depth -
+    focal_depth|, and zone boundaries r_n = sqrt(n lambda f) normalised to [0, 1].  lambda = clamp(|_wavelength_raw|,
+    wavelength_min, wavelength_max); `_wavelength_raw` is a parameter (learnable_wavelength) or a buffer.  Same constructor
+    arguments and defaults, methods and state-dict key."""
+
+    def __init__(self, num_zones: int = 8, wavelength: float = 0.05, focal_depth: float = 0.5, learnable_wavelength: bool = True,
+                 wavelength_min: float = 0.01, wavelength_max: float = 0.5):
+        super().__init__()
+        self.num_zones, self.focal_depth = num_zones, focal_depth
+        self.wavelength_min, self.wavelength_max = wavelength_min, wavelength_max
+        if learnable_wavelength:
+            self._wavelength_raw = nn.Parameter(torch.tensor(wavelength))
+        else:
+            self.register_buffer("_wavelength_raw", torch.tensor(wavelength))
+        self.learnable_wavelength = learnable_wavelength
+
+    @property
+    def wavelength(self) -> torch.Tensor:
+        return torch.clamp(torch.abs(self._wavelength_raw), self.wavelength_min, self.wavelength_max)
+
+    def compute_zone_boundaries(self, device=None) -> torch.Tensor:
+        """(num_zones + 1,) boundaries in [0, 1]: sqrt(n lambda f) over its last value (+ 1e-8)."""
+        device = self._wavelength_raw.device if device is None else device
+        n = torch.arange(self.num_zones + 1, device=device, dtype=torch.float32)
+        r = torch.sqrt(n * self.wavelength * self.focal_depth)
+        return r / (r[-1] + 1e-8)
+
+    def get_zone_index(self, depth: torch.Tensor) -> torch.Tensor:
+        idx = torch.bucketize(depth, self.compute_zone_boundaries(depth.device)[1:-1])
+        return torch.clamp(idx, 0, self.num_zones - 1)
+
+    def get_zone_phase(self, zone_idx: torch.Tensor) -> torch.Tensor:
+        """Alternating 0, pi, 0, ..."""
+        return (zone_idx % 2).float() * torch.pi
+
+    def compute_path_difference(self, depth: torch.Tensor) -> torch.Tensor:
+        return torch.abs(depth - self.focal_depth)
+
+    def depth_to_phase(self, depth: torch.Tensor) -> torch.Tensor:
+        """Unwrapped phase in radians."""
+        return (2 * torch.pi / self.wavelength) * self.compute_path_difference(depth)
+
+    def forward(self, depth: torch.Tensor, return_all: bool = False):
+        phase = self.depth_to_phase(depth)
+        if not return_all:
+            return phase
+        zone_idx = self.get_zone_index(depth)
+        return {"phase": phase, "zone_idx": zone_idx, "zone_phase": self.get_zone_phase(zone_idx),
+                "path_difference": self.compute_path_difference(depth), "boundaries": self.compute_zone_boundaries(depth.device),
+                "wavelength": self.wavelength}
+
+    def extra_repr(self) -> str:
+        return (f"num_zones={self.num_zones}, wavelength={self.wavelength.item():.4f}, focal_depth={self.focal_depth}, "
+                f"learnable={self.learnable_wavelength}")
+
+
+class FresnelIntegralTables(nn.Module):
+    """What the reference's FresnelDiffraction (FZ:828-903) adds to a PhysicsDirectPatchDecoder: three 1000-element buffers -- the
+    sample points w in [0, 5] and running sums of cos(pi t^2 / 2) dt, sin(pi t^2 / 2) dt, the Fresnel integrals C(w), S(w).  The
+    decoder constructs the module and never calls it (GDM:1027-1030), so only the buffers are mirrored; they
+    exist so that checkpoints load strictly."""
+
+    def __init__(self, wavelength: float = 0.05, lut_size: int = 1000, lut_max_w: float = 5.0):
+        super().__init__()
+        self.wavelength, self.lut_size, self.lut_max_w = wavelength, lut_size, lut_max_w
+        w = torch.linspace(0, lut_max_w, lut_size)
+        dt = w[1] - w[0]
+        self.register_buffer("_w_lut", w)
+        self.register_buffer("_C_lut", torch.cumsum(torch.cos(torch.pi * w ** 2 / 2), dim=0) * dt)
+        self.register_buffer("_S_lut", torch.cumsum(torch.sin(torch.pi * w ** 2 / 2), dim=0) * dt)
+
+
+def _physics_head_torch(raw, base_xy, base_z, wavelength_raw, K, focal_depth, wavelength_min, wavelength_max, xy_gain):
+    """The head in torch ops, expression by expression as GDM:1085-1126 and FZ:463-467, 553, 569-573."""
+    Bn, P = raw.shape[:2]
+    o = raw[:, :, :K, :]
+    z = base_z.view(Bn, P, 1).expand(Bn, P, K)
+    positions = torch.stack([base_xy[:, 0].view(1, P, 1) + o[..., 0] * xy_gain, base_xy[:, 1].view(1, P, 1) + o[..., 1] * xy_gain, z],
+                            dim=-1)
+    scales = F.softplus(o[..., 3:6] + 1.0) * 0.15
+    rotations = rotation_6d_to_quaternion(o[..., 6:12])
+    colors = torch.sigmoid(o[..., 12:15])
+    opacities = torch.sigmoid(o[..., 15])
+    z_min, z_max = z.min(), z.max()
+    z_normalized = (z - z_min) / (z_max - z_min + 1e-8)
+    wavelength = torch.clamp(torch.abs(wavelength_raw), wavelength_min, wavelength_max)
+    phases = ((2 * torch.pi / wavelength) * torch.abs(z_normalized - focal_depth)) % (2 * torch.pi)
+    N = P * K
+    return (positions.reshape(Bn, N, 3), scales.reshape(Bn, N, 3), rotations.reshape(Bn, N, 4), colors.reshape(Bn, N, 3),
+            opacities.reshape(Bn, N), phases.reshape(Bn, N))
+
+
+class _PhysicsHeadHip(torch.autograd.Function):
+    """fgs_physics_forward / fgs_physics_backward.  Saved: the inputs and the 16 bytes of the range stage; the backward recomputes
+    from `raw`.  The wavelength is read on the device: nothing synchronises with the host."""
+
+    @staticmethod
+    def forward(ctx, raw, base_xy, base_z, wavelength_raw, K, focal_depth, wavelength_min, wavelength_max, xy_gain):
+        if not (raw.is_cuda and base_z.is_cuda and wavelength_raw.is_cuda):
+            raise B.FgsError("physics_head (backend 'hip') needs CUDA/ROCm tensors; there is no CPU fallback")
+        lib = B.load()
+        dev = raw.device
+        Bn, P, KF, _ = raw.shape
+        d = B.FgsPhysicsDims(Bn, P, KF, int(K), float(xy_gain), float(focal_depth), float(wavelength_min), float(wavelength_max))
+        raw_, xy_, z_, wl_ = (_f32c(t) for t in (raw, base_xy, base_z, wavelength_raw))
+        N = P * int(K)
+        with torch.cuda.device(dev):
+            nb = ctypes.c_size_t(0)
+            B.check(lib.fgs_physics_workspace_bytes(ctypes.byref(d), ctypes.byref(nb)), "fgs_physics_workspace_bytes")
+            outs = [torch.empty((Bn, N, w) if w else (Bn, N), dtype=torch.float32, device=dev) for w in (3, 3, 4, 3, 0, 0)]
+            rng = torch.empty(B.FGS_PHYSICS_RANGE_BYTES, dtype=torch.uint8, device=dev)
+            scratch = torch.empty(nb.value, dtype=torch.uint8, device=dev)
+            B.check(lib.fgs_physics_forward(ctypes.byref(d), _ptr(raw_), _ptr(xy_), _ptr(z_), _ptr(wl_), *[_ptr(t) for t in outs],
+                                            _ptr(rng), _ptr(scratch), _stream()), "fgs_physics_forward")
+        ctx.dims, ctx.scratch_bytes = d, nb.value
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(raw_, z_, wl_, rng)
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *g_outs):
+        lib = B.load()
+        raw_, z_, wl_, rng = ctx.saved_tensors
+        d = ctx.dims
+        gs = [_f32c(g) for g in g_outs]
+        dev = raw_.device
+        with torch.cuda.device(dev):
+            g_raw = torch.empty_like(raw_)
+            g_z = torch.empty((d.batch, d.points), dtype=torch.float32, device=dev) if ctx.needs_input_grad[2] else None
+            g_wl = torch.empty((), dtype=torch.float32, device=dev) if ctx.needs_input_grad[3] else None
+            scratch = torch.empty(ctx.scratch_bytes, dtype=torch.uint8, device=dev)
+            B.check(lib.fgs_physics_backward(ctypes.byref(d), _ptr(raw_), _ptr(z_), _ptr(wl_), _ptr(rng), *[_ptr(g) for g in gs],
+                                             _ptr(g_raw), _ptr(g_z), _ptr(g_wl), _ptr(scratch), _stream()), "fgs_physics_backward")
+        return (g_raw, None, g_z, g_wl, None, None, None, None, None)
+
+
+def physics_head(raw: torch.Tensor, base_xy: torch.Tensor, base_z: torch.Tensor, wavelength_raw: torch.Tensor, *,
+                 num_gaussians: Optional[int] = None, focal_depth: float = 0.5, wavelength_min: float = 0.01,
+                 wavelength_max: float = 0.5, xy_gain: float = 0.25, backend: str = "torch") -> Dict[str, torch.Tensor]:
+    """The head of the reference's PhysicsDirectPatchDecoder (GDM:1071-1147): the MLP's raw (B, P, K_full, 16) output -> the wave
+    renderer's inputs, N = P x K with K = min(num_gaussians, K_full): positions (B,N,3), scales (B,N,3) = softplus(raw + 1) 0.15
+    (no clamps), rotations (B,N,4), colors (B,N,3), opacities (B,N) and phases (B,N) in radians in [0, 2 pi]: (2 pi / lambda) |u -
+    focal_depth| mod 2 pi with u = (z - z_min) / (z_max - z_min + 1e-8) over the WHOLE batch and lambda = clamp(|wavelength_raw|,
+    wavelength_min, wavelength_max).  base_xy (P,2): grid coordinates; base_z (B,P): depth_offset - 2 depth; wavelength_raw: a
+    0-dim tensor on raw's device.  Gradients flow to raw, base_z (through the position, through u, and in equal shares through the
+    minimum and maximum to every element that holds them) and wavelength_raw.
+    backend "torch": the reference's expressions, any device.  backend "hip": csrc/fgs_physics.hip, two launches forward and
+    three backward, bitwise repeatable, nothing read on the host (capturable); CUDA/ROCm tensors only."""
+    if backend not in HEAD_BACKENDS:
+        raise ValueError(f"unknown head backend {backend!r}: one of {HEAD_BACKENDS}")
+    if raw.dim() != 4 or raw.shape[-1] != 16:
+        raise ValueError(f"raw must be (B, P, K_full, 16), got {tuple(raw.shape)}")
+    Bn, P, KF, _ = raw.shape
+    K = KF if num_gaussians is None else max(1, min(int(num_gaussians), KF))
+    if tuple(base_xy.shape) != (P, 2) or tuple(base_z.shape) != (Bn, P):
+        raise ValueError(f"base_xy must be ({P}, 2) and base_z ({Bn}, {P}), got {tuple(base_xy.shape)} and {tuple(base_z.shape)}")
+    if wavelength_raw.numel() != 1:
+        raise ValueError(f"wavelength_raw must hold one value, got {tuple(wavelength_raw.shape)}")
+    args = (raw, base_xy, base_z, wavelength_raw.reshape(()), K, focal_depth, wavelength_min, wavelength_max, xy_gain)
+    outs = _PhysicsHeadHip.apply(*args) if backend == "hip" else _physics_head_torch(*args)
+    return dict(zip(HEAD_OUTPUTS, outs))
+
+
+class PhysicsDirectPatchDecoder(nn.Module):
+    """The reference's PhysicsDirectPatchDecoder (GDM:955-1147): DirectPatchDecoder's grid and MLP, unclamped scales, no pose / edge
+    inputs, and a phase COMPUTED from the depth by the wave equation with one (learnable) wavelength.  Same constructor arguments
+    and defaults, forward signature (no elevation / azimuth: DESIGN.md section 7.6), returned dict, state-dict keys (mlp.net.*,
+    depth_offset, fresnel_zones._wavelength_raw [, diffraction._{w,C,S}_lut]) and registration order.  `head_backend`: "torch" |
+    "hip" (physics_head)."""
+
+    def __init__(self, feature_dim: int = 384, gaussians_per_patch: int = 8, hidden_dims=(512, 512, 256, 128), dropout: float = 0.1,
+                 wavelength: float = 0.05, learnable_wavelength: bool = True, focal_depth: float = 0.5,
+                 use_diffraction_placement: bool = False, head_backend: str = "torch"):
+        super().__init__()
+        self.feature_dim, self.gaussians_per_patch, self.wavelength = feature_dim, gaussians_per_patch, wavelength
+        self.use_diffraction_placement = use_diffraction_placement
+        self.head_backend = _check_backend(head_backend)
+        self.output_per_gaussian = 16
+        self.mlp = _MLP(feature_dim, list(hidden_dims), gaussians_per_patch * 16, dropout)
+        self.depth_offset = nn.Parameter(torch.tensor(-2.0))
+        self.fresnel_zones = PhysicsFresnelZones(wavelength=wavelength, focal_depth=focal_depth,
+                                                 learnable_wavelength=learnable_wavelength)
+        self.diffraction = FresnelIntegralTables(wavelength=wavelength) if use_diffraction_placement else None
+        self._grids = {}  # (H, W, device) -> (P, 2) grid coordinates
+
+    _grid_xy = DirectPatchDecoder._grid_xy
+
+    def forward(self, features: torch.Tensor, depth: Optional[torch.Tensor] = None, image_size: Tuple[int, int] = (518, 518),
+                num_gaussians: Optional[int] = None) -> Dict[str, torch.Tensor]:
+        """features (B, C, H, W) channel-first; depth (B, 1, h, w) in [0, 1] or None; num_gaussians: progressive growing.
+        -> positions, scales, rotations, colors, opacities, phases (B, N) radians."""
+        Bn, C, H, W = features.shape
+        raw = self.mlp(features.permute(0, 2, 3, 1).reshape(Bn * H * W, C)).reshape(Bn, H * W, self.gaussians_per_patch, 16)
+        if depth is not None:
+            depth_grid = F.interpolate(depth, (H, W), mode="bilinear", align_corners=False)
+            base_z = self.depth_offset + depth_grid.reshape(Bn, H * W) * (-2)
+        else:  # (the reference reads the offset with .item() here: no gradient to it, and none here; no host synchronisation)
+            base_z = self.depth_offset.detach().reshape(1, 1).expand(Bn, H * W).contiguous()
+        fz = self.fresnel_zones
+        return physics_head(raw, self._grid_xy(H, W, features.device), base_z, fz._wavelength_raw, num_gaussians=num_gaussians,
+                            focal_depth=fz.focal_depth, wavelength_min=fz.wavelength_min, wavelength_max=fz.wavelength_max,
+                            xy_gain=0.25, backend=self.head_backend)

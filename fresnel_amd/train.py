@@ -21,7 +21,11 @@ Kept from TGD (same flag names / defaults / behaviour):
                     --experiment 1 implies saag: SAAGRefinementNet refines the dataset's SAAG clouds (`{name}_saag.bin`; a dummy
                     cloud of 1000 Gaussians where a batch has none, TGD:1043-1067), the residual regulariser --residual_weight
                     (TGD:932-939) joins the loss, --saag_backend hip runs its input gather and residual head as HIP kernels
-                    (csrc/fgs_saag.hip)
+                    (csrc/fgs_saag.hip);
+                    --decoder physics: PhysicsDirectPatchDecoder (TGD:1803-1810; --wavelength, --learnable_wavelength,
+                    --focal_depth, --use_diffraction_placement), the reference's decoder for --use_wave_rendering without
+                    --use_qsr: (B,N) phases computed from the depth; --head_backend hip runs its head as HIP kernels
+                    (csrc/fgs_physics.hip); called without elevation / azimuth (the class takes neither)
   renderer choice   TileBasedRenderer(res, res, use_phase_blending, phase_amplitude)   TGD:1898-1907;
                     --experiment 4 --use_phase_blending: FourierGaussianRenderer(res, res, 0.65, 0.55, 0.45)  TGD:1877-1890
   camera            fx = fy = 0.8*res, cx = cy = res/2, view = I                       TGD:1910-1917
@@ -75,7 +79,7 @@ from torch.optim.lr_scheduler import CosineAnnealingLR
 import numpy as np
 
 from .decoder import (HEAD_BACKENDS, NCA_BACKENDS, SAAG_BACKENDS, DirectPatchDecoder, FibonacciPatchDecoder, NCAGaussianDecoder,
-                      PatchGaussianDecoder, SAAGRefinementNet)
+                      PatchGaussianDecoder, PhysicsDirectPatchDecoder, SAAGRefinementNet)
 from .data import collate_host_items
 from .dist import DPContext
 from .handoff import HFTSConfig, camera_for_batch, importance_subsample, sample_training_pose
@@ -129,6 +133,10 @@ class TrainingConfig:  # subset of TGD:97-162 that this path uses; same names an
     # spectral / stencil losses after the renderer (TGD:191, 225-229; fresnel_amd/losses.py)
     wave_equation_weight: float = 0.0
     wavelength: float = 0.05
+    learnable_wavelength: bool = False   # --decoder physics: the command line's default (TGD:1473)
+    focal_depth: float = 0.5
+    use_physics_zones: bool = False      # parsed as the reference parses it; selects nothing by itself here
+    use_diffraction_placement: bool = False
     use_phase_retrieval_loss: bool = False
     phase_retrieval_weight: float = 0.1
     use_frequency_loss: bool = False
@@ -554,6 +562,8 @@ def train_step(model, renderer, camera, batch, optimizer, cfg: TrainingConfig, d
             saag = create_dummy_saag(feats.shape[0], DUMMY_SAAG_POINTS, feats.device, generator=sample_gen)
         out = model(feats.permute(0, 3, 1, 2), *saag)  # (a view: the hip backend samples the patch-major tensor in place)
         residuals = {k: out.pop(k) for k in RESIDUAL_KEYS}  # taken before any subsampling (TGD:1067 against :1154)
+    elif cfg.decoder == "physics":  # the class's forward takes no pose arguments (the reference's call at TGD:1100 raises TypeError)
+        out = model(feats.permute(0, 3, 1, 2), depth, num_gaussians=num_gaussians)
     else:
         out = model(feats.permute(0, 3, 1, 2) if mirror else feats, depth, num_gaussians=num_gaussians, elevation=el_t, azimuth=az_t)
     out.pop("edge_strength", None)
@@ -565,7 +575,8 @@ def train_step(model, renderer, camera, batch, optimizer, cfg: TrainingConfig, d
     phases = out.get("phases")
     if cfg.use_wave_rendering and phases is not None and not mirror:
         phases = phases * (2.0 * math.pi)  # wave renderers take radians (DR:772), the stand-in decoder emits [0,1]
-    # (a mirror's (B,N,3) phases go on as they are: radians for the wave renderer, ignored by the Fourier renderer; on the
+    # (the physics decoder's (B,N) radians go on as they are;
+    # a mirror's (B,N,3) phases go on as they are: radians for the wave renderer, ignored by the Fourier renderer; on the
     # TileBasedRenderer phase path the renderer's RuntimeError for (N,3) phases surfaces, as in the reference -- SURVEY section 0.4)
     render_camera = camera_for_batch(camera, el, az, res, cfg.multi_pose_augmentation)  # TGD:1196-1207
     # ONE batched call replaces the per-image loop of TGD:1209-1223
@@ -595,7 +606,7 @@ def train_step(model, renderer, camera, batch, optimizer, cfg: TrainingConfig, d
     return StepResult(terms, skipped)
 
 
-DECODERS = ("standin", "direct", "fibonacci", "nca", "saag")
+DECODERS = ("standin", "direct", "fibonacci", "nca", "saag", "physics")
 
 
 def make_decoder(cfg: TrainingConfig):
@@ -615,6 +626,14 @@ def make_decoder(cfg: TrainingConfig):
         return SAAGRefinementNet(feature_dim=cfg.feature_dim, backend=cfg.saag_backend)  # (the class's defaults, as TGD:1786)
     if cfg.head_backend not in HEAD_BACKENDS:
         raise ValueError(f"unknown head_backend {cfg.head_backend!r}: one of {HEAD_BACKENDS}")
+    if cfg.decoder == "physics":  # TGD:1803-1810
+        if cfg.use_pose_encoding:
+            raise ValueError("--decoder physics cannot be combined with --use_pose_encoding: PhysicsDirectPatchDecoder has no pose "
+                             "inputs (GDM:1032-1038)")
+        return PhysicsDirectPatchDecoder(feature_dim=cfg.feature_dim, gaussians_per_patch=cfg.gaussians_per_patch,
+                                         wavelength=cfg.wavelength, learnable_wavelength=cfg.learnable_wavelength,
+                                         focal_depth=cfg.focal_depth, use_diffraction_placement=cfg.use_diffraction_placement,
+                                         head_backend=cfg.head_backend)
     if cfg.decoder == "direct":
         return DirectPatchDecoder(feature_dim=cfg.feature_dim, gaussians_per_patch=cfg.gaussians_per_patch,
                                   use_fresnel_zones=cfg.use_fresnel_zones, num_fresnel_zones=cfg.num_fresnel_zones,
@@ -889,6 +908,13 @@ def arg_parser() -> argparse.ArgumentParser:
     ap.add_argument("--use_qsr", action="store_true", help="macro flag: implies --use_wave_rendering (TGD:1550-1553)")
     ap.add_argument("--wave_equation_weight", type=float, default=c.wave_equation_weight, help="TGD:1483")
     ap.add_argument("--wavelength", type=float, default=c.wavelength)
+    ap.add_argument("--learnable_wavelength", dest="learnable_wavelength", action="store_true", default=c.learnable_wavelength,
+                    help="--decoder physics: the wavelength is a parameter (TGD:1473)")
+    ap.add_argument("--no_learnable_wavelength", dest="learnable_wavelength", action="store_false")
+    ap.add_argument("--focal_depth", type=float, default=c.focal_depth, help="focal plane of the physics phase (TGD:1479)")
+    ap.add_argument("--use_physics_zones", action="store_true", help="TGD:1475 (recorded; selects no decoder by itself here)")
+    ap.add_argument("--use_diffraction_placement", action="store_true",
+                    help="TGD:1477: --decoder physics carries the Fresnel-integral tables (never evaluated, as in the reference)")
     ap.add_argument("--use_phase_retrieval_loss", action="store_true", help="TGD:1494 (--use_qsr implies it, TGD:1553)")
     ap.add_argument("--phase_retrieval_weight", type=float, default=c.phase_retrieval_weight)
     ap.add_argument("--use_frequency_loss", action="store_true", help="TGD:1498")
@@ -906,7 +932,8 @@ def arg_parser() -> argparse.ArgumentParser:
                     help="L1 / boundary / depth terms: torch expressions (default) or this package's fused HIP kernels")
     ap.add_argument("--decoder", default=c.decoder, choices=list(DECODERS),
                     help="the stand-in decoder (default) or a mirror of the reference's DirectPatchDecoder / FibonacciPatchDecoder "
-                         "(loads its checkpoints); --experiment 4 implies fibonacci")
+                         "(loads its checkpoints); --experiment 4 implies fibonacci; physics: PhysicsDirectPatchDecoder, the "
+                         "reference's decoder for --use_wave_rendering without --use_qsr")
     ap.add_argument("--head_backend", default=c.head_backend, choices=list(HEAD_BACKENDS),
                     help="Gaussian-parameter head of --decoder direct / fibonacci: torch expressions (default) or the fused HIP kernels")
     ap.add_argument("--n_spiral_points", type=int, default=c.n_spiral_points, help="TGD:1427 (--decoder fibonacci / nca)")
@@ -941,6 +968,8 @@ def config_from_args(a) -> TrainingConfig:
         decoder = "saag"
     elif decoder == "saag":
         raise SystemExit("--decoder saag is --experiment 1")
+    elif decoder == "physics" and a.experiment != 2:
+        raise SystemExit("--decoder physics is an --experiment 2 decoder (TGD:1779-1782)")
     elif a.experiment == 4:
         if decoder in ("direct", "nca"):
             raise SystemExit(f"--experiment 4 trains the Fibonacci decoder: --decoder {decoder} contradicts it")
@@ -974,7 +1003,9 @@ def config_from_args(a) -> TrainingConfig:
                           pixel_loss_backend=a.pixel_loss_backend, workspace=a.workspace,
                           decoder=decoder, head_backend=a.head_backend, n_spiral_points=a.n_spiral_points,
                           nca_steps=a.nca_steps, nca_neighbors=a.nca_neighbors, nca_backend=a.nca_backend,
-                          nca_step_size=a.nca_step_size, saag_backend=a.saag_backend, residual_weight=a.residual_weight)
+                          nca_step_size=a.nca_step_size, saag_backend=a.saag_backend, residual_weight=a.residual_weight,
+                          learnable_wavelength=a.learnable_wavelength, focal_depth=a.focal_depth,
+                          use_physics_zones=a.use_physics_zones, use_diffraction_placement=a.use_diffraction_placement)
 
 
 def main(argv=None):

@@ -554,6 +554,53 @@ int fgs_saag_refine_backward(const FgsSaagDims *dims, const float *raw, const fl
                              const float *g_opacity_delta, float *g_raw, float *g_gains, void *scratch, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Parameter head of the reference's PhysicsDirectPatchDecoder (scripts/models/gaussian_decoder_models.py, GDM:955-1147) with the
+ * physics-derived phase of PhysicsFresnelZones.depth_to_phase (scripts/utils/fresnel_zones.py:555-575).  All tensors fp32,
+ * contiguous, DEVICE.
+ *   raw             (B, P, K_full, 16)  xyz offset 3 (z unused), scale 3, rotation-6D 6, colour 3, opacity 1; the first K = k_used
+ *                                       Gaussians of every patch are used; N = P x K, Gaussian n = p K + k
+ *   base_xy         (P, 2) grid coordinates       base_z  (B, P)  depth_offset - 2 depth
+ *   wavelength_raw  one DEVICE float: never read on the host, so the calls can be captured in a graph
+ *   outputs         positions (B,N,3) = (base_xy + xy_gain raw[0:2], base_z);  scales (B,N,3) = softplus(raw + 1) 0.15 (softplus
+ *                   linear above 20; NO clamps);  rotations (B,N,4) as the head's above;  colors (B,N,3), opacities (B,N) sigmoids
+ *                   phases (B,N) radians in [0, 2 pi]: with z the Gaussian's base_z and z_min, z_max over all B x P values,
+ *                       D = (z_max - z_min) + 1e-8        u = (z - z_min) / D        lambda = min(max(|wavelength_raw|, wavelength_min), wavelength_max)
+ *                       c = fp32(2 pi) / lambda           pd = |u - focal_depth|     phase = fmod(c pd, fp32(2 pi))
+ *                   every operation rounded to fp32 on its own (IEEE divide, no FMA): torch's fp32 result, bit for bit.
+ *                   A NaN in base_z makes z_min and z_max NaN and with them EVERY phase (as torch's min / max); the other outputs
+ *                   are NaN only where their own inputs are.
+ *   range           16 bytes, written by the forward and read by the backward (all that is saved): float z_min, z_max; int32 n_min,
+ *                   n_max = how many of the B x P values equal z_min / z_max (0 when NaN)
+ * fgs_physics_forward:  two launches (range, head) while B x P <= 16 384, three beyond (the range in up to 32 blocks, then a fold).
+ * fgs_physics_backward: recomputes the forward from raw, base_z and range.  Any of the six upstream gradients may be NULL (= 0).
+ *     g_raw (B, P, K_full, 16): every element written (zeros for channel 2 and for the K_full - K unused Gaussians).
+ *     g_base_z (B, P) or NULL = the patch's K position-z gradients + g_u / D + [z = z_min] g_z_min / n_min + [z = z_max] g_z_max /
+ *       n_max, with G = the patch's K phase gradients (both sums added in k order), g_u = (G c) sgn(u - focal_depth) (sgn(0) = 0),
+ *       g_z_min = (S2 - S1) / D, g_z_max = -S2 / D, S1 = sum g_u, S2 = sum g_u u: torch's min() / max() share their gradient
+ *       equally among tied elements.
+ *     g_wavelength_raw, one float, or NULL = -S3 c / lambda x sign(wavelength_raw) where wavelength_min <= |wavelength_raw| <=
+ *       wavelength_max (closed interval; sign(0) = 0), else 0;  S3 = sum G pd.
+ *     S1, S2, S3 are sums over the B x P patches of products of two floats, exact in double, added in a fixed order (fixed-shape
+ *     block tree, block partials from `scratch` added in a fixed order) and rounded to fp32 once.  No atomics: two calls agree
+ *     to the bit.  scratch (fgs_physics_workspace_bytes; both calls) is written, never read before it is written.
+ * Shapes: B, P >= 1, 1 <= K <= K_full <= 64, B <= 65535, B P K_full 16 < 2^31, 0 < wavelength_min <= wavelength_max; otherwise
+ * FGS_EINVAL (bad dims, null pointers) / FGS_EUNSUPPORTED before anything touches the device. */
+typedef struct FgsPhysicsDims {
+    int32_t batch, points, k_full, k_used;
+    float xy_gain;                 /* 0.25 (GDM:1098) */
+    float focal_depth;             /* of the normalised depth u, 0.5 by default */
+    float wavelength_min, wavelength_max;   /* 0.01, 0.5 (fresnel_zones.py:429-430) */
+} FgsPhysicsDims;
+int fgs_physics_workspace_bytes(const FgsPhysicsDims *dims, size_t *scratch_bytes);
+int fgs_physics_forward(const FgsPhysicsDims *dims, const float *raw, const float *base_xy, const float *base_z,
+                        const float *wavelength_raw, float *positions, float *scales, float *rotations, float *colors,
+                        float *opacities, float *phases, void *range, void *scratch, void *stream);
+int fgs_physics_backward(const FgsPhysicsDims *dims, const float *raw, const float *base_z, const float *wavelength_raw,
+                         const void *range, const float *g_positions, const float *g_scales, const float *g_rotations,
+                         const float *g_colors, const float *g_opacities, const float *g_phases, float *g_raw, float *g_base_z,
+                         float *g_wavelength_raw, void *scratch, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Importance-subsampling hand-off between decoder and rasterizer (--stochastic_k; reference
  * scripts/training/train_gaussian_decoder.py:1160-1187): the n_out Gaussians whose indices torch.multinomial
  * drew (DEVICE int64 (n_out,), unique, shared by the batch) are gathered out of every (B, n_in, .) tensor into
