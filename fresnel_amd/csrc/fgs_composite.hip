@@ -68,6 +68,13 @@ __device__ __forceinline__ float blend_alpha1(float e, uint32_t mask) {
     return __uint_as_float(__float_as_uint(__builtin_amdgcn_fmed3f(__builtin_amdgcn_exp2f(e), 0.0f, 1.0f)) & mask);
 }
 
+// (x < 1) ? v : 0, the 1.0 an inline constant (1 > x): select_lt (fgs_wave.h) without a VGPR for the limit
+__device__ __forceinline__ float select_lt1(float x, float v) {
+    float o;
+    asm("v_cmp_gt_f32 vcc, 1.0, %1\n\tv_cndmask_b32 %0, 0, %2, vcc" : "=v"(o) : "v"(x), "v"(v) : "vcc");
+    return o;
+}
+
 struct TileCtx {
     uint32_t tile, b, tx, ty, X0, Y0, start, end;
 };
@@ -482,109 +489,42 @@ __global__ __launch_bounds__(64 * NP * (1 + WIDE)) __attribute__((amdgpu_waves_p
 //
 // Work unit = (tile, depth segment of FGS_SEG list entries): the unit restarts from the forward's
 // per-pixel checkpoint in front of its segment, so units are independent and of bounded length.
+// DEAD UNITS (round 10).  Once the forward's transmittance is <= 2^-25 its accumulated alpha rounds to 1.0f, so a later unit
+// restarts with T == +0.0f exactly and keeps it (fma(+0, -0.99, +0) = +0).  A unit ALL of whose in-frame pixels restart so
+// (one ballot in the prologue, from the T the prologue holds anyway: 78 % of config 3's units, 33 % of config 2's, 90 % of the
+// decoder-like scene's) is walked by composite_bwd_dead_walk, whose pass leaves out the terms that are exact zeros there --
+// w = a' T, the four ops of q, the S update, T q, the T update, the four colour / depth sums: 11 plain VALU + v_exp + v_rcp per pass
+// instead of 19 + 2 -- and forms the rest in exactly the instruction forms of the general pass, so the gradient rows are the
+// same bits (S in a dead unit is the rounding residue of Total - sum w q, NOT zero: the rows are small, not zero, and nothing is
+// skipped).  The one thing not reproduced is the SIGN of a dalpha that is an exact zero (S == +0: no upstream gradient on the
+// pixel); it can show only as the sign of a row value that is an exact zero on every pixel of the tile.  Every other unit takes
+// the general walk, which is the loop it was, instruction for instruction.
 // Six waves per SIMD (80 VGPRs): the loop is bound by VALU issue with dependent chains in every pass (exp -> alpha -> w
 // -> S -> rcp -> dalpha), and the sixth wave buys 4 % (1.37 -> 1.31 ms at config 3); a seventh needs spills and loses 35 %.
 // NSX = sub-tile columns of the tile: 2 (16 x 16 tiles) or 4 (32 x 16 tiles: eight sub-tiles per lane, ~0.6x as many list
 // entries, reductions and gradient rows; 5 waves per SIMD instead of 6 -- the loop is issue-bound, not latency-bound).
-#ifndef FGS_BWD_WIDE_WAVES
-#define FGS_BWD_WIDE_WAVES 5  /* waves per SIMD of k_composite_bwd<4>; re-measured in round 3 under the clause scheduler: see DESIGN_LOG.md 10.3 */
-#endif
-#ifndef FGS_BWD_DYN_LDS
-#define FGS_BWD_DYN_LDS 0  /* experiment builds: unused dynamic LDS per block, to cap the waves per SIMD below what the registers allow */
-#endif
-template <int NSX>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NSX == 2 ? 6 : FGS_BWD_WIDE_WAVES, NSX == 2 ? 6 : FGS_BWD_WIDE_WAVES))) void k_composite_bwd(
-    uint32_t tiles, uint32_t tiles_x, uint32_t W, uint32_t H, float bg0, float bg1, float bg2, uint32_t dcap,
-    const uint32_t *__restrict__ counters, const uint32_t *__restrict__ seg_off,
-    const uint32_t *__restrict__ seg_tile, const float *__restrict__ seg_ckpt, const uint32_t *__restrict__ ranges,
-    const uint32_t *__restrict__ dup_ids, const float *__restrict__ rec, const uint32_t *__restrict__ dup_off,
-    const float *__restrict__ pix_state, const float *__restrict__ g_rgb, const float *__restrict__ g_depth,
-    float *__restrict__ grad_rows, float t_eps) {
-    __shared__ float4 sh0[CH], sh1[CH], sh2[CH];
-    __shared__ uint32_t she[CH];
-    __shared__ __attribute__((aligned(16))) float red[10 * FGS_RED_PITCH];  // per-lane partial sums of one list entry
-    // work unit = (tile, depth segment): blockIdx.x indexes the unit list built by k_tile_order; the grid is
-    // sized from the capacity, surplus blocks leave at once
-    constexpr int NS = 2 * NSX, PL = NS * 64, SLOT = 5 * PL;  // sub-tiles per tile, floats per checkpoint plane / slot
+// LDS of k_composite_bwd, at file scope: the kernel and the dead unit's walk (a function of its own, below) name the same arrays
+__shared__ float4 bwd_sh0[CH], bwd_sh1[CH], bwd_sh2[CH];
+__shared__ uint32_t bwd_she[CH];
+__shared__ __attribute__((aligned(16))) float bwd_red[10 * FGS_RED_PITCH];  // per-lane partial sums of one list entry
+#define FGS_BWD_G __attribute__((address_space(1)))  /* global memory, also where the pointer arrives as a function argument */
+
+// The chunk / list loop of k_composite_bwd over the unit's entries [c.start, c.end), in two instantiations: DEAD = false the general
+// walk, inlined into the kernel; DEAD = true the walk of a dead unit (see the kernel), whose pass computes only what is not an exact
+// zero there (see `pass`; g*, T are not read).  Staging, the LDS record layout, the emission slot, the deferred reduction and the row
+// store are the same code in both.
+template <int NSX, bool DEAD>
+__device__ __forceinline__ void composite_bwd_walk(const TileCtx &c, uint32_t lane, uint32_t lx, uint32_t ly, uint32_t dcap, uint32_t alive,
+                                                   const uint32_t *__restrict__ dup_ids, const float *__restrict__ rec,
+                                                   const uint32_t *__restrict__ dup_off, float *__restrict__ grad_rows,
+                                                   const float (&gr)[2 * NSX], const float (&gg)[2 * NSX], const float (&gb)[2 * NSX],
+                                                   const float (&gd)[2 * NSX], float (&S)[2 * NSX], float (&T)[2 * NSX]) {
+    constexpr int NS = 2 * NSX;
     // geometric sums per sub-tile row, folded once per list entry (below).  32 x 16 tiles only: with at most four passes per
     // entry the fold costs what the passes save, and 16 x 16 tiles measured 0.8 % SLOWER that way (DESIGN_LOG.md 15)
     constexpr bool ROW_MOMENTS = NSX == 4;
-    const uint32_t num_units = counters[2];
-    if (blockIdx.x >= num_units) return;
-    // units are listed tile by tile: an XCD gets a contiguous run of them, so neighbouring tiles -- which share
-    // Gaussians, and write adjacent 40-byte gradient rows -- meet in one L2
-    const uint32_t unit = fgs_xcd_remap(blockIdx.x, num_units);
-    // the split the forward ran with, as the forward recorded it (k_tile_order): segment length, and the number of
-    // list parts of the depth-split forward (> 1: checkpoints inside a later part are part-local)
-    const uint32_t seg_len = counters[4];
-    const uint32_t fwd_parts = (int32_t)counters[5] > 1 ? counters[5] : 0u;
-    const uint32_t unit_tile = seg_tile[unit];
-    const uint32_t seg = unit - seg_off[unit_tile];
-    TileCtx c = tile_ctx_of(unit_tile, tiles, tiles_x, ranges, 8u * NSX);
-    uint32_t rebase_seg = seg;  // first segment of this segment's list part if its checkpoint is part-local
-    if (fwd_parts > 1) {
-        const uint32_t nseg = (c.end - c.start + seg_len - 1) / seg_len;
-        const uint32_t spp = (nseg + fwd_parts - 1) / fwd_parts, first = seg / spp * spp;
-        if (first != 0) rebase_seg = first;
-    }
-    c.start += seg * seg_len;
-    c.end = min(c.end, c.start + seg_len);
-    const uint32_t lane = threadIdx.x;
-    const uint32_t lx = lane & 7u, ly = lane >> 3;
-    const size_t HW = (size_t)W * H;
-    if (t_eps > 0.0f) {
-        // FgsDims.saturation_skip: the forward stopped walking this tile's list after `live` segments (count
-        // parked in the checkpoint slot of segment 0); the entries of a dead segment get all-zero gradient rows
-        const uint32_t live = reinterpret_cast<const uint32_t *>(seg_ckpt + (size_t)seg_off[unit_tile] * SLOT)[0];
-        if (seg >= live) {
-            for (uint32_t i = c.start + lane; i < c.end; i += 64) {
-                const uint32_t gid = dup_ids[i];
-                const float4 q2 = reinterpret_cast<const float4 *>(rec + (size_t)gid * FGS_REC_FLOATS)[2];
-                const uint32_t e = fgs_emission_slot<8 * NSX>(c.tx, c.ty, gid, __float_as_uint(q2.z), __float_as_uint(q2.w), dup_off);
-                if (e < dcap) {
-                    float2 *row = reinterpret_cast<float2 *>(grad_rows + (size_t)e * FGS_BLEND_ROW_FLOATS);
-#pragma unroll
-                    for (int q = 0; q < FGS_BLEND_ROW_FLOATS / 2; ++q) row[q] = make_float2(0.0f, 0.0f);
-                }
-            }
-            return;
-        }
-    }
-    // T: running transmittance (w = alpha T, T -= w: one instruction less per pixel than T = 1 - A, A += w)
-    // S: T_fin (gI.bg) + sum over not-yet-visited w q
-    float gr[NS], gg[NS], gb[NS], gd[NS], S[NS], T[NS];
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-        const uint32_t px = c.X0 + 8u * (s % NSX) + lx, py = c.Y0 + 8u * (s / NSX) + ly;
-        gr[s] = gg[s] = gb[s] = gd[s] = S[s] = 0.0f;
-        T[s] = 1.0f;
-        if (px < W && py < H) {
-            const PixelGrad g = pixel_grad_load(pix_state, g_rgb, g_depth, c.b, HW, (size_t)py * W + px, bg0, bg1, bg2);
-            gr[s] = g.gr; gg[s] = g.gg; gb[s] = g.gb; gd[s] = g.gd;
-            S[s] = g.Tf * (gr[s] * bg0 + gg[s] * bg1 + gb[s] * bg2) + (gr[s] * g.Cr + gg[s] * g.Cg + gb[s] * g.Cb) + gd[s] * g.D;
-        }
-        if (seg) {
-            // restart from the forward's state in front of this segment: T, and S minus the part of Total that
-            // belongs to the list entries before it.  After a depth-split forward (k_blend_fwd_parts, fwd_parts
-            // waves per tile) the checkpoint of a segment inside part p > 0 is local to that part and is re-based
-            // with the absolute state kept in the slot of the part's first segment.
-            BlendState st = ckpt_load<PL>(seg_ckpt + (size_t)unit * SLOT + s * 64 + lane);
-            if (rebase_seg != seg) {
-                const size_t slot = (size_t)unit - seg + rebase_seg;
-                st = compose(ckpt_load<PL>(seg_ckpt + slot * SLOT + s * 64 + lane), st);
-            }
-            T[s] = st.T;
-            S[s] -= gr[s] * st.Cr + gg[s] * st.Cg + gb[s] * st.Cb + gd[s] * st.D;
-        }
-    }
+    auto &sh0 = bwd_sh0; auto &sh1 = bwd_sh1; auto &sh2 = bwd_sh2; auto &she = bwd_she; auto &red = bwd_red;
     const uint32_t shx = lx, shy = 16u + ly;  // this lane's column bit in the staged column bits / row bit in the flags
-    uint32_t alive = (1u << NS) - 1u;  // sub-tiles still composited (FgsDims.saturation_skip; 16 x 16 tiles only)
-    if (t_eps > 0.0f) {
-        alive = 0u;
-#pragma unroll
-        for (int s = 0; s < NS; ++s)
-            if (__ballot(T[s] >= t_eps) != 0ull) alive |= 1u << s;  // T = 1 - A of the checkpoint, as in the forward
-    }
     float fx0 = (float)(c.X0 + lx), fy0 = (float)(c.Y0 + ly);
     asm("" : "+v"(fx0), "+v"(fy0));  // hoisted for good: no v_cvt in the list loop
     // The reduction of a list entry's ten sums is DEFERRED by one entry: the passes of entry j end with the sums parked in `red`
@@ -596,18 +536,24 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NSX == 2 ? 6
     auto reduce_parked = [&]() {
         const float tot = wave_sum_addtid_finish(red, lane, 10u);
         // (16-float rows: all sixteen quads' last lanes store, lanes >= 40 a zero -- one whole 64-byte line)
-        if ((lane & 3u) == 3u && lane < 4u * FGS_BLEND_ROW_FLOATS && e_prev < dcap) grad_rows[(size_t)e_prev * FGS_BLEND_ROW_FLOATS + (lane >> 2)] = tot;
+        if ((lane & 3u) == 3u && lane < 4u * FGS_BLEND_ROW_FLOATS && e_prev < dcap) ((FGS_BWD_G float *)grad_rows)[(size_t)e_prev * FGS_BLEND_ROW_FLOATS + (lane >> 2)] = tot;
     };
     for (uint32_t base = c.start; base < c.end; base += CH) {
         // the list loop's trip count, pinned to an SGPR: left to itself the compiler keeps it in a VGPR (it is compared with `lane`
         // here) and counts the list loop down with a v_add_u32 / v_cmp_eq_u32 pair per entry
         const uint32_t n = __builtin_amdgcn_readfirstlane(min((uint32_t)CH, c.end - base));
-        if (lane < n) {
-            const uint32_t gid = dup_ids[base + lane];
+        // The staging's own lane id, formed afresh per chunk behind an asm volatile so that NOTHING derived from it is loop-invariant.
+        // With `lane` here the staging's LDS addresses and 64-bit index pairs are hoisted out of the chunk loop and held across the list
+        // loop; at 96 VGPRs the allocator then spills them, and with them the gradient row's lane address, which it reloads INSIDE the
+        // list loop (one scratch load per entry: DESIGN_LOG.md 18, 21).  Check after a compiler change: no scratch instruction in a list loop.
+        uint32_t sl;
+        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(sl));
+        if (sl < n) {
+            const uint32_t gid = ((FGS_BWD_G const uint32_t *)dup_ids)[base + sl];
             const float4 *r = reinterpret_cast<const float4 *>(rec + (size_t)gid * FGS_REC_FLOATS);
             float4 q2 = r[2];
             const uint32_t bbx = __float_as_uint(q2.z), bby = __float_as_uint(q2.w);
-            she[lane] = fgs_emission_slot<8 * NSX>(c.tx, c.ty, gid, bbx, bby, dup_off);
+            she[sl] = fgs_emission_slot<8 * NSX>(c.tx, c.ty, gid, bbx, bby, dup_off);
             float4 q0 = r[0], q1 = r[1];
             // m = a dx^2 + (b+c) dx dy + d dy^2 >= 0 everywhere (so G <= 1): positive definite, with a margin
             // that covers the fp32 rounding of m
@@ -616,7 +562,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NSX == 2 ? 6
             stage_decode_w<NSX>(c.X0, c.Y0, bbx, bby, q1.y, flags, cbits, conic_ok);
             // (blend_stage_fold: the forward's record, but for the floored opacities' lop -- see there, with the row contract)
             blend_stage_fold(q0, q1, q2, flags, cbits, fgs_opacity_floored(q1.y) ? FGS_FOLD_FLOOR_LOG2 : blend_lop(q1.y));
-            sh0[lane] = q0; sh1[lane] = q1; sh2[lane] = q2;
+            sh0[sl] = q0; sh1[sl] = q1; sh2[sl] = q2;
         }
         __syncthreads();
         for (uint32_t j = 0; j < n; ++j) {
@@ -671,6 +617,37 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NSX == 2 ? 6
                     // a' is zeroed outside the bbox: w and every gradient term below then vanish by themselves
                     const int col = s % NSX, row = s / NSX;
                     const float dx = dxs[col], dy = row ? dyb : dya;
+                    if constexpr (DEAD) {
+                        // T == +0 on every pixel that is not masked: w = a' T = +0, S keeps its value (S -= w q), the colour / depth sums
+                        // get exact zeros and dalpha = T q - S r = -(S r) (T q = +-0; q is finite, or S is already NaN: a non-finite colour
+                        // or upstream gradient reaches S through the forward's saved state in the prologue).  What is left is written in
+                        // exactly the forms the general pass compiles to (contraction is on in this unit, and nothing makes two copies of
+                        // one expression contract alike): exponent = two FMAs; -(S r) = S rcp(a' - 1 / 0.99); every moment an FMA onto
+                        // its sum, from the ROUNDED dG and dG dx.  The rows are the general walk's to the bit.
+                        const float t = __builtin_fmaf(dx, ca, row ? bdyb : bdya);
+                        const float a1 = blend_alpha1(__builtin_fmaf(t, dx, row ? cyyb : cyya), mk);
+                        float dalpha = S[s] * __builtin_amdgcn_rcpf(a1 - INV_ALPHA_MAX);
+                        uint32_t cf = cflag;
+                        asm("" : "+s"(cf));
+                        if (!cf) dalpha = select_lt1(a1, dalpha);
+                        // (opaque products: under fast-math the first pass of a row, whose sums start from zero, otherwise re-associates
+                        // (dG dx) dx into (dx dx) dG -- another rounding than the general pass's)
+                        float dG = dalpha * a1;
+                        asm("" : "+v"(dG));
+                        if constexpr (ROW_MOMENTS) {
+                            mA[row] = __builtin_fmaf(dalpha, a1, mA[row]);
+                            float dmx = dG * dx;
+                            asm("" : "+v"(dmx));
+                            mB[row] = __builtin_fmaf(dG, dx, mB[row]); mC[row] = __builtin_fmaf(dmx, dx, mC[row]);
+                        } else {
+                            v_op = __builtin_fmaf(dalpha, a1, v_op);
+                            float dmx = dG * dx, dmy = dG * dy;
+                            asm("" : "+v"(dmx), "+v"(dmy));
+                            v_mx = __builtin_fmaf(dG, dx, v_mx); v_my = __builtin_fmaf(dG, dy, v_my);
+                            v_ca = __builtin_fmaf(dmx, dx, v_ca); v_cbc = __builtin_fmaf(dmx, dy, v_cbc); v_cd = __builtin_fmaf(dmy, dy, v_cd);
+                        }
+                        return;
+                    }
                     const float t = ca * dx + (row ? bdyb : bdya);
                     const float a1 = blend_alpha1(t * dx + (row ? cyyb : cyya), mk);  // alpha / 0.99: v_exp ... clamp, v_and
                     const float w = a1 * T[s];  // w / 0.99
@@ -681,7 +658,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NSX == 2 ? 6
                     T[s] = fmaf(w, -ALPHA_MAX, T[s]);
                     uint32_t cf = cflag;
                     asm("" : "+s"(cf));  // an opaque scalar per use: one s_cmp + branch, nothing on the vector side
-                    if (!cf) dalpha = select_lt(a1, 1.0f, dalpha);  // the clamp binds where G op / 0.99 reaches 1
+                    if (!cf) dalpha = select_lt1(a1, dalpha);  // the clamp binds where G op / 0.99 reaches 1
                     const float dG = dalpha * a1;  // op' x (0.99 dL/dalpha G): the opacity is already in the rows
                     if constexpr (ROW_MOMENTS) {
                         mA[row] += dG;
@@ -718,6 +695,135 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NSX == 2 ? 6
         __syncthreads();
     }
     reduce_parked();  // the unit's last entry
+}
+
+// The dead unit's walk as a function of its own, CALLED by the kernel: inlined next to the general walk it cost that walk registers
+// (scratch traffic in front of every chunk, +1 % on a launch without a dead unit; DESIGN_LOG.md 21).  It needs S and the tile alone.
+template <int NSX>
+struct BwdDeadArgs {
+    TileCtx c;
+    uint32_t dcap;
+    const uint32_t *dup_ids; const float *rec; const uint32_t *dup_off; float *grad_rows;
+    float S[2 * NSX];
+};
+template <int NSX>
+__device__ __attribute__((noinline)) void composite_bwd_dead_walk(BwdDeadArgs<NSX> a) {
+    const uint32_t lane = threadIdx.x;
+    float z[2 * NSX] = {}, T[2 * NSX] = {};
+    composite_bwd_walk<NSX, true>(a.c, lane, lane & 7u, lane >> 3, a.dcap, (1u << (2 * NSX)) - 1u, a.dup_ids, a.rec, a.dup_off, a.grad_rows, z, z, z, z,
+                                  a.S, T);
+}
+
+#ifndef FGS_BWD_WIDE_WAVES
+#define FGS_BWD_WIDE_WAVES 5  /* waves per SIMD of k_composite_bwd<4>; re-measured in round 3 under the clause scheduler: see DESIGN_LOG.md 10.3 */
+#endif
+#ifndef FGS_BWD_DYN_LDS
+#define FGS_BWD_DYN_LDS 0  /* experiment builds: unused dynamic LDS per block, to cap the waves per SIMD below what the registers allow */
+#endif
+template <int NSX>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NSX == 2 ? 6 : FGS_BWD_WIDE_WAVES, NSX == 2 ? 6 : FGS_BWD_WIDE_WAVES))) void k_composite_bwd(
+    uint32_t tiles, uint32_t tiles_x, uint32_t W, uint32_t H, float bg0, float bg1, float bg2, uint32_t dcap,
+    const uint32_t *__restrict__ counters, const uint32_t *__restrict__ seg_off,
+    const uint32_t *__restrict__ seg_tile, const float *__restrict__ seg_ckpt, const uint32_t *__restrict__ ranges,
+    const uint32_t *__restrict__ dup_ids, const float *__restrict__ rec, const uint32_t *__restrict__ dup_off,
+    const float *__restrict__ pix_state, const float *__restrict__ g_rgb, const float *__restrict__ g_depth,
+    float *__restrict__ grad_rows, float t_eps) {
+    // work unit = (tile, depth segment): blockIdx.x indexes the unit list built by k_tile_order; the grid is
+    // sized from the capacity, surplus blocks leave at once
+    constexpr int NS = 2 * NSX, PL = NS * 64, SLOT = 5 * PL;  // sub-tiles per tile, floats per checkpoint plane / slot
+    const uint32_t num_units = counters[2];
+    if (blockIdx.x >= num_units) return;
+    // units are listed tile by tile: an XCD gets a contiguous run of them, so neighbouring tiles -- which share
+    // Gaussians, and write adjacent 40-byte gradient rows -- meet in one L2
+    const uint32_t unit = fgs_xcd_remap(blockIdx.x, num_units);
+    // the split the forward ran with, as the forward recorded it (k_tile_order): segment length, and the number of
+    // list parts of the depth-split forward (> 1: checkpoints inside a later part are part-local)
+    const uint32_t seg_len = counters[4];
+    const uint32_t fwd_parts = (int32_t)counters[5] > 1 ? counters[5] : 0u;
+    const uint32_t unit_tile = seg_tile[unit];
+    const uint32_t seg = unit - seg_off[unit_tile];
+    TileCtx c = tile_ctx_of(unit_tile, tiles, tiles_x, ranges, 8u * NSX);
+    uint32_t rebase_seg = seg;  // first segment of this segment's list part if its checkpoint is part-local
+    if (fwd_parts > 1) {
+        const uint32_t nseg = (c.end - c.start + seg_len - 1) / seg_len;
+        const uint32_t spp = (nseg + fwd_parts - 1) / fwd_parts, first = seg / spp * spp;
+        if (first != 0) rebase_seg = first;
+    }
+    c.start += seg * seg_len;
+    c.end = min(c.end, c.start + seg_len);
+    const uint32_t lane = threadIdx.x;
+    const uint32_t lx = lane & 7u, ly = lane >> 3;
+    const size_t HW = (size_t)W * H;
+    if (t_eps > 0.0f) {
+        // FgsDims.saturation_skip: the forward stopped walking this tile's list after `live` segments (count
+        // parked in the checkpoint slot of segment 0); the entries of a dead segment get all-zero gradient rows
+        const uint32_t live = reinterpret_cast<const uint32_t *>(seg_ckpt + (size_t)seg_off[unit_tile] * SLOT)[0];
+        if (seg >= live) {
+            for (uint32_t i = c.start + lane; i < c.end; i += 64) {
+                const uint32_t gid = dup_ids[i];
+                const float4 q2 = reinterpret_cast<const float4 *>(rec + (size_t)gid * FGS_REC_FLOATS)[2];
+                const uint32_t e = fgs_emission_slot<8 * NSX>(c.tx, c.ty, gid, __float_as_uint(q2.z), __float_as_uint(q2.w), dup_off);
+                if (e < dcap) {
+                    float2 *row = reinterpret_cast<float2 *>(grad_rows + (size_t)e * FGS_BLEND_ROW_FLOATS);
+#pragma unroll
+                    for (int q = 0; q < FGS_BLEND_ROW_FLOATS / 2; ++q) row[q] = make_float2(0.0f, 0.0f);
+                }
+            }
+            return;
+        }
+    }
+    // T: running transmittance (w = alpha T, T -= w: one instruction less per pixel than T = 1 - A, A += w)
+    // S: T_fin (gI.bg) + sum over not-yet-visited w q
+    float gr[NS], gg[NS], gb[NS], gd[NS], S[NS], T[NS];
+    bool live_px = false;  // an in-frame pixel of this lane restarts with T != 0
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        const uint32_t px = c.X0 + 8u * (s % NSX) + lx, py = c.Y0 + 8u * (s / NSX) + ly;
+        gr[s] = gg[s] = gb[s] = gd[s] = S[s] = 0.0f;
+        T[s] = 1.0f;
+        if (px < W && py < H) {
+            const PixelGrad g = pixel_grad_load(pix_state, g_rgb, g_depth, c.b, HW, (size_t)py * W + px, bg0, bg1, bg2);
+            gr[s] = g.gr; gg[s] = g.gg; gb[s] = g.gb; gd[s] = g.gd;
+            S[s] = g.Tf * (gr[s] * bg0 + gg[s] * bg1 + gb[s] * bg2) + (gr[s] * g.Cr + gg[s] * g.Cg + gb[s] * g.Cb) + gd[s] * g.D;
+        }
+        if (seg) {
+            // restart from the forward's state in front of this segment: T, and S minus the part of Total that
+            // belongs to the list entries before it.  After a depth-split forward (k_blend_fwd_parts, fwd_parts
+            // waves per tile) the checkpoint of a segment inside part p > 0 is local to that part and is re-based
+            // with the absolute state kept in the slot of the part's first segment.
+            BlendState st = ckpt_load<PL>(seg_ckpt + (size_t)unit * SLOT + s * 64 + lane);
+            if (rebase_seg != seg) {
+                const size_t slot = (size_t)unit - seg + rebase_seg;
+                st = compose(ckpt_load<PL>(seg_ckpt + slot * SLOT + s * 64 + lane), st);
+            }
+            T[s] = st.T;
+            // (the sum written out in the order it has always been formed in: under fast-math the compiler is free to re-associate
+            // it, and did as soon as the code behind the prologue changed -- S, and every geometry row, moved by an ulp)
+            S[s] -= __builtin_fmaf(gd[s], st.D, __builtin_fmaf(gb[s], st.Cb, __builtin_fmaf(gg[s], st.Cg, gr[s] * st.Cr)));
+            if (px < W && py < H && T[s] != 0.0f) live_px = true;  // (a NaN checkpoint is live: the general walk carries it)
+        }
+    }
+    // DEAD UNIT: every in-frame pixel of the tile restarts with T == +0.0f (the forward's A rounded to 1.0f: its T <= 2^-25) and
+    // keeps it for the whole unit (fma(+0, -0.99, +0) = +0).  Lanes outside the frame (T = 1, g = 0, S = 0) do not veto: the
+    // bboxes are clipped to the frame (k_project), so stage_decode_w's column / row bits mask their a' to zero and they add
+    // exact zeros in either walk.  Never with FgsDims.saturation_skip, never for a tile's first segment (T = 1).
+    const bool dead_unit = seg != 0 && !(t_eps > 0.0f) && __ballot(live_px) == 0ull;
+    uint32_t alive = (1u << NS) - 1u;  // sub-tiles still composited (FgsDims.saturation_skip; 16 x 16 tiles only)
+    if (t_eps > 0.0f) {
+        alive = 0u;
+#pragma unroll
+        for (int s = 0; s < NS; ++s)
+            if (__ballot(T[s] >= t_eps) != 0ull) alive |= 1u << s;  // T = 1 - A of the checkpoint, as in the forward
+    }
+    if (dead_unit) {
+        BwdDeadArgs<NSX> a;
+        a.c = c; a.dcap = dcap; a.dup_ids = dup_ids; a.rec = rec; a.dup_off = dup_off; a.grad_rows = grad_rows;
+#pragma unroll
+        for (int s = 0; s < NS; ++s) a.S[s] = S[s];
+        composite_bwd_dead_walk<NSX>(a);
+        return;
+    }
+    composite_bwd_walk<NSX, false>(c, lane, lx, ly, dcap, alive, dup_ids, rec, dup_off, grad_rows, gr, gg, gb, gd, S, T);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
