@@ -506,12 +506,16 @@ __global__ __launch_bounds__(64 * NP * (1 + WIDE)) __attribute__((amdgpu_waves_p
 // LDS of k_composite_bwd, at file scope: the kernel and the dead unit's walk (a function of its own, below) name the same arrays
 __shared__ float4 bwd_sh0[CH], bwd_sh1[CH], bwd_sh2[CH];
 __shared__ uint32_t bwd_she[CH];
-__shared__ __attribute__((aligned(16))) float bwd_red[10 * FGS_RED_PITCH];  // per-lane partial sums of one list entry
+// per-lane partial sums of one list entry (ten values) -- on 32 x 16 tiles also of a PAIR of a dead unit's entries (six values each:
+// cells 0-5 and 6-11).  One array per tile shape, so that k_composite_bwd<2> keeps its 6048 bytes: with twelve pitches (6592 bytes)
+// config 2's backward measured 3.3 % slower -- its 24 one-wave blocks per CU apparently no longer fit the LDS (DESIGN_LOG.md 22)
+__shared__ __attribute__((aligned(16))) float bwd_red[10 * FGS_RED_PITCH];
+__shared__ __attribute__((aligned(16))) float bwd_red_pairs[12 * FGS_RED_PITCH];
 #define FGS_BWD_G __attribute__((address_space(1)))  /* global memory, also where the pointer arrives as a function argument */
 
 // The chunk / list loop of k_composite_bwd over the unit's entries [c.start, c.end), in two instantiations: DEAD = false the general
 // walk, inlined into the kernel; DEAD = true the walk of a dead unit (see the kernel), whose pass computes only what is not an exact
-// zero there (see `pass`; g*, T are not read).  Staging, the LDS record layout, the emission slot, the deferred reduction and the row
+// zero there (see `dead_passes`; g*, T are not read).  Staging, the LDS record layout, the emission slot, the deferred reduction and the row
 // store are the same code in both.
 template <int NSX, bool DEAD>
 __device__ __forceinline__ void composite_bwd_walk(const TileCtx &c, uint32_t lane, uint32_t lx, uint32_t ly, uint32_t dcap, uint32_t alive,
@@ -523,7 +527,8 @@ __device__ __forceinline__ void composite_bwd_walk(const TileCtx &c, uint32_t la
     // geometric sums per sub-tile row, folded once per list entry (below).  32 x 16 tiles only: with at most four passes per
     // entry the fold costs what the passes save, and 16 x 16 tiles measured 0.8 % SLOWER that way (DESIGN_LOG.md 15)
     constexpr bool ROW_MOMENTS = NSX == 4;
-    auto &sh0 = bwd_sh0; auto &sh1 = bwd_sh1; auto &sh2 = bwd_sh2; auto &she = bwd_she; auto &red = bwd_red;
+    auto &sh0 = bwd_sh0; auto &sh1 = bwd_sh1; auto &sh2 = bwd_sh2; auto &she = bwd_she;
+    auto &red = *[]() { if constexpr (NSX == 4) return &bwd_red_pairs; else return &bwd_red; }();
     const uint32_t shx = lx, shy = 16u + ly;  // this lane's column bit in the staged column bits / row bit in the flags
     float fx0 = (float)(c.X0 + lx), fy0 = (float)(c.Y0 + ly);
     asm("" : "+v"(fx0), "+v"(fy0));  // hoisted for good: no v_cvt in the list loop
@@ -537,6 +542,140 @@ __device__ __forceinline__ void composite_bwd_walk(const TileCtx &c, uint32_t la
         const float tot = wave_sum_addtid_finish(red, lane, 10u);
         // (16-float rows: all sixteen quads' last lanes store, lanes >= 40 a zero -- one whole 64-byte line)
         if ((lane & 3u) == 3u && lane < 4u * FGS_BLEND_ROW_FLOATS && e_prev < dcap) ((FGS_BWD_G float *)grad_rows)[(size_t)e_prev * FGS_BLEND_ROW_FLOATS + (lane >> 2)] = tot;
+    };
+    // ---- the list loop of a DEAD unit (round 11; DESIGN_LOG.md 22) ----
+    // T == +0 on every pixel that is not masked: w = a' T = +0, S keeps its value (S -= w q), the colour / depth sums are exact
+    // zeros and dalpha = T q - S r = -(S r) (T q = +-0; q is finite, or S is already NaN: a non-finite colour or upstream gradient
+    // reaches S through the forward's saved state in the prologue).  So a dead entry has SIX sums, not ten, and -- S being read-only,
+    // T constant -- needs nothing from the entry before it.  On 32 x 16 tiles the walk therefore takes its entries in PAIRS: entries
+    // j, j + 1 of a chunk (CH is even: only a unit's last entry can be single) share one reduction round and one row store.  A parks
+    // its sums in value cells 0-5 of `red`, B in 6-11; one wave_sum_addtid_finish over 12 values -- the same 16-partial sums and DPP
+    // steps per value -- leaves value k in the quad-last lane of quad k < 12, which stores float k % 6 of row e[k / 6]; lanes 48-55,
+    // whose `tot` is +0.0f, store floats 6-9 of the two rows (the sum of 64 parked +0 is +0: the bits of the rows are unchanged).
+    // Still deferred by one round: the read-back travels with the next pair's records.  16 x 16 tiles take one entry per round (six
+    // values, lanes 24-27 the zeros): the two pitches more of LDS cost their kernel 3.3 %, which is more than the pairing saves.
+    // (Running a wholly touched sub-tile row's passes as one branch-free block, select hoisted, was built and measured 0.5 % SLOWER.)
+    // What a pass computes is written in exactly the forms the general pass compiles to (contraction is on in this unit, and nothing
+    // makes two copies of one expression contract alike): exponent = two FMAs; -(S r) = S rcp(a' - 1 / 0.99); every moment an FMA onto
+    // its sum, from the ROUNDED dG and dG dx; the fold's three dy sums as the FMAs the general walk's fold contracts to.  The rows are
+    // the general walk's to the bit (but for the sign of an exact zero: see the kernel).
+    constexpr bool PAIRS = NSX == 4;
+    constexpr uint32_t DSUMS = 6, DROWS = PAIRS ? 2 : 1, DZERO = FGS_BLEND_ROW_FLOATS - DSUMS;  // sums / rows per round, zero floats per row
+    static_assert(4 * DSUMS * DROWS + DROWS * DZERO <= 64, "dead walk: one lane per zero float behind the sums' lanes");
+    [[maybe_unused]] uint32_t e_prevB = ~0u;  // row of the parked pair's second entry (none: no row passes e < dcap)
+    [[maybe_unused]] auto reduce_parked_dead = [&]() {
+        const float tot = wave_sum_addtid_finish(red, lane, DSUMS * DROWS);  // lanes >= 4 DSUMS DROWS: +0.0f
+        const uint32_t k = lane >> 2, z = lane - 4u * DSUMS * DROWS;
+        const bool sum_lane = (lane & 3u) == 3u && k < DSUMS * DROWS, zero_lane = lane >= 4u * DSUMS * DROWS && z < DROWS * DZERO;
+        const bool second = sum_lane ? k >= DSUMS : z >= DZERO;  // this lane stores into the pair's second row
+        const uint32_t col = sum_lane ? (second ? k - DSUMS : k) : DSUMS + (second ? z - DZERO : z);
+        const uint32_t e = PAIRS && second ? e_prevB : e_prev;
+        if ((sum_lane || zero_lane) && e < dcap) ((FGS_BWD_G float *)grad_rows)[(size_t)e * FGS_BLEND_ROW_FLOATS + col] = tot;
+    };
+    // what the passes of one entry read: formed for both entries of a pair before either's passes run
+    struct DeadTerms {
+        float ca, dya, dyb, bdya, bdyb, cyya, cyyb, dxs[NSX];
+        uint32_t mxs[NSX], my0, my1, msk, cflag;
+    };
+    [[maybe_unused]] auto dead_terms = [&](const float4 &q0, const float4 &q1, const float4 &q2, const uint32_t fl) {
+        DeadTerms t;
+        t.msk = fl & alive;
+        t.cflag = fl & 256u;  // clear: the clamp-gradient select (a scalar, tested where it is used: see the general walk)
+        asm("" : "+s"(t.cflag));
+        const uint32_t cbits = __float_as_uint(q2.z), rbits = __float_as_uint(q2.w);
+        const float cbc = q0.w, cd = q1.x, lop = q1.y;
+        t.ca = q0.z;
+        const float dxa = fx0 - q0.x;
+        t.dya = fy0 - q0.y; t.dyb = t.dya + 8.0f;
+        t.bdya = cbc * t.dya; t.bdyb = cbc * t.dyb; t.cyya = fmaf(cd * t.dya, t.dya, lop); t.cyyb = fmaf(cd * t.dyb, t.dyb, lop);
+        asm("" : "+v"(t.bdya), "+v"(t.bdyb), "+v"(t.cyya), "+v"(t.cyyb));
+#pragma unroll
+        for (int col = 0; col < NSX; ++col) {
+            t.mxs[col] = (uint32_t)__builtin_amdgcn_sbfe((int)cbits, shx + 8u * col, 1);
+            t.dxs[col] = dxa + 8.0f * col;
+        }
+        t.my0 = (uint32_t)__builtin_amdgcn_sbfe((int)rbits, shy, 1); t.my1 = (uint32_t)__builtin_amdgcn_sbfe((int)rbits, shy + 8u, 1);
+        return t;
+    };
+    // the passes and the fold of one dead entry: its six sums {mx, my, ca, cbc, cd, op} (see the general walk for what they are)
+    [[maybe_unused]] auto dead_passes = [&](const DeadTerms &t, float (&vals)[DSUMS]) {
+        float v_mx = 0, v_my = 0, v_ca = 0, v_cbc = 0, v_cd = 0, v_op = 0;
+        float mA[2] = {0.0f, 0.0f}, mB[2] = {0.0f, 0.0f}, mC[2] = {0.0f, 0.0f};  // per sub-tile row (ROW_MOMENTS)
+        auto pass = [&](const int s) {
+            const int col = s % NSX, row = s / NSX;
+            const float dx = t.dxs[col], dy = row ? t.dyb : t.dya;
+            const uint32_t mk = t.mxs[col] & (row ? t.my1 : t.my0);
+            const float tt = __builtin_fmaf(dx, t.ca, row ? t.bdyb : t.bdya);
+            const float a1 = blend_alpha1(__builtin_fmaf(tt, dx, row ? t.cyyb : t.cyya), mk);
+            float dalpha = S[s] * __builtin_amdgcn_rcpf(a1 - INV_ALPHA_MAX);
+            uint32_t cf = t.cflag;
+            asm("" : "+s"(cf));  // an opaque scalar per use: one s_cmp + branch, nothing on the vector side
+            if (!cf) dalpha = select_lt1(a1, dalpha);
+            // (opaque products: under fast-math the first pass of a row, whose sums start from zero, otherwise re-associates
+            // (dG dx) dx into (dx dx) dG -- another rounding than the general pass's)
+            float dG = dalpha * a1;
+            asm("" : "+v"(dG));
+            if constexpr (ROW_MOMENTS) {
+                mA[row] = __builtin_fmaf(dalpha, a1, mA[row]);
+                float dmx = dG * dx;
+                asm("" : "+v"(dmx));
+                mB[row] = __builtin_fmaf(dG, dx, mB[row]); mC[row] = __builtin_fmaf(dmx, dx, mC[row]);
+            } else {
+                v_op = __builtin_fmaf(dalpha, a1, v_op);
+                float dmx = dG * dx, dmy = dG * dy;
+                asm("" : "+v"(dmx), "+v"(dmy));
+                v_mx = __builtin_fmaf(dG, dx, v_mx); v_my = __builtin_fmaf(dG, dy, v_my);
+                v_ca = __builtin_fmaf(dmx, dx, v_ca); v_cbc = __builtin_fmaf(dmx, dy, v_cbc); v_cd = __builtin_fmaf(dmy, dy, v_cd);
+            }
+        };
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            if (!((t.msk >> s) & 1u)) continue;  // scalar branch: sub-tile not touched
+            pass(s);
+        }
+        if constexpr (ROW_MOMENTS) {  // the general walk's fold, its three dy sums written as what they contract to there
+            v_op = mA[0] + mA[1]; v_mx = mB[0] + mB[1]; v_ca = mC[0] + mC[1];
+            float t0 = t.dya * mA[0], t1 = t.dyb * mA[1];
+            asm("" : "+v"(t0), "+v"(t1));
+            float p0 = t0 * t.dya, pb = mB[0] * t.dya;
+            asm("" : "+v"(p0), "+v"(pb));
+            v_my = __builtin_fmaf(mA[1], t.dyb, t0);
+            v_cd = __builtin_fmaf(t1, t.dyb, p0);
+            v_cbc = __builtin_fmaf(mB[1], t.dyb, pb);
+        }
+        vals[0] = v_mx; vals[1] = v_my; vals[2] = v_ca; vals[3] = v_cbc; vals[4] = v_cd; vals[5] = v_op;
+    };
+    // one staged chunk of n entries.  The second record of a single entry (n odd: j + 1 = n <= CH - 1) is read from LDS like any
+    // other but has no flags (no pass runs) and no row (nothing is stored).
+    [[maybe_unused]] auto dead_chunk = [&](const uint32_t n) {
+        for (uint32_t j = 0; j < n; j += DROWS) {
+            const float4 a0 = sh0[j], a1 = sh1[j], a2 = sh2[j];
+            uint32_t eA = __builtin_amdgcn_readfirstlane(she[j]), eB = ~0u;
+            float4 b0 = a0, b1 = a1, b2 = a2;
+            if constexpr (PAIRS) {
+                b0 = sh0[j + 1]; b1 = sh1[j + 1]; b2 = sh2[j + 1];
+                eB = __builtin_amdgcn_readfirstlane(she[j + 1]);
+            }
+            reduce_parked_dead();  // the previous round's sums
+            asm volatile("" : "+s"(eA), "+s"(eB));  // taken here, with the records (see the general walk)
+            const bool paired = PAIRS && j + 1 < n;
+            e_prev = eA; e_prevB = paired ? eB : ~0u;
+            const uint32_t flA = __builtin_amdgcn_readfirstlane(__float_as_uint(a2.w));
+            const DeadTerms ta = dead_terms(a0, a1, a2, flA);
+            float va[DSUMS];
+            if constexpr (PAIRS) {
+                const uint32_t flB = paired ? __builtin_amdgcn_readfirstlane(__float_as_uint(b2.w)) : 0u;
+                const DeadTerms tb = dead_terms(b0, b1, b2, flB);
+                float vb[DSUMS];
+                dead_passes(ta, va);
+                addtid_park(red, va);
+                dead_passes(tb, vb);
+                addtid_park(red + DSUMS * FGS_RED_PITCH, vb);
+            } else {
+                dead_passes(ta, va);
+                addtid_park(red, va);
+            }
+        }
     };
     for (uint32_t base = c.start; base < c.end; base += CH) {
         // the list loop's trip count, pinned to an SGPR: left to itself the compiler keeps it in a VGPR (it is compared with `lane`
@@ -565,7 +704,8 @@ __device__ __forceinline__ void composite_bwd_walk(const TileCtx &c, uint32_t la
             sh0[sl] = q0; sh1[sl] = q1; sh2[sl] = q2;
         }
         __syncthreads();
-        for (uint32_t j = 0; j < n; ++j) {
+        if constexpr (DEAD) dead_chunk(n);
+        for (uint32_t j = 0; !DEAD && j < n; ++j) {  // the general walk's list loop
             const float4 q0 = sh0[j], q1 = sh1[j], q2 = sh2[j];
             uint32_t e = __builtin_amdgcn_readfirstlane(she[j]);
             reduce_parked();  // the previous entry's sums
@@ -617,37 +757,6 @@ __device__ __forceinline__ void composite_bwd_walk(const TileCtx &c, uint32_t la
                     // a' is zeroed outside the bbox: w and every gradient term below then vanish by themselves
                     const int col = s % NSX, row = s / NSX;
                     const float dx = dxs[col], dy = row ? dyb : dya;
-                    if constexpr (DEAD) {
-                        // T == +0 on every pixel that is not masked: w = a' T = +0, S keeps its value (S -= w q), the colour / depth sums
-                        // get exact zeros and dalpha = T q - S r = -(S r) (T q = +-0; q is finite, or S is already NaN: a non-finite colour
-                        // or upstream gradient reaches S through the forward's saved state in the prologue).  What is left is written in
-                        // exactly the forms the general pass compiles to (contraction is on in this unit, and nothing makes two copies of
-                        // one expression contract alike): exponent = two FMAs; -(S r) = S rcp(a' - 1 / 0.99); every moment an FMA onto
-                        // its sum, from the ROUNDED dG and dG dx.  The rows are the general walk's to the bit.
-                        const float t = __builtin_fmaf(dx, ca, row ? bdyb : bdya);
-                        const float a1 = blend_alpha1(__builtin_fmaf(t, dx, row ? cyyb : cyya), mk);
-                        float dalpha = S[s] * __builtin_amdgcn_rcpf(a1 - INV_ALPHA_MAX);
-                        uint32_t cf = cflag;
-                        asm("" : "+s"(cf));
-                        if (!cf) dalpha = select_lt1(a1, dalpha);
-                        // (opaque products: under fast-math the first pass of a row, whose sums start from zero, otherwise re-associates
-                        // (dG dx) dx into (dx dx) dG -- another rounding than the general pass's)
-                        float dG = dalpha * a1;
-                        asm("" : "+v"(dG));
-                        if constexpr (ROW_MOMENTS) {
-                            mA[row] = __builtin_fmaf(dalpha, a1, mA[row]);
-                            float dmx = dG * dx;
-                            asm("" : "+v"(dmx));
-                            mB[row] = __builtin_fmaf(dG, dx, mB[row]); mC[row] = __builtin_fmaf(dmx, dx, mC[row]);
-                        } else {
-                            v_op = __builtin_fmaf(dalpha, a1, v_op);
-                            float dmx = dG * dx, dmy = dG * dy;
-                            asm("" : "+v"(dmx), "+v"(dmy));
-                            v_mx = __builtin_fmaf(dG, dx, v_mx); v_my = __builtin_fmaf(dG, dy, v_my);
-                            v_ca = __builtin_fmaf(dmx, dx, v_ca); v_cbc = __builtin_fmaf(dmx, dy, v_cbc); v_cd = __builtin_fmaf(dmy, dy, v_cd);
-                        }
-                        return;
-                    }
                     const float t = ca * dx + (row ? bdyb : bdya);
                     const float a1 = blend_alpha1(t * dx + (row ? cyyb : cyya), mk);  // alpha / 0.99: v_exp ... clamp, v_and
                     const float w = a1 * T[s];  // w / 0.99
@@ -694,7 +803,7 @@ __device__ __forceinline__ void composite_bwd_walk(const TileCtx &c, uint32_t la
         }
         __syncthreads();
     }
-    reduce_parked();  // the unit's last entry
+    if constexpr (DEAD) reduce_parked_dead(); else reduce_parked();  // the unit's last entry (or pair)
 }
 
 // The dead unit's walk as a function of its own, CALLED by the kernel: inlined next to the general walk it cost that walk registers

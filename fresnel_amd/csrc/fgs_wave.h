@@ -95,6 +95,9 @@ typedef __attribute__((address_space(3))) float fgs_lds_float;
                      : __VA_ARGS__, [base] "s"((uint32_t)(uintptr_t)(fgs_lds_float *)red)                          \
                      : "memory");                                                                                  \
     }
+// (6: one dead-unit entry of the blend backward, which parks two entries' values side by side: cells 0-5 and 6-11 of one `red`)
+FGS_DEFINE_PARK(6, FGS_PARK_ST(0, 0) FGS_PARK_ST(1, 272) FGS_PARK_ST(2, 544) FGS_PARK_ST(3, 816) FGS_PARK_ST(4, 1088) FGS_PARK_ST(5, 1360),
+                FGS_PARK_OP(0), FGS_PARK_OP(1), FGS_PARK_OP(2), FGS_PARK_OP(3), FGS_PARK_OP(4), FGS_PARK_OP(5))
 FGS_DEFINE_PARK(10, FGS_PARK_ST10, FGS_PARK_OP10)
 FGS_DEFINE_PARK(11, FGS_PARK_ST10 FGS_PARK_ST(10, 2720), FGS_PARK_OP10, FGS_PARK_OP(10))
 FGS_DEFINE_PARK(12, FGS_PARK_ST10 FGS_PARK_ST(10, 2720) FGS_PARK_ST(11, 2992), FGS_PARK_OP10, FGS_PARK_OP(10), FGS_PARK_OP(11))
@@ -107,7 +110,7 @@ FGS_DEFINE_PARK(13, FGS_PARK_ST10 FGS_PARK_ST(10, 2720) FGS_PARK_ST(11, 2992) FG
 #undef FGS_PARK_ST
 
 // Second half of the sum: adds the parked values up; returns, in lanes with (lane & 3) == 3 and lane < 4 nv, the total of value
-// lane >> 2 (other lanes: junk).  `red` is 16-B aligned.
+// lane >> 2 (other lanes below 4 nv: junk; lanes >= 4 nv: +0.0f, which the blend backward's dead walk stores).  `red` is 16-B aligned.
 __device__ __forceinline__ float wave_sum_addtid_finish(const float *red, uint32_t lane, uint32_t nv) {
     __builtin_amdgcn_wave_barrier();
     float tot = 0.0f;
