@@ -31,6 +31,7 @@ EXPORTED_SYMBOLS = [
     "fgs_nca_update_backward",
     "fgs_saag_workspace_bytes", "fgs_saag_inputs_forward", "fgs_saag_refine_forward", "fgs_saag_refine_backward",
     "fgs_physics_workspace_bytes", "fgs_physics_forward", "fgs_physics_backward",
+    "fgs_surface_workspace_bytes", "fgs_surface_count", "fgs_surface_emit",
 ]
 
 STAGES = ["project", "depth_sort", "dup_emit", "tile_sort", "tile_ranges", "composite_fwd",
@@ -141,6 +142,33 @@ class FgsPhysicsDims(ctypes.Structure):
 FGS_PHYSICS_RANGE_BYTES = 16  # float z_min, z_max; int32 n_min, n_max (include/fgs.h)
 
 
+class FgsSurfaceDims(ctypes.Structure):
+    _fields_ = [("batch", ctypes.c_int32), ("height", ctypes.c_int32), ("width", ctypes.c_int32)]
+
+
+class FgsSurfaceParams(ctypes.Structure):
+    _fields_ = [("fx", ctypes.c_float), ("fy", ctypes.c_float), ("cx", ctypes.c_float), ("cy", ctypes.c_float),
+                ("depth_scale", ctypes.c_float), ("subsample", ctypes.c_int32), ("opacity", ctypes.c_float),
+                ("normalize_extent", ctypes.c_float),
+                ("base_size", ctypes.c_float), ("aspect_ratio", ctypes.c_float), ("edge_threshold", ctypes.c_float),
+                ("edge_shrink", ctypes.c_float), ("min_confidence", ctypes.c_float), ("gradient_scale", ctypes.c_float),
+                ("normal_strength", ctypes.c_float),
+                ("wrap_enabled", ctypes.c_int32), ("wrap_edge_threshold", ctypes.c_float), ("wrap_layers", ctypes.c_int32),
+                ("wrap_layer_spacing", ctypes.c_float), ("wrap_opacity_falloff", ctypes.c_float),
+                ("wrap_max_angle", ctypes.c_float), ("wrap_aspect", ctypes.c_float),
+                ("shell_enabled", ctypes.c_int32), ("shell_thickness", ctypes.c_float), ("shell_back_opacity", ctypes.c_float),
+                ("shell_back_darken", ctypes.c_float), ("shell_connect_walls", ctypes.c_int32),
+                ("shell_wall_segments", ctypes.c_int32), ("shell_wall_opacity", ctypes.c_float),
+                ("shell_edge_threshold", ctypes.c_float),
+                ("density_enabled", ctypes.c_int32), ("density_gradient_threshold", ctypes.c_float),
+                ("density_extra_count", ctypes.c_int32), ("density_position_jitter", ctypes.c_float),
+                ("density_size_variance", ctypes.c_float), ("density_opacity_scale", ctypes.c_float), ("seed", ctypes.c_uint32)]
+
+
+FGS_SURFACE_STATE_OFFSET = 64
+(FGS_SURFACE_KEPT, FGS_SURFACE_BASE, FGS_SURFACE_BACK, FGS_SURFACE_WALLS, FGS_SURFACE_WRAPS, FGS_SURFACE_FILLS) = (1, 2, 4, 8, 16, 32)
+
+
 class FgsError(RuntimeError):
     pass
 
@@ -242,6 +270,12 @@ def load():
     lib.fgs_physics_forward.argtypes = [phd] + [vp] * 13
     lib.fgs_physics_backward.argtypes = [phd] + [vp] * 15
     for fn in (lib.fgs_physics_workspace_bytes, lib.fgs_physics_forward, lib.fgs_physics_backward):
+        fn.restype = ctypes.c_int
+    sfd, sfp = cp(FgsSurfaceDims), cp(FgsSurfaceParams)
+    lib.fgs_surface_workspace_bytes.argtypes = [sfd, sfp, cp(ctypes.c_size_t)]
+    lib.fgs_surface_count.argtypes = [sfd, sfp] + [vp] * 4
+    lib.fgs_surface_emit.argtypes = [sfd, sfp] + [vp] * 9 + [ctypes.c_int64, vp]
+    for fn in (lib.fgs_surface_workspace_bytes, lib.fgs_surface_count, lib.fgs_surface_emit):
         fn.restype = ctypes.c_int
     for fn in (lib.fgs_asm_propagate_workspace_bytes, lib.fgs_asm_propagate_forward, lib.fgs_asm_propagate_backward,
                lib.fgs_spectral_workspace_bytes, lib.fgs_spectral_loss_forward, lib.fgs_spectral_loss_backward,

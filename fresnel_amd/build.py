@@ -72,6 +72,9 @@ SOURCES = {
     # as the head (the backward recomputes the forward); and the z_norm / phase chain is DEFINED with every operation rounded on its
     # own and an IEEE divide (include/fgs.h): the wrapped phase of an unwrapped value up to 314 is torch's fp32 result bit for bit
     "fgs_physics.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
+    # the "canonical fp32" contract of fgs_project.hip again: how many rows a point emits, and in which order, is decided by
+    # compares of values that a literal fp32 restatement of the reference must reproduce bit for bit (include/fgs.h)
+    "fgs_surface.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
 }
 LINK_LIBS = ["-lhipfft"]
 

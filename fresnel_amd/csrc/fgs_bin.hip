@@ -8,31 +8,9 @@
 // sized from capacities and kernels read D from saved.counters, so the whole forward is
 // free of host synchronisation and can be captured in a hipGraph.
 #include "fgs_internal.h"
+#include "fgs_scan.h"  // block_exclusive_scan_256
 
 namespace {
-
-// exclusive scan of one value per thread over a 256-thread block; returns block total in *tot
-__device__ __forceinline__ uint32_t block_exclusive_scan_256(uint32_t v, uint32_t *tot) {
-    __shared__ uint32_t wsum[4];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t s = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t t = __shfl_up(s, o, 64);
-        if ((int)lane >= o) s += t;
-    }
-    if (lane == 63) wsum[wave] = s;
-    __syncthreads();
-    uint32_t pre = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-        const uint32_t x = wsum[w];
-        pre += (w < (int)wave) ? x : 0u;
-        all += x;
-    }
-    *tot = all;
-    return pre + s - v;
-}
 
 // tile count of the r-th Gaussian (depth order) of image b
 __device__ __forceinline__ uint32_t sorted_count(uint32_t i, uint32_t total, uint32_t N,

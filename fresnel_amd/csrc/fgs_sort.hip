@@ -32,6 +32,7 @@
 // harness with --use_fresnel_zones, bench.py --workload config4), never a default: any data sorts correctly in either mode.
 #include <type_traits>
 #include "fgs_internal.h"
+#include "fgs_scan.h"  // wave_incl_scan
 
 namespace {
 
@@ -78,17 +79,6 @@ __device__ __forceinline__ void match_rank(uint32_t digit, bool valid, uint32_t 
     }
     rank = __builtin_amdgcn_mbcnt_hi(mhi, __builtin_amdgcn_mbcnt_lo(mlo, 0u));
     count = (uint32_t)__popc(mlo) + (uint32_t)__popc(mhi);
-}
-
-// Inclusive sum over the wave's lanes 0 ... own.
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t s) {
-    const uint32_t lane = threadIdx.x & 63u;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t t = __shfl_up(s, o, 64);
-        if ((int)lane >= o) s += t;
-    }
-    return s;
 }
 
 // Stable rank of a key among the keys of digit `digit` that its wave has ranked so far, this chunk of 64 included: ranking against

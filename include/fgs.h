@@ -601,6 +601,107 @@ int fgs_physics_backward(const FgsPhysicsDims *dims, const float *raw, const flo
                          float *g_wavelength_raw, void *scratch, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * SAAG surface-aligned Gaussian clouds from depth: the producer of the `{name}_saag.bin` caches that --experiment 1 refines.
+ * Mirrors the reference's C++ application: PointCloud::from_depth (src/core/pointcloud.cpp:8-76), center / normalize (:433-479),
+ * to_surface_gaussians (:100-431), DepthMap::compute_surface_info (src/core/image.cpp:157-225), driven as the viewer drives them
+ * (src/viewer/viewer.cpp:354-428).  Forward only.  All tensors fp32, contiguous, DEVICE.
+ *   depth      (B, H, W)     already curve-adjusted (the caller applies pow(depth, depth_exponent))
+ *   color      (B, 3, H, W)  or NULL = grey 0.7
+ *   points     one per (x, y) with x = 0, s, 2 s ... < W and y likewise (s = subsample), row-major: P = ceil(W / s) ceil(H / s) per image
+ *   outputs    positions (N,3), scales (N,3), rotations (N,4) w,x,y,z, colors (N,3), opacities (N,): the images' clouds one after the
+ *              other; image b owns the rows offsets[b] ... offsets[b + 1] - 1, N = offsets[B].  offsets: B + 1 DEVICE int32.
+ * Per image: [min_d, max_d] over ALL pixels, range = max_d - min_d (1 when < 1e-6f).  Per point: u = (d - min_d) / range (also the
+ * confidence), z = (1 - u) depth_scale, dropped when z < 0.01f depth_scale; X = (x - cx) / fx z, Y = (cy - y) / fy z, Z = -z.  With
+ * normalize_extent > 0 the kept points are centred on their bounding box's centre, centred AGAIN (normalize() centres itself), then
+ * scaled by normalize_extent / (largest extent) unless that extent is < 1e-6f.  (p - c is monotone in p, so the second and third
+ * bounding boxes are the first one shifted: one reduction, the same bits as three.)  Sobel gradient (gx, gy) of the depth at the point's
+ * pixel with ZERO outside the frame (border pixels carry large gradients, as in the reference); max_gradient = largest
+ * sqrt(gx gx + gy gy) over the KEPT points, those skipped below included (1 when < 1e-6f).  Rows of a point, in this order:
+ *   nothing when confidence < min_confidence; else 1 base;
+ *   + 1 back when shell_enabled and g > shell_edge_threshold (g = gradient magnitude / max_gradient), + wall_segments walls when also
+ *     connect_walls and the wall tangent is longer than 0.1;
+ *   + wrap_layers wraps when wrap_enabled, g > wrap_edge_threshold and the gradient direction is longer than 0.1;
+ *   + extra_count fills when density_enabled and g > density_gradient_threshold (jitter: the reference's integer hash of pixel, index, seed).
+ * Every quantity behind these decisions is built from + - * / sqrt min max only, each rounded to fp32 on its own (no FMA, IEEE
+ * divide and sqrt, the reference's operation order): counts and row order are exact.  Rotations and wrap opacities go through
+ * acos / sin / cos / pow and agree with another implementation to a few ulps.
+ * Defaults of fx, fy, cx, cy: fx <= 0 means 0.8f W (the viewer's), fy <= 0 means fx; cx <= 0, cy <= 0 mean W / 2, H / 2.
+ *
+ * Two phases, so that the caller sizes the outputs and the library never allocates or synchronises:
+ * fgs_surface_count:  five launches (depth range, point bounds + max gradient, per-image fold, per-point decisions + block sums,
+ *     scan of the block sums).  Writes offsets (all B + 1) and, in scratch, what the emit needs.  scratch + FGS_SURFACE_STATE_OFFSET
+ *     holds one byte per point, image-major (B P bytes): FGS_SURFACE_KEPT | _BASE | _BACK | _WALLS | _WRAPS | _FILLS; the rest of
+ *     scratch is private.  scratch is written, never read before it is written.
+ * fgs_surface_emit:   one launch.  Reads depth, color, offsets and the scratch of the count call with the SAME dims and params; writes
+ *     every row below offsets[B] and nothing else.  `capacity` = the rows the caller allocated: when offsets[B] > capacity the kernel
+ *     writes NO row and sets the first int32 of scratch to 1 (else 0).  The total lives on the device, so the return value cannot
+ *     report that case without a synchronisation: the caller, who read offsets[B] to size the outputs, compares it first (as
+ *     fresnel_amd.surface does, which raises).  No atomics anywhere: two calls agree to the bit, and a batch equals its single images.
+ * NaN / Inf depth pixels: min_d / max_d ignore NaN (fminf / fmaxf); a NaN confidence fails both the drop and the skip compare, so
+ *     the point is kept and emits its base row; NaN gradients fail every threshold compare.  Float outputs may then be non-finite,
+ *     in that image only.  offsets stays monotone, a point never emits more than 2 + wall_segments + wrap_layers + extra_count rows,
+ *     and nothing is written outside the rows below offsets[B].
+ * Shapes: B, H, W >= 1, B <= 65535, B H W < 2^31, subsample >= 1, wall_segments, wrap_layers, extra_count >= 0,
+ * B P (2 + wall_segments + wrap_layers + extra_count) < 2^31; otherwise FGS_EINVAL (bad dims or params, null pointers) before anything
+ * touches the device. */
+typedef struct FgsSurfaceDims {
+    int32_t batch, height, width;
+} FgsSurfaceDims;
+typedef struct FgsSurfaceParams {
+    float fx, fy, cx, cy;              /* <= 0: see above */
+    float depth_scale;                 /* 2.5  (viewer.hpp:143) */
+    int32_t subsample;                 /* 1 */
+    float opacity;                     /* 0.9 */
+    float normalize_extent;            /* 3.0 (viewer.cpp:385-386); <= 0: neither centred nor normalised */
+    /* SurfaceGaussianParams (pointcloud.hpp:18-26) */
+    float base_size;                   /* 0.008 */
+    float aspect_ratio;                /* 5 */
+    float edge_threshold;              /* 0.15 */
+    float edge_shrink;                 /* 0.3 */
+    float min_confidence;              /* 0.1 */
+    float gradient_scale;              /* 50 */
+    float normal_strength;             /* 1 */
+    /* SilhouetteWrapParams (pointcloud.hpp:35-43) */
+    int32_t wrap_enabled;              /* 1 */
+    float wrap_edge_threshold;         /* 0.15 */
+    int32_t wrap_layers;               /* 3 */
+    float wrap_layer_spacing;          /* 0.5 */
+    float wrap_opacity_falloff;        /* 0.7 */
+    float wrap_max_angle;              /* 75; carried for completeness: the reference never reads it */
+    float wrap_aspect;                 /* 2 */
+    /* VolumetricShellParams (pointcloud.hpp:54-63) */
+    int32_t shell_enabled;             /* 1 */
+    float shell_thickness;             /* 0.3 */
+    float shell_back_opacity;          /* 0.6 */
+    float shell_back_darken;           /* 0.8 */
+    int32_t shell_connect_walls;       /* 1 */
+    int32_t shell_wall_segments;       /* 3 */
+    float shell_wall_opacity;          /* 0.5 */
+    float shell_edge_threshold;        /* 0.1 */
+    /* AdaptiveDensityParams (pointcloud.hpp:72-80) */
+    int32_t density_enabled;           /* 1 */
+    float density_gradient_threshold;  /* 0.08 */
+    int32_t density_extra_count;       /* 4 */
+    float density_position_jitter;     /* 0.6 */
+    float density_size_variance;       /* 0.3 */
+    float density_opacity_scale;       /* 0.7 */
+    uint32_t seed;                     /* 12345 */
+} FgsSurfaceParams;
+#define FGS_SURFACE_STATE_OFFSET 64
+#define FGS_SURFACE_KEPT 1
+#define FGS_SURFACE_BASE 2
+#define FGS_SURFACE_BACK 4
+#define FGS_SURFACE_WALLS 8
+#define FGS_SURFACE_WRAPS 16
+#define FGS_SURFACE_FILLS 32
+int fgs_surface_workspace_bytes(const FgsSurfaceDims *dims, const FgsSurfaceParams *params, size_t *scratch_bytes);
+int fgs_surface_count(const FgsSurfaceDims *dims, const FgsSurfaceParams *params, const float *depth, void *scratch,
+                      int32_t *offsets, void *stream);
+int fgs_surface_emit(const FgsSurfaceDims *dims, const FgsSurfaceParams *params, const float *depth, const float *color,
+                     void *scratch, const int32_t *offsets, float *o_positions, float *o_scales, float *o_rotations,
+                     float *o_colors, float *o_opacities, int64_t capacity, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Importance-subsampling hand-off between decoder and rasterizer (--stochastic_k; reference
  * scripts/training/train_gaussian_decoder.py:1160-1187): the n_out Gaussians whose indices torch.multinomial
  * drew (DEVICE int64 (n_out,), unique, shared by the batch) are gathered out of every (B, n_in, .) tensor into
