@@ -138,6 +138,14 @@ constexpr uint32_t MB_RANKS = FGS_BIN_G; // depth ranks per k_mask_build block (
 static_assert(MB_RANKS == 256, "k_mask_build: one 256-thread block = four 64-bit rank words per line");
 constexpr uint32_t TO_TILES = FGS_TILE_TABLE_TILES;     // tiles per block of the tile-table kernels (k_tile_pre / k_tile_post below)
 __device__ __forceinline__ uint32_t length_bucket(uint32_t len);
+// launch order of the blend backward's units (behind k_tile_post below): slice `g` by one block of THREADS threads.  The emit kernels of
+// the mask binning run it in `nub` (0 | 8) blocks of their own in front of their other blocks -- it needs k_tile_post's tables, as they do,
+// and nothing waits for it before the backward -- so that the table costs no launch there.
+constexpr uint32_t UO_BOUNDS = 256;                 // chunk boundaries kept in LDS; the chunks of longer launches read theirs from memory
+constexpr uint32_t UO_LDS_WORDS = 64 + 16 + 1 + UO_BOUNDS + 1;  // block-shared scratch of unit_order_slice
+template <uint32_t THREADS>
+__device__ void unit_order_slice(uint32_t g, uint32_t ntiles, const uint32_t *__restrict__ ranges, const uint32_t *__restrict__ seg_off,
+                                 const uint32_t *__restrict__ counters, uint32_t *__restrict__ unit_order, uint32_t *lds);
 constexpr uint32_t MB_MAX_LINES = FGS_MASK_MAX_LINES;  // tile columns + rows the build kernel keeps in LDS
 
 // order[b][i] = i: the "depth order" of a consumer that does not composite in depth order (FgsPlan.depth_ordered == false)
@@ -329,24 +337,31 @@ __global__ __launch_bounds__(256) void k_mask_emit(uint32_t B, uint32_t N, uint3
                                                    const uint32_t *__restrict__ ranges,
                                                    const uint32_t *__restrict__ bsum,
                                                    uint32_t *__restrict__ dup_ids, uint32_t *__restrict__ dup_off,
-                                                   const uint32_t *__restrict__ counters) {
+                                                   const uint32_t *__restrict__ counters, uint32_t nub,
+                                                   const uint32_t *__restrict__ seg_off, uint32_t *__restrict__ unit_order) {
     __shared__ uint32_t park[4][ME_CAP];
-    if (blockIdx.x < nrb) {
+    if (blockIdx.x < nub) {  // the first nub blocks: launch order of the backward's units, one slice each (first, so that they run
+        // beside the list blocks instead of behind them)
+        unit_order_slice<256>(blockIdx.x, B * layers * tiles, ranges, seg_off, counters, unit_order, &park[0][0]);
+        return;
+    }
+    const uint32_t bid = blockIdx.x - nub;
+    if (bid < nrb) {
         // duplicate offsets of one block of depth ranks: dup_off[g] = first gradient-row / emission slot of Gaussian
         // g = scanned block sum + prefix of the tile counts inside the block (rank order)
-        const uint32_t b = blockIdx.x / bpi, blk = blockIdx.x - b * bpi;
+        const uint32_t b = bid / bpi, blk = bid - b * bpi;
         const uint32_t r = blk * MB_RANKS + threadIdx.x;
         uint32_t g = 0, c = 0, tot;
         if (r < N) { g = b * N + order[b * N + r]; c = tile_count[g]; }
         const uint32_t ex = block_exclusive_scan_256(c, &tot);
-        if (r < N) dup_off[g] = bsum[blockIdx.x] + ex;
+        if (r < N) dup_off[g] = bsum[bid] + ex;
         return;
     }
+    const uint32_t ntb = gridDim.x - nrb - nub;
     if (counters[1] != 0u) return;  // duplicate-capacity overflow: every list is empty (k_tile_post), nothing to emit
     // consecutive tiles' lists are adjacent in dup_ids: an XCD gets a contiguous run of tiles (whole images at B = 8)
-    const uint32_t ntb = gridDim.x - nrb;
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t tile = fgs_xcd_remap(blockIdx.x - nrb, ntb) * 4u + wave;
+    const uint32_t tile = fgs_xcd_remap(bid - nrb, ntb) * 4u + wave;
     if (tile >= B * layers * tiles) return;
     const RankRange rr = rank_range(tile, N, tiles, layers, plane_start);
     const uint32_t b = rr.b, y = rr.t / tiles_x, x = rr.t - y * tiles_x;
@@ -471,21 +486,28 @@ __global__ __launch_bounds__(256) void k_mask_emit_group(uint32_t B, uint32_t N,
                                                          const uint32_t *__restrict__ ranges,
                                                          const uint32_t *__restrict__ bsum,
                                                          uint32_t *__restrict__ dup_ids, uint32_t *__restrict__ dup_off,
-                                                         const uint32_t *__restrict__ counters) {
+                                                         const uint32_t *__restrict__ counters, uint32_t nub,
+                                                         const uint32_t *__restrict__ seg_off, uint32_t *__restrict__ unit_order) {
     __shared__ uint32_t park[16][MG_CAP];
-    if (blockIdx.x < nrb) {  // duplicate offsets of one block of depth ranks (as in k_mask_emit)
-        const uint32_t b = blockIdx.x / bpi, blk = blockIdx.x - b * bpi;
+    if (blockIdx.x < nub) {  // the first nub blocks: launch order of the backward's units, one slice each (first, so that they run
+        // beside the list blocks instead of behind them)
+        unit_order_slice<256>(blockIdx.x, B * layers * tiles, ranges, seg_off, counters, unit_order, &park[0][0]);
+        return;
+    }
+    const uint32_t bid = blockIdx.x - nub;
+    if (bid < nrb) {  // duplicate offsets of one block of depth ranks (as in k_mask_emit)
+        const uint32_t b = bid / bpi, blk = bid - b * bpi;
         const uint32_t r = blk * MB_RANKS + threadIdx.x;
         uint32_t g = 0, c = 0, tot;
         if (r < N) { g = b * N + order[b * N + r]; c = tile_count[g]; }
         const uint32_t ex = block_exclusive_scan_256(c, &tot);
-        if (r < N) dup_off[g] = bsum[blockIdx.x] + ex;
+        if (r < N) dup_off[g] = bsum[bid] + ex;
         return;
     }
+    const uint32_t ntb = gridDim.x - nrb - nub;
     if (counters[1] != 0u) return;  // duplicate-capacity overflow: every list is empty (k_tile_post), nothing to emit
-    const uint32_t ntb = gridDim.x - nrb;
     const uint32_t glane = threadIdx.x & 15u, grp = threadIdx.x >> 4;
-    const uint32_t list = fgs_xcd_remap(blockIdx.x - nrb, ntb) * 16u + grp;
+    const uint32_t list = fgs_xcd_remap(bid - nrb, ntb) * 16u + grp;
     if (list >= B * layers * tiles) return;  // whole groups leave together
     const RankRange rr = rank_range(list, N, tiles, layers, plane_start);
     const uint32_t b = rr.b, y = rr.t / tiles_x, x = rr.t - y * tiles_x;
@@ -554,23 +576,30 @@ __global__ __launch_bounds__(256) void k_mask_emit_block(uint32_t B, uint32_t N,
                                                          const uint32_t *__restrict__ ranges,
                                                          const uint32_t *__restrict__ bsum,
                                                          uint32_t *__restrict__ dup_ids, uint32_t *__restrict__ dup_off,
-                                                         const uint32_t *__restrict__ counters) {
+                                                         const uint32_t *__restrict__ counters, uint32_t nub,
+                                                         const uint32_t *__restrict__ seg_off, uint32_t *__restrict__ unit_order) {
     constexpr uint32_t CAP = 4u * ME_CAP;
     __shared__ uint32_t park[CAP];
     __shared__ uint32_t wtot[4];
-    if (blockIdx.x < nrb) {  // duplicate offsets of one block of depth ranks (as in k_mask_emit)
-        const uint32_t b = blockIdx.x / bpi, blk = blockIdx.x - b * bpi;
+    if (blockIdx.x < nub) {  // the first nub blocks: launch order of the backward's units, one slice each (first, so that they run
+        // beside the list blocks instead of behind them)
+        unit_order_slice<256>(blockIdx.x, B * layers * tiles, ranges, seg_off, counters, unit_order, park);
+        return;
+    }
+    const uint32_t bid = blockIdx.x - nub;
+    if (bid < nrb) {  // duplicate offsets of one block of depth ranks (as in k_mask_emit)
+        const uint32_t b = bid / bpi, blk = bid - b * bpi;
         const uint32_t r = blk * MB_RANKS + threadIdx.x;
         uint32_t g = 0, c = 0, tot;
         if (r < N) { g = b * N + order[b * N + r]; c = tile_count[g]; }
         const uint32_t ex = block_exclusive_scan_256(c, &tot);
-        if (r < N) dup_off[g] = bsum[blockIdx.x] + ex;
+        if (r < N) dup_off[g] = bsum[bid] + ex;
         return;
     }
+    const uint32_t ntb = gridDim.x - nrb - nub;  // = number of lists
     if (counters[1] != 0u) return;  // duplicate-capacity overflow: every list is empty (k_tile_post), nothing to emit
-    const uint32_t ntb = gridDim.x - nrb;  // = number of lists
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const uint32_t tile = fgs_xcd_remap(blockIdx.x - nrb, ntb);
+    const uint32_t tile = fgs_xcd_remap(bid - nrb, ntb);
     const RankRange rr = rank_range(tile, N, tiles, layers, plane_start);
     const uint32_t b = rr.b, y = rr.t / tiles_x, x = rr.t - y * tiles_x;
     const unsigned long long *col = masks + ((size_t)b * lines + x) * w64p;
@@ -873,10 +902,108 @@ __global__ __launch_bounds__(256) void k_tile_post(uint32_t ntiles, uint32_t *__
     }
 }
 
+// unit_order: launch slot -> unit of the blend backward (k_composite_bwd reads unit_order[fgs_xcd_remap(blockIdx.x, U)]).
+// The backward's units are listed tile by tile, so when the dispatcher runs dry every SIMD holds units at random progress and the
+// launch drains at falling occupancy.  A list of `len` entries has len / seg_len FULL units and, unless seg_len divides len, one
+// PARTIAL unit, its last; the partial ones go to the END of the launch, longest first, and fill the slots the last full units free
+// (the forward's tile_order does the same for whole tiles).  XCD g keeps the units it has in unit order -- slice g = the g-th
+// contiguous slot range of fgs_xcd_remap(., U), so it still walks neighbouring tiles -- and one block orders slice g:
+//   full unit u     slot = slice start + number of full units of the slice in front of u (a block scan over the slice's tiles);
+//   partial unit    behind them, by a counting sort over the quarter-octave of its entry count (length_bucket; order inside a
+//                   bucket arbitrary -- scheduling only).
+// Tiles are walked in chunks of one per thread; a chunk none of whose units lies in the slice is skipped by all threads together.
+// One block per slice: the table has U entries, a few thousand per slice at the benchmark's sizes, and no value crosses blocks.
+// The blocks ride in the mask binning's emit kernel (see the declaration above); the radix binning launches k_unit_order.
+constexpr uint32_t UO_THREADS = 1024;  // block of the table's own launch (k_unit_order: the radix binning)
+struct UnitSpan { uint32_t full_lo, full_hi, partial, bucket; bool has_partial; };
+// the units of list t inside the slice [s, e): its full units [full_lo, full_hi) and its partial unit
+__device__ __forceinline__ UnitSpan unit_span(uint32_t t, uint32_t ntiles, const uint32_t *__restrict__ ranges,
+                                              const uint32_t *__restrict__ seg_off, uint32_t seg_len, uint32_t s, uint32_t e) {
+    UnitSpan r = {0u, 0u, 0u, 0u, false};
+    if (t >= ntiles) return r;
+    const uint2 rg = reinterpret_cast<const uint2 *>(ranges)[t];
+    const uint32_t len = rg.y - rg.x, off = seg_off[t], nfull = len / seg_len, rem = len - nfull * seg_len;
+    r.full_lo = max(off, s);
+    r.full_hi = max(min(off + nfull, e), r.full_lo);
+    r.partial = off + nfull;
+    r.has_partial = rem != 0u && r.partial >= s && r.partial < e;
+    r.bucket = length_bucket(rem);
+    return r;
+}
+
+template <uint32_t THREADS>
+__device__ void unit_order_slice(uint32_t g, uint32_t ntiles, const uint32_t *__restrict__ ranges, const uint32_t *__restrict__ seg_off,
+                                 const uint32_t *__restrict__ counters, uint32_t *__restrict__ unit_order, uint32_t *lds) {
+    static_assert(THREADS % 64 == 0 && THREADS <= 1024, "unit_order_slice: whole waves, sixteen at most");
+    uint32_t *hist = lds, *wsum = lds + 64, &run_sh = lds[80], *cb = lds + 81;
+    const uint32_t nchunks = (ntiles + THREADS - 1) / THREADS;
+    // first unit of every chunk, fetched by all threads at once (the loops below would wait for them one chunk after the other)
+    for (uint32_t i = threadIdx.x; i <= min(nchunks, UO_BOUNDS); i += THREADS) cb[i] = seg_off[min(i * THREADS, ntiles)];
+    const auto chunk_begin = [&](uint32_t c) { return c <= UO_BOUNDS ? cb[c] : seg_off[min(c * THREADS, ntiles)]; };
+    const uint32_t U = counters[2], seg_len = counters[4];
+    const uint32_t q = U >> 3, r = U & 7u;
+    const uint32_t s = g < r ? g * (q + 1u) : r * (q + 1u) + (g - r) * q, e = s + (g < r ? q + 1u : q);
+    if (s == e) return;  // no unit (capacity overflow, nothing visible) or fewer units than slices
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    if (threadIdx.x < 64) hist[threadIdx.x] = 0;
+    if (threadIdx.x == 0) run_sh = 0;
+    __syncthreads();
+    // (1) full units to their slots, histogram of the partial ones
+    for (uint32_t c = 0; c < nchunks; ++c) {
+        const uint32_t t0 = c * THREADS;
+        if (chunk_begin(c) >= e || chunk_begin(c + 1u) <= s) continue;  // uniform
+        const UnitSpan sp = unit_span(t0 + threadIdx.x, ntiles, ranges, seg_off, seg_len, s, e);
+        const uint32_t nf = sp.full_hi - sp.full_lo;
+        uint32_t x = nf;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t y = __shfl_up(x, o, 64);
+            if (lane >= (uint32_t)o) x += y;
+        }
+        if (lane == 63) wsum[wave] = x;
+        __syncthreads();
+        uint32_t slot = s + run_sh + x - nf;
+        for (uint32_t w = 0; w < wave; ++w) slot += wsum[w];
+        for (uint32_t u = sp.full_lo; u < sp.full_hi; ++u) unit_order[slot++] = u;
+        if (sp.has_partial) atomicAdd(&hist[sp.bucket], 1u);
+        __syncthreads();  // run_sh and wsum are rewritten
+        if (threadIdx.x == THREADS - 1) run_sh = slot - s;  // the last thread's end = all full units so far
+    }
+    __syncthreads();
+    // (2) first slot of every bucket: behind the slice's full units, longer partial units (smaller bucket numbers) first
+    if (threadIdx.x < 64) {
+        const uint32_t mine = hist[threadIdx.x];
+        uint32_t x = mine;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t y = __shfl_up(x, o, 64);
+            if (lane >= (uint32_t)o) x += y;
+        }
+        hist[threadIdx.x] = s + run_sh + x - mine;
+    }
+    __syncthreads();
+    // (3) the partial units
+    for (uint32_t c = 0; c < nchunks; ++c) {
+        const uint32_t t0 = c * THREADS;
+        if (chunk_begin(c) >= e || chunk_begin(c + 1u) <= s) continue;
+        const UnitSpan sp = unit_span(t0 + threadIdx.x, ntiles, ranges, seg_off, seg_len, s, e);
+        if (sp.has_partial) unit_order[atomicAdd(&hist[sp.bucket], 1u)] = sp.partial;
+    }
+}
+
+__global__ __launch_bounds__(UO_THREADS) void k_unit_order(uint32_t ntiles, const uint32_t *__restrict__ ranges,
+                                                           const uint32_t *__restrict__ seg_off,
+                                                           const uint32_t *__restrict__ counters,
+                                                           uint32_t *__restrict__ unit_order) {
+    __shared__ uint32_t lds[UO_LDS_WORDS];
+    unit_order_slice<UO_THREADS>(blockIdx.x, ntiles, ranges, seg_off, counters, unit_order, lds);
+}
+
 // scratch of the two kernels above: (sums, histograms) per block of TO_TILES tiles
 static int launch_tile_tables(uint32_t ntiles, uint32_t *ranges, const uint32_t *lens, uint32_t *tile_order,
                               uint32_t *seg_off, uint32_t *seg_tile, uint32_t *counters, uint32_t seg_len,
-                              uint32_t fwd_variant, uint32_t *scratch_words, hipStream_t st, uint32_t ngroups = 1) {
+                              uint32_t fwd_variant, uint32_t *scratch_words, hipStream_t st, uint32_t ngroups = 1,
+                              uint32_t *unit_order = nullptr) {
     const uint32_t nblk = (ntiles + TO_TILES - 1) / TO_TILES;
     unsigned long long *pre64 = reinterpret_cast<unsigned long long *>(scratch_words);
     uint32_t *bhist = scratch_words + 2 * (size_t)nblk;  // [nblk][64 * ngroups]
@@ -887,6 +1014,10 @@ static int launch_tile_tables(uint32_t ntiles, uint32_t *ranges, const uint32_t 
     hipLaunchKernelGGL(k_tile_post, dim3(nblk), dim3(256), 0, st, ntiles, ranges, lens, tile_order, seg_off, seg_tile,
                        counters, seg_len, fwd_variant, pre64, bhist, ngroups);
     FGS_LAUNCH_CHECK("k_tile_post");
+    if (unit_order) {  // (the mask binning passes none: its emit kernel builds the table)
+        hipLaunchKernelGGL(k_unit_order, dim3(8), dim3(UO_THREADS), 0, st, ntiles, ranges, seg_off, counters, unit_order);
+        FGS_LAUNCH_CHECK("k_unit_order");
+    }
     return FGS_OK;
 }
 
@@ -990,6 +1121,7 @@ int fgs_launch_binning(const FgsPlan &p, char *saved, char *scratch, hipStream_t
     uint32_t *tile_order = reinterpret_cast<uint32_t *>(saved + p.L.tile_order);
     uint32_t *seg_off = p.L.seg_capacity ? reinterpret_cast<uint32_t *>(saved + p.L.seg_off) : nullptr;
     uint32_t *seg_tile = p.L.seg_capacity ? reinterpret_cast<uint32_t *>(saved + p.L.seg_tile) : nullptr;
+    uint32_t *unit_order = p.has_unit_order ? reinterpret_cast<uint32_t *>(saved + p.L.unit_order) : nullptr;
     if (p.direct_binning) {
         // mask binning (see k_mask_build): 5 launches, none of them serial over Gaussians
         const uint32_t bpi = (N + MB_RANKS - 1) / MB_RANKS, nrb = B * bpi;
@@ -1027,19 +1159,21 @@ int fgs_launch_binning(const FgsPlan &p, char *saved, char *scratch, hipStream_t
             return rc;
         fgs_stage_end(ST_TILE_RANGES, st);
         fgs_stage_begin(ST_TILE_SORT, st);
-#define FGS_MASK_EMIT(W) hipLaunchKernelGGL(k_mask_emit<W>, dim3(nrb + ntb), dim3(256), 0, st, B, N, layers, plane_start, \
+        const uint32_t nub = unit_order ? 8u : 0u;  // blocks in front of the others that order the backward's units (unit_order_slice)
+#define FGS_MASK_EMIT(W) hipLaunchKernelGGL(k_mask_emit<W>, dim3(nrb + ntb + nub), dim3(256), 0, st, B, N, layers, plane_start, \
                                             (uint32_t)p.tiles, tiles_x, lines, w64p, nrb, bpi, dcap, masks, order,         \
-                                            tile_count, ranges, bsum, dup_ids, dup_off, counters)
-#define FGS_MASK_EMIT_BLOCK(W) hipLaunchKernelGGL(k_mask_emit_block<W>, dim3(nrb + ntiles_all), dim3(256), 0, st, B, N, layers, \
+                                            tile_count, ranges, bsum, dup_ids, dup_off, counters, nub, seg_off, unit_order)
+#define FGS_MASK_EMIT_BLOCK(W) hipLaunchKernelGGL(k_mask_emit_block<W>, dim3(nrb + ntiles_all + nub), dim3(256), 0, st, B, N, layers, \
                                                   plane_start, (uint32_t)p.tiles, tiles_x, lines, w64p, nrb, bpi, dcap, masks, \
-                                                  order, tile_count, ranges, bsum, dup_ids, dup_off, counters)
+                                                  order, tile_count, ranges, bsum, dup_ids, dup_off, counters, nub, seg_off, unit_order)
         // few lists (<= 8192: the blend path's frames; the ASM renderer's (image, plane, tile) lists are many and short)
         // over more than 128 rank words (N > 8192 per image): a block per list, a quarter of the rank words per wave.
         // Measured: config 3 (4096 lists of ~1000 entries) 40 -> 28 us, decoder-like (~2500 entries) 119 -> 38 us;
         // config 2 (N = 8192, ~130 entries per list) 13 -> 17 us, so it keeps the wave-per-list kernel.
         if (grouped) {
-            hipLaunchKernelGGL(k_mask_emit_group, dim3(nrb + ngb), dim3(256), 0, st, B, N, layers, plane_start, (uint32_t)p.tiles,
-                               tiles_x, lines, w64p, nrb, bpi, dcap, masks, order, tile_count, ranges, bsum, dup_ids, dup_off, counters);
+            hipLaunchKernelGGL(k_mask_emit_group, dim3(nrb + ngb + nub), dim3(256), 0, st, B, N, layers, plane_start, (uint32_t)p.tiles,
+                               tiles_x, lines, w64p, nrb, bpi, dcap, masks, order, tile_count, ranges, bsum, dup_ids, dup_off, counters,
+                               nub, seg_off, unit_order);
         } else if (ntiles_all <= FGS_EMIT_BLOCK_MAX_LISTS && wpl >= 4) {
             if (wpl == 4) FGS_MASK_EMIT_BLOCK(1); else FGS_MASK_EMIT_BLOCK(2);
         } else if (wpl == 1) FGS_MASK_EMIT(1); else if (wpl == 2) FGS_MASK_EMIT(2); else if (wpl == 4) FGS_MASK_EMIT(4); else FGS_MASK_EMIT(8);
@@ -1081,7 +1215,7 @@ int fgs_launch_binning(const FgsPlan &p, char *saved, char *scratch, hipStream_t
     // (vals0 is free again: the sort's final payload went to dup_ids, its last keys are in `ks`)
     if ((rc = launch_tile_tables(ntiles_all, ranges, nullptr, tile_order, seg_off, seg_tile, counters,
                                  (uint32_t)p.L.seg_len, (uint32_t)p.fwd_variant, ks == keys0 ? keys1 : keys0, st,
-                                 (uint32_t)p.order_groups)))
+                                 (uint32_t)p.order_groups, unit_order)))
         return rc;
     fgs_stage_end(ST_TILE_RANGES, st);
     return FGS_OK;

@@ -20,7 +20,8 @@
 #include "fgs_internal.h"
 #include "fgs_wave.h"
 
-#if (defined(FGS_BWD_DYN_LDS) || defined(FGS_BWD_WIDE_WAVES) || defined(FGS_PHASE_SCAN) || defined(FGS_CKPT_NT) || defined(FGS_PHASE_WAVE_BLOCKS)) && !defined(FGS_EXPERIMENT_BUILD)
+#if (defined(FGS_BWD_DYN_LDS) || defined(FGS_BWD_WIDE_WAVES) || defined(FGS_PHASE_SCAN) || defined(FGS_CKPT_NT) || defined(FGS_PHASE_WAVE_BLOCKS) || \
+     defined(FGS_BWD_UNIT_TRACE) || defined(FGS_BWD_TILE_ORDER)) && !defined(FGS_EXPERIMENT_BUILD)
 #error "work-split / timing switches of this unit are for experiment builds: python -m fresnel_amd.build --define ... (sets FGS_EXPERIMENT_BUILD; fgs_version() then says so)"
 #endif
 
@@ -829,6 +830,23 @@ __device__ __attribute__((noinline)) void composite_bwd_dead_walk(BwdDeadArgs<NS
 #ifndef FGS_BWD_DYN_LDS
 #define FGS_BWD_DYN_LDS 0  /* experiment builds: unused dynamic LDS per block, to cap the waves per SIMD below what the registers allow */
 #endif
+// Experiment builds.  FGS_BWD_TILE_ORDER: the units launch in unit (= tile) order, unit_order is not read -- the order before the
+// table existed.  FGS_BWD_UNIT_TRACE: every launch slot records wall_clock64() (100 MHz) at entry and exit, its unit and whether it
+// took the dead walk, three 64-bit words per slot in a buffer the launcher owns; fgs_bwd_unit_trace() copies the last launch's out
+// (scratch/profile/bwd_unit_drain.py turns it into the drain profile of profiles/r12_ab_bwd_unit_order.txt).
+#ifdef FGS_BWD_UNIT_TRACE
+#define FGS_BWD_TRACE_PARAM , unsigned long long *__restrict__ trace
+#define FGS_BWD_TRACE_EXIT(dead)                                                                                        \
+    do {                                                                                                                \
+        if (threadIdx.x == 0) {                                                                                         \
+            trace[3 * (size_t)blockIdx.x + 1] = wall_clock64();                                                         \
+            trace[3 * (size_t)blockIdx.x + 2] = (unsigned long long)unit | ((unsigned long long)(dead) << 32) | (1ull << 63); \
+        }                                                                                                               \
+    } while (0)
+#else
+#define FGS_BWD_TRACE_PARAM
+#define FGS_BWD_TRACE_EXIT(dead) do { } while (0)
+#endif
 template <int NSX>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NSX == 2 ? 6 : FGS_BWD_WIDE_WAVES, NSX == 2 ? 6 : FGS_BWD_WIDE_WAVES))) void k_composite_bwd(
     uint32_t tiles, uint32_t tiles_x, uint32_t W, uint32_t H, float bg0, float bg1, float bg2, uint32_t dcap,
@@ -836,15 +854,23 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NSX == 2 ? 6
     const uint32_t *__restrict__ seg_tile, const float *__restrict__ seg_ckpt, const uint32_t *__restrict__ ranges,
     const uint32_t *__restrict__ dup_ids, const float *__restrict__ rec, const uint32_t *__restrict__ dup_off,
     const float *__restrict__ pix_state, const float *__restrict__ g_rgb, const float *__restrict__ g_depth,
-    float *__restrict__ grad_rows, float t_eps) {
+    float *__restrict__ grad_rows, float t_eps, const uint32_t *__restrict__ unit_order FGS_BWD_TRACE_PARAM) {
     // work unit = (tile, depth segment): blockIdx.x indexes the unit list built by k_tile_order; the grid is
     // sized from the capacity, surplus blocks leave at once
     constexpr int NS = 2 * NSX, PL = NS * 64, SLOT = 5 * PL;  // sub-tiles per tile, floats per checkpoint plane / slot
     const uint32_t num_units = counters[2];
     if (blockIdx.x >= num_units) return;
+#ifdef FGS_BWD_UNIT_TRACE
+    if (threadIdx.x == 0) trace[3 * (size_t)blockIdx.x] = wall_clock64();
+#endif
     // units are listed tile by tile: an XCD gets a contiguous run of them, so neighbouring tiles -- which share
-    // Gaussians, and write adjacent 40-byte gradient rows -- meet in one L2
+    // Gaussians, and write adjacent 40-byte gradient rows -- meet in one L2.  Inside its run an XCD takes the full units first and
+    // the partial ones last, longest first (unit_order, fgs_bin.hip k_unit_order): the short units fill the launch's drain
+#ifdef FGS_BWD_TILE_ORDER
     const uint32_t unit = fgs_xcd_remap(blockIdx.x, num_units);
+#else
+    const uint32_t unit = unit_order[fgs_xcd_remap(blockIdx.x, num_units)];
+#endif
     // the split the forward ran with, as the forward recorded it (k_tile_order): segment length, and the number of
     // list parts of the depth-split forward (> 1: checkpoints inside a later part are part-local)
     const uint32_t seg_len = counters[4];
@@ -878,6 +904,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NSX == 2 ? 6
                     for (int q = 0; q < FGS_BLEND_ROW_FLOATS / 2; ++q) row[q] = make_float2(0.0f, 0.0f);
                 }
             }
+            FGS_BWD_TRACE_EXIT(2);
             return;
         }
     }
@@ -930,9 +957,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NSX == 2 ? 6
 #pragma unroll
         for (int s = 0; s < NS; ++s) a.S[s] = S[s];
         composite_bwd_dead_walk<NSX>(a);
+        FGS_BWD_TRACE_EXIT(1);
         return;
     }
     composite_bwd_walk<NSX, false>(c, lane, lx, ly, dcap, alive, dup_ids, rec, dup_off, grad_rows, gr, gg, gb, gd, S, T);
+    FGS_BWD_TRACE_EXIT(0);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1298,6 +1327,19 @@ int fgs_launch_composite_fwd(const FgsPlan &p, const float *phase, char *saved, 
     return FGS_OK;
 }
 
+#ifdef FGS_BWD_UNIT_TRACE
+static unsigned long long *g_bwd_trace = nullptr;
+static uint32_t g_bwd_trace_slots = 0, g_bwd_trace_last = 0;
+// experiment builds only: the records of the last k_composite_bwd launch, three words per launch slot (entry clock, exit clock,
+// unit | walk << 32 | 1 << 63; all zero for the surplus slots); returns the number of slots copied, or -1
+extern "C" long fgs_bwd_unit_trace(unsigned long long *host, size_t slots) {
+    if (!g_bwd_trace || hipDeviceSynchronize() != hipSuccess) return -1;
+    const size_t n = slots < g_bwd_trace_last ? slots : g_bwd_trace_last;
+    if (hipMemcpy(host, g_bwd_trace, n * 24, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    return (long)n;
+}
+#endif
+
 int fgs_launch_composite_bwd(const FgsPlan &p, const float *phase, const char *saved, char *scratch,
                              const float *g_rgb, const float *g_depth, float *g_phase, hipStream_t st) {
     (void)g_phase;  // dL/dphase travels in the gradient rows and is written by k_project_bwd
@@ -1323,11 +1365,27 @@ int fgs_launch_composite_bwd(const FgsPlan &p, const float *phase, const char *s
     const uint32_t *seg_tile = fgs_at<const uint32_t>(saved, p.L.seg_tile);
     const float *seg_ckpt = fgs_at<const float>(saved, p.L.seg_ckpt);
     const float t_eps = p.d.saturation_skip ? FGS_SATURATION_EPS : 0.0f;
+    if (!p.has_unit_order) { fgs_set_error("k_composite_bwd: the plan has no unit_order table"); return FGS_EINVAL; }
+    const uint32_t *unit_order = fgs_at<const uint32_t>(saved, p.L.unit_order);
+#ifdef FGS_BWD_UNIT_TRACE
+    if (g_bwd_trace_slots < ugrid) {
+        if (g_bwd_trace) (void)hipFree(g_bwd_trace);
+        g_bwd_trace = nullptr; g_bwd_trace_slots = 0;
+        if (hipMalloc(&g_bwd_trace, (size_t)ugrid * 24) != hipSuccess) { fgs_set_error("unit trace: hipMalloc"); return FGS_ELAUNCH; }
+        g_bwd_trace_slots = ugrid;
+    }
+    if (hipMemsetAsync(g_bwd_trace, 0, (size_t)ugrid * 24, st) != hipSuccess) { fgs_set_error("unit trace: memset"); return FGS_ELAUNCH; }
+    g_bwd_trace_last = ugrid;
+#define FGS_BWD_TRACE_ARG , g_bwd_trace
+#else
+#define FGS_BWD_TRACE_ARG
+#endif
 #define FGS_BWD_LAUNCH(NSXV)                                                                                              \
     hipLaunchKernelGGL(k_composite_bwd<NSXV>, dim3(ugrid), dim3(64), FGS_BWD_DYN_LDS, st, tiles, tiles_x, W, H, bg0, bg1, bg2, dcap, \
-                       counters, seg_off, seg_tile, seg_ckpt, ranges, dup_ids, rec, dup_off, pix, g_rgb, g_depth, grad_rows, t_eps)
+                       counters, seg_off, seg_tile, seg_ckpt, ranges, dup_ids, rec, dup_off, pix, g_rgb, g_depth, grad_rows, t_eps, unit_order FGS_BWD_TRACE_ARG)
     if (p.tile_w == 32) FGS_BWD_LAUNCH(4); else FGS_BWD_LAUNCH(2);
 #undef FGS_BWD_LAUNCH
+#undef FGS_BWD_TRACE_ARG
     FGS_LAUNCH_CHECK("k_composite_bwd");
     return FGS_OK;
 }

@@ -171,6 +171,10 @@ int fgs_make_plan(const FgsDims *d, FgsPlan *p, int layers, bool segment_ckpt) {
         L.seg_ckpt = o;
         if (segment_ckpt && layers == 1) o = align256(o + ucap * 5 * 64 * (size_t)(p->tile_w / 4) * 4);  // 5 x sub-tiles x 64 floats per slot
     }
+    // launch order of the blend backward's units: behind every older section, and only where that backward runs
+    L.unit_order = o;
+    p->has_unit_order = !d->use_phase && segment_ckpt && layers == 1;
+    if (p->has_unit_order) o = align256(o + ucap * 4);
     L.total_bytes = o;
     L.dup_capacity = dcap;
     L.tiles_x = tx; L.tiles_y = ty;

@@ -46,8 +46,9 @@ struct FgsPlan {
                               // index order -- the order the reference's own loop adds them in
     int32_t order_groups;     // XCD groups of the forward's launch order (fgs_bin.hip tile_group): 8 on the blend path's
                               // depth-split forward, 1 elsewhere
+    bool has_unit_order;      // saved.unit_order exists: the blend backward (k_composite_bwd) runs on this plan's units
     // scratch layout (bytes)
-    size_t sort_words;        // uint32 words of EACH of the four sort buffers below
+    size_t sort_words;       // uint32 words of EACH of the four sort buffers below
     size_t tile_table_words;  // words the tile-table kernels need in the one sort buffer they borrow (<= sort_words)
     size_t s_total;
     size_t s_keys0, s_keys1;  // uint32 [max(B*N, Dcap)] radix ping/pong keys

@@ -574,6 +574,8 @@ def inspect_saved(saved: torch.Tensor, dims) -> dict:
     if L.seg_capacity:  # depth segments = work units of the backward (non-phase path)
         out["seg_off"] = view(L.seg_off, Bn * T + 1, torch.int32)
         out["seg_tile"] = view(L.seg_tile, L.seg_capacity, torch.int32)
+        if L.unit_order < L.total_bytes:  # launch order of those units (blend path only; counters[2] entries are valid)
+            out["unit_order"] = view(L.unit_order, L.seg_capacity, torch.int32)
     return out
 
 

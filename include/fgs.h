@@ -158,6 +158,11 @@ typedef struct FgsSavedLayout {
                             shorter work units for launches that would not fill the chip), else 128   */
     int32_t tile_w;      /* tile width in pixels (16 | 32; tiles_x counts tiles of this width); a tile has
                             tile_w / 8 x 2 sub-tiles of 8 x 8 pixels, and seg_ckpt slots hold 5 x that many x 64 floats */
+    size_t unit_order;   /* uint32 [Ucap], U valid: launch slot -> unit of the blend backward (scheduling only).  The slots
+                            are cut into the eight contiguous ranges the XCDs walk; a range keeps the units it has in unit
+                            order, but lists its full units (seg_len entries) first, in increasing index, and then its
+                            partial units, longest first by quarter-octave of their entry count.  Exists only on the blend
+                            path (no phase, one layer); == total_bytes elsewhere.  Not written when U == 0 */
 } FgsSavedLayout;
 
 /* Sizes of the two caller-provided device buffers.  `saved` must stay untouched between
