@@ -32,6 +32,7 @@ EXPORTED_SYMBOLS = [
     "fgs_saag_workspace_bytes", "fgs_saag_inputs_forward", "fgs_saag_refine_forward", "fgs_saag_refine_backward",
     "fgs_physics_workspace_bytes", "fgs_physics_forward", "fgs_physics_backward",
     "fgs_surface_workspace_bytes", "fgs_surface_count", "fgs_surface_emit",
+    "fgs_surface_emit_guided", "fgs_surface_guided_backward_bytes", "fgs_surface_guided_backward",
 ]
 
 STAGES = ["project", "depth_sort", "dup_emit", "tile_sort", "tile_ranges", "composite_fwd",
@@ -276,7 +277,11 @@ def load():
     lib.fgs_surface_workspace_bytes.argtypes = [sfd, sfp, cp(ctypes.c_size_t)]
     lib.fgs_surface_count.argtypes = [sfd, sfp] + [vp] * 4
     lib.fgs_surface_emit.argtypes = [sfd, sfp] + [vp] * 9 + [ctypes.c_int64, vp]
-    for fn in (lib.fgs_surface_workspace_bytes, lib.fgs_surface_count, lib.fgs_surface_emit):
+    lib.fgs_surface_emit_guided.argtypes = [sfd, sfp] + [vp] * 5 + [ctypes.c_int32] * 2 + [vp] * 6 + [ctypes.c_int64, vp]
+    lib.fgs_surface_guided_backward_bytes.argtypes = [sfd, sfp, ctypes.c_int32, ctypes.c_int32, cp(ctypes.c_size_t)]
+    lib.fgs_surface_guided_backward.argtypes = [sfd, sfp] + [vp] * 4 + [ctypes.c_int32] * 2 + [vp] * 8
+    for fn in (lib.fgs_surface_workspace_bytes, lib.fgs_surface_count, lib.fgs_surface_emit, lib.fgs_surface_emit_guided,
+               lib.fgs_surface_guided_backward_bytes, lib.fgs_surface_guided_backward):
         fn.restype = ctypes.c_int
     for fn in (lib.fgs_asm_propagate_workspace_bytes, lib.fgs_asm_propagate_forward, lib.fgs_asm_propagate_backward,
                lib.fgs_spectral_workspace_bytes, lib.fgs_spectral_loss_forward, lib.fgs_spectral_loss_backward,

@@ -13,6 +13,9 @@
 //   k_surface_emit     (PB, B) blocks   row offset = block base + scan of the block's counts; every thread writes its point's rows
 //                                       (a thread per ROW, fed from LDS, was tried: coalesced stores, but every row then redoes the
 //                                       view frame and its divides, and the kernel is bound by that arithmetic: 233 us against 193)
+// Feature-guided SAAG (include/fgs.h): k_surface_emit<true> is the same emit with six parameters read per patch of a guide map, and
+//   k_surface_guided_backward (Hp Wp S, B) blocks of one wave   dL/d maps as a gather: a patch owns a rectangle of grid points
+//   k_surface_guided_fold                                        adds the S partials of a patch that was split (S > 1 only)
 //
 // Compiled with -ffp-contract=off and IEEE divide / sqrt, and written in the reference's operation order: every value that feeds a
 // decision (drop, skip, thresholds, guards, the wrap direction's flip) is the fp32 value a literal restatement computes
@@ -338,10 +341,44 @@ __device__ __forceinline__ void put_row(const SurfOut &o, uint32_t row, V3 p, V3
     o.opacity[r] = op;
 }
 
+// The six parameters a guide may modulate per patch (include/fgs.h, "Feature-guided SAAG"), as the point sees them.
+struct SurfEff {
+    float aspect_ratio, edge_threshold, edge_shrink, normal_strength, base_size, opacity;
+};
+struct SurfGuide {
+    const float *mods;  // (B, 6, Hp, Wp)
+    int32_t Hp, Wp;
+};
+__device__ __forceinline__ SurfEff plain_params(const FgsSurfaceParams &prm) {
+    SurfEff e;
+    e.aspect_ratio = prm.aspect_ratio; e.edge_threshold = prm.edge_threshold; e.edge_shrink = prm.edge_shrink;
+    e.normal_strength = prm.normal_strength; e.base_size = prm.base_size; e.opacity = prm.opacity;
+    return e;
+}
+// the patch of pixel (x, y): integer division on PIXEL coordinates (W Wp and H Hp are below 2^31)
+__device__ __forceinline__ size_t patch_of(const SurfGeom &g, const SurfGuide &gd, uint32_t b, uint32_t x, uint32_t y) {
+    const uint32_t px = (x * (uint32_t)gd.Wp) / (uint32_t)g.W, py = (y * (uint32_t)gd.Hp) / (uint32_t)g.H;
+    return ((size_t)b * 6 * gd.Hp + py) * gd.Wp + px;
+}
+// one fp32 operation each, rounded on its own; m = (1, 0, 1, 1, 1, 1) leaves every parameter's bits alone
+__device__ __forceinline__ SurfEff guided_params(const FgsSurfaceParams &prm, const float *__restrict__ m, size_t plane) {
+    SurfEff e;
+    e.aspect_ratio = prm.aspect_ratio * m[0];
+    e.edge_threshold = prm.edge_threshold + m[plane];
+    e.edge_shrink = prm.edge_shrink * m[2 * plane];
+    e.normal_strength = prm.normal_strength * m[3 * plane];
+    e.base_size = prm.base_size * m[4 * plane];
+    e.opacity = prm.opacity * m[5 * plane];
+    return e;
+}
+
+// GUIDED: fgs_surface_emit_guided -- the six parameters come from the point's patch, and point_rows gets every point's first row
+template <bool GUIDED>
 __global__ __launch_bounds__(SB) void k_surface_emit(SurfGeom g, FgsSurfaceParams prm, const float *__restrict__ depth,
                                                      const float *__restrict__ color, const float *__restrict__ img,
                                                      const uint8_t *__restrict__ flags, const uint32_t *__restrict__ boff,
-                                                     const int32_t *__restrict__ offsets, int32_t *__restrict__ status, SurfOut out) {
+                                                     const int32_t *__restrict__ offsets, int32_t *__restrict__ status, SurfGuide guide,
+                                                     int32_t *__restrict__ point_rows, SurfOut out) {
     const bool overflow = (int64_t)offsets[g.B] > out.capacity;
     if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *status = overflow ? 1 : 0;
     if (overflow) return;
@@ -349,12 +386,15 @@ __global__ __launch_bounds__(SB) void k_surface_emit(SurfGeom g, FgsSurfaceParam
     const uint32_t f = idx < (uint32_t)g.P ? flags[(size_t)b * g.P + idx] : 0u;
     uint32_t tot;
     uint32_t row = boff[(size_t)b * g.PB + blockIdx.x] + block_exclusive_scan_256(rows_of(f, prm), &tot);
+    if (GUIDED && idx < (uint32_t)g.P) point_rows[(size_t)b * g.P + idx] = (f & FGS_SURFACE_BASE) ? (int32_t)row : -1;
     if (!(f & FGS_SURFACE_BASE)) return;
 
     const size_t hw = (size_t)g.H * g.W;
     const float *d = depth + (size_t)b * hw;
     const float *ic = img + (size_t)b * IMG_FLOATS;
     const uint32_t x = (idx % g.gw) * g.sub, y = (idx / g.gw) * g.sub;
+    const SurfEff e = GUIDED ? guided_params(prm, guide.mods + patch_of(g, guide, b, x, y), (size_t)guide.Hp * guide.Wp)
+                             : plain_params(prm);
     float conf;
     V3 pos;
     raw_point(g, prm.depth_scale, d[(size_t)y * g.W + x], ic[IC_MIN_D], ic[IC_RANGE], x, y, conf, pos);
@@ -375,18 +415,18 @@ __global__ __launch_bounds__(SB) void k_surface_emit(SurfGeom g, FgsSurfaceParam
     normal = nlen > 1e-6f ? normal / nlen : v3(0.0f, 0.0f, 1.0f);
 
     // the base Gaussian, PC:225-261
-    const Quat rotation = slerp_from_identity(quat_from_normal(normal), prm.normal_strength);
-    const float base = prm.base_size * (0.5f + 0.5f * conf);
-    const float tangent_scale = base, normal_scale = base / prm.aspect_ratio;
+    const Quat rotation = slerp_from_identity(quat_from_normal(normal), e.normal_strength);
+    const float base = e.base_size * (0.5f + 0.5f * conf);
+    const float tangent_scale = base, normal_scale = base / e.aspect_ratio;
     const float ng = mag / ic[IC_MAX_GRAD];
     float edge_factor = 1.0f;
-    if (ng > prm.edge_threshold) {
-        float t = (ng - prm.edge_threshold) / (1.0f - prm.edge_threshold);
+    if (ng > e.edge_threshold) {
+        float t = (ng - e.edge_threshold) / (1.0f - e.edge_threshold);
         t = clampf(t, 0.0f, 1.0f);
-        edge_factor = 1.0f - t * (1.0f - prm.edge_shrink);
+        edge_factor = 1.0f - t * (1.0f - e.edge_shrink);
     }
     const V3 scale = v3(tangent_scale * edge_factor, tangent_scale * edge_factor, normal_scale * edge_factor);
-    const float final_opacity = prm.opacity * conf * (0.7f + 0.3f * edge_factor);
+    const float final_opacity = e.opacity * conf * (0.7f + 0.3f * edge_factor);
     put_row(out, row++, pos, scale, rotation, col, final_opacity);
 
     // volumetric shell: back surface and side walls, PC:268-343
@@ -419,7 +459,7 @@ __global__ __launch_bounds__(SB) void k_surface_emit(SurfGeom g, FgsSurfaceParam
         const float wrap_base = base * 0.8f;
         const V3 wrap_scale = v3(wrap_base, wrap_base, wrap_base / prm.wrap_aspect);
         for (int layer = 0; layer < prm.wrap_layers; ++layer) {
-            const float offset = (float)(layer + 1) * prm.wrap_layer_spacing * prm.base_size;
+            const float offset = (float)(layer + 1) * prm.wrap_layer_spacing * e.base_size;
             put_row(out, row++, pos + wrap_dir * offset, wrap_scale, wrap_rot, col,
                     final_opacity * powf(prm.wrap_opacity_falloff, (float)(layer + 1)));
         }
@@ -436,6 +476,182 @@ __global__ __launch_bounds__(SB) void k_surface_emit(SurfGeom g, FgsSurfaceParam
             put_row(out, row++, pos + v3(rx, ry, rz) * jitter, scale * size_var * 0.8f, rotation, col, extra_opacity);
         }
     }
+}
+
+// ---- the guided emit's backward: dL/d mods, include/fgs.h "Feature-guided SAAG" -------------------------------------------------------
+// d slerp_from_identity(q, t) / dt, each branch differentiated as written
+__device__ Quat slerp_from_identity_dt(Quat q, float t) {
+    float c = q.w;
+    if (c < 0.0f) { q.w = -q.w; q.x = -q.x; q.y = -q.y; q.z = -q.z; c = -c; }
+    Quat r;
+    if (c > 1.0f - FLT_EPSILON) {
+        r.w = q.w - 1.0f; r.x = q.x; r.y = q.y; r.z = q.z;
+    } else {
+        const float a = acosf(c), s = sinf(a), d0 = -a * cosf((1.0f - t) * a), d1 = a * cosf(t * a);
+        r.w = (d0 + d1 * q.w) / s; r.x = d1 * q.x / s; r.y = d1 * q.y / s; r.z = d1 * q.z / s;
+    }
+    return r;
+}
+
+struct SurfGrads {
+    const float *pos, *scale, *rot, *opacity;  // upstream gradients of the rows; NULL = zeros
+};
+__device__ __forceinline__ V3 grad3(const float *__restrict__ g, size_t r) { return g ? v3(g[r * 3], g[r * 3 + 1], g[r * 3 + 2]) : v3(0.0f, 0.0f, 0.0f); }
+__device__ __forceinline__ float grad1(const float *__restrict__ g, size_t r) { return g ? g[r] : 0.0f; }
+
+constexpr int GB = 64;                  // one wave per (patch, split, image)
+constexpr int GUIDE_THREAD_POINTS = 4;  // points a lane walks before a patch is split over more waves
+constexpr int GUIDE_MAX_SPLITS = 256;
+
+// grid points whose pixel coordinate lies in patch p of n over `size` pixels: indices [lo, hi) of the subsample grid
+__device__ __forceinline__ void patch_span(int32_t p, int32_t n, int32_t size, int32_t sub, int32_t grid, int32_t &lo, int32_t &hi) {
+    const int64_t x0 = ((int64_t)p * size + n - 1) / n, x1 = ((int64_t)(p + 1) * size + n - 1) / n;  // pixels [x0, x1): x n / size == p
+    lo = (int32_t)((x0 + sub - 1) / sub);
+    hi = (int32_t)((x1 + sub - 1) / sub);
+    if (hi > grid) hi = grid;
+    if (lo > hi) lo = hi;
+}
+
+// One wave per (patch, split, image): lane l of split s takes the patch's grid points s GB + l, + S GB, ... in row-major order,
+// recomputes each point's forward, folds the upstream gradients of its rows into six partials; a butterfly of fixed shape sums
+// the wave.  S == 1: the sums are g_mods; else they go to `dst` = partials (B, Hp Wp, S, 6) for k_surface_guided_fold.
+__global__ __launch_bounds__(GB) void k_surface_guided_backward(SurfGeom g, FgsSurfaceParams prm, const float *__restrict__ depth,
+                                                                const float *__restrict__ img, const uint8_t *__restrict__ flags,
+                                                                const int32_t *__restrict__ offsets, SurfGuide guide, int32_t S,
+                                                                const int32_t *__restrict__ point_rows, SurfGrads gr,
+                                                                float *__restrict__ dst) {
+    const uint32_t b = blockIdx.y, patch = blockIdx.x / (uint32_t)S, split = blockIdx.x % (uint32_t)S;
+    const int32_t py = (int32_t)(patch / (uint32_t)guide.Wp), px = (int32_t)(patch % (uint32_t)guide.Wp);
+    const size_t plane = (size_t)guide.Hp * guide.Wp;
+    int32_t gx0, gx1, gy0, gy1;
+    patch_span(px, guide.Wp, g.W, g.sub, g.gw, gx0, gx1);
+    patch_span(py, guide.Hp, g.H, g.sub, g.gh, gy0, gy1);
+    const uint32_t nx = (uint32_t)(gx1 - gx0), n = nx * (uint32_t)(gy1 - gy0);
+    const SurfEff e = guided_params(prm, guide.mods + ((size_t)b * 6 * guide.Hp + py) * guide.Wp + px, plane);
+    const float *d = depth + (size_t)b * g.H * g.W;
+    const float *ic = img + (size_t)b * IMG_FLOATS;
+    const int64_t total = offsets[g.B];
+    float acc[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    for (uint32_t k = split * GB + threadIdx.x; k < n; k += (uint32_t)S * GB) {
+        const uint32_t idx = (uint32_t)(gy0 + (int32_t)(k / nx)) * (uint32_t)g.gw + (uint32_t)(gx0 + (int32_t)(k % nx));
+        const uint32_t f = flags[(size_t)b * g.P + idx];
+        if (!(f & FGS_SURFACE_BASE)) continue;
+        const int64_t first = point_rows[(size_t)b * g.P + idx];
+        if (first < 0 || first + (int64_t)rows_of(f, prm) > total) continue;  // never true for the emit's point_rows: keeps the reads inside
+        size_t r = (size_t)first;
+        const uint32_t x = (idx % g.gw) * g.sub, y = (idx / g.gw) * g.sub;
+        float conf;
+        V3 pos;
+        raw_point(g, prm.depth_scale, d[(size_t)y * g.W + x], ic[IC_MIN_D], ic[IC_RANGE], x, y, conf, pos);
+        pos = placed(pos, prm.normalize_extent, ic);
+        float gx, gy;
+        sobel(d, g.W, g.H, (int)x, (int)y, gx, gy);
+        const float mag = sqrtf(gx * gx + gy * gy);
+        float dir_x = 0.0f, dir_y = 0.0f;
+        if (mag > 1e-6f) { dir_x = gx / mag; dir_y = gy / mag; }
+        V3 normal = v3(-gx * prm.gradient_scale, -gy * prm.gradient_scale, 1.0f);
+        const float nlen = length3(normal);
+        normal = nlen > 1e-6f ? normal / nlen : v3(0.0f, 0.0f, 1.0f);
+        // the forward's values, as k_surface_emit computes them
+        const float c1 = 0.5f + 0.5f * conf, base = e.base_size * c1, normal_scale = base / e.aspect_ratio;
+        const float ng = mag / ic[IC_MAX_GRAD];
+        float edge_factor = 1.0f, t = 0.0f;
+        bool edge = false, inside = false;
+        if (ng > e.edge_threshold) {
+            edge = true;
+            t = (ng - e.edge_threshold) / (1.0f - e.edge_threshold);
+            inside = !(t < 0.0f) && !(1.0f < t);  // the clamp passes its gradient on the closed interval
+            t = clampf(t, 0.0f, 1.0f);
+            edge_factor = 1.0f - t * (1.0f - e.edge_shrink);
+        }
+        // upstream gradients, row by row in emit order, folded into: the shared scale (Gs), the shared rotation (Gq),
+        // final_opacity (Gfo), `base` beyond the shared scale (Gbase) and base_size' through the wrap offsets (Gbs)
+        V3 Gs = grad3(gr.scale, r);
+        Quat Gq;
+        Gq.w = Gq.x = Gq.y = Gq.z = 0.0f;
+        if (gr.rot) { Gq.w = gr.rot[r * 4]; Gq.x = gr.rot[r * 4 + 1]; Gq.y = gr.rot[r * 4 + 2]; Gq.z = gr.rot[r * 4 + 3]; }
+        float Gfo = grad1(gr.opacity, r), Gbase = 0.0f, Gbs = 0.0f;
+        ++r;
+        if (f & FGS_SURFACE_BACK) {
+            Gs = Gs + grad3(gr.scale, r);
+            Gfo += grad1(gr.opacity, r) * prm.shell_back_opacity;
+            ++r;
+            if (f & FGS_SURFACE_WALLS)
+                for (int seg = 1; seg < prm.shell_wall_segments + 1; ++seg, ++r) {
+                    Gs = Gs + grad3(gr.scale, r) * 0.9f;
+                    Gfo += grad1(gr.opacity, r) * prm.shell_wall_opacity;
+                }
+        }
+        if (f & FGS_SURFACE_WRAPS) {
+            const V3 view_dir = normalize3(pos);
+            const V3 grad_3d = gradient_3d(view_dir, dir_x, dir_y);
+            V3 wrap = cross3(normal, grad_3d);
+            if (dot3(wrap, view_dir) < 0.0f) wrap = -wrap;
+            const float wrap_len = length3(wrap);
+            const V3 wrap_dir = wrap_len < 1e-6f ? normalize3(grad_3d) : wrap / wrap_len;
+            for (int layer = 0; layer < prm.wrap_layers; ++layer, ++r) {
+                const V3 gs = grad3(gr.scale, r);
+                Gbase += (gs.x + gs.y) * 0.8f + gs.z * (0.8f / prm.wrap_aspect);
+                Gbs += dot3(grad3(gr.pos, r), wrap_dir) * ((float)(layer + 1) * prm.wrap_layer_spacing);
+                Gfo += grad1(gr.opacity, r) * powf(prm.wrap_opacity_falloff, (float)(layer + 1));
+            }
+        }
+        if (f & FGS_SURFACE_FILLS)
+            for (int i = 0; i < prm.density_extra_count; ++i, ++r) {
+                const float rx = (pseudo_random(x, y, i * 3 + 0, prm.seed) - 0.5f) * 2.0f;
+                const float ry = (pseudo_random(x, y, i * 3 + 1, prm.seed) - 0.5f) * 2.0f;
+                const float rz = (pseudo_random(x, y, i * 3 + 2, prm.seed) - 0.5f) * 2.0f;
+                const float size_var = 1.0f + (pseudo_random(x, y, i * 3 + 100, prm.seed) - 0.5f) * prm.density_size_variance * 2.0f;
+                Gs = Gs + grad3(gr.scale, r) * (size_var * 0.8f);
+                Gbase += dot3(grad3(gr.pos, r), v3(rx, ry, rz)) * prm.density_position_jitter;
+                Gfo += grad1(gr.opacity, r) * prm.density_opacity_scale;
+                if (gr.rot) { Gq.w += gr.rot[r * 4]; Gq.x += gr.rot[r * 4 + 1]; Gq.y += gr.rot[r * 4 + 2]; Gq.z += gr.rot[r * 4 + 3]; }
+            }
+        // scale = (base, base, base / aspect') edge_factor;  final_opacity = opacity' conf (0.7 + 0.3 edge_factor)
+        const float d_tangent = (Gs.x + Gs.y) * edge_factor, d_normal = Gs.z * edge_factor;
+        const float d_ef = (Gs.x + Gs.y) * base + Gs.z * normal_scale + Gfo * (e.opacity * conf) * 0.3f;
+        const float d_base = d_tangent + d_normal / e.aspect_ratio + Gbase;
+        acc[0] += d_normal * (-normal_scale / e.aspect_ratio) * prm.aspect_ratio;
+        if (edge) {
+            if (inside) {  // dt / d threshold' = (ng - 1) / (1 - threshold')^2
+                const float u = 1.0f - e.edge_threshold;
+                acc[1] += -d_ef * (1.0f - e.edge_shrink) * ((ng - 1.0f) / (u * u));
+            }
+            acc[2] += d_ef * t * prm.edge_shrink;
+        }
+        if (gr.rot) {
+            const Quat dq = slerp_from_identity_dt(quat_from_normal(normal), e.normal_strength);
+            acc[3] += (Gq.w * dq.w + Gq.x * dq.x + Gq.y * dq.y + Gq.z * dq.z) * prm.normal_strength;
+        }
+        acc[4] += (d_base * c1 + Gbs) * prm.base_size;
+        acc[5] += Gfo * (conf * (0.7f + 0.3f * edge_factor)) * prm.opacity;
+    }
+#pragma unroll
+    for (int c = 0; c < 6; ++c) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) acc[c] += __shfl_xor(acc[c], o, 64);
+    }
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int c = 0; c < 6; ++c) {
+            if (S == 1) dst[((size_t)b * 6 + c) * plane + patch] = acc[c];
+            else dst[(((size_t)b * plane + patch) * S + split) * 6 + c] = acc[c];
+        }
+    }
+}
+
+// one thread per (patch, image): the S partials summed in split order
+__global__ __launch_bounds__(SB) void k_surface_guided_fold(uint32_t plane, int32_t S, const float *__restrict__ part,
+                                                            float *__restrict__ g_mods) {
+    const uint32_t b = blockIdx.y, patch = blockIdx.x * SB + threadIdx.x;
+    if (patch >= plane) return;
+    float acc[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    const float *p = part + ((size_t)b * plane + patch) * S * 6;
+    for (int s = 0; s < S; ++s)
+#pragma unroll
+        for (int c = 0; c < 6; ++c) acc[c] += p[(size_t)s * 6 + c];
+#pragma unroll
+    for (int c = 0; c < 6; ++c) g_mods[((size_t)b * 6 + c) * plane + patch] = acc[c];
 }
 
 int geometry(const FgsSurfaceDims *d, const FgsSurfaceParams *p, SurfGeom *g, SurfLayout *L, const char *who) {
@@ -478,6 +694,30 @@ int geometry(const FgsSurfaceDims *d, const FgsSurfaceParams *p, SurfGeom *g, Su
     L->bsum = up(L->img + (size_t)d->batch * IMG_FLOATS * sizeof(float));
     L->boff = up(L->bsum + bpb * sizeof(uint32_t));
     L->total = up(L->boff + bpb * sizeof(uint32_t));
+    return FGS_OK;
+}
+
+// the guide's shape (host only, before anything touches the device); *splits: waves per patch of the backward
+int guide_geometry(const SurfGeom &g, int32_t mods_h, int32_t mods_w, int32_t *splits, const char *who) {
+    if (mods_h < 1 || mods_w < 1) { fgs_set_error("%s: invalid guide: mods_h = %d, mods_w = %d (both >= 1)", who, mods_h, mods_w); return FGS_EINVAL; }
+    if ((int64_t)g.W * mods_w >= (1ll << 31) || (int64_t)g.H * mods_h >= (1ll << 31)) {
+        fgs_set_error("%s: invalid guide: W x mods_w = %d x %d or H x mods_h = %d x %d is beyond 2^31", who, g.W, mods_w, g.H, mods_h);
+        return FGS_EINVAL;
+    }
+    if ((uint64_t)g.B * 6ull * (uint64_t)mods_h * (uint64_t)mods_w >= (1ull << 31)) {
+        fgs_set_error("%s: invalid guide: B x 6 x mods_h x mods_w = %d x 6 x %d x %d is beyond 2^31", who, g.B, mods_h, mods_w);
+        return FGS_EINVAL;
+    }
+    // the most grid points a patch can own: ceil(W / Wp) pixels hold at most ceil(that / subsample) multiples of subsample
+    const int64_t pw = ((int64_t)g.W + mods_w - 1) / mods_w, ph = ((int64_t)g.H + mods_h - 1) / mods_h;
+    const int64_t pts = ((pw + g.sub - 1) / g.sub) * ((ph + g.sub - 1) / g.sub);
+    int64_t s = (pts + (int64_t)GB * GUIDE_THREAD_POINTS - 1) / ((int64_t)GB * GUIDE_THREAD_POINTS);
+    s = s < 1 ? 1 : (s > GUIDE_MAX_SPLITS ? GUIDE_MAX_SPLITS : s);
+    if ((uint64_t)mods_h * (uint64_t)mods_w * (uint64_t)s >= (1ull << 31)) {
+        fgs_set_error("%s: invalid guide: mods_h x mods_w x %lld waves per patch is beyond 2^31", who, (long long)s);
+        return FGS_EINVAL;
+    }
+    *splits = (int32_t)s;
     return FGS_OK;
 }
 
@@ -536,10 +776,83 @@ int fgs_surface_emit(const FgsSurfaceDims *dims, const FgsSurfaceParams *params,
     }
     char *s = reinterpret_cast<char *>(scratch);
     SurfOut out{o_positions, o_scales, o_rotations, o_colors, o_opacities, capacity};
-    hipLaunchKernelGGL(k_surface_emit, dim3(g.PB, g.B), dim3(SB), 0, reinterpret_cast<hipStream_t>(stream), g, *params, depth, color,
+    hipLaunchKernelGGL(k_surface_emit<false>, dim3(g.PB, g.B), dim3(SB), 0, reinterpret_cast<hipStream_t>(stream), g, *params, depth, color,
                        reinterpret_cast<const float *>(s + L.img), reinterpret_cast<const uint8_t *>(s + L.flags),
-                       reinterpret_cast<const uint32_t *>(s + L.boff), offsets, reinterpret_cast<int32_t *>(s), out);
+                       reinterpret_cast<const uint32_t *>(s + L.boff), offsets, reinterpret_cast<int32_t *>(s), SurfGuide{nullptr, 0, 0},
+                       static_cast<int32_t *>(nullptr), out);
     FGS_LAUNCH_CHECK("k_surface_emit");
+    return FGS_OK;
+}
+
+int fgs_surface_emit_guided(const FgsSurfaceDims *dims, const FgsSurfaceParams *params, const float *depth, const float *color,
+                            void *scratch, const int32_t *offsets, const float *mods, int32_t mods_h, int32_t mods_w,
+                            float *o_positions, float *o_scales, float *o_rotations, float *o_colors, float *o_opacities,
+                            int32_t *point_rows, int64_t capacity, void *stream) {
+    SurfGeom g;
+    SurfLayout L;
+    int32_t splits;
+    int rc = geometry(dims, params, &g, &L, "fgs_surface_emit_guided");
+    if (rc) return rc;
+    rc = guide_geometry(g, mods_h, mods_w, &splits, "fgs_surface_emit_guided");
+    if (rc) return rc;
+    if (capacity < 0) { fgs_set_error("fgs_surface_emit_guided: invalid capacity %lld", (long long)capacity); return FGS_EINVAL; }
+    if (!depth || !scratch || !offsets || !mods || !point_rows ||
+        (capacity > 0 && (!o_positions || !o_scales || !o_rotations || !o_colors || !o_opacities))) {
+        fgs_set_error("fgs_surface_emit_guided: null pointer argument");
+        return FGS_EINVAL;
+    }
+    char *s = reinterpret_cast<char *>(scratch);
+    SurfOut out{o_positions, o_scales, o_rotations, o_colors, o_opacities, capacity};
+    hipLaunchKernelGGL(k_surface_emit<true>, dim3(g.PB, g.B), dim3(SB), 0, reinterpret_cast<hipStream_t>(stream), g, *params, depth, color,
+                       reinterpret_cast<const float *>(s + L.img), reinterpret_cast<const uint8_t *>(s + L.flags),
+                       reinterpret_cast<const uint32_t *>(s + L.boff), offsets, reinterpret_cast<int32_t *>(s),
+                       SurfGuide{mods, mods_h, mods_w}, point_rows, out);
+    FGS_LAUNCH_CHECK("k_surface_emit<guided>");
+    return FGS_OK;
+}
+
+int fgs_surface_guided_backward_bytes(const FgsSurfaceDims *dims, const FgsSurfaceParams *params, int32_t mods_h, int32_t mods_w,
+                                      size_t *bytes) {
+    SurfGeom g;
+    SurfLayout L;
+    int32_t splits;
+    int rc = geometry(dims, params, &g, &L, "fgs_surface_guided_backward_bytes");
+    if (rc) return rc;
+    rc = guide_geometry(g, mods_h, mods_w, &splits, "fgs_surface_guided_backward_bytes");
+    if (rc) return rc;
+    if (!bytes) { fgs_set_error("fgs_surface_guided_backward_bytes: null output pointer"); return FGS_EINVAL; }
+    *bytes = splits == 1 ? 0 : (size_t)g.B * mods_h * mods_w * splits * 6 * sizeof(float);
+    return FGS_OK;
+}
+
+int fgs_surface_guided_backward(const FgsSurfaceDims *dims, const FgsSurfaceParams *params, const float *depth, const void *scratch,
+                                const int32_t *offsets, const float *mods, int32_t mods_h, int32_t mods_w, const int32_t *point_rows,
+                                const float *g_positions, const float *g_scales, const float *g_rotations, const float *g_opacities,
+                                float *g_mods, void *bwd_scratch, void *stream) {
+    SurfGeom g;
+    SurfLayout L;
+    int32_t splits;
+    int rc = geometry(dims, params, &g, &L, "fgs_surface_guided_backward");
+    if (rc) return rc;
+    rc = guide_geometry(g, mods_h, mods_w, &splits, "fgs_surface_guided_backward");
+    if (rc) return rc;
+    if (!depth || !scratch || !offsets || !mods || !point_rows || !g_mods || (splits > 1 && !bwd_scratch)) {
+        fgs_set_error("fgs_surface_guided_backward: null pointer argument");
+        return FGS_EINVAL;
+    }
+    const char *s = reinterpret_cast<const char *>(scratch);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const uint32_t plane = (uint32_t)mods_h * (uint32_t)mods_w;
+    float *part = reinterpret_cast<float *>(bwd_scratch);
+    hipLaunchKernelGGL(k_surface_guided_backward, dim3(plane * (uint32_t)splits, g.B), dim3(GB), 0, st, g, *params, depth,
+                       reinterpret_cast<const float *>(s + L.img), reinterpret_cast<const uint8_t *>(s + L.flags), offsets,
+                       SurfGuide{mods, mods_h, mods_w}, splits, point_rows, SurfGrads{g_positions, g_scales, g_rotations, g_opacities},
+                       splits == 1 ? g_mods : part);
+    FGS_LAUNCH_CHECK("k_surface_guided_backward");
+    if (splits > 1) {
+        hipLaunchKernelGGL(k_surface_guided_fold, dim3((plane + SB - 1) / SB, g.B), dim3(SB), 0, st, plane, splits, part, g_mods);
+        FGS_LAUNCH_CHECK("k_surface_guided_fold");
+    }
     return FGS_OK;
 }
 

@@ -925,6 +925,33 @@ class SAAGRefinementNet(nn.Module):
         return saag_refine_head(raw, *cloud, gains, residual_scale=self.residual_scale, backend=self.backend)
 
 
+class FeatureGuidedSAAG(nn.Module):
+    """The reference's FeatureGuidedSAAG (GDM:1422-1490, --experiment 3): two linear layers predict, per feature patch, six
+    modifications of the SAAG generator's parameters.  Same constructor arguments and defaults, forward(features (B,C,H,W)),
+    returned dict of six (B,H,W) maps (surface.MOD_KEYS, in that order) and state_dict keys (net.0.*, net.2.*).  The last layer
+    starts at zero: an untrained model returns (1, 0, 1, 1, 1, 1) everywhere, the plain SAAG cloud.  The maps go into
+    surface.guided_surface_gaussians, whose backward gives every one of them a gradient (the reference has no such path)."""
+
+    def __init__(self, feature_dim: int = 384, num_params: int = 6, hidden_dim: int = 64):
+        super().__init__()
+        self.feature_dim, self.num_params = feature_dim, num_params
+        self.net = nn.Sequential(nn.Linear(feature_dim, hidden_dim), nn.ReLU(inplace=True), nn.Linear(hidden_dim, num_params))
+        nn.init.zeros_(self.net[-1].weight)
+        nn.init.zeros_(self.net[-1].bias)
+
+    def forward(self, features: torch.Tensor) -> Dict[str, torch.Tensor]:
+        Bn, C, H, W = features.shape
+        p = self.net(features.permute(0, 2, 3, 1).reshape(Bn * H * W, C)).reshape(Bn, H, W, self.num_params)
+        return {
+            "aspect_ratio_mult": 1.0 + torch.tanh(p[..., 0]) * 0.5,     # [0.5, 1.5]
+            "edge_threshold_add": torch.tanh(p[..., 1]) * 0.1,          # [-0.1, 0.1]
+            "edge_shrink_mult": 1.0 + torch.tanh(p[..., 2]) * 0.3,      # [0.7, 1.3]
+            "normal_strength_mult": 1.0 + torch.tanh(p[..., 3]) * 0.3,  # [0.7, 1.3]
+            "base_size_mult": 1.0 + torch.tanh(p[..., 4]) * 0.5,        # [0.5, 1.5]
+            "opacity_mult": 1.0 + torch.tanh(p[..., 5]) * 0.3,          # [0.7, 1.3]
+        }
+
+
 # =================================================================================================================================
 # The reference's PhysicsDirectPatchDecoder (GDM:955-1147) with PhysicsFresnelZones (scripts/utils/fresnel_zones.py, "FZ": 400-614)
 # =================================================================================================================================

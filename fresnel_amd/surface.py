@@ -8,8 +8,11 @@ DepthMap::compute_surface_info, driven as its viewer drives them); kernels in cs
     clouds = surface_gaussians(depth, image)            # depth (B,H,W) in [0,1], image (B,3,H,W); one dict per image
 
     python -m fresnel_amd.surface --data_dir D [--image_size S] [--subsample K] [--batch_size B] [--overwrite] [--<parameter> V]
+                                  [--guide CHECKPOINT]
 
-A producer: it accepts no gradient.  There is no CPU fallback.
+`surface_gaussians` is a producer: it accepts no gradient.  `guided_surface_gaussians(depth, image, mods)` is the feature-guided
+variant (the reference's experiment 3, decoder.FeatureGuidedSAAG): six of the generator's parameters are modulated per patch of
+`mods`, and autograd carries dL/d rows back to `mods` through fgs_surface_guided_backward.  There is no CPU fallback.
 """
 import argparse
 import ctypes
@@ -22,6 +25,8 @@ import torch
 from . import _binding as B
 
 KEYS = ("positions", "scales", "rotations", "colors", "opacities")
+# channels of a guide map, in the order of FeatureGuidedSAAG's dict (include/fgs.h, "Feature-guided SAAG")
+MOD_KEYS = ("aspect_ratio_mult", "edge_threshold_add", "edge_shrink_mult", "normal_strength_mult", "base_size_mult", "opacity_mult")
 
 
 @dataclasses.dataclass
@@ -197,6 +202,122 @@ def surface_gaussians(depth, image=None, params=None, *, depth_exponent=0.7):
     return [{k: out[k][off[b]:off[b + 1]] for k in KEYS} for b in range(len(off) - 1)]
 
 
+# ---- feature-guided emit ----------------------------------------------------------------------------------------------------------
+def mods_tensor(mods):
+    """FeatureGuidedSAAG's dict of six (B,Hp,Wp) maps, or a (B,6,Hp,Wp) tensor -> (B,6,Hp,Wp) (part of the autograd graph)."""
+    if isinstance(mods, dict):
+        missing = [k for k in MOD_KEYS if k not in mods]
+        if missing:
+            raise B.FgsError(f"guide maps: missing {missing}")
+        mods = torch.stack([mods[k] for k in MOD_KEYS], dim=1)
+    if mods.dim() != 4 or mods.shape[1] != len(MOD_KEYS):
+        raise B.FgsError(f"guide maps must be (B,6,Hp,Wp), got {tuple(mods.shape)}")
+    return mods
+
+
+def _check_mods(state, mods):
+    if not mods.is_cuda or mods.device != state.depth.device:
+        raise B.FgsError("guide maps must live on the depth's GPU; there is no CPU fallback")
+    if mods.dim() != 4 or mods.shape[0] != state.dims.batch or mods.shape[1] != len(MOD_KEYS):
+        raise B.FgsError(f"guide maps must be ({state.dims.batch},6,Hp,Wp), got {tuple(mods.shape)}")
+    return mods.detach().contiguous().float()
+
+
+def emit_guided_raw(state, mods, outputs, point_rows, capacity):
+    """fgs_surface_emit_guided as it is (mods: (B,6,Hp,Wp) fp32 contiguous)."""
+    B.check(B.load().fgs_surface_emit_guided(ctypes.byref(state.dims), ctypes.byref(state.cparams), _ptr(state.depth), _ptr(state.color),
+                                             _ptr(state.scratch), _ptr(state.offsets), _ptr(mods), int(mods.shape[2]),
+                                             int(mods.shape[3]), *[_ptr(outputs[k]) for k in KEYS], _ptr(point_rows),
+                                             ctypes.c_int64(int(capacity)), _stream()), "fgs_surface_emit_guided")
+
+
+def _emit_guided_detached(state, mods, capacity=None):
+    if state.offsets_host is None:
+        state.offsets_host = state.offsets.cpu().tolist()   # THE host read: sizes the outputs
+    total = state.offsets_host[-1]
+    capacity = total if capacity is None else int(capacity)
+    if capacity < total:
+        raise B.FgsError(f"fgs_surface_emit_guided: capacity {capacity} is below the {total} rows of this cloud")
+    dev = state.depth.device
+    outputs = dict(positions=torch.empty(capacity, 3, dtype=torch.float32, device=dev),
+                   scales=torch.empty(capacity, 3, dtype=torch.float32, device=dev),
+                   rotations=torch.empty(capacity, 4, dtype=torch.float32, device=dev),
+                   colors=torch.empty(capacity, 3, dtype=torch.float32, device=dev),
+                   opacities=torch.empty(capacity, dtype=torch.float32, device=dev))
+    point_rows = torch.empty(state.dims.batch, state.points_per_image, dtype=torch.int32, device=dev)
+    emit_guided_raw(state, mods, outputs, point_rows, capacity)
+    return outputs, point_rows
+
+
+def guided_backward(state, mods, point_rows, g_positions=None, g_scales=None, g_rotations=None, g_opacities=None):
+    """fgs_surface_guided_backward: upstream gradients of the rows (None = zeros) -> dL/d mods (B,6,Hp,Wp), every element written."""
+    mods = _check_mods(state, mods)
+    lib = B.load()
+    Hp, Wp = int(mods.shape[2]), int(mods.shape[3])
+    n = ctypes.c_size_t(0)
+    B.check(lib.fgs_surface_guided_backward_bytes(ctypes.byref(state.dims), ctypes.byref(state.cparams), Hp, Wp, ctypes.byref(n)),
+            "fgs_surface_guided_backward_bytes")
+    total = state.offsets_host[-1] if state.offsets_host is not None else None
+    grads = []
+    for name, g, width in (("positions", g_positions, 3), ("scales", g_scales, 3), ("rotations", g_rotations, 4), ("opacities", g_opacities, 0)):
+        if g is not None:
+            g = g.detach().contiguous().float()
+            rows = g.shape[0] if g.dim() else 0
+            if not g.is_cuda or (total is not None and rows < total) or tuple(g.shape[1:]) != ((width,) if width else ()):
+                raise B.FgsError(f"guided_backward: the gradient of {name} has shape {tuple(g.shape)} for a cloud of {total} rows")
+        grads.append(g)
+    g_mods = torch.empty(mods.shape, dtype=torch.float32, device=mods.device)
+    bwd_scratch = torch.empty(n.value, dtype=torch.uint8, device=mods.device) if n.value else None
+    B.check(lib.fgs_surface_guided_backward(ctypes.byref(state.dims), ctypes.byref(state.cparams), _ptr(state.depth), _ptr(state.scratch),
+                                            _ptr(state.offsets), _ptr(mods), Hp, Wp, _ptr(point_rows), *[_ptr(g) for g in grads],
+                                            _ptr(g_mods), _ptr(bwd_scratch), _stream()), "fgs_surface_guided_backward")
+    return g_mods
+
+
+class _GuidedEmit(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, mods, state):
+        m = _check_mods(state, mods)
+        out, point_rows = _emit_guided_detached(state, m)
+        ctx.state, ctx.in_dtype = state, mods.dtype
+        ctx.save_for_backward(m, point_rows)
+        ctx.mark_non_differentiable(out["colors"], point_rows)
+        ctx.set_materialize_grads(False)
+        return tuple(out[k] for k in KEYS) + (point_rows,)
+
+    @staticmethod
+    def backward(ctx, g_pos, g_scale, g_rot, g_col, g_op, g_rows):
+        m, point_rows = ctx.saved_tensors
+        return guided_backward(ctx.state, m, point_rows, g_pos, g_scale, g_rot, g_op).to(ctx.in_dtype), None
+
+
+def emit_guided(state, mods):
+    """Phase 2 with a guide (fgs_surface_emit_guided): `state` of `count`, `mods` FeatureGuidedSAAG's dict or (B,6,Hp,Wp) -> dict
+    of the five concatenated tensors plus `point_rows` (B,P) int32, the first row of every point with a base row (-1: none).
+    Differentiable with respect to `mods` (fgs_surface_guided_backward).  One host read, of the offsets, as `emit`."""
+    out = _GuidedEmit.apply(mods_tensor(mods), state)
+    return dict(zip(KEYS + ("point_rows",), out))
+
+
+def guided_surface_gaussians(depth, image, mods, params=None, *, depth_exponent=0.7):
+    """`surface_gaussians` with the generator's aspect ratio, edge threshold, edge shrink, normal strength, base size and opacity
+    modulated per patch by `mods` (decoder.FeatureGuidedSAAG's dict of six (B,Hp,Wp) maps, or a (B,6,Hp,Wp) tensor on the GPU).
+    One dict per image; the tensors are views of the concatenated outputs, so autograd flows back to `mods`.  `depth` and `image`
+    accept no gradient.  Counts, offsets and row order are those of the plain cloud; identity maps (1, 0, 1, 1, 1, 1) give its bits."""
+    if depth.requires_grad or (image is not None and image.requires_grad):
+        raise B.FgsError("guided_surface_gaussians: depth and image accept no gradient (detach them)")
+    if depth.dim() == 2:
+        depth = depth.unsqueeze(0)
+    elif depth.dim() == 4 and depth.shape[1] == 1:
+        depth = depth[:, 0]
+    if image is not None and image.dim() == 3:
+        image = image.unsqueeze(0)
+    state = count(depth.float().pow(float(depth_exponent)), image, params)
+    out = emit_guided(state, mods)
+    off = state.offsets_host
+    return [{k: out[k][off[b]:off[b + 1]] for k in KEYS} for b in range(len(off) - 1)]
+
+
 # ---- command line ---------------------------------------------------------------------------------------------------------------
 def build_parser():
     ap = argparse.ArgumentParser(
@@ -212,6 +333,9 @@ def build_parser():
     ap.add_argument("--max_images", type=int, default=None)
     ap.add_argument("--depth_exponent", type=float, default=0.7)
     ap.add_argument("--overwrite", action="store_true", help="replace existing _saag.bin files (default: refuse)")
+    ap.add_argument("--guide", default=None, metavar="CHECKPOINT",
+                    help="modulate the clouds with a trained --experiment 3 checkpoint (decoder.FeatureGuidedSAAG) applied to each "
+                         "image's cached DINOv2 features (default: the plain generator)")
     for f in dataclasses.fields(SurfaceGaussianParams):
         if f.type in (bool, "bool"):
             ap.add_argument("--" + f.name, type=int, choices=(0, 1), default=int(f.default))
@@ -225,9 +349,20 @@ def params_from_args(args):
                                     for f in dataclasses.fields(SurfaceGaussianParams)})
 
 
+def load_guide(path, feature_dim):
+    """The FeatureGuidedSAAG of an --experiment 3 checkpoint ({model_state_dict: ...} or a bare state dict), strictly loaded."""
+    from .decoder import FeatureGuidedSAAG
+    ck = torch.load(path, map_location="cpu", weights_only=True)
+    sd = ck.get("model_state_dict", ck)
+    model = FeatureGuidedSAAG(feature_dim=feature_dim, num_params=sd["net.2.weight"].shape[0], hidden_dim=sd["net.0.weight"].shape[0])
+    model.load_state_dict(sd, strict=True)
+    return model.eval()
+
+
 def main(argv=None, generator=None, out=None):
     """`generator(depth (B,H,W), image (B,3,H,W), params, depth_exponent=) -> list of dicts`: surface_gaussians on the GPU by
-    default (tests pass a stub)."""
+    default (tests pass a stub).  With --guide it is also given `mods=` (B,6,37,37), the checkpoint's maps of the batch's cached
+    features, and defaults to guided_surface_gaussians."""
     from .data import ImageDataset
     from . import io as fio
     args = build_parser().parse_args(argv)
@@ -247,16 +382,24 @@ def main(argv=None, generator=None, out=None):
     if existing and not args.overwrite:
         print(f"refusing to overwrite {len(existing)} existing file(s), e.g. {existing[0]}: pass --overwrite", file=sys.stderr)
         return 2
+    guide = load_guide(args.guide, ds.feature_dim) if args.guide else None
     if generator is None:
-        def generator(depth, image, params, depth_exponent):
+        def generator(depth, image, params, depth_exponent, mods=None):
             dev = torch.device("cuda")
-            return surface_gaussians(depth.to(dev), image.to(dev), params, depth_exponent=depth_exponent)
+            if mods is None:
+                return surface_gaussians(depth.to(dev), image.to(dev), params, depth_exponent=depth_exponent)
+            return guided_surface_gaussians(depth.to(dev), image.to(dev), mods.to(dev), params, depth_exponent=depth_exponent)
     for i in range(0, len(todo), max(1, args.batch_size)):
         chunk = todo[i:i + max(1, args.batch_size)]
         items = [ds._step_tensors(idx) for idx, _, _ in chunk]
         depth = torch.stack([it[3][0] for it in items])
         image = torch.stack([it[1] for it in items])
-        clouds = generator(depth, image, params, depth_exponent=args.depth_exponent)
+        extra = {}
+        if guide is not None:
+            with torch.no_grad():
+                extra["mods"] = mods_tensor(guide(torch.stack([it[2] for it in items]).float()))
+        clouds = generator(depth, image, params, depth_exponent=args.depth_exponent, **extra)
+        clouds = [{k: v.detach() for k, v in c.items()} for c in clouds]
         for (_, name, target), cloud in zip(chunk, clouds):
             fio.save_gaussians_to_binary(str(target), cloud)
             print(f"{name}: {cloud['positions'].shape[0]} Gaussians -> {target}", file=out)

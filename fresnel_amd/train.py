@@ -22,6 +22,10 @@ Kept from TGD (same flag names / defaults / behaviour):
                     cloud of 1000 Gaussians where a batch has none, TGD:1043-1067), the residual regulariser --residual_weight
                     (TGD:932-939) joins the loss, --saag_backend hip runs its input gather and residual head as HIP kernels
                     (csrc/fgs_saag.hip);
+                    --experiment 3 --decoder guided_saag: FeatureGuidedSAAG (GDM:1422-1490) predicts six per-patch parameter maps
+                    and fresnel_amd.surface.guided_surface_gaussians builds every batch image's SAAG cloud from its own depth map
+                    under them (csrc/fgs_surface.hip, differentiable with respect to the maps; --surface_subsample); refused with
+                    --hip_graph, --stochastic_k and --fast_mode; bare --experiment 3 (the reference's dummy-cloud step, TGD:1135-1152) stays refused;
                     --decoder physics: PhysicsDirectPatchDecoder (TGD:1803-1810; --wavelength, --learnable_wavelength,
                     --focal_depth, --use_diffraction_placement), the reference's decoder for --use_wave_rendering without
                     --use_qsr: (B,N) phases computed from the depth; --head_backend hip runs its head as HIP kernels
@@ -78,8 +82,8 @@ from torch.optim.lr_scheduler import CosineAnnealingLR
 
 import numpy as np
 
-from .decoder import (HEAD_BACKENDS, NCA_BACKENDS, SAAG_BACKENDS, DirectPatchDecoder, FibonacciPatchDecoder, NCAGaussianDecoder,
-                      PatchGaussianDecoder, PhysicsDirectPatchDecoder, SAAGRefinementNet)
+from .decoder import (HEAD_BACKENDS, NCA_BACKENDS, SAAG_BACKENDS, DirectPatchDecoder, FeatureGuidedSAAG, FibonacciPatchDecoder,
+                      NCAGaussianDecoder, PatchGaussianDecoder, PhysicsDirectPatchDecoder, SAAGRefinementNet)
 from .data import collate_host_items
 from .dist import DPContext
 from .handoff import HFTSConfig, camera_for_batch, importance_subsample, sample_training_pose
@@ -165,6 +169,10 @@ class TrainingConfig:  # subset of TGD:97-162 that this path uses; same names an
     # "saag" (--experiment 1, TGD:1043-1067): backend of SAAGRefinementNet's input gather and residual head (torch: the
     # reference's ops | hip: csrc/fgs_saag.hip) and the weight of the residual regulariser (TGD:120, 932-939)
     saag_backend: str = "torch"
+    # "guided_saag" (--experiment 3 --decoder guided_saag): FeatureGuidedSAAG's maps modulate the SAAG generator, which builds every
+    # batch image's cloud from its own depth map on one point per surface_subsample x surface_subsample pixels (4: 4 096 points
+    # and at most 49 152 rows at 256 x 256 -- a setting, not a measured optimum)
+    surface_subsample: int = 4
     residual_weight: float = 0.01
     workspace: str = "worst"  # rasterizer workspaces: "worst" (sized for the radius cap) | "adaptive" (sized by the duplicates
                               # the previous steps needed, TileBasedRenderer(workspace="adaptive"); a step whose scene outgrew
@@ -332,6 +340,42 @@ def create_dummy_saag(batch_size: int, num_gaussians: int, device, generator: Op
     colors = torch.rand(batch_size, num_gaussians, 3, device=device, generator=generator)
     return (positions, torch.full((batch_size, num_gaussians, 3), 0.05, device=device), rotations, colors,
             torch.full((batch_size, num_gaussians), 0.8, device=device))
+
+
+GUIDED_PAD_Z = -1.0e6  # a padding row's position: beyond the far plane of every training camera (far = 100)
+
+
+def guided_saag_clouds(model, feats, depth, images, cfg: "TrainingConfig"):
+    """The --experiment 3 step's Gaussians: FeatureGuidedSAAG turns the batch's features (B,37,37,C) into six parameter maps,
+    surface.guided_surface_gaussians builds every image's SAAG cloud from its OWN depth map (B,1,S,S) and target image under
+    those maps (HIP, differentiable with respect to the maps; one host read, of the row offsets; the viewer's parameters except
+    that the cloud is left un-normalised, in the training camera's frame), and the clouds are padded to
+    the batch's largest count with rows the rasterizer culls (depth past the far plane, opacity 0): they reach no tile and get
+    no gradient.  -> dict of (B,N,.) tensors for the renderer.  (The reference's step, TGD:1135-1152, renders a 500-point random
+    cloud scaled by the mean of two of the maps instead: four maps never get a gradient there.)"""
+    from .surface import KEYS, SurfaceGaussianParams, guided_surface_gaussians
+    mods = model(feats.permute(0, 3, 1, 2))
+    # normalize_extent 0: the generator's un-normalised points are the depth map's own unprojection under fx = 0.8 W, cx = W / 2 --
+    # the training camera (TGD:1910-1917) -- so every Gaussian lands on the pixel it came from.  (The viewer's centring and
+    # normalisation would put the cloud AROUND that camera: half of it behind the near plane, the frame's border outside the view.)
+    params = SurfaceGaussianParams(subsample=cfg.surface_subsample, normalize_extent=0.0)
+    clouds = guided_surface_gaussians(depth.detach(), images.detach(), mods, params)
+    n = max(max(c["positions"].shape[0] for c in clouds), 1)
+    out = {}
+    for k in KEYS:
+        rows = []
+        for c in clouds:
+            t = c[k]
+            pad = t.new_zeros((n - t.shape[0],) + tuple(t.shape[1:]))
+            if k == "positions":
+                pad[:, 2] = GUIDED_PAD_Z
+            elif k == "scales":
+                pad.fill_(1e-3)
+            elif k == "rotations":
+                pad[:, 0] = 1.0
+            rows.append(torch.cat([t, pad]) if pad.shape[0] else t)
+        out[k] = torch.stack(rows)
+    return out
 
 
 def compute_losses(rendered, target, rendered_depth, target_depth, cfg: TrainingConfig, dp=None, vlm_density=None, residuals=None):
@@ -562,6 +606,9 @@ def train_step(model, renderer, camera, batch, optimizer, cfg: TrainingConfig, d
             saag = create_dummy_saag(feats.shape[0], DUMMY_SAAG_POINTS, feats.device, generator=sample_gen)
         out = model(feats.permute(0, 3, 1, 2), *saag)  # (a view: the hip backend samples the patch-major tensor in place)
         residuals = {k: out.pop(k) for k in RESIDUAL_KEYS}  # taken before any subsampling (TGD:1067 against :1154)
+    elif cfg.decoder == "guided_saag":  # frontal camera, no progressive K, no pose arguments, as experiment 1
+        el = az = None
+        out = guided_saag_clouds(model, feats, depth, images, cfg)
     elif cfg.decoder == "physics":  # the class's forward takes no pose arguments (the reference's call at TGD:1100 raises TypeError)
         out = model(feats.permute(0, 3, 1, 2), depth, num_gaussians=num_gaussians)
     else:
@@ -570,7 +617,7 @@ def train_step(model, renderer, camera, batch, optimizer, cfg: TrainingConfig, d
     if not (cfg.use_phase_blending or cfg.use_wave_rendering):
         out.pop("phases", None)
     # stochastic Gaussian rendering: K Gaussians by opacity importance, gathered on the device (TGD:1154-1187)
-    if hfts is not None:
+    if hfts is not None and cfg.decoder != "guided_saag":  # (refused with K < N for guided_saag: run_training)
         out, _ = importance_subsample(out, hfts.get_stochastic_k(out["positions"].shape[1]), generator=sample_gen)
     phases = out.get("phases")
     if cfg.use_wave_rendering and phases is not None and not mirror:
@@ -606,7 +653,7 @@ def train_step(model, renderer, camera, batch, optimizer, cfg: TrainingConfig, d
     return StepResult(terms, skipped)
 
 
-DECODERS = ("standin", "direct", "fibonacci", "nca", "saag", "physics")
+DECODERS = ("standin", "direct", "fibonacci", "nca", "saag", "physics", "guided_saag")
 
 
 def make_decoder(cfg: TrainingConfig):
@@ -620,6 +667,8 @@ def make_decoder(cfg: TrainingConfig):
                                     use_phase_output=phase_out,
                                     use_edge_aware=cfg.use_edge_aware, edge_scale_factor=cfg.edge_scale_factor,
                                     edge_opacity_boost=cfg.edge_opacity_boost)
+    if cfg.decoder == "guided_saag":  # the class's defaults (GDM:1440-1445)
+        return FeatureGuidedSAAG(feature_dim=cfg.feature_dim)
     if cfg.decoder == "saag":
         if cfg.saag_backend not in SAAG_BACKENDS:
             raise ValueError(f"unknown saag_backend {cfg.saag_backend!r}: one of {SAAG_BACKENDS}")
@@ -762,6 +811,15 @@ def run_training(cfg: TrainingConfig, dp: Optional[DPContext] = None,
     if cfg.decoder == "saag" and cfg.hip_graph:
         raise ValueError("--experiment 1 cannot be combined with --hip_graph: the size of the SAAG cloud follows the files, so "
                          "the step's shapes change from batch to batch")
+    if cfg.decoder == "guided_saag":
+        if device.type != "cuda":
+            raise ValueError("--decoder guided_saag needs a GPU device: the SAAG generator's HIP kernels have no CPU fallback")
+        if cfg.hip_graph:
+            raise ValueError("--decoder guided_saag cannot be combined with --hip_graph: a host read of the row offsets sizes the "
+                             "cloud of every batch")
+        if hfts is not None and (hfts.stochastic_k is not None or hfts.fast_mode):
+            raise ValueError("--decoder guided_saag cannot be combined with --stochastic_k / --fast_mode: the sampled indices are "
+                             "shared by the batch, and the batch's clouds differ in size")
     model = make_decoder(cfg).to(device)
     dp.broadcast_parameters(model)
     train_res = hfts.get_effective_train_resolution(cfg.image_size) if hfts is not None else cfg.image_size
@@ -943,6 +1001,9 @@ def arg_parser() -> argparse.ArgumentParser:
                     help="initial value of the learnable step size (the reference parses this flag, TGD:1439, and never uses it)")
     ap.add_argument("--saag_backend", default=c.saag_backend, choices=list(SAAG_BACKENDS),
                     help="input gather and residual head of --experiment 1: the reference's torch ops (default) or the fused HIP kernels")
+    ap.add_argument("--surface_subsample", type=int, default=c.surface_subsample,
+                    help="--decoder guided_saag: one SAAG point per K x K pixels of the depth map (default 4: 4 096 points and at most "
+                         "49 152 Gaussians per 256 x 256 image; a setting, not a measured optimum)")
     ap.add_argument("--residual_weight", type=float, default=c.residual_weight,
                     help="weight of the residual regulariser of --experiment 1 (TGD:120)")
     ap.add_argument("--nca_backend", default=c.nca_backend, choices=list(NCA_BACKENDS),
@@ -954,12 +1015,29 @@ def config_from_args(a) -> TrainingConfig:
     """The TrainingConfig of a parsed command line (no device yet).  --experiment 1 trains the SAAG refinement net
     (TGD:1043-1067), --experiment 2 a patch-grid decoder, --experiment 4 the Fibonacci decoder (TGD:1829-1841), with
     --use_phase_blending through the Fourier renderer (TGD:1877-1890), --experiment 5 the NCA decoder (TGD:1841-1849) through the
-    TileBasedRenderer; the reference's experiment 3 has no counterpart here."""
-    if a.experiment not in (1, 2, 4, 5):
-        raise SystemExit("only --experiment 1 (SAAG refinement), --experiment 2 (patch-grid decoder), --experiment 4 (Fibonacci "
-                         "decoder) and --experiment 5 (NCA decoder) are on this repo's hot path")
+    TileBasedRenderer; --experiment 3 --decoder guided_saag the feature-guided SAAG generator (FeatureGuidedSAAG, GDM:1422-1490,
+    through surface.guided_surface_gaussians).  Bare --experiment 3 stays refused: it names the reference's step (TGD:1135-1152),
+    which renders a random dummy cloud and is not offered here."""
+    if a.experiment == 3 and a.decoder != "guided_saag":
+        raise SystemExit("--experiment 3 alone names the reference's dummy-cloud step, which this repo does not offer: pass "
+                         "--experiment 3 --decoder guided_saag to train the feature-guided SAAG generator")
+    if a.experiment not in (1, 2, 3, 4, 5):
+        raise SystemExit("only --experiment 1 (SAAG refinement), --experiment 2 (patch-grid decoder), --experiment 3 --decoder "
+                         "guided_saag (feature-guided SAAG), --experiment 4 (Fibonacci decoder) and --experiment 5 (NCA decoder) "
+                         "are on this repo's hot path")
     decoder = a.decoder
-    if a.experiment == 1:
+    if a.experiment == 3:
+        if a.hip_graph:
+            raise SystemExit("--decoder guided_saag cannot be combined with --hip_graph: a host read of the row offsets sizes the "
+                             "cloud of every batch")
+        if a.stochastic_k is not None or a.fast_mode:
+            raise SystemExit("--decoder guided_saag cannot be combined with --stochastic_k / --fast_mode: the sampled indices are "
+                             "shared by the batch, and the batch's clouds differ in size")
+        if a.surface_subsample < 1:
+            raise SystemExit("--surface_subsample must be at least 1")
+    elif decoder == "guided_saag":
+        raise SystemExit("--decoder guided_saag is --experiment 3")
+    elif a.experiment == 1:
         if decoder in ("direct", "fibonacci", "nca"):
             raise SystemExit(f"--experiment 1 trains the SAAG refinement net: --decoder {decoder} contradicts it")
         if a.hip_graph:
@@ -1004,6 +1082,7 @@ def config_from_args(a) -> TrainingConfig:
                           decoder=decoder, head_backend=a.head_backend, n_spiral_points=a.n_spiral_points,
                           nca_steps=a.nca_steps, nca_neighbors=a.nca_neighbors, nca_backend=a.nca_backend,
                           nca_step_size=a.nca_step_size, saag_backend=a.saag_backend, residual_weight=a.residual_weight,
+                          surface_subsample=a.surface_subsample,
                           learnable_wavelength=a.learnable_wavelength, focal_depth=a.focal_depth,
                           use_physics_zones=a.use_physics_zones, use_diffraction_placement=a.use_diffraction_placement)
 

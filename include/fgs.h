@@ -706,6 +706,48 @@ int fgs_surface_emit(const FgsSurfaceDims *dims, const FgsSurfaceParams *params,
                      void *scratch, const int32_t *offsets, float *o_positions, float *o_scales, float *o_rotations,
                      float *o_colors, float *o_opacities, int64_t capacity, void *stream);
 
+/* Feature-guided SAAG (the reference's experiment 3, FeatureGuidedSAAG, scripts/models/gaussian_decoder_models.py:1422-1490): the emit
+ * above with six of its parameters modulated per patch of a guide map, and the gradient of the rows with respect to that map.
+ *   mods       (B, 6, Hp, Wp) fp32 contiguous DEVICE; channels in the order of the decoder's dict:
+ *              aspect_ratio_mult, edge_threshold_add, edge_shrink_mult, normal_strength_mult, base_size_mult, opacity_mult
+ *   patch      the point at pixel (x, y) reads m = mods[b, :, (y Hp) / H, (x Wp) / W]: integer division on PIXEL coordinates
+ *   effective  aspect_ratio' = aspect_ratio * m[0]     edge_threshold' = edge_threshold + m[1]    edge_shrink' = edge_shrink * m[2]
+ *              normal_strength' = normal_strength * m[3]   base_size' = base_size * m[4]          opacity' = opacity * m[5]
+ *              one fp32 operation each, rounded on its own.  Everything else is fgs_surface_emit in its operation order; the effective
+ *              values are read by base, normal_scale and edge_factor, by final_opacity, by the slerp parameter (not clamped:
+ *              normal_strength' may exceed 1), by wrap_base and the wrap offset (layer + 1) wrap_layer_spacing base_size', and by the
+ *              fill jitter.  None of the six feeds a count decision: fgs_surface_count, the flags, the offsets and the row order are
+ *              those of the plain cloud.  With m = (1, 0, 1, 1, 1, 1) everywhere the guided emit is BIT-EQUAL to fgs_surface_emit.
+ * fgs_surface_emit_guided: one launch on fgs_surface_emit's grid, after fgs_surface_count with the same dims and params.  Also writes
+ *     point_rows (B P int32): the first row of every point that has its BASE flag, -1 for every other point.  Capacity and status as
+ *     fgs_surface_emit (offsets[B] > capacity: nothing is written, point_rows included, and the first int32 of scratch is 1).
+ * fgs_surface_guided_backward: g_mods (B, 6, Hp, Wp) = dL/d mods from the upstream gradients of positions, scales, rotations and
+ *     opacities (any may be NULL = zeros; colours carry no gradient).  EVERY element of g_mods is written, a patch without a point
+ *     gets exact zeros.  Recomputes each point's forward from depth, mods, the count's scratch (read only) and point_rows; nothing
+ *     else is saved.  At the kinks the derivative follows the branch the forward took: `ng > edge_threshold'` is strict; the clamp
+ *     of t passes its gradient on the closed interval [0, 1] (as torch.clamp); the lerp and slerp branches of slerp(identity, q, t)
+ *     are each differentiated as written.  Covered: base_size through the scales of all five row kinds and the positions of wrap
+ *     and fill rows; aspect_ratio through scale.z of base, back, wall and fill rows; edge_threshold and edge_shrink through
+ *     edge_factor into those rows' scales and every row's opacity; normal_strength through the rotations of base and fill rows;
+ *     opacity through every row's opacity.
+ *     One wave per (patch, image) walks the patch's rectangle of grid points and sums six partials in a fixed order; a patch that
+ *     can own more than 256 grid points is split over up to 256 waves whose partials a second launch adds in split order, through
+ *     bwd_scratch (fgs_surface_guided_backward_bytes; 0 bytes and NULL allowed when no patch is split).  NO atomics: two calls agree
+ *     to the bit, and a batch equals its single images to the bit.  fp32, not built to the emit's operation order: agreement
+ *     with an fp64 differentiation is to fp32 rounding.
+ * Shapes: those of fgs_surface_emit, and mods_h, mods_w >= 1, W mods_w < 2^31, H mods_h < 2^31, B 6 mods_h mods_w < 2^31, mods and
+ * point_rows (and g_mods) non-null; otherwise FGS_EINVAL with a message before anything touches the device. */
+int fgs_surface_emit_guided(const FgsSurfaceDims *dims, const FgsSurfaceParams *params, const float *depth, const float *color,
+                            void *scratch, const int32_t *offsets, const float *mods, int32_t mods_h, int32_t mods_w,
+                            float *o_positions, float *o_scales, float *o_rotations, float *o_colors, float *o_opacities,
+                            int32_t *point_rows, int64_t capacity, void *stream);
+int fgs_surface_guided_backward_bytes(const FgsSurfaceDims *dims, const FgsSurfaceParams *params, int32_t mods_h, int32_t mods_w,
+                                      size_t *bytes);
+int fgs_surface_guided_backward(const FgsSurfaceDims *dims, const FgsSurfaceParams *params, const float *depth, const void *scratch,
+                                const int32_t *offsets, const float *mods, int32_t mods_h, int32_t mods_w, const int32_t *point_rows,
+                                const float *g_positions, const float *g_scales, const float *g_rotations, const float *g_opacities,
+                                float *g_mods, void *bwd_scratch, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * Importance-subsampling hand-off between decoder and rasterizer (--stochastic_k; reference
  * scripts/training/train_gaussian_decoder.py:1160-1187): the n_out Gaussians whose indices torch.multinomial
