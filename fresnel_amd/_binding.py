@@ -33,6 +33,7 @@ EXPORTED_SYMBOLS = [
     "fgs_physics_workspace_bytes", "fgs_physics_forward", "fgs_physics_backward",
     "fgs_surface_workspace_bytes", "fgs_surface_count", "fgs_surface_emit",
     "fgs_surface_emit_guided", "fgs_surface_guided_backward_bytes", "fgs_surface_guided_backward",
+    "fgs_match_workspace_bytes", "fgs_match_forward", "fgs_match_backward",
 ]
 
 STAGES = ["project", "depth_sort", "dup_emit", "tile_sort", "tile_ranges", "composite_fwd",
@@ -171,6 +172,15 @@ FGS_SURFACE_STATE_OFFSET = 64
 (FGS_SURFACE_KEPT, FGS_SURFACE_BASE, FGS_SURFACE_BACK, FGS_SURFACE_WALLS, FGS_SURFACE_WRAPS, FGS_SURFACE_FILLS) = (1, 2, 4, 8, 16, 32)
 
 
+FGS_MATCH_TILE = 1024  # candidates per LDS tile of the matching kernel (include/fgs.h)
+
+
+class FgsMatchDims(ctypes.Structure):
+    _fields_ = [("batch", ctypes.c_int32), ("num_pred", ctypes.c_int32), ("num_target", ctypes.c_int32),
+                ("w_pos", ctypes.c_float), ("w_scale", ctypes.c_float), ("w_rot", ctypes.c_float),
+                ("w_color", ctypes.c_float), ("w_opacity", ctypes.c_float), ("w_coverage", ctypes.c_float)]
+
+
 class FgsError(RuntimeError):
     pass
 
@@ -282,6 +292,12 @@ def load():
     lib.fgs_surface_guided_backward.argtypes = [sfd, sfp] + [vp] * 4 + [ctypes.c_int32] * 2 + [vp] * 8
     for fn in (lib.fgs_surface_workspace_bytes, lib.fgs_surface_count, lib.fgs_surface_emit, lib.fgs_surface_emit_guided,
                lib.fgs_surface_guided_backward_bytes, lib.fgs_surface_guided_backward):
+        fn.restype = ctypes.c_int
+    md = cp(FgsMatchDims)
+    lib.fgs_match_workspace_bytes.argtypes = [md, cp(ctypes.c_size_t), cp(ctypes.c_size_t)]
+    lib.fgs_match_forward.argtypes = [md] + [vp] * 9
+    lib.fgs_match_backward.argtypes = [md] + [vp] * 7
+    for fn in (lib.fgs_match_workspace_bytes, lib.fgs_match_forward, lib.fgs_match_backward):
         fn.restype = ctypes.c_int
     for fn in (lib.fgs_asm_propagate_workspace_bytes, lib.fgs_asm_propagate_forward, lib.fgs_asm_propagate_backward,
                lib.fgs_spectral_workspace_bytes, lib.fgs_spectral_loss_forward, lib.fgs_spectral_loss_backward,

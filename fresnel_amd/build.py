@@ -75,6 +75,9 @@ SOURCES = {
     # the "canonical fp32" contract of fgs_project.hip again: how many rows a point emits, and in which order, is decided by
     # compares of values that a literal fp32 restatement of the reference must reproduce bit for bit (include/fgs.h)
     "fgs_surface.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
+    # as fgs_nca.hip: the match distance d2 = (dx dx + dy dy) + dz dz and the gradient rows are DEFINED with every operation
+    # rounded on its own, divisions and the square root IEEE (include/fgs.h); tests/match_checker.py restates them bit for bit
+    "fgs_match.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
 }
 LINK_LIBS = ["-lhipfft"]
 

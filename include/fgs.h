@@ -749,6 +749,66 @@ int fgs_surface_guided_backward(const FgsSurfaceDims *dims, const FgsSurfacePara
                                 float *g_mods, void *bwd_scratch, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * GaussianMatchingLoss of the reference's distillation path (scripts/training/train_direct_decoder.py, "TDD" 158-357): the
+ * bidirectional Chamfer loss between a predicted and a target cloud.  pred (B, Np, 14), target (B, Nt, 14) fp32 contiguous; a
+ * row is position 0..2, scale 3..5, quaternion 6..9, colour 10..12, opacity 13.  pred_keep (B, Np), target_keep (B, Nt): uint8,
+ * NULL = all ones.
+ *
+ * Active rows.  A row is active iff its keep byte is non-zero and (|x| + |y|) + |z| > 1e-6f || |opacity| > 1e-6f, the sums
+ * rounded to fp32, a NaN comparing false (the reference's zero-padding filter, TDD:268-273).  n_p, n_t: the active counts of an
+ * image.  An image with n_p == 0 or n_t == 0 is SKIPPED: all its terms are 0, its match entries -1, its gradient rows 0; it
+ * still counts in the division by B (TDD:263-276, 347).
+ *
+ * Canonical match (this library's definition; the reference takes the minimum of cdist chunk by chunk with a strict `<`):
+ * d2(i, j) = (dx dx + dy dy) + dz dz of the coordinate differences, every operation rounded to fp32; a NaN d2 counts as +inf;
+ * the match of an active query is the active candidate with the smallest (d2, j) -- the lowest index wins ties.  Inactive
+ * queries get -1.  For ANY input, NaN and Inf included, a written index is -1 or an active row's index.  fwd (B, Np):
+ * predictions -> targets; bwd (B, Nt): targets -> predictions.
+ *
+ * Terms of a non-skipped image (t_m: the matched target of a prediction; p_m: the matched prediction of a target):
+ *     position, scale, colour   mean over the 3 n_p elements of (p - t_m)^2      opacity   mean over the n_p elements
+ *     rotation                  1 - mean_i |q^p . q^t|, q^ = q / max(|q|, 1e-8f), |q| = sqrt(((q0 q0 + q1 q1) + q2 q2) + q3 q3),
+ *                               the dot product (((a0 b0 + a1 b1) + a2 b2) + a3 b3) of the divided components
+ *     coverage                  2 cov_position + 0.5 cov_scale + 0.5 cov_colour + 2 cov_opacity, the same four means over the n_t
+ *                               targets against p_m
+ *     batch                     w_pos position + w_scale scale + w_rot rotation + w_color colour + w_opacity opacity + w_coverage coverage
+ * Every per-element value ((p - t)^2, |dot|) is formed in fp32; the sums are accumulated in double in a fixed order (fixed grid,
+ * fixed-shape block tree, block partials in block order); means, coverage and batch are formed in double from those sums and
+ * each is rounded to fp32 once.  terms (B, 8): position, scale, rotation, colour, opacity, coverage, batch, 0.
+ * total = sum_b batch_b / B is the caller's (fresnel_amd/losses.py).
+ *
+ * Gradient: dL/dpred only, for L = *g_total x total.  Nothing flows through the indices; the target gets none.  Inactive rows and
+ * skipped images get exact zeros.  Every operation below is rounded to fp32 on its own (no FMA), divisions and the square
+ * root IEEE.  Per image:
+ *     gs = *g_total x (1.0f / (float)B)
+ *     a3 = 2.0f / (float)(3 n_p)   a1 = 2.0f / (float)n_p   r1 = 1.0f / (float)n_p   b3 = 2.0f / (float)(3 n_t)   b1 = 2.0f / (float)n_t
+ *     k_position = (gs w_pos) a3, k_scale = (gs w_scale) a3, k_colour = (gs w_color) a3, k_opacity = (gs w_opacity) a1
+ *     gc = gs w_coverage;  c_position = (gc 2.0f) b3, c_scale = (gc 0.5f) b3, c_colour = (gc 0.5f) b3, c_opacity = (gc 2.0f) b1
+ * Row i, active, t = target[fwd[i]], channel c of group X in {position, scale, colour, opacity}:
+ *     g[c] = k_X (p[c] - t[c]);  then for every target j with bwd[j] == i, in ascending j:  g[c] = g[c] + c_X (p[c] - target[j][c])
+ * (any in-degree 0 ... n_t, no float atomics: two calls agree to the bit).  Quaternion: n = |q_p|, cp = n < 1e-8f ? 1e-8f : n,
+ * ct likewise of t; dot as above; s = (dot > 0) - (dot < 0) (torch's subgradient: 0 at 0); e = -(((gs w_rot) r1) s);
+ * gh[c] = e (t_q[c] / ct);  where the clamp is active (n < 1e-8f) it passes no gradient: g_q[c] = gh[c] / cp;  elsewhere
+ * u = ((gh0 q0 + gh1 q1) + gh2 q2) + gh3 q3, v = ((u / cp) / cp) / n, g_q[c] = gh[c] / cp - q[c] v.
+ *
+ * saved: fwd (B, Np), bwd (B, Nt), counts (B, 2) = (n_p, n_t), int32, in this order without padding; every element is written by
+ * the forward and it goes unchanged through the backward.  counts (B, 2) is the same pair as an output.  The backward needs no
+ * scratch (NULL is accepted).  FGS_MATCH_TILE: the candidates per LDS tile of the matching kernel -- the size at which its inner
+ * loop starts over (the tests put Nt on and beside it).
+ * Shapes: 1 <= Np, Nt <= 65536, B <= 65535; otherwise FGS_EINVAL (bad dims, null pointers) / FGS_EUNSUPPORTED before anything
+ * touches the device.  Neither call synchronises the host or allocates. */
+#define FGS_MATCH_TILE 1024
+typedef struct FgsMatchDims {
+    int32_t batch, num_pred, num_target;
+    float w_pos, w_scale, w_rot, w_color, w_opacity, w_coverage;
+} FgsMatchDims;
+int fgs_match_workspace_bytes(const FgsMatchDims *dims, size_t *saved_bytes, size_t *scratch_bytes);
+int fgs_match_forward(const FgsMatchDims *dims, const float *pred, const float *target, const uint8_t *pred_keep,
+                      const uint8_t *target_keep, float *terms, int32_t *counts, void *saved, void *scratch, void *stream);
+int fgs_match_backward(const FgsMatchDims *dims, const float *pred, const float *target, const void *saved, const float *g_total,
+                       float *g_pred, void *scratch, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Importance-subsampling hand-off between decoder and rasterizer (--stochastic_k; reference
  * scripts/training/train_gaussian_decoder.py:1160-1187): the n_out Gaussians whose indices torch.multinomial
  * drew (DEVICE int64 (n_out,), unique, shared by the batch) are gathered out of every (B, n_in, .) tensor into
