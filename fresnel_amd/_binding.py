@@ -40,6 +40,9 @@ STAGES = ["project", "depth_sort", "dup_emit", "tile_sort", "tile_ranges", "comp
           "composite_bwd", "project_bwd", "splat_fwd", "field_fwd", "field_bwd", "splat_bwd"]
 
 
+FWD_EXIT_OFF, FWD_EXIT_ON = 0x100, 0x200  # include/fgs.h: flags of FgsDims.fwd_variant
+
+
 class FgsDims(ctypes.Structure):
     _fields_ = [("batch", ctypes.c_int32), ("num_gaussians", ctypes.c_int32),
                 ("width", ctypes.c_int32), ("height", ctypes.c_int32),
@@ -60,7 +63,7 @@ class FgsSavedLayout(ctypes.Structure):
                 ("tiles_x", ctypes.c_int32), ("tiles_y", ctypes.c_int32),
                 ("seg_off", ctypes.c_size_t), ("seg_tile", ctypes.c_size_t), ("seg_ckpt", ctypes.c_size_t),
                 ("seg_capacity", ctypes.c_size_t), ("seg_len", ctypes.c_int32), ("tile_w", ctypes.c_int32),
-                ("unit_order", ctypes.c_size_t)]
+                ("unit_order", ctypes.c_size_t), ("fwd_open", ctypes.c_size_t)]
 
 
 class FgsAsmDims(ctypes.Structure):
@@ -326,7 +329,8 @@ def check(rc, what):
 
 def make_dims(batch, num_gaussians, width, height, max_radius=64.0, background=(0.0, 0.0, 0.0),
               use_phase=False, phase_amplitude=0.25, num_cameras=1, saturation_skip=False, tuning=None, dup_capacity=0):
-    """`tuning`: optional dict of FgsDims overrides {seg_len, fwd_variant, bin_mode, tile_w, sort_mode} (0 / absent = automatic).
+    """`tuning`: optional dict of FgsDims overrides {seg_len, fwd_variant, bin_mode, tile_w, sort_mode} (0 / absent = automatic), and
+    `fwd_exit`: 0 | 1 | -1 = the exiting depth-split forward automatic | on | off -- the FGS_FWD_EXIT_ON / _OFF flag of FgsDims.fwd_variant.
     `dup_capacity`: room for that many (tile, Gaussian) duplicates instead of the worst case (0 = worst case; a call that needs
     more overflows: NaN images, zero gradients, saved.counters[1] = 1 -- include/fgs.h)."""
     if isinstance(dup_capacity, bool) or int(dup_capacity) != dup_capacity or not 0 <= int(dup_capacity) <= 0xFFFFFFFF:
@@ -340,10 +344,15 @@ def make_dims(batch, num_gaussians, width, height, max_radius=64.0, background=(
     d.phase_amplitude = float(phase_amplitude)
     d.num_cameras = int(num_cameras)
     d.saturation_skip = 1 if saturation_skip else 0
-    for k, v in (tuning or {}).items():
+    tuning = dict(tuning or {})
+    fwd_exit = int(tuning.pop("fwd_exit", 0))
+    for k, v in tuning.items():
         if k not in ("seg_len", "fwd_variant", "bin_mode", "tile_w", "sort_mode"):
             raise FgsError(f"unknown tuning field {k!r}")
         setattr(d, k, int(v))
+    if fwd_exit not in (0, 1, -1) or (fwd_exit and d.fwd_variant < 0):
+        raise FgsError(f"fwd_exit must be 0, 1 or -1, and 0 with the row-split forward (fwd_variant < 0), got {fwd_exit!r}")
+    d.fwd_variant |= {0: 0, 1: FWD_EXIT_ON, -1: FWD_EXIT_OFF}[fwd_exit]
     d.dup_capacity = int(dup_capacity)
     return d
 

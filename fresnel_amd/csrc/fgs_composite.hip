@@ -21,7 +21,7 @@
 #include "fgs_wave.h"
 
 #if (defined(FGS_BWD_DYN_LDS) || defined(FGS_BWD_WIDE_WAVES) || defined(FGS_PHASE_SCAN) || defined(FGS_CKPT_NT) || defined(FGS_PHASE_WAVE_BLOCKS) || \
-     defined(FGS_BWD_UNIT_TRACE) || defined(FGS_BWD_TILE_ORDER)) && !defined(FGS_EXPERIMENT_BUILD)
+     defined(FGS_BWD_UNIT_TRACE) || defined(FGS_BWD_TILE_ORDER) || defined(FGS_FWD_HEAD_ENTRIES)) && !defined(FGS_EXPERIMENT_BUILD)
 #error "work-split / timing switches of this unit are for experiment builds: python -m fresnel_amd.build --define ... (sets FGS_EXPERIMENT_BUILD; fgs_version() then says so)"
 #endif
 
@@ -335,18 +335,79 @@ __device__ __forceinline__ BlendState ckpt_load(const float *ck) {
     return {nt_load(ck), nt_load(ck + PL), nt_load(ck + 2 * PL), 1.0f - nt_load(ck + 3 * PL), nt_load(ck + 4 * PL)};
 }
 
+// One chunk (<= 64 list entries from `base`) of a wave's walk in the depth-split forward, k_blend_fwd_parts and k_blend_fwd_head:
+// stage the chunk in the wave's own LDS rows, then composite it onto the lane's four sub-tile states.
+struct BlendLane { uint32_t shx, shy; float fx0, fx1, fy0; };  // the lane's column / row bit in cbits / flags and its pixel coordinates
+__device__ __forceinline__ void blend_fwd_chunk(float4 *__restrict__ w0, float4 *__restrict__ w1, float4 *__restrict__ w2, uint32_t lane,
+                                                uint32_t base, uint32_t n, uint32_t X0, uint32_t Y0, const uint32_t *__restrict__ dup_ids,
+                                                const float *__restrict__ rec, const BlendLane &ln, float (&T)[4], float (&Cr)[4],
+                                                float (&Cg)[4], float (&Cb)[4], float (&Dm)[4]) {
+    // staging COMPACTS the chunk: only the records that touch this wave's 16 x 16 pixels are parked (in list order),
+    // so the list loop below has no skip test -- on 32 x 16 tiles ~15 % of a list's entries touch only the other half
+    float4 q0, q1, q2;
+    uint32_t flags = 0, cbits = 0;
+    if (lane < n) {
+        const uint32_t gid = dup_ids[base + lane];
+        const float4 *r = reinterpret_cast<const float4 *>(rec + (size_t)gid * FGS_REC_FLOATS);
+        q0 = r[0]; q1 = r[1]; q2 = r[2];
+        stage_decode_w<2>(X0, Y0, __float_as_uint(q2.z), __float_as_uint(q2.w), q1.y, flags, cbits);
+    }
+    const unsigned long long tmask = __ballot((flags & 15u) != 0u);
+    const uint32_t nt = (uint32_t)__popcll(tmask);
+    if (flags & 15u) {
+        const uint32_t slot = __builtin_amdgcn_mbcnt_hi((uint32_t)(tmask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)tmask, 0u));
+        blend_stage_fold(q0, q1, q2, flags, cbits, blend_lop(q1.y));
+        w0[slot] = q0; w1[slot] = q1; w2[slot] = q2;
+    }
+    __builtin_amdgcn_wave_barrier();  // wave-private LDS: one wave's LDS instructions execute in order
+    for (uint32_t j = 0; j < nt; ++j) {
+        const uint32_t fl = __builtin_amdgcn_readfirstlane(__float_as_uint(w2[j].w));  // stage_decode_w flags
+        const uint32_t msk = fl & 15u;
+        const float4 q0 = w0[j], q1 = w1[j], q2 = w2[j];
+        // (Skipping the lane masks for entries whose bbox covers the tile, or the min for opacities <= 0.98, behind
+        // wave-uniform branches -- what pays in the backward -- made this loop 10 % SLOWER: 0.68 -> 0.75 ms at config 3;
+        // its passes are too short to amortise a branch.)
+        const uint32_t cbits = __float_as_uint(q2.z), rbits = __float_as_uint(q2.w);
+        // the lane's two column masks once per entry (3.3 sub-tile passes per entry on average: -2.8 %)
+        const uint32_t mxc[2] = {(uint32_t)__builtin_amdgcn_sbfe((int)cbits, ln.shx, 1), (uint32_t)__builtin_amdgcn_sbfe((int)cbits, ln.shx + 8u, 1)};
+        // ... and its two column offsets (3.3 passes per entry: one subtraction per pass would be more)
+        float dxc[2] = {ln.fx0 - q0.x, ln.fx1 - q0.x};
+        asm("" : "+v"(dxc[0]), "+v"(dxc[1]));
+#pragma unroll
+        for (int row = 0; row < 2; ++row) {
+            if (!((msk >> (2 * row)) & 3u)) continue;
+            const float dy = row ? ln.fy0 + 8.0f - q0.y : ln.fy0 - q0.y;
+            const float bdy = q0.w * dy, cyy = fmaf(q1.x * dy, dy, q1.y);  // the row's part of the exponent, lop included
+            const uint32_t my = (uint32_t)__builtin_amdgcn_sbfe((int)rbits, ln.shy + 8u * row, 1);
+#pragma unroll
+            for (int col = 0; col < 2; ++col) {
+                const int s = 2 * row + col;
+                if (!((msk >> s) & 1u)) continue;  // scalar branch: sub-tile not touched
+                const float dx = dxc[col];
+                const float t = q0.z * dx + bdy;
+                const uint32_t mk = my & mxc[col];
+                const float a1 = blend_alpha1(t * dx + cyy, mk);  // alpha / 0.99, zero outside the bbox
+                const float w = a1 * T[s];  // (alpha T) / 0.99
+                Cr[s] += w * q1.z; Cg[s] += w * q1.w; Cb[s] += w * q2.x; Dm[s] += w * q2.y;
+                T[s] = fmaf(w, -ALPHA_MAX, T[s]);
+            }
+        }
+    }
+    __builtin_amdgcn_wave_barrier();
+}
+
 // WIDE = 1: 32 x 16 tiles (FgsSavedLayout.tile_w = 32; the backward then has eight sub-tiles per lane and ~0.6x as many
 // list entries, reductions and gradient rows).  The forward keeps its 16 x 16 register budget -- holding eight sub-tiles per
 // lane here cost 99 VGPRs, 4-5 waves per SIMD and +5 ... 35 % -- by giving every list part TWO waves, one per 16 x 16 half
 // of the tile: a wave stages the part's records with the flags of ITS half and skips the entries that do not touch it, so
 // its work is that of the 16 x 16 tile's list plus one LDS read and a branch per skipped entry.
-template <int NP, int WIDE>
+template <int NP, int WIDE, bool REST>
 __global__ __launch_bounds__(64 * NP * (1 + WIDE)) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_blend_fwd_parts(  // 64 VGPRs: -2.6 %
     uint32_t tiles, uint32_t tiles_x, uint32_t W, uint32_t H, float bg0, float bg1, float bg2,
     const uint32_t *__restrict__ tile_order, const uint32_t *__restrict__ ranges,
     const uint32_t *__restrict__ dup_ids, const float *__restrict__ rec, float *__restrict__ pix_state,
     float *__restrict__ out_rgb, float *__restrict__ out_depth, const uint32_t *__restrict__ seg_off,
-    float *__restrict__ seg_ckpt, uint32_t seg_len, uint32_t order_groups) {
+    float *__restrict__ seg_ckpt, uint32_t seg_len, uint32_t order_groups, const uint32_t *__restrict__ fwd_open, uint32_t head_segs) {
     constexpr int NW = NP * (1 + WIDE);                   // waves per block
     constexpr int TSX = WIDE ? 4 : 2;                     // sub-tile columns of the whole tile
     constexpr int PL = 2 * TSX * 64, SLOT = 5 * PL;       // floats per checkpoint plane / slot: [5][2 TSX][64]
@@ -358,6 +419,14 @@ __global__ __launch_bounds__(64 * NP * (1 + WIDE)) __attribute__((amdgpu_waves_p
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t part = WIDE ? wave >> 1 : wave, half = WIDE ? wave & 1u : 0u;
+    // REST: the launch behind k_blend_fwd_head (below).  A half that the head closed or finished has its pixels and every
+    // checkpoint slot already: its waves touch nothing and only keep the block's barrier; a block without an open half leaves.
+    bool mine = true;
+    if (REST) {
+        const uint32_t open0 = fwd_open[2u * c.tile], open1 = WIDE ? fwd_open[2u * c.tile + 1u] : 0u;
+        if (!(open0 | open1)) return;
+        mine = (half ? open1 : open0) != 0u;
+    }
     const uint32_t X0 = c.X0 + 16u * half;                // this wave's 16 x 16 half of the tile
     const uint32_t lx = lane & 7u, ly = lane >> 3;
     const uint32_t nseg = (c.end - c.start + seg_len - 1) / seg_len;
@@ -372,80 +441,43 @@ __global__ __launch_bounds__(64 * NP * (1 + WIDE)) __attribute__((amdgpu_waves_p
     float T[4], Cr[4], Cg[4], Cb[4], Dm[4];
 #pragma unroll
     for (int s = 0; s < 4; ++s) { T[s] = 1.0f; Cr[s] = 0; Cg[s] = 0; Cb[s] = 0; Dm[s] = 0; }
-    const uint32_t shx = lx, shy = 16u + ly;  // this lane's column bit in cbits / row bit in flags
-    float fx0 = (float)(X0 + lx), fx1 = (float)(X0 + lx + 8u), fy0 = (float)(c.Y0 + ly);
-    asm("" : "+v"(fx0), "+v"(fx1), "+v"(fy0));
-    for (uint32_t base = pstart; base < pend; base += 64) {
-        const uint32_t n = min(64u, pend - base);
-        if (base != pstart && ((base - c.start) % seg_len) == 0) {  // LOCAL state in front of this segment
+    BlendLane ln = {lx, 16u + ly, (float)(X0 + lx), (float)(X0 + lx + 8u), (float)(c.Y0 + ly)};
+    asm("" : "+v"(ln.fx0), "+v"(ln.fx1), "+v"(ln.fy0));
+    uint32_t wstart = pstart;  // where this wave's walk begins
+    if (REST && part == 0 && mine) {
+        // part 0 of an open half resumes behind the head's min(spp, head_segs) segments, from the state the head left in the slot
+        // in front of the next one -- with T ITSELF in the A plane (1 - (1 - T) is not T), which is put right here
+        const uint32_t hs = min(spp, head_segs);
+        float *ck = slot0 + (size_t)hs * SLOT;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            float *k = ck + cell(s);
+            Cr[s] = nt_load(k); Cg[s] = nt_load(k + PL); Cb[s] = nt_load(k + 2 * PL); T[s] = nt_load(k + 3 * PL); Dm[s] = nt_load(k + 4 * PL);
+            nt_store(k + 3 * PL, 1.0f - T[s]);
+        }
+        wstart = c.start + hs * seg_len;
+    }
+    const uint32_t wend = (!REST || mine) ? pend : wstart;
+    for (uint32_t base = wstart; base < wend; base += 64) {
+        const uint32_t n = min(64u, wend - base);
+        if (base != wstart && ((base - c.start) % seg_len) == 0) {  // LOCAL state in front of this segment
             float *ck = slot0 + (size_t)((base - c.start) / seg_len) * SLOT;
 #pragma unroll
             for (int s = 0; s < 4; ++s) ckpt_store<PL>(ck + cell(s), BlendState{Cr[s], Cg[s], Cb[s], T[s], Dm[s]});
         }
-        // staging COMPACTS the chunk: only the records that touch this wave's 16 x 16 pixels are parked (in list order),
-        // so the list loop below has no skip test -- on 32 x 16 tiles ~15 % of a list's entries touch only the other half
-        float4 q0, q1, q2;
-        uint32_t flags = 0, cbits = 0;
-        if (lane < n) {
-            const uint32_t gid = dup_ids[base + lane];
-            const float4 *r = reinterpret_cast<const float4 *>(rec + (size_t)gid * FGS_REC_FLOATS);
-            q0 = r[0]; q1 = r[1]; q2 = r[2];
-            stage_decode_w<2>(X0, c.Y0, __float_as_uint(q2.z), __float_as_uint(q2.w), q1.y, flags, cbits);
-        }
-        const unsigned long long tmask = __ballot((flags & 15u) != 0u);
-        const uint32_t nt = (uint32_t)__popcll(tmask);
-        if (flags & 15u) {
-            const uint32_t slot = __builtin_amdgcn_mbcnt_hi((uint32_t)(tmask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)tmask, 0u));
-            blend_stage_fold(q0, q1, q2, flags, cbits, blend_lop(q1.y));
-            sh0[wave][slot] = q0; sh1[wave][slot] = q1; sh2[wave][slot] = q2;
-        }
-        __builtin_amdgcn_wave_barrier();  // wave-private LDS: one wave's LDS instructions execute in order
-        for (uint32_t j = 0; j < nt; ++j) {
-            const uint32_t fl = __builtin_amdgcn_readfirstlane(__float_as_uint(sh2[wave][j].w));  // stage_decode_w flags
-            const uint32_t msk = fl & 15u;
-            const float4 q0 = sh0[wave][j], q1 = sh1[wave][j], q2 = sh2[wave][j];
-            // (Skipping the lane masks for entries whose bbox covers the tile, or the min for opacities <= 0.98, behind
-            // wave-uniform branches -- what pays in the backward -- made this loop 10 % SLOWER: 0.68 -> 0.75 ms at config 3;
-            // its passes are too short to amortise a branch.)
-            const uint32_t cbits = __float_as_uint(q2.z), rbits = __float_as_uint(q2.w);
-            // the lane's two column masks once per entry (3.3 sub-tile passes per entry on average: -2.8 %)
-            const uint32_t mxc[2] = {(uint32_t)__builtin_amdgcn_sbfe((int)cbits, shx, 1), (uint32_t)__builtin_amdgcn_sbfe((int)cbits, shx + 8u, 1)};
-            // ... and its two column offsets (3.3 passes per entry: one subtraction per pass would be more)
-            float dxc[2] = {fx0 - q0.x, fx1 - q0.x};
-            asm("" : "+v"(dxc[0]), "+v"(dxc[1]));
-#pragma unroll
-            for (int row = 0; row < 2; ++row) {
-                if (!((msk >> (2 * row)) & 3u)) continue;
-                const float dy = row ? fy0 + 8.0f - q0.y : fy0 - q0.y;
-                const float bdy = q0.w * dy, cyy = fmaf(q1.x * dy, dy, q1.y);  // the row's part of the exponent, lop included
-                const uint32_t my = (uint32_t)__builtin_amdgcn_sbfe((int)rbits, shy + 8u * row, 1);
-#pragma unroll
-                for (int col = 0; col < 2; ++col) {
-                    const int s = 2 * row + col;
-                    if (!((msk >> s) & 1u)) continue;  // scalar branch: sub-tile not touched
-                    const float dx = dxc[col];
-                    const float t = q0.z * dx + bdy;
-                    const uint32_t mk = my & mxc[col];
-                    const float a1 = blend_alpha1(t * dx + cyy, mk);  // alpha / 0.99, zero outside the bbox
-                    const float w = a1 * T[s];  // (alpha T) / 0.99
-                    Cr[s] += w * q1.z; Cg[s] += w * q1.w; Cb[s] += w * q2.x; Dm[s] += w * q2.y;
-                    T[s] = fmaf(w, -ALPHA_MAX, T[s]);
-                }
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
+        blend_fwd_chunk(sh0[wave], sh1[wave], sh2[wave], lane, base, n, X0, c.Y0, dup_ids, rec, ln, T, Cr, Cg, Cb, Dm);
     }
     // ---- hand the part results over and compose them (the part-0 wave of each half) ----
     const uint32_t last = nseg ? (nseg - 1) / spp : 0u;
     if (NP > 1 && nseg > spp) {  // more than one part
-        if (active && part != 0) {
+        if (active && part != 0 && (!REST || mine)) {
             float *ck = (part == last) ? slot0 : slot0 + (size_t)((part + 1) * spp) * SLOT;
 #pragma unroll
             for (int s = 0; s < 4; ++s) ckpt_store<PL>(ck + cell(s), BlendState{Cr[s], Cg[s], Cb[s], T[s], Dm[s]});
         }
         __threadfence_block();
         __syncthreads();
-        if (part != 0) return;
+        if (part != 0 || (REST && !mine)) return;
         // part 0: its own result is the absolute state in front of part 1
         {
             float *ck = slot0 + (size_t)spp * SLOT;
@@ -462,7 +494,7 @@ __global__ __launch_bounds__(64 * NP * (1 + WIDE)) __attribute__((amdgpu_waves_p
                 if (pp != last) ckpt_store<PL>(dst + cell(s), acc);
             }
         }
-    } else if (part != 0) {
+    } else if (part != 0 || (REST && !mine)) {
         return;
     }
     const size_t HW = (size_t)W * H;
@@ -472,6 +504,125 @@ __global__ __launch_bounds__(64 * NP * (1 + WIDE)) __attribute__((amdgpu_waves_p
         if (px < W && py < H)
             pixel_store(pix_state, out_rgb, out_depth, c.b, HW, (size_t)py * W + px, bg0, bg1, bg2, Cr[s], Cg[s], Cb[s], 1.0f - T[s],
                         T[s], Dm[s]);
+    }
+}
+
+// The exiting forward (FgsDims.fwd_variant without FGS_FWD_EXIT_OFF; automatic from 8192 tile halves per launch): k_blend_fwd_head, then k_blend_fwd_parts<NP, WIDE, true> for what it leaves open.
+//
+// ABSORBING STATE.  The update of a pixel's state by a list entry is w' = a' T (0 <= a' <= 1), X <- fma(w', x', X) for the four
+// accumulators X = C_r, C_g, C_b, D with the staged multipliers x' (0.99 colour, 0.99 depth), T <- fma(w', -0.99, T): T never
+// grows.  With K >= |x'| for every entry that can still come, |w' x'| <= T K, and once
+//     T <= 2^-26   and   T K < 2^-26 |X|   for each of the four X
+// every later addend is below a quarter ulp of X: fma returns X itself (round to nearest, either sign, also at a binade
+// boundary), 1 - T is 1.0f, and pixel_store's C + T bg is C (K_colour covers |bg| as well).  The state the caller sees -- C, D,
+// A = 1 -- is then a fixed point of the rest of the list, and the SAME fixed point under the depth split: a later part's lump
+// T_abs C_p has |C_p| <= K (sum of w') <= K (1 + eps), which the factor of two between a quarter and half an ulp covers, as it
+// covers the rounding of the test itself.  The comparisons are strict: a zero accumulator or a NaN / infinite bound closes nothing.
+// K is per image and from the data (k_project's per-block maxima, folded here); nothing assumes colours <= 1.
+// A tile half is CLOSED when the test holds on every in-frame pixel of its four sub-tiles (pixels outside the frame keep T = 1 for
+// ever and do not veto).
+//
+// One wave per 16 x 16 tile half walks the first min(spp, head_segs) segments of part 0 -- the whole list when there is one part --
+// and tests at every 64-entry chunk boundary.  Part 0's state is absolute, so stopping there keeps the parent's association.
+//   closed, or the list ended: the wave stores the pixels and fills every later checkpoint slot of its half with what the
+//     backward's re-basing turns into the parent's bits: the closing state (C, A = 1 - T, D) in the later slots of part 0 and in the
+//     slot of every later part's first segment, the local identity (0, A = 0, 0) in the inner slots of later parts
+//     (compose(abs, identity) = C_abs + 0 * 0 and T = 0 * 1 = +0).  fwd_open[tile][half] = 0.
+//   still open: its state goes into the slot in front of the next segment (the slot part 0 writes there anyway), T itself in the
+//     A plane, and fwd_open[tile][half] = 1: part 0's wave of the rest kernel resumes from it, the other parts run as they did.
+// head_segs bounds the launch for scenes that never saturate: one wave per half for a quarter of the longest list would leave
+// most of the chip waiting.
+template <int WIDE>
+__global__ __launch_bounds__(64 * (1 + WIDE)) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_blend_fwd_head(
+    uint32_t tiles, uint32_t tiles_x, uint32_t W, uint32_t H, float bg0, float bg1, float bg2,
+    const uint32_t *__restrict__ tile_order, const uint32_t *__restrict__ ranges,
+    const uint32_t *__restrict__ dup_ids, const float *__restrict__ rec, float *__restrict__ pix_state,
+    float *__restrict__ out_rgb, float *__restrict__ out_depth, const uint32_t *__restrict__ seg_off,
+    float *__restrict__ seg_ckpt, uint32_t seg_len, uint32_t order_groups, uint32_t *__restrict__ fwd_open, uint32_t head_segs,
+    uint32_t np, const uint32_t *__restrict__ fwd_max, uint32_t max_recs) {
+    constexpr int NW = 1 + WIDE;
+    constexpr int TSX = WIDE ? 4 : 2;
+    constexpr int PL = 2 * TSX * 64, SLOT = 5 * PL;
+    __shared__ float4 sh0[NW][64], sh1[NW][64], sh2[NW][64];
+    const uint32_t slot_in_order = order_groups > 1u ? fgs_xcd_remap(blockIdx.x, gridDim.x) : blockIdx.x;
+    const TileCtx c = tile_ctx_of(tile_order[slot_in_order], tiles, tiles_x, ranges, 8u * TSX);
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t half = WIDE ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : 0u;
+    const uint32_t X0 = c.X0 + 16u * half;
+    const uint32_t lx = lane & 7u, ly = lane >> 3;
+    const uint32_t len = c.end - c.start;
+    const uint32_t nseg = (len + seg_len - 1) / seg_len;
+    const uint32_t spp = (nseg + np - 1) / np;
+    const uint32_t hs = np == 1u ? nseg : min(spp, head_segs);  // segments of part 0 this wave walks at most
+    const uint32_t hlen = min(len, hs * seg_len);
+    float *slot0 = seg_ckpt + (size_t)seg_off[c.tile] * SLOT + 2u * half * 64u + lane;
+    auto cell = [](int s) { return ((s >> 1) * TSX + (s & 1)) * 64; };
+    // the image's bound: maxima of bit patterns (fgs_project.hip), the background's channels among the colours
+    uint32_t kcb = 0u, kdb = 0u;
+    {
+        const uint32_t *fm = fwd_max + (size_t)c.b * max_recs * 2u;
+        for (uint32_t i = lane; i < max_recs; i += 64u) { kcb = max(kcb, fm[2u * i]); kdb = max(kdb, fm[2u * i + 1u]); }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { kcb = max(kcb, (uint32_t)__shfl_xor(kcb, o, 64)); kdb = max(kdb, (uint32_t)__shfl_xor(kdb, o, 64)); }
+        kcb = max(max(kcb, __float_as_uint(bg0) & 0x7FFFFFFFu), max(__float_as_uint(bg1) & 0x7FFFFFFFu, __float_as_uint(bg2) & 0x7FFFFFFFu));
+    }
+    const float Kc = __uint_as_float(__builtin_amdgcn_readfirstlane(kcb)), Kd = __uint_as_float(__builtin_amdgcn_readfirstlane(kdb));  // scalars
+    bool inframe[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) inframe[s] = X0 + 8u * (s & 1) + lx < W && c.Y0 + 8u * (s >> 1) + ly < H;
+    float T[4], Cr[4], Cg[4], Cb[4], Dm[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) { T[s] = 1.0f; Cr[s] = 0; Cg[s] = 0; Cb[s] = 0; Dm[s] = 0; }
+    BlendLane ln = {lx, 16u + ly, (float)(X0 + lx), (float)(X0 + lx + 8u), (float)(c.Y0 + ly)};
+    asm("" : "+v"(ln.fx0), "+v"(ln.fx1), "+v"(ln.fy0));
+    constexpr float Q = 1.490116119384765625e-8f;  // 2^-26
+    uint32_t done = 0;  // entries walked
+    bool closed = false;
+    while (done < hlen && !closed) {
+        if (done != 0u && (done % seg_len) == 0) {  // state in front of this segment (part 0: absolute)
+            float *ck = slot0 + (size_t)(done / seg_len) * SLOT;
+#pragma unroll
+            for (int s = 0; s < 4; ++s) ckpt_store<PL>(ck + cell(s), BlendState{Cr[s], Cg[s], Cb[s], T[s], Dm[s]});
+        }
+        const uint32_t n = min(64u, hlen - done);
+        blend_fwd_chunk(sh0[half], sh1[half], sh2[half], lane, c.start + done, n, X0, c.Y0, dup_ids, rec, ln, T, Cr, Cg, Cb, Dm);
+        done += n;
+        bool veto = false;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const float tc = T[s] * Kc;
+            const bool ok = T[s] <= Q && tc < Q * fabsf(Cr[s]) && tc < Q * fabsf(Cg[s]) && tc < Q * fabsf(Cb[s]) && T[s] * Kd < Q * fabsf(Dm[s]);
+            veto |= inframe[s] && !ok;
+        }
+        closed = __ballot(veto) == 0ull;
+    }
+    const bool finished = closed || done == len;
+    if (lane == 0) fwd_open[2u * c.tile + half] = finished ? 0u : 1u;
+    if (!finished) {
+        float *ck = slot0 + (size_t)hs * SLOT;  // done == hs * seg_len < len
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            float *k = ck + cell(s);
+            nt_store(k, Cr[s]); nt_store(k + PL, Cg[s]); nt_store(k + 2 * PL, Cb[s]); nt_store(k + 3 * PL, T[s]); nt_store(k + 4 * PL, Dm[s]);
+        }
+        return;
+    }
+    const size_t HW = (size_t)W * H;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        const uint32_t px = X0 + 8u * (s & 1) + lx, py = c.Y0 + 8u * (s >> 1) + ly;
+        if (px < W && py < H)
+            pixel_store(pix_state, out_rgb, out_depth, c.b, HW, (size_t)py * W + px, bg0, bg1, bg2, Cr[s], Cg[s], Cb[s], 1.0f - T[s],
+                        T[s], Dm[s]);
+    }
+    // the slots the walk did not reach (none when the list ended)
+#pragma clang loop unroll(disable) vectorize(disable)
+    for (uint32_t k =(done + seg_len - 1) / seg_len; k < nseg; ++k) {
+        const bool absolute = k < spp || k % spp == 0u;
+        float *ck = slot0 + (size_t)k * SLOT;
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+            ckpt_store<PL>(ck + cell(s), absolute ? BlendState{Cr[s], Cg[s], Cb[s], T[s], Dm[s]} : BlendState{0.0f, 0.0f, 0.0f, 1.0f, 0.0f});
     }
 }
 
@@ -1279,6 +1430,12 @@ static T *fgs_at(const char *base, size_t offset) {
     return reinterpret_cast<T *>(const_cast<char *>(base) + offset);
 }
 
+// List entries of part 0 that k_blend_fwd_head walks at most (in whole segments, one at least).  The halves of the benchmark scenes
+// that close at all close within 384 entries (DESIGN_LOG.md 24); a longer head only lengthens the launch for scenes that never do.
+#ifndef FGS_FWD_HEAD_ENTRIES
+#define FGS_FWD_HEAD_ENTRIES 384u
+#endif
+
 int fgs_launch_composite_fwd(const FgsPlan &p, const float *phase, char *saved, float *out_rgb,
                              float *out_depth, hipStream_t st) {
     const uint32_t grid = (uint32_t)p.d.batch * p.tiles;
@@ -1300,9 +1457,34 @@ int fgs_launch_composite_fwd(const FgsPlan &p, const float *phase, char *saved, 
     const int fw = p.fwd_waves;
     if (const int np = p.fwd_parts) {
         const uint32_t seg_len = (uint32_t)p.L.seg_len, order_groups = (uint32_t)p.order_groups;
+        // The exiting forward: the head kernel (one wave per tile half over the front of part 0), then the parts kernel for the
+        // halves it left open.  One part: the head walks the whole list and there is nothing left.
+        const bool exiting = p.fwd_exit;
+        uint32_t *fwd_open = exiting ? fgs_at<uint32_t>(saved, p.L.fwd_open) : nullptr;
+        const uint32_t head_segs = FGS_FWD_HEAD_ENTRIES / seg_len > 0u ? FGS_FWD_HEAD_ENTRIES / seg_len : 1u;
+        if (exiting) {
+            const uint32_t *fwd_max = fgs_at<const uint32_t>(saved, p.s_fwd_max);
+            const uint32_t max_recs = ((uint32_t)p.d.num_gaussians + 255u) / 256u;
+#define FGS_HEAD_LAUNCH(WD)                                                                                               \
+    hipLaunchKernelGGL((k_blend_fwd_head<WD>), dim3(grid), dim3(64 * (1 + WD)), 0, st, tiles, tiles_x, W, H, bg0, bg1, bg2, tile_order, \
+                       ranges, dup_ids, rec, pix, out_rgb, out_depth, seg_off, seg_ckpt, seg_len, order_groups, fwd_open, head_segs, \
+                       (uint32_t)np, fwd_max, max_recs)
+            if (p.tile_w == 32) FGS_HEAD_LAUNCH(1); else FGS_HEAD_LAUNCH(0);
+#undef FGS_HEAD_LAUNCH
+            FGS_LAUNCH_CHECK("k_blend_fwd_head");
+            if (np == 1) return FGS_OK;
+        }
 #define FGS_PARTS_LAUNCH(NP, WD)                                                                                          \
-    hipLaunchKernelGGL((k_blend_fwd_parts<NP, WD>), dim3(grid), dim3(64 * NP * (1 + WD)), 0, st, tiles, tiles_x, W, H, bg0, bg1, \
-                       bg2, tile_order, ranges, dup_ids, rec, pix, out_rgb, out_depth, seg_off, seg_ckpt, seg_len, order_groups)
+    do {                                                                                                                  \
+        if (exiting)                                                                                                      \
+            hipLaunchKernelGGL((k_blend_fwd_parts<NP, WD, true>), dim3(grid), dim3(64 * NP * (1 + WD)), 0, st, tiles, tiles_x, W, H, bg0, \
+                               bg1, bg2, tile_order, ranges, dup_ids, rec, pix, out_rgb, out_depth, seg_off, seg_ckpt, seg_len,   \
+                               order_groups, fwd_open, head_segs);                                                        \
+        else                                                                                                              \
+            hipLaunchKernelGGL((k_blend_fwd_parts<NP, WD, false>), dim3(grid), dim3(64 * NP * (1 + WD)), 0, st, tiles, tiles_x, W, H, bg0, \
+                               bg1, bg2, tile_order, ranges, dup_ids, rec, pix, out_rgb, out_depth, seg_off, seg_ckpt, seg_len,   \
+                               order_groups, fwd_open, head_segs);                                                        \
+    } while (0)
         if (p.tile_w == 32) {
             if (np == 1) FGS_PARTS_LAUNCH(1, 1); else if (np == 2) FGS_PARTS_LAUNCH(2, 1); else if (np == 4) FGS_PARTS_LAUNCH(4, 1);
             else FGS_PARTS_LAUNCH(8, 1);

@@ -33,9 +33,12 @@ int fgs_make_plan(const FgsDims *d, FgsPlan *p, int layers, bool segment_ckpt) {
                       d->num_gaussians, d->width, d->height, (double)d->max_radius, d->num_cameras);
         return FGS_EINVAL;
     }
-    const int fv = d->fwd_variant, afv = fv < -16 || fv > 16 ? 3 /* invalid; INT_MIN has no negation */ : (fv < 0 ? -fv : fv);
+    // fwd_variant >= 0 may carry one of the two exit flags (include/fgs.h); fv is the work split without them
+    const int exit_flags = d->fwd_variant >= 0 ? (d->fwd_variant & (FGS_FWD_EXIT_OFF | FGS_FWD_EXIT_ON)) : 0;
+    const int fv = d->fwd_variant - exit_flags, afv = fv < -16 || fv > 16 ? 3 /* invalid; INT_MIN has no negation */ : (fv < 0 ? -fv : fv);
     if (d->seg_len < 0 || d->seg_len > 512 || d->seg_len % 64 != 0 || (afv != 0 && afv != 1 && afv != 2 && afv != 4 && !(fv == 8 || fv == 16)) ||
-        d->bin_mode < 0 || d->bin_mode > 2 || (d->tile_w != 0 && d->tile_w != 16 && d->tile_w != 32) || d->sort_mode < 0 || d->sort_mode > 11) {
+        d->bin_mode < 0 || d->bin_mode > 2 || (d->tile_w != 0 && d->tile_w != 16 && d->tile_w != 32) || d->sort_mode < 0 || d->sort_mode > 11 ||
+        exit_flags == (FGS_FWD_EXIT_OFF | FGS_FWD_EXIT_ON)) {
         fgs_set_error("invalid tuning: seg_len=%d fwd_variant=%d bin_mode=%d tile_w=%d sort_mode=%d", d->seg_len, d->fwd_variant,
                       d->bin_mode, d->tile_w, d->sort_mode);
         return FGS_EINVAL;
@@ -50,7 +53,7 @@ int fgs_make_plan(const FgsDims *d, FgsPlan *p, int layers, bool segment_ckpt) {
     // terms, the ten-sum reduction and its gradient row, the row-sum traffic, the lists -- is paid 0.6x as often.  The phase
     // path (one wave per sub-tile), the row-split forward (saturation_skip / fwd_variant < 0) and the splat renderers
     // (layers > 1 or no segment checkpoints) keep 16 x 16.
-    const bool wide_ok = !d->use_phase && !d->saturation_skip && d->fwd_variant >= 0 && layers == 1 && segment_ckpt;
+    const bool wide_ok = !d->use_phase && !d->saturation_skip && fv >= 0 && layers == 1 && segment_ckpt;
     if (d->tile_w == 32 && !wide_ok) {
         fgs_set_error("tile_w=32 needs the blend path with the depth-split forward");
         return FGS_EINVAL;
@@ -175,6 +178,21 @@ int fgs_make_plan(const FgsDims *d, FgsPlan *p, int layers, bool segment_ckpt) {
     L.unit_order = o;
     p->has_unit_order = !d->use_phase && segment_ckpt && layers == 1;
     if (p->has_unit_order) o = align256(o + ucap * 4);
+    // the exiting forward (FgsDims.fwd_variant flags): one word per (tile, 16 x 16 half) that the head kernel leaves for the rest kernel, then
+    // per projection block the largest staged colour and depth multiplier (k_project -> the head's bound).  Behind every older
+    // section, and only where the depth-split forward runs with segment checkpoints.
+    L.fwd_open = o;
+    // Automatic: on when the head kernel's one wave per tile half fills the chip's 8192 wave slots at least once.  Below that the
+    // head runs part 0 at a fraction of the occupancy the four-waves-per-tile launch has, IN FRONT of the other parts instead of beside
+    // them: config 2 (4096 tiles of 16 x 16, a third of its units saturated) measured forward 0.096 -> 0.149 ms with the exit, config 3
+    // (8192 halves) 0.471 -> 0.212, the decoder-like scene 1.23 -> 0.31 (DESIGN_LOG.md 24).  Sizes in between are not measured.
+    const bool exit_ok = p->fwd_parts > 0 && layers == 1 && segment_ckpt;
+    p->fwd_exit = exit_ok && (exit_flags == FGS_FWD_EXIT_ON || (exit_flags == 0 && B * p->tiles * (size_t)(p->tile_w / 16) >= 8192));
+    p->s_fwd_max = o;
+    if (p->fwd_exit) {
+        p->s_fwd_max = o = align256(o + B * p->tiles * 2 * 4);
+        o = align256(o + B * ((N + 255) / 256) * 2 * 4);
+    }
     L.total_bytes = o;
     L.dup_capacity = dcap;
     L.tiles_x = tx; L.tiles_y = ty;

@@ -47,6 +47,10 @@ struct FgsPlan {
     int32_t order_groups;     // XCD groups of the forward's launch order (fgs_bin.hip tile_group): 8 on the blend path's
                               // depth-split forward, 1 elsewhere
     bool has_unit_order;      // saved.unit_order exists: the blend backward (k_composite_bwd) runs on this plan's units
+    bool fwd_exit;            // the depth-split forward stops a tile half's walk once its pixels absorb every entry (flags of FgsDims.fwd_variant):
+                              // k_blend_fwd_head, then k_blend_fwd_parts for the halves it left open; saved.fwd_open and s_fwd_max exist
+    size_t s_fwd_max;         // saved: uint32 [B][ceil(N / 256)][2]: per projection block, the largest |0.99 colour channel| and
+                              // |0.99 depth| of its Gaussians as fp32 bit patterns (a NaN is the largest: the bound is then NaN)
     // scratch layout (bytes)
     size_t sort_words;       // uint32 words of EACH of the four sort buffers below
     size_t tile_table_words;  // words the tile-table kernels need in the one sort buffer they borrow (<= sort_words)

@@ -91,7 +91,7 @@ __global__ __launch_bounds__(256) void k_project(
     const float *__restrict__ quat, const float *__restrict__ color, const float *__restrict__ opacity,
     float *__restrict__ rec, uint32_t *__restrict__ depth_key, uint32_t *__restrict__ tile_count,
     uint32_t *__restrict__ layer, int32_t num_planes, float plane_near, float plane_far, int32_t tile_w,
-    uint32_t *__restrict__ key_bits, uint32_t *__restrict__ zero_words, uint32_t zero_count) {
+    uint32_t *__restrict__ key_bits, uint32_t *__restrict__ zero_words, uint32_t zero_count, uint32_t *__restrict__ fwd_max) {
     // the depth sort's hand-off words (fgs_sort.hip, sort_mode bits 1-2 = 3) must read "not published" when its passes start: this
     // launch precedes them on the stream, so it clears them on the side (<= 1 store per thread)
     for (uint32_t i = (blockIdx.y * gridDim.x + blockIdx.x) * 256u + threadIdx.x; i < zero_count; i += gridDim.x * gridDim.y * 256u)
@@ -100,6 +100,7 @@ __global__ __launch_bounds__(256) void k_project(
     // (below) is one record
     const int32_t n = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
     uint32_t key = 0xFFFFFFFFu;
+    uint32_t cmax = 0u, dmax = 0u;  // |0.99 colour channel|, |0.99 depth| as bit patterns (fwd_max, below)
     if (n < N) {
         const int32_t idx = b * N + n;
         const float *__restrict__ cam = cams + (num_cameras > 1 ? b : 0) * FGS_CAMERA_FLOATS;
@@ -150,6 +151,12 @@ __global__ __launch_bounds__(256) void k_project(
         key = vis ? fgs_float_key(o.dep) : 0xFFFFFFFFu;
         depth_key[idx] = key;
         tile_count[idx] = ntiles;
+        if (fwd_max && ntiles) {  // (a Gaussian in no list bounds nothing)
+            const float m = 0.99f;  // the products the blend kernels stage (blend_stage_fold, fgs_composite.hip)
+            cmax = max(max(__float_as_uint(color[3 * idx] * m) & 0x7FFFFFFFu, __float_as_uint(color[3 * idx + 1] * m) & 0x7FFFFFFFu),
+                       __float_as_uint(color[3 * idx + 2] * m) & 0x7FFFFFFFu);
+            dmax = __float_as_uint(o.dep * m) & 0x7FFFFFFFu;
+        }
         if (layer) {
             // nearest depth plane, DR:1106 (torch.linspace) + DR:1147-1148 (first argmin of |depth - plane|)
             const float step = (plane_far - plane_near) / (float)(num_planes - 1);
@@ -194,6 +201,24 @@ __global__ __launch_bounds__(256) void k_project(
             // the maxima follow the [B][blocks][4] records as one word per block
             key_bits[(size_t)gridDim.y * gridDim.x * 4 + (size_t)b * gridDim.x + blockIdx.x] =
                 max(max(wv[0][4], wv[1][4]), max(wv[2][4], wv[3][4]));
+        }
+    }
+    // The exiting forward's bound (k_blend_fwd_head, fgs_composite.hip): the largest |0.99 c| over the colour channels and the
+    // largest |0.99 depth| of this block's listed Gaussians, one record of two words per block.  Maxima of the fp32 BIT PATTERNS
+    // with the sign cleared: the order of the magnitudes, with every NaN above infinity, so that a NaN colour makes the bound NaN
+    // and nothing closes.  A maximum does not depend on the order it is formed in.
+    if (fwd_max) {
+#pragma unroll
+        for (int o2 = 32; o2 > 0; o2 >>= 1) {
+            cmax = max(cmax, (uint32_t)__shfl_xor(cmax, o2, 64)); dmax = max(dmax, (uint32_t)__shfl_xor(dmax, o2, 64));
+        }
+        __shared__ uint32_t wm[4][2];
+        if ((threadIdx.x & 63u) == 0) { wm[threadIdx.x >> 6][0] = cmax; wm[threadIdx.x >> 6][1] = dmax; }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            uint32_t *o4 = fwd_max + ((size_t)b * gridDim.x + blockIdx.x) * 2;
+            o4[0] = max(max(wm[0][0], wm[1][0]), max(wm[2][0], wm[3][0]));
+            o4[1] = max(max(wm[0][1], wm[1][1]), max(wm[2][1], wm[3][1]));
         }
     }
 }
@@ -648,7 +673,7 @@ int fgs_launch_project(const FgsPlan &p, const float *cams, const float *pos, co
                        reinterpret_cast<uint32_t *>(saved + p.L.tile_count),
                        num_planes > 1 ? reinterpret_cast<uint32_t *>(saved + p.s_layer) : nullptr, num_planes,  // one plane: layer 0
                        plane_near, plane_far, p.tile_w, reinterpret_cast<uint32_t *>(saved + p.s_keybits), zero_words,
-                       zero_words ? zero_count : 0u);
+                       zero_words ? zero_count : 0u, p.fwd_exit ? reinterpret_cast<uint32_t *>(saved + p.s_fwd_max) : nullptr);
     FGS_LAUNCH_CHECK("k_project");
     return FGS_OK;
 }

@@ -576,6 +576,8 @@ def inspect_saved(saved: torch.Tensor, dims) -> dict:
         out["seg_tile"] = view(L.seg_tile, L.seg_capacity, torch.int32)
         if L.unit_order < L.total_bytes:  # launch order of those units (blend path only; counters[2] entries are valid)
             out["unit_order"] = view(L.unit_order, L.seg_capacity, torch.int32)
+        if 0 < L.fwd_open < L.total_bytes:  # halves the exiting forward's head left to the rest kernel (tuning key fwd_exit)
+            out["fwd_open"] = view(L.fwd_open, Bn * T * 2, torch.int32).view(Bn, T, 2)
     return out
 
 

@@ -58,6 +58,8 @@ extern "C" {
 #define FGS_TILE 16        /* tile height in pixels, and the width unless FgsSavedLayout.tile_w says 32 */
 #define FGS_SEG 128        /* largest depth segment: list entries per backward work unit; a call uses
                               FgsSavedLayout.seg_len (64 for small problems, else FGS_SEG)            */
+#define FGS_FWD_EXIT_OFF 0x100 /* FgsDims.fwd_variant flags (values >= 0 only): the exiting depth-split forward off / forced on */
+#define FGS_FWD_EXIT_ON 0x200
 #define FGS_TUNE_AUTO 0    /* FgsDims.seg_len / fwd_variant / bin_mode: let the library choose        */
 #ifndef FGS_PHASE_CKPT
 #define FGS_PHASE_CKPT 8   /* phase path: entries of a sub-tile's (compacted) list between (A, Phi) checkpoints */
@@ -87,7 +89,14 @@ typedef struct FgsDims {
     int32_t seg_len;        /* list entries per depth segment: 0 | a multiple of 64 up to 512 (saturation_skip: 128) */
     int32_t fwd_variant;    /* forward work split: 0 | 1, 2, 4, 8, 16 = depth-split forward with that many list parts
                                per tile (16 x 16 tiles; at most 8 on 32 x 16 tiles) | -1, -2, -4 = row-split forward with that many waves per tile.
-                               Phase path: one work split (0 or 4).                                             */
+                               Phase path: one work split (0 or 4).
+                               A value >= 0 may carry ONE of two flags, FGS_FWD_EXIT_OFF | FGS_FWD_EXIT_ON (below): the exiting
+                               form of the depth-split forward -- a tile half's list walk stops once the state of every
+                               in-frame pixel is a fixed point of the blend update for every entry that can still come, the
+                               same bits (k_blend_fwd_head, fgs_composite.hip).  No flag = automatic: on for launches of
+                               >= 8192 16 x 16 tile halves.  OFF: every entry is walked, by k_blend_fwd_parts alone (tests and
+                               A/B runs); ON: forced.  Like every tuning override the flags change how the work is split, never
+                               what is computed.  (FgsDims itself cannot grow: dup_capacity stays its last field.)      */
     int32_t bin_mode;       /* tile binning: 0 | 1 = direct (column / row rank masks) | 2 = emit + stable radix sort */
     int32_t tile_w;         /* tile width in pixels: 0 | 16 | 32 (tiles are always 16 rows high).  0 = automatic:
                                32 on the blend path with the depth-split forward for frames >= 512 pixels wide
@@ -163,6 +172,9 @@ typedef struct FgsSavedLayout {
                             order, but lists its full units (seg_len entries) first, in increasing index, and then its
                             partial units, longest first by quarter-octave of their entry count.  Exists only on the blend
                             path (no phase, one layer); == total_bytes elsewhere.  Not written when U == 0 */
+    size_t fwd_open;     /* uint32 [B*T][2]: 1 where the exiting forward's head kernel left that 16 x 16 half of the tile open for the
+                            rest kernel, else 0 (index 1 is written on 32 x 16 tiles only).  Exists with the depth-split forward
+                            where the exit is on (FgsDims.fwd_variant flags); == total_bytes elsewhere */
 } FgsSavedLayout;
 
 /* Sizes of the two caller-provided device buffers.  `saved` must stay untouched between
