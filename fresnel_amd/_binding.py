@@ -63,7 +63,8 @@ class FgsSavedLayout(ctypes.Structure):
                 ("tiles_x", ctypes.c_int32), ("tiles_y", ctypes.c_int32),
                 ("seg_off", ctypes.c_size_t), ("seg_tile", ctypes.c_size_t), ("seg_ckpt", ctypes.c_size_t),
                 ("seg_capacity", ctypes.c_size_t), ("seg_len", ctypes.c_int32), ("tile_w", ctypes.c_int32),
-                ("unit_order", ctypes.c_size_t), ("fwd_open", ctypes.c_size_t)]
+                ("unit_order", ctypes.c_size_t), ("fwd_open", ctypes.c_size_t),
+                ("fwd_close", ctypes.c_size_t)]
 
 
 class FgsAsmDims(ctypes.Structure):

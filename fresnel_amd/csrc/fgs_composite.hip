@@ -420,7 +420,8 @@ __global__ __launch_bounds__(64 * NP * (1 + WIDE)) __attribute__((amdgpu_waves_p
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t part = WIDE ? wave >> 1 : wave, half = WIDE ? wave & 1u : 0u;
     // REST: the launch behind k_blend_fwd_head (below).  A half that the head closed or finished has its pixels and every
-    // checkpoint slot already: its waves touch nothing and only keep the block's barrier; a block without an open half leaves.
+    // checkpoint slot the backward will read already (a closed half: its closing slot alone, saved.fwd_close): its waves touch
+    // nothing -- they neither read nor write a slot -- and only keep the block's barrier; a block without an open half leaves.
     bool mine = true;
     if (REST) {
         const uint32_t open0 = fwd_open[2u * c.tile], open1 = WIDE ? fwd_open[2u * c.tile + 1u] : 0u;
@@ -524,10 +525,13 @@ __global__ __launch_bounds__(64 * NP * (1 + WIDE)) __attribute__((amdgpu_waves_p
 //
 // One wave per 16 x 16 tile half walks the first min(spp, head_segs) segments of part 0 -- the whole list when there is one part --
 // and tests at every 64-entry chunk boundary.  Part 0's state is absolute, so stopping there keeps the parent's association.
-//   closed, or the list ended: the wave stores the pixels and fills every later checkpoint slot of its half with what the
-//     backward's re-basing turns into the parent's bits: the closing state (C, A = 1 - T, D) in the later slots of part 0 and in the
-//     slot of every later part's first segment, the local identity (0, A = 0, 0) in the inner slots of later parts
-//     (compose(abs, identity) = C_abs + 0 * 0 and T = 0 * 1 = +0).  fwd_open[tile][half] = 0.
+//   closed, or the list ended: the wave stores the pixels; fwd_open[tile][half] = 0.  A half closed after `done` entries stores its
+//     closing state (C, A = 1 - T = 1.0f, D) into ONE slot, k = ceil(done / seg_len) -- the first slot its walk did not reach -- and
+//     leaves k in fwd_close[tile][half] (0xFFFFFFFF when k is no slot of the tile: the closing fell into the last segment; and for
+//     every half that did not close).  k <= min(spp, head_segs): slot k belongs to part 0 or is the first slot of part 1, an ABSOLUTE
+//     state where the backward reads it.  The half's cells of the slots behind k are never written: k_composite_bwd restarts every
+//     unit of the half with segment >= k from slot k (see there why those are the bits a full walk leaves), the rest kernel's
+//     waves of a closed half touch nothing, and no other kernel reads checkpoint slots.
 //   still open: its state goes into the slot in front of the next segment (the slot part 0 writes there anyway), T itself in the
 //     A plane, and fwd_open[tile][half] = 1: part 0's wave of the rest kernel resumes from it, the other parts run as they did.
 // head_segs bounds the launch for scenes that never saturate: one wave per half for a quarter of the longest list would leave
@@ -539,7 +543,7 @@ __global__ __launch_bounds__(64 * (1 + WIDE)) __attribute__((amdgpu_waves_per_eu
     const uint32_t *__restrict__ dup_ids, const float *__restrict__ rec, float *__restrict__ pix_state,
     float *__restrict__ out_rgb, float *__restrict__ out_depth, const uint32_t *__restrict__ seg_off,
     float *__restrict__ seg_ckpt, uint32_t seg_len, uint32_t order_groups, uint32_t *__restrict__ fwd_open, uint32_t head_segs,
-    uint32_t np, const uint32_t *__restrict__ fwd_max, uint32_t max_recs) {
+    uint32_t np, const uint32_t *__restrict__ fwd_max, uint32_t max_recs, uint32_t *__restrict__ fwd_close) {
     constexpr int NW = 1 + WIDE;
     constexpr int TSX = WIDE ? 4 : 2;
     constexpr int PL = 2 * TSX * 64, SLOT = 5 * PL;
@@ -597,7 +601,15 @@ __global__ __launch_bounds__(64 * (1 + WIDE)) __attribute__((amdgpu_waves_per_eu
         closed = __ballot(veto) == 0ull;
     }
     const bool finished = closed || done == len;
-    if (lane == 0) fwd_open[2u * c.tile + half] = finished ? 0u : 1u;
+    // the closing slot: the first slot the walk did not reach (closed => done >= 64, so kclose >= 1; kclose <= hs <= spp: a slot of part 0 or
+    // the first slot of part 1 -- absolute in the backward's sense either way)
+    const uint32_t kclose = (done + seg_len - 1) / seg_len;
+    const bool close_slot = closed && kclose < nseg;
+    if (lane == 0) {
+        fwd_open[2u * c.tile + half] = finished ? 0u : 1u;
+        fwd_close[2u * c.tile + half] = close_slot ? kclose : 0xFFFFFFFFu;
+    }
+    if (!WIDE && lane == 1) fwd_close[2u * c.tile + 1u] = 0xFFFFFFFFu;  // (the backward of 16 x 16 tiles reads index 0 only)
     if (!finished) {
         float *ck = slot0 + (size_t)hs * SLOT;  // done == hs * seg_len < len
 #pragma unroll
@@ -615,14 +627,11 @@ __global__ __launch_bounds__(64 * (1 + WIDE)) __attribute__((amdgpu_waves_per_eu
             pixel_store(pix_state, out_rgb, out_depth, c.b, HW, (size_t)py * W + px, bg0, bg1, bg2, Cr[s], Cg[s], Cb[s], 1.0f - T[s],
                         T[s], Dm[s]);
     }
-    // the slots the walk did not reach (none when the list ended)
-#pragma clang loop unroll(disable) vectorize(disable)
-    for (uint32_t k =(done + seg_len - 1) / seg_len; k < nseg; ++k) {
-        const bool absolute = k < spp || k % spp == 0u;
-        float *ck = slot0 + (size_t)k * SLOT;
+    // the closing state into the ONE slot behind the walk; the half's cells of every later slot stay unwritten and unread
+    if (close_slot) {
+        float *ck = slot0 + (size_t)kclose * SLOT;
 #pragma unroll
-        for (int s = 0; s < 4; ++s)
-            ckpt_store<PL>(ck + cell(s), absolute ? BlendState{Cr[s], Cg[s], Cb[s], T[s], Dm[s]} : BlendState{0.0f, 0.0f, 0.0f, 1.0f, 0.0f});
+        for (int s = 0; s < 4; ++s) ckpt_store<PL>(ck + cell(s), BlendState{Cr[s], Cg[s], Cb[s], T[s], Dm[s]});
     }
 }
 
@@ -1005,7 +1014,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NSX == 2 ? 6
     const uint32_t *__restrict__ seg_tile, const float *__restrict__ seg_ckpt, const uint32_t *__restrict__ ranges,
     const uint32_t *__restrict__ dup_ids, const float *__restrict__ rec, const uint32_t *__restrict__ dup_off,
     const float *__restrict__ pix_state, const float *__restrict__ g_rgb, const float *__restrict__ g_depth,
-    float *__restrict__ grad_rows, float t_eps, const uint32_t *__restrict__ unit_order FGS_BWD_TRACE_PARAM) {
+    float *__restrict__ grad_rows, float t_eps, const uint32_t *__restrict__ unit_order,
+    const uint32_t *__restrict__ fwd_close FGS_BWD_TRACE_PARAM) {
     // work unit = (tile, depth segment): blockIdx.x indexes the unit list built by k_tile_order; the grid is
     // sized from the capacity, surplus blocks leave at once
     constexpr int NS = 2 * NSX, PL = NS * 64, SLOT = 5 * PL;  // sub-tiles per tile, floats per checkpoint plane / slot
@@ -1027,6 +1037,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NSX == 2 ? 6
     const uint32_t seg_len = counters[4];
     const uint32_t fwd_parts = (int32_t)counters[5] > 1 ? counters[5] : 0u;
     const uint32_t unit_tile = seg_tile[unit];
+    // the closing slots of the tile's 16 x 16 halves (saved.fwd_close; null without the exiting forward: no half has one).  They
+    // depend on the tile alone and are loaded here, beside seg_off and the ranges, not behind them
+    uint32_t kclose[NSX / 2];
+#pragma unroll
+    for (int h = 0; h < NSX / 2; ++h) kclose[h] = 0xFFFFFFFFu;
+    if (fwd_close) {
+#pragma unroll
+        for (int h = 0; h < NSX / 2; ++h) kclose[h] = fwd_close[2u * unit_tile + h];
+    }
     const uint32_t seg = unit - seg_off[unit_tile];
     TileCtx c = tile_ctx_of(unit_tile, tiles, tiles_x, ranges, 8u * NSX);
     uint32_t rebase_seg = seg;  // first segment of this segment's list part if its checkpoint is part-local
@@ -1078,8 +1097,19 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NSX == 2 ? 6
             // belongs to the list entries before it.  After a depth-split forward (k_blend_fwd_parts, fwd_parts
             // waves per tile) the checkpoint of a segment inside part p > 0 is local to that part and is re-based
             // with the absolute state kept in the slot of the part's first segment.
-            BlendState st = ckpt_load<PL>(seg_ckpt + (size_t)unit * SLOT + s * 64 + lane);
-            if (rebase_seg != seg) {
+            // CLOSED HALF (the exiting forward, k_blend_fwd_head): the half of this sub-tile stopped its walk in front of slot k =
+            // kclose and left its closing state (C, A = 1.0f, D) there, absolute; its cells of the later slots are not written.
+            // A unit of segment >= k restarts from slot k as it is.  Those are the bits a full walk's slots give: behind a closing
+            // the state is a fixed point, so a later slot of part 0 and a later part's first slot hold the closing state itself;
+            // an inner slot of a later part holds a local state (C_p, T_p, D_p) that the re-basing turns into
+            // compose(closing, local) = (C + T' C_p, T' T_p, D + T' D_p) with T' = 1 - 1.0f = +0: T = +0, and C + 0 = C also in
+            // sign, because the strict comparisons of the absorbing test exclude a zero accumulator on an in-frame pixel (and
+            // the local state is finite: a non-finite multiplier makes the bound NaN or infinite, which closes nothing).  Lanes outside the frame carry (0, T = 1, 0) in
+            // every slot either way.  Per s the half is a compile-time constant and the test a scalar one.
+            const bool behind = seg >= kclose[(s % NSX) >> 1];
+            const size_t own = behind ? (size_t)unit - seg + kclose[(s % NSX) >> 1] : (size_t)unit;
+            BlendState st = ckpt_load<PL>(seg_ckpt + own * SLOT + s * 64 + lane);
+            if (rebase_seg != seg && !behind) {
                 const size_t slot = (size_t)unit - seg + rebase_seg;
                 st = compose(ckpt_load<PL>(seg_ckpt + slot * SLOT + s * 64 + lane), st);
             }
@@ -1465,10 +1495,11 @@ int fgs_launch_composite_fwd(const FgsPlan &p, const float *phase, char *saved, 
         if (exiting) {
             const uint32_t *fwd_max = fgs_at<const uint32_t>(saved, p.s_fwd_max);
             const uint32_t max_recs = ((uint32_t)p.d.num_gaussians + 255u) / 256u;
+            uint32_t *fwd_close = fgs_at<uint32_t>(saved, p.L.fwd_close);
 #define FGS_HEAD_LAUNCH(WD)                                                                                               \
     hipLaunchKernelGGL((k_blend_fwd_head<WD>), dim3(grid), dim3(64 * (1 + WD)), 0, st, tiles, tiles_x, W, H, bg0, bg1, bg2, tile_order, \
                        ranges, dup_ids, rec, pix, out_rgb, out_depth, seg_off, seg_ckpt, seg_len, order_groups, fwd_open, head_segs, \
-                       (uint32_t)np, fwd_max, max_recs)
+                       (uint32_t)np, fwd_max, max_recs, fwd_close)
             if (p.tile_w == 32) FGS_HEAD_LAUNCH(1); else FGS_HEAD_LAUNCH(0);
 #undef FGS_HEAD_LAUNCH
             FGS_LAUNCH_CHECK("k_blend_fwd_head");
@@ -1549,6 +1580,9 @@ int fgs_launch_composite_bwd(const FgsPlan &p, const float *phase, const char *s
     const float t_eps = p.d.saturation_skip ? FGS_SATURATION_EPS : 0.0f;
     if (!p.has_unit_order) { fgs_set_error("k_composite_bwd: the plan has no unit_order table"); return FGS_EINVAL; }
     const uint32_t *unit_order = fgs_at<const uint32_t>(saved, p.L.unit_order);
+    // the closing slots of the exiting forward's closed halves; null where that forward did not run (the plan is a pure function of
+    // the dims: the forward's choice)
+    const uint32_t *fwd_close = p.fwd_exit ? fgs_at<const uint32_t>(saved, p.L.fwd_close) : nullptr;
 #ifdef FGS_BWD_UNIT_TRACE
     if (g_bwd_trace_slots < ugrid) {
         if (g_bwd_trace) (void)hipFree(g_bwd_trace);
@@ -1564,7 +1598,7 @@ int fgs_launch_composite_bwd(const FgsPlan &p, const float *phase, const char *s
 #endif
 #define FGS_BWD_LAUNCH(NSXV)                                                                                              \
     hipLaunchKernelGGL(k_composite_bwd<NSXV>, dim3(ugrid), dim3(64), FGS_BWD_DYN_LDS, st, tiles, tiles_x, W, H, bg0, bg1, bg2, dcap, \
-                       counters, seg_off, seg_tile, seg_ckpt, ranges, dup_ids, rec, dup_off, pix, g_rgb, g_depth, grad_rows, t_eps, unit_order FGS_BWD_TRACE_ARG)
+                       counters, seg_off, seg_tile, seg_ckpt, ranges, dup_ids, rec, dup_off, pix, g_rgb, g_depth, grad_rows, t_eps, unit_order, fwd_close FGS_BWD_TRACE_ARG)
     if (p.tile_w == 32) FGS_BWD_LAUNCH(4); else FGS_BWD_LAUNCH(2);
 #undef FGS_BWD_LAUNCH
 #undef FGS_BWD_TRACE_ARG

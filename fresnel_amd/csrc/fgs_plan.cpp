@@ -193,6 +193,10 @@ int fgs_make_plan(const FgsDims *d, FgsPlan *p, int layers, bool segment_ckpt) {
         p->s_fwd_max = o = align256(o + B * p->tiles * 2 * 4);
         o = align256(o + B * ((N + 255) / 256) * 2 * 4);
     }
+    // ... and one more word per tile half: the closing slot of a half the head kernel closed (k_blend_fwd_head writes it,
+    // k_composite_bwd restarts the half's later units from that one slot).  Behind the maxima, so that every older offset stays.
+    L.fwd_close = o;
+    if (p->fwd_exit) o = align256(o + B * p->tiles * 2 * 4);
     L.total_bytes = o;
     L.dup_capacity = dcap;
     L.tiles_x = tx; L.tiles_y = ty;

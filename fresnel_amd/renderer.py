@@ -578,6 +578,8 @@ def inspect_saved(saved: torch.Tensor, dims) -> dict:
             out["unit_order"] = view(L.unit_order, L.seg_capacity, torch.int32)
         if 0 < L.fwd_open < L.total_bytes:  # halves the exiting forward's head left to the rest kernel (tuning key fwd_exit)
             out["fwd_open"] = view(L.fwd_open, Bn * T * 2, torch.int32).view(Bn, T, 2)
+        if 0 < L.fwd_close < L.total_bytes:  # closing slot of the halves the head closed, -1 (0xFFFFFFFF) elsewhere (include/fgs.h)
+            out["fwd_close"] = view(L.fwd_close, Bn * T * 2, torch.int32).view(Bn, T, 2)
     return out
 
 

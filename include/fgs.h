@@ -161,7 +161,8 @@ typedef struct FgsSavedLayout {
                                           (also counters[2])                                        */
     size_t seg_tile;   /* uint32 [Ucap]: (image,tile) of each unit; segment index = unit - seg_off    */
     size_t seg_ckpt;   /* float  [Ucap][5][4][64]: per-pixel C_r,C_g,C_b,A,D of the tile at the START
-                                          of each unit with segment index >= 1 (written by the forward) */
+                                          of each unit with segment index >= 1 (written by the forward; with the
+                                          exiting forward, see fwd_close for the slots behind a closing)   */
     size_t seg_capacity; /* Ucap = Dcap / seg_len + B*T                                             */
     int32_t seg_len;     /* list entries per depth segment for these dims: 64 when B*N <= 200 000 (more,
                             shorter work units for launches that would not fill the chip), else 128   */
@@ -175,6 +176,14 @@ typedef struct FgsSavedLayout {
     size_t fwd_open;     /* uint32 [B*T][2]: 1 where the exiting forward's head kernel left that 16 x 16 half of the tile open for the
                             rest kernel, else 0 (index 1 is written on 32 x 16 tiles only).  Exists with the depth-split forward
                             where the exit is on (FgsDims.fwd_variant flags); == total_bytes elsewhere */
+    size_t fwd_close;    /* uint32 [B*T][2]: the CLOSING SLOT of that 16 x 16 half of the tile.  A half whose walk the head kernel
+                            stopped at `done` entries because its pixels absorb every later entry has k = ceil(done / seg_len);
+                            where k is less than the tile's number of segments, the word is k, seg_ckpt slot seg_off + k holds the
+                            half's closing state (C, A = 1, D) as an ABSOLUTE state, the half's cells of every later slot of the tile
+                            are NOT WRITTEN, and the backward restarts every unit of segment >= k of that half from slot k.
+                            0xFFFFFFFF everywhere else: a half left open, a list that ended, a closing inside the last segment,
+                            index 1 on 16 x 16 tiles.  Behind the per-block maxima that follow fwd_open; exists where fwd_open
+                            exists; == total_bytes elsewhere */
 } FgsSavedLayout;
 
 /* Sizes of the two caller-provided device buffers.  `saved` must stay untouched between
