@@ -5,6 +5,7 @@ The product path FAILS LOUDLY when the HIP library is missing -- there is no CPU
 """
 import ctypes
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FGS_LIB", os.path.join(_HERE, "_lib", "libfgs_hip.so"))  # FGS_LIB: A/B builds
@@ -12,29 +13,109 @@ LIB_PATH = os.environ.get("FGS_LIB", os.path.join(_HERE, "_lib", "libfgs_hip.so"
 FGS_CAMERA_FLOATS = 24
 FGS_TILE = 16
 
-# every symbol include/fgs.h declares (checked by tests/test_abi.py)
-EXPORTED_SYMBOLS = [
-    "fgs_workspace_bytes", "fgs_saved_layout", "fgs_forward", "fgs_backward", "fgs_count_pairs",
-    "fgs_last_error", "fgs_version", "fgs_stage_timing_enable", "fgs_stage_timing_read",
-    "fgs_asm_workspace_bytes", "fgs_asm_forward", "fgs_asm_backward",
-    "fgs_wave_workspace_bytes", "fgs_wave_forward", "fgs_wave_backward",
-    "fgs_fourier_workspace_bytes", "fgs_fourier_forward", "fgs_fourier_backward",
-    "fgs_gather_forward", "fgs_gather_backward",
-    "fgs_asm_propagate_workspace_bytes", "fgs_asm_propagate_forward", "fgs_asm_propagate_backward",
-    "fgs_spectral_workspace_bytes", "fgs_spectral_loss_forward", "fgs_spectral_loss_backward",
-    "fgs_helmholtz_loss_forward", "fgs_helmholtz_loss_backward", "fgs_reduction_scratch_bytes",
-    "fgs_ssim_workspace_bytes", "fgs_ssim_forward", "fgs_ssim_backward",
-    "fgs_pixel_loss_workspace_bytes", "fgs_pixel_loss_stage1", "fgs_pixel_loss_stage2", "fgs_pixel_loss_stage3",
-    "fgs_pixel_loss_forward", "fgs_pixel_loss_backward",
-    "fgs_head_workspace_bytes", "fgs_head_forward", "fgs_head_backward",
-    "fgs_nca_workspace_bytes", "fgs_nca_perceive_forward", "fgs_nca_perceive_backward", "fgs_nca_update_forward",
-    "fgs_nca_update_backward",
-    "fgs_saag_workspace_bytes", "fgs_saag_inputs_forward", "fgs_saag_refine_forward", "fgs_saag_refine_backward",
-    "fgs_physics_workspace_bytes", "fgs_physics_forward", "fgs_physics_backward",
-    "fgs_surface_workspace_bytes", "fgs_surface_count", "fgs_surface_emit",
-    "fgs_surface_emit_guided", "fgs_surface_guided_backward_bytes", "fgs_surface_guided_backward",
-    "fgs_match_workspace_bytes", "fgs_match_forward", "fgs_match_backward",
-]
+# Every symbol include/fgs.h declares, as the header writes it: return type, then the parameters in order.  A comma-separated group
+# is a kind and the names that share it, as in C's `int32_t height, width`; `stream` is the trailing `void *stream`.  Kinds: pointer to
+# a named struct (`FgsDims*`), `size_t*`, any other pointer (`ptr`), the header's scalar types; `str` is `const char *`.  load()
+# makes argtypes and restype from this table, tests/test_call_layer.py holds it against the header name by name.
+_PROTOTYPES = """
+int fgs_workspace_bytes(FgsDims* dims, size_t* saved_bytes scratch_bytes)
+int fgs_saved_layout(FgsDims* dims, FgsSavedLayout* layout)
+int fgs_forward(FgsDims* dims, ptr cameras pos scale quat color opacity phase out_rgb out_depth saved scratch, stream)
+int fgs_backward(FgsDims* dims, ptr cameras pos scale quat color opacity phase saved scratch g_rgb g_depth g_pos g_scale g_quat g_color
+                 g_opacity g_phase, stream)
+int fgs_count_pairs(FgsDims* dims, ptr saved out_pairs, stream)
+int fgs_asm_workspace_bytes(FgsAsmDims* dims, size_t* saved_bytes scratch_bytes)
+int fgs_asm_forward(FgsAsmDims* dims, ptr cameras pos scale quat color opacity phase wavelengths out_rgb saved scratch, stream)
+int fgs_asm_backward(FgsAsmDims* dims, ptr cameras pos scale quat color opacity phase wavelengths saved scratch g_rgb g_pos g_scale
+                     g_quat g_color g_opacity g_phase g_wavelengths, stream)
+int fgs_wave_workspace_bytes(FgsWaveDims* dims, size_t* saved_bytes scratch_bytes)
+int fgs_wave_forward(FgsWaveDims* dims, ptr cameras pos scale quat color opacity phase out_rgb out_depth saved scratch, stream)
+int fgs_wave_backward(FgsWaveDims* dims, ptr cameras pos scale quat color opacity phase saved scratch g_rgb g_depth g_pos g_scale
+                      g_quat g_color g_opacity g_phase, stream)
+int fgs_fourier_workspace_bytes(FgsFourierDims* dims, size_t* saved_bytes scratch_bytes)
+int fgs_fourier_forward(FgsFourierDims* dims, ptr cameras pos scale quat color opacity out_rgb saved scratch, stream)
+int fgs_fourier_backward(FgsFourierDims* dims, ptr cameras pos scale quat color opacity saved scratch g_rgb g_pos g_scale g_quat
+                         g_color g_opacity, stream)
+int fgs_asm_propagate_workspace_bytes(int32_t height width channels, size_t* scratch_bytes)
+int fgs_asm_propagate_forward(int32_t height width channels, double pixel_pitch, int32_t band_limit, ptr field z wavelengths out
+                              spectrum scratch, stream)
+int fgs_asm_propagate_backward(int32_t height width channels, double pixel_pitch, int32_t band_limit, ptr spectrum z wavelengths
+                               g_out g_field g_z g_wavelengths scratch, stream)
+int fgs_spectral_workspace_bytes(FgsSpectralDims* dims, size_t* saved_bytes scratch_bytes)
+int fgs_spectral_loss_forward(FgsSpectralDims* dims, ptr rendered target depth wavelength loss saved scratch, stream)
+int fgs_spectral_loss_backward(FgsSpectralDims* dims, ptr rendered target depth wavelength saved scratch g_loss g_rendered g_target
+                               g_depth g_wavelength, stream)
+int fgs_helmholtz_loss_forward(int32_t images height width, float wavelength pixel_spacing, ptr field loss residual scratch, stream)
+int fgs_helmholtz_loss_backward(int32_t images height width, float wavelength pixel_spacing, ptr residual g_loss g_field, stream)
+size_t fgs_reduction_scratch_bytes()
+int fgs_ssim_workspace_bytes(FgsSsimDims* dims, size_t* saved_bytes scratch_bytes)
+int fgs_ssim_forward(FgsSsimDims* dims, ptr x y out saved scratch, stream)
+int fgs_ssim_backward(FgsSsimDims* dims, ptr x y saved g_out g_x g_y scratch, stream)
+int fgs_pixel_loss_workspace_bytes(FgsPixelLossDims* dims, size_t* stats_bytes scratch_bytes)
+int fgs_pixel_loss_stage1(FgsPixelLossDims* dims, ptr rendered target rendered_depth target_depth density out stats scratch, stream)
+int fgs_pixel_loss_stage2(FgsPixelLossDims* dims, ptr rendered_depth target_depth stats scratch, stream)
+int fgs_pixel_loss_stage3(FgsPixelLossDims* dims, ptr rendered_depth target_depth out stats scratch, stream)
+int fgs_pixel_loss_forward(FgsPixelLossDims* dims, ptr rendered target rendered_depth target_depth density out stats scratch, stream)
+int fgs_pixel_loss_backward(FgsPixelLossDims* dims, ptr rendered target rendered_depth target_depth density stats g_rgb g_boundary
+                            g_depth g_rendered g_rendered_depth, stream)
+int fgs_head_workspace_bytes(FgsHeadDims* dims, size_t* scratch_bytes)
+int fgs_head_forward(FgsHeadDims* dims, ptr raw base_xy base_z pose opacity_mod edge positions scales rotations colors opacities
+                     phases, stream)
+int fgs_head_backward(FgsHeadDims* dims, ptr raw pose opacity_mod edge g_positions g_scales g_rotations g_colors g_opacities g_phases
+                      g_raw g_base_z g_edge g_opacity_mod scratch, stream)
+int fgs_nca_workspace_bytes(FgsNcaDims* dims, size_t* scratch_bytes)
+int fgs_nca_perceive_forward(FgsNcaDims* dims, ptr state perception neighbors, stream)
+int fgs_nca_perceive_backward(FgsNcaDims* dims, ptr neighbors g_perception g_state, stream)
+int fgs_nca_update_forward(FgsNcaDims* dims, ptr state delta step_size uniform, float update_prob, ptr new_state, stream)
+int fgs_nca_update_backward(FgsNcaDims* dims, ptr delta step_size uniform, float update_prob, ptr g_new_state g_delta g_step_size
+                            scratch, stream)
+int fgs_saag_workspace_bytes(FgsSaagDims* dims, size_t* scratch_bytes)
+int fgs_saag_inputs_forward(FgsSaagDims* dims, ptr features positions scales rotations colors opacities mlp_inputs, stream)
+int fgs_saag_refine_forward(FgsSaagDims* dims, ptr raw positions scales rotations colors opacities gains o_positions o_scales
+                            o_rotations o_colors o_opacities pos_delta scale_delta color_delta opacity_delta, stream)
+int fgs_saag_refine_backward(FgsSaagDims* dims, ptr raw scales rotations colors opacities gains g_positions g_scales g_rotations
+                             g_colors g_opacities g_pos_delta g_scale_delta g_color_delta g_opacity_delta g_raw g_gains scratch, stream)
+int fgs_physics_workspace_bytes(FgsPhysicsDims* dims, size_t* scratch_bytes)
+int fgs_physics_forward(FgsPhysicsDims* dims, ptr raw base_xy base_z wavelength_raw positions scales rotations colors opacities phases
+                        range scratch, stream)
+int fgs_physics_backward(FgsPhysicsDims* dims, ptr raw base_z wavelength_raw range g_positions g_scales g_rotations g_colors
+                         g_opacities g_phases g_raw g_base_z g_wavelength_raw scratch, stream)
+int fgs_surface_workspace_bytes(FgsSurfaceDims* dims, FgsSurfaceParams* params, size_t* scratch_bytes)
+int fgs_surface_count(FgsSurfaceDims* dims, FgsSurfaceParams* params, ptr depth scratch offsets, stream)
+int fgs_surface_emit(FgsSurfaceDims* dims, FgsSurfaceParams* params, ptr depth color scratch offsets o_positions o_scales o_rotations
+                     o_colors o_opacities, int64_t capacity, stream)
+int fgs_surface_emit_guided(FgsSurfaceDims* dims, FgsSurfaceParams* params, ptr depth color scratch offsets mods, int32_t mods_h mods_w,
+                            ptr o_positions o_scales o_rotations o_colors o_opacities point_rows, int64_t capacity, stream)
+int fgs_surface_guided_backward_bytes(FgsSurfaceDims* dims, FgsSurfaceParams* params, int32_t mods_h mods_w, size_t* bytes)
+int fgs_surface_guided_backward(FgsSurfaceDims* dims, FgsSurfaceParams* params, ptr depth scratch offsets mods, int32_t mods_h mods_w,
+                                ptr point_rows g_positions g_scales g_rotations g_opacities g_mods bwd_scratch, stream)
+int fgs_match_workspace_bytes(FgsMatchDims* dims, size_t* saved_bytes scratch_bytes)
+int fgs_match_forward(FgsMatchDims* dims, ptr pred target pred_keep target_keep terms counts saved scratch, stream)
+int fgs_match_backward(FgsMatchDims* dims, ptr pred target saved g_total g_pred scratch, stream)
+int fgs_gather_forward(int32_t batch n_in n_out phase_channels, ptr indices pos scale quat color opacity phase o_pos o_scale o_quat
+                       o_color o_opacity o_phase, stream)
+int fgs_gather_backward(int32_t batch n_in n_out phase_channels, ptr indices g_o_pos g_o_scale g_o_quat g_o_color g_o_opacity
+                        g_o_phase g_pos g_scale g_quat g_color g_opacity g_phase, stream)
+int fgs_stage_timing_enable(int enable)
+int fgs_stage_timing_read(ptr ms count)
+str fgs_last_error()
+str fgs_version()
+"""
+
+
+def _parse_prototypes(text):
+    """-> {symbol: (return kind, ((kind, name), ...))}, in the order written."""
+    table = {}
+    for ret, name, params in re.findall(r"(\S+) (fgs_\w+)\(([^)]*)\)", text):
+        flat = []
+        for kind, *names in (group.split() for group in params.split(",") if group.strip()):
+            flat += [(kind, n) for n in names or [kind]]  # a bare `stream` is its own name
+        table[name] = (ret, tuple(flat))
+    return table
+
+
+SIGNATURES = _parse_prototypes(_PROTOTYPES)
+EXPORTED_SYMBOLS = list(SIGNATURES)  # (checked against the header by tests/test_abi.py)
 
 STAGES = ["project", "depth_sort", "dup_emit", "tile_sort", "tile_ranges", "composite_fwd",
           "composite_bwd", "project_bwd", "splat_fwd", "field_fwd", "field_bwd", "splat_bwd"]
@@ -191,6 +272,17 @@ class FgsError(RuntimeError):
 
 _lib = None
 
+_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint32_t": ctypes.c_uint32,
+            "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t, "str": ctypes.c_char_p,
+            "ptr": ctypes.c_void_p, "stream": ctypes.c_void_p}
+
+
+def _ctype(kind):
+    """The ctypes type of a kind of the table: `FgsDims*` and `size_t*` are typed pointers, every other pointer a c_void_p."""
+    if kind.endswith("*"):
+        return ctypes.POINTER(_SCALARS.get(kind[:-1]) or globals()[kind[:-1]])
+    return _SCALARS[kind]
+
 
 def load():
     """Load libfgs_hip.so; raise (never fall back) if it is missing."""
@@ -205,115 +297,12 @@ def load():
     # it would bring up a second runtime from /opt/rocm that cannot see torch's device context.
     import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
-    vp, cp = ctypes.c_void_p, ctypes.POINTER
-    lib.fgs_last_error.restype = ctypes.c_char_p
-    lib.fgs_version.restype = ctypes.c_char_p
+    for name, (ret, params) in SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = _ctype(ret), [_ctype(kind) for kind, _ in params]
     if b"EXPERIMENT" in lib.fgs_version():  # an A/B build selected through FGS_LIB: say so, once, where nobody can miss it
         import sys
         sys.stderr.write(f"fresnel_amd: loaded {LIB_PATH}: {lib.fgs_version().decode()}\n")
-    lib.fgs_workspace_bytes.argtypes = [cp(FgsDims), cp(ctypes.c_size_t), cp(ctypes.c_size_t)]
-    lib.fgs_saved_layout.argtypes = [cp(FgsDims), cp(FgsSavedLayout)]
-    lib.fgs_forward.argtypes = [cp(FgsDims)] + [vp] * 12
-    lib.fgs_backward.argtypes = [cp(FgsDims)] + [vp] * 18
-    lib.fgs_count_pairs.argtypes = [cp(FgsDims), vp, vp, vp]
-    lib.fgs_stage_timing_enable.argtypes = [ctypes.c_int]
-    lib.fgs_stage_timing_read.argtypes = [cp(ctypes.c_float), cp(ctypes.c_int32)]
-    lib.fgs_stage_timing_enable.restype = ctypes.c_int
-    lib.fgs_stage_timing_read.restype = ctypes.c_int
-    lib.fgs_asm_workspace_bytes.argtypes = [cp(FgsAsmDims), cp(ctypes.c_size_t), cp(ctypes.c_size_t)]
-    lib.fgs_asm_forward.argtypes = [cp(FgsAsmDims)] + [vp] * 12
-    lib.fgs_asm_backward.argtypes = [cp(FgsAsmDims)] + [vp] * 19
-    lib.fgs_wave_workspace_bytes.argtypes = [cp(FgsWaveDims), cp(ctypes.c_size_t), cp(ctypes.c_size_t)]
-    lib.fgs_wave_forward.argtypes = [cp(FgsWaveDims)] + [vp] * 12
-    lib.fgs_wave_backward.argtypes = [cp(FgsWaveDims)] + [vp] * 18
-    lib.fgs_fourier_workspace_bytes.argtypes = [cp(FgsFourierDims), cp(ctypes.c_size_t), cp(ctypes.c_size_t)]
-    lib.fgs_fourier_forward.argtypes = [cp(FgsFourierDims)] + [vp] * 10
-    lib.fgs_fourier_backward.argtypes = [cp(FgsFourierDims)] + [vp] * 15
-    for fn in (lib.fgs_fourier_workspace_bytes, lib.fgs_fourier_forward, lib.fgs_fourier_backward):
-        fn.restype = ctypes.c_int
-    i32 = ctypes.c_int32
-    lib.fgs_gather_forward.argtypes = [i32, i32, i32, i32] + [vp] * 14
-    lib.fgs_gather_backward.argtypes = [i32, i32, i32, i32] + [vp] * 14
-    lib.fgs_gather_forward.restype = lib.fgs_gather_backward.restype = ctypes.c_int
-    f32 = ctypes.c_float
-    lib.fgs_asm_propagate_workspace_bytes.argtypes = [i32, i32, i32, cp(ctypes.c_size_t)]
-    lib.fgs_asm_propagate_forward.argtypes = [i32, i32, i32, ctypes.c_double, i32] + [vp] * 7   # (the pitch is a double: fgs.h)
-    lib.fgs_asm_propagate_backward.argtypes = [i32, i32, i32, ctypes.c_double, i32] + [vp] * 9
-    lib.fgs_spectral_workspace_bytes.argtypes = [cp(FgsSpectralDims), cp(ctypes.c_size_t), cp(ctypes.c_size_t)]
-    lib.fgs_spectral_loss_forward.argtypes = [cp(FgsSpectralDims)] + [vp] * 8
-    lib.fgs_spectral_loss_backward.argtypes = [cp(FgsSpectralDims)] + [vp] * 12
-    lib.fgs_helmholtz_loss_forward.argtypes = [i32, i32, i32, f32, f32] + [vp] * 5
-    lib.fgs_helmholtz_loss_backward.argtypes = [i32, i32, i32, f32, f32] + [vp] * 4
-    lib.fgs_reduction_scratch_bytes.argtypes = []
-    lib.fgs_ssim_workspace_bytes.argtypes = [cp(FgsSsimDims), cp(ctypes.c_size_t), cp(ctypes.c_size_t)]
-    lib.fgs_ssim_forward.argtypes = [cp(FgsSsimDims)] + [vp] * 6
-    lib.fgs_ssim_backward.argtypes = [cp(FgsSsimDims)] + [vp] * 8
-    lib.fgs_reduction_scratch_bytes.restype = ctypes.c_size_t
-    pd = cp(FgsPixelLossDims)
-    lib.fgs_pixel_loss_workspace_bytes.argtypes = [pd, cp(ctypes.c_size_t), cp(ctypes.c_size_t)]
-    lib.fgs_pixel_loss_stage1.argtypes = [pd] + [vp] * 9
-    lib.fgs_pixel_loss_stage2.argtypes = [pd] + [vp] * 5
-    lib.fgs_pixel_loss_stage3.argtypes = [pd] + [vp] * 6
-    lib.fgs_pixel_loss_forward.argtypes = [pd] + [vp] * 9
-    lib.fgs_pixel_loss_backward.argtypes = [pd] + [vp] * 12
-    for fn in (lib.fgs_pixel_loss_workspace_bytes, lib.fgs_pixel_loss_stage1, lib.fgs_pixel_loss_stage2,
-               lib.fgs_pixel_loss_stage3, lib.fgs_pixel_loss_forward, lib.fgs_pixel_loss_backward):
-        fn.restype = ctypes.c_int
-    lib.fgs_head_workspace_bytes.argtypes = [cp(FgsHeadDims), cp(ctypes.c_size_t)]
-    lib.fgs_head_forward.argtypes = [cp(FgsHeadDims)] + [vp] * 13
-    lib.fgs_head_backward.argtypes = [cp(FgsHeadDims)] + [vp] * 16
-    for fn in (lib.fgs_head_workspace_bytes, lib.fgs_head_forward, lib.fgs_head_backward):
-        fn.restype = ctypes.c_int
-    nd = cp(FgsNcaDims)
-    lib.fgs_nca_workspace_bytes.argtypes = [nd, cp(ctypes.c_size_t)]
-    lib.fgs_nca_perceive_forward.argtypes = [nd] + [vp] * 4
-    lib.fgs_nca_perceive_backward.argtypes = [nd] + [vp] * 4
-    lib.fgs_nca_update_forward.argtypes = [nd] + [vp] * 4 + [f32, vp, vp]
-    lib.fgs_nca_update_backward.argtypes = [nd] + [vp] * 3 + [f32] + [vp] * 5
-    for fn in (lib.fgs_nca_workspace_bytes, lib.fgs_nca_perceive_forward, lib.fgs_nca_perceive_backward,
-               lib.fgs_nca_update_forward, lib.fgs_nca_update_backward):
-        fn.restype = ctypes.c_int
-    sd = cp(FgsSaagDims)
-    lib.fgs_saag_workspace_bytes.argtypes = [sd, cp(ctypes.c_size_t)]
-    lib.fgs_saag_inputs_forward.argtypes = [sd] + [vp] * 8
-    lib.fgs_saag_refine_forward.argtypes = [sd] + [vp] * 17
-    lib.fgs_saag_refine_backward.argtypes = [sd] + [vp] * 19
-    for fn in (lib.fgs_saag_workspace_bytes, lib.fgs_saag_inputs_forward, lib.fgs_saag_refine_forward,
-               lib.fgs_saag_refine_backward):
-        fn.restype = ctypes.c_int
-    phd = cp(FgsPhysicsDims)
-    lib.fgs_physics_workspace_bytes.argtypes = [phd, cp(ctypes.c_size_t)]
-    lib.fgs_physics_forward.argtypes = [phd] + [vp] * 13
-    lib.fgs_physics_backward.argtypes = [phd] + [vp] * 15
-    for fn in (lib.fgs_physics_workspace_bytes, lib.fgs_physics_forward, lib.fgs_physics_backward):
-        fn.restype = ctypes.c_int
-    sfd, sfp = cp(FgsSurfaceDims), cp(FgsSurfaceParams)
-    lib.fgs_surface_workspace_bytes.argtypes = [sfd, sfp, cp(ctypes.c_size_t)]
-    lib.fgs_surface_count.argtypes = [sfd, sfp] + [vp] * 4
-    lib.fgs_surface_emit.argtypes = [sfd, sfp] + [vp] * 9 + [ctypes.c_int64, vp]
-    lib.fgs_surface_emit_guided.argtypes = [sfd, sfp] + [vp] * 5 + [ctypes.c_int32] * 2 + [vp] * 6 + [ctypes.c_int64, vp]
-    lib.fgs_surface_guided_backward_bytes.argtypes = [sfd, sfp, ctypes.c_int32, ctypes.c_int32, cp(ctypes.c_size_t)]
-    lib.fgs_surface_guided_backward.argtypes = [sfd, sfp] + [vp] * 4 + [ctypes.c_int32] * 2 + [vp] * 8
-    for fn in (lib.fgs_surface_workspace_bytes, lib.fgs_surface_count, lib.fgs_surface_emit, lib.fgs_surface_emit_guided,
-               lib.fgs_surface_guided_backward_bytes, lib.fgs_surface_guided_backward):
-        fn.restype = ctypes.c_int
-    md = cp(FgsMatchDims)
-    lib.fgs_match_workspace_bytes.argtypes = [md, cp(ctypes.c_size_t), cp(ctypes.c_size_t)]
-    lib.fgs_match_forward.argtypes = [md] + [vp] * 9
-    lib.fgs_match_backward.argtypes = [md] + [vp] * 7
-    for fn in (lib.fgs_match_workspace_bytes, lib.fgs_match_forward, lib.fgs_match_backward):
-        fn.restype = ctypes.c_int
-    for fn in (lib.fgs_asm_propagate_workspace_bytes, lib.fgs_asm_propagate_forward, lib.fgs_asm_propagate_backward,
-               lib.fgs_spectral_workspace_bytes, lib.fgs_spectral_loss_forward, lib.fgs_spectral_loss_backward,
-               lib.fgs_helmholtz_loss_forward, lib.fgs_helmholtz_loss_backward,
-               lib.fgs_ssim_workspace_bytes, lib.fgs_ssim_forward, lib.fgs_ssim_backward):
-        fn.restype = ctypes.c_int
-    for fn in (lib.fgs_asm_workspace_bytes, lib.fgs_asm_forward, lib.fgs_asm_backward,
-               lib.fgs_wave_workspace_bytes, lib.fgs_wave_forward, lib.fgs_wave_backward):
-        fn.restype = ctypes.c_int
-    for fn in (lib.fgs_workspace_bytes, lib.fgs_saved_layout, lib.fgs_forward, lib.fgs_backward,
-               lib.fgs_count_pairs):
-        fn.restype = ctypes.c_int
     _lib = lib
     return lib
 
@@ -358,11 +347,23 @@ def make_dims(batch, num_gaussians, width, height, max_radius=64.0, background=(
     return d
 
 
+_SIZE_OUTS = {name: sum(kind == "size_t*" for kind, _ in params) for name, (_, params) in SIGNATURES.items()}
+
+
+def sizes(name, *args):
+    """Call a `*_workspace_bytes` / `*_backward_bytes` entry point: `args` are its inputs (structures go by reference, scalars as
+    they are), the trailing `size_t *` outputs are the table's.  -> the one size as an int, or the two as a tuple of ints.
+    The hipFFT-backed queries (fgs_asm_, fgs_asm_propagate_, fgs_spectral_workspace_bytes) build and cache the current device's
+    plan and return ITS work size: their callers make the tensors' device current first (`_hip.on_device`)."""
+    n = _SIZE_OUTS[name]
+    out = [ctypes.c_size_t(0) for _ in range(n)]
+    check(getattr(load(), name)(*[ctypes.byref(a) if isinstance(a, ctypes.Structure) else a for a in args],
+                                *[ctypes.byref(o) for o in out]), name)
+    return out[0].value if n == 1 else tuple(o.value for o in out)
+
+
 def workspace_bytes(dims):
-    s, c = ctypes.c_size_t(0), ctypes.c_size_t(0)
-    check(load().fgs_workspace_bytes(ctypes.byref(dims), ctypes.byref(s), ctypes.byref(c)),
-          "fgs_workspace_bytes")
-    return s.value, c.value
+    return sizes("fgs_workspace_bytes", dims)
 
 
 def saved_layout(dims):

@@ -24,7 +24,6 @@ patch -> dict{positions (B,N,3), scales (B,N,3) in [1e-6,2], rotations (B,N,4) u
 colors/opacities in [0,1] [, phases (B,N) in [0,1]]}, N = 37*37*K (K=4 -> 5476).  It is the
 module whose gradients the data-parallel step all-reduces (~0.63 M parameters at K=4).
 """
-import ctypes
 import math
 from typing import Dict, Optional, Tuple
 
@@ -33,6 +32,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _binding as B
+from . import _hip as hip
 
 
 def rotate_positions_for_pose(positions: torch.Tensor, elevation: torch.Tensor, azimuth: torch.Tensor) -> torch.Tensor:
@@ -207,16 +207,7 @@ def _head_torch(raw, base_xy, base_z, pose, opacity_mod, edge, K, xy_gain, edge_
     return tuple(out)
 
 
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _f32c(t):
-    return None if t is None else t.detach().contiguous().float()
+_f32c = hip.f32c
 
 
 class _HeadHip(torch.autograd.Function):
@@ -224,20 +215,16 @@ class _HeadHip(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, raw, base_xy, base_z, pose, opacity_mod, edge, K, xy_gain, edge_scale_factor, edge_opacity_boost):
-        if not raw.is_cuda:
-            raise B.FgsError("gaussian_head (backend 'hip') needs CUDA/ROCm tensors; there is no CPU fallback")
-        lib = B.load()
+        hip.need_cuda(raw, "gaussian_head (backend 'hip')")
         dev = raw.device
         Bn, P, KF, C = raw.shape
         d = B.FgsHeadDims(Bn, P, KF, int(K), C, float(xy_gain), float(edge_scale_factor), float(edge_opacity_boost))
         raw_, xy_, z_, pose_, mod_, edge_ = (_f32c(t) for t in (raw, base_xy, base_z, pose, opacity_mod, edge))
         N = P * int(K)
-        with torch.cuda.device(dev):
-            outs = [torch.empty((Bn, N, w) if w else (Bn, N), dtype=torch.float32, device=dev) for w in (3, 3, 4, 3, 0)]
-            if C == 19:
-                outs.append(torch.empty((Bn, N, 3), dtype=torch.float32, device=dev))
-            B.check(lib.fgs_head_forward(ctypes.byref(d), _ptr(raw_), _ptr(xy_), _ptr(z_), _ptr(pose_), _ptr(mod_), _ptr(edge_),
-                                         *[_ptr(t) for t in outs], *([None] if C != 19 else []), _stream()), "fgs_head_forward")
+        outs = [torch.empty((Bn, N, w) if w else (Bn, N), dtype=torch.float32, device=dev) for w in (3, 3, 4, 3, 0)]
+        if C == 19:
+            outs.append(torch.empty((Bn, N, 3), dtype=torch.float32, device=dev))
+        hip.call(dev, "fgs_head_forward", d, raw_, xy_, z_, pose_, mod_, edge_, *outs, *([None] if C != 19 else []))
         ctx.dims = d
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(raw_, pose_, mod_, edge_)
@@ -245,25 +232,19 @@ class _HeadHip(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *g_outs):
-        lib = B.load()
         raw_, pose_, mod_, edge_ = ctx.saved_tensors
         d = ctx.dims
         need_z, need_mod, need_edge = ctx.needs_input_grad[2], ctx.needs_input_grad[4], ctx.needs_input_grad[5]
         gs = [_f32c(g) for g in g_outs] + [None] * (6 - len(g_outs))
         dev = raw_.device
-        with torch.cuda.device(dev):
-            g_raw = torch.empty_like(raw_)
-            g_z = torch.empty((d.batch, d.points), dtype=torch.float32, device=dev) if need_z else None
-            g_edge = torch.empty((d.batch, d.points), dtype=torch.float32, device=dev) if need_edge and edge_ is not None else None
-            g_mod = scratch = None
-            if need_mod and mod_ is not None:
-                nb = ctypes.c_size_t(0)
-                B.check(lib.fgs_head_workspace_bytes(ctypes.byref(d), ctypes.byref(nb)), "fgs_head_workspace_bytes")
-                g_mod = torch.empty((d.batch,), dtype=torch.float32, device=dev)
-                scratch = torch.empty(nb.value, dtype=torch.uint8, device=dev)
-            B.check(lib.fgs_head_backward(ctypes.byref(d), _ptr(raw_), _ptr(pose_), _ptr(mod_), _ptr(edge_), *[_ptr(g) for g in gs],
-                                          _ptr(g_raw), _ptr(g_z), _ptr(g_edge), _ptr(g_mod), _ptr(scratch), _stream()),
-                    "fgs_head_backward")
+        g_raw = torch.empty_like(raw_)
+        g_z = torch.empty((d.batch, d.points), dtype=torch.float32, device=dev) if need_z else None
+        g_edge = torch.empty((d.batch, d.points), dtype=torch.float32, device=dev) if need_edge and edge_ is not None else None
+        g_mod = scratch = None
+        if need_mod and mod_ is not None:
+            g_mod = torch.empty((d.batch,), dtype=torch.float32, device=dev)
+            scratch = torch.empty(B.sizes("fgs_head_workspace_bytes", d), dtype=torch.uint8, device=dev)
+        hip.call(dev, "fgs_head_backward", d, raw_, pose_, mod_, edge_, *gs, g_raw, g_z, g_edge, g_mod, scratch)
         return (g_raw, None, g_z, None, g_mod, g_edge, None, None, None, None)
 
 
@@ -524,17 +505,13 @@ class _NcaPerceiveHip(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, state, k):
-        if not state.is_cuda:
-            raise B.FgsError("nca_perceive (backend 'hip') needs CUDA/ROCm tensors; there is no CPU fallback")
-        lib = B.load()
+        hip.need_cuda(state, "nca_perceive (backend 'hip')")
         state_ = _f32c(state)
         d = _nca_dims(state_, k)
         dev = state_.device
-        with torch.cuda.device(dev):
-            perception = torch.empty((d.batch, d.points, (d.k + 1) * d.state_dim), dtype=torch.float32, device=dev)
-            neighbors = torch.empty((d.batch, d.points, d.k), dtype=torch.int32, device=dev)
-            B.check(lib.fgs_nca_perceive_forward(ctypes.byref(d), _ptr(state_), _ptr(perception), _ptr(neighbors), _stream()),
-                    "fgs_nca_perceive_forward")
+        perception = torch.empty((d.batch, d.points, (d.k + 1) * d.state_dim), dtype=torch.float32, device=dev)
+        neighbors = torch.empty((d.batch, d.points, d.k), dtype=torch.int32, device=dev)
+        hip.call(dev, "fgs_nca_perceive_forward", d, state_, perception, neighbors)
         ctx.dims = d
         ctx.save_for_backward(neighbors)
         ctx.mark_non_differentiable(neighbors)
@@ -542,14 +519,11 @@ class _NcaPerceiveHip(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_perception, _g_neighbors):
-        lib = B.load()
         neighbors, = ctx.saved_tensors
         d = ctx.dims
         g_ = _f32c(g_perception)
-        with torch.cuda.device(g_.device):
-            g_state = torch.empty((d.batch, d.points, d.state_dim), dtype=torch.float32, device=g_.device)
-            B.check(lib.fgs_nca_perceive_backward(ctypes.byref(d), _ptr(neighbors), _ptr(g_), _ptr(g_state), _stream()),
-                    "fgs_nca_perceive_backward")
+        g_state = torch.empty((d.batch, d.points, d.state_dim), dtype=torch.float32, device=g_.device)
+        hip.call(g_.device, "fgs_nca_perceive_backward", d, neighbors, g_, g_state)
         return g_state, None
 
 
@@ -586,34 +560,25 @@ class _NcaUpdateHip(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, state, delta, step_size, uniform, update_prob):
-        if not state.is_cuda:
-            raise B.FgsError("nca_update (backend 'hip') needs CUDA/ROCm tensors; there is no CPU fallback")
-        lib = B.load()
+        hip.need_cuda(state, "nca_update (backend 'hip')")
         state_, delta_, step_, uni_ = _f32c(state), _f32c(delta), _f32c(step_size), _f32c(uniform)
         d = _nca_dims(state_, 1)
-        with torch.cuda.device(state_.device):
-            new_state = torch.empty_like(state_)
-            B.check(lib.fgs_nca_update_forward(ctypes.byref(d), _ptr(state_), _ptr(delta_), _ptr(step_), _ptr(uni_),
-                                               float(update_prob), _ptr(new_state), _stream()), "fgs_nca_update_forward")
+        new_state = torch.empty_like(state_)
+        hip.call(state_.device, "fgs_nca_update_forward", d, state_, delta_, step_, uni_, float(update_prob), new_state)
         ctx.dims, ctx.update_prob = d, float(update_prob)
         ctx.save_for_backward(delta_, step_, uni_)
         return new_state
 
     @staticmethod
     def backward(ctx, g_new_state):
-        lib = B.load()
         delta_, step_, uni_ = ctx.saved_tensors
         d = ctx.dims
         g_ = _f32c(g_new_state)
         dev = g_.device
-        with torch.cuda.device(dev):
-            nb = ctypes.c_size_t(0)
-            B.check(lib.fgs_nca_workspace_bytes(ctypes.byref(d), ctypes.byref(nb)), "fgs_nca_workspace_bytes")
-            g_delta = torch.empty_like(delta_)
-            g_step = torch.empty((), dtype=torch.float32, device=dev)
-            scratch = torch.empty(nb.value, dtype=torch.uint8, device=dev)
-            B.check(lib.fgs_nca_update_backward(ctypes.byref(d), _ptr(delta_), _ptr(step_), _ptr(uni_), ctx.update_prob, _ptr(g_),
-                                                _ptr(g_delta), _ptr(g_step), _ptr(scratch), _stream()), "fgs_nca_update_backward")
+        g_delta = torch.empty_like(delta_)
+        g_step = torch.empty((), dtype=torch.float32, device=dev)
+        scratch = torch.empty(B.sizes("fgs_nca_workspace_bytes", d), dtype=torch.uint8, device=dev)
+        hip.call(dev, "fgs_nca_update_backward", d, delta_, step_, uni_, ctx.update_prob, g_, g_delta, g_step, scratch)
         return g_new_state, g_delta, g_step, None, None
 
 
@@ -772,10 +737,9 @@ def _saag_dims(Bn, N, C=1, H=1, W=1, strides=(1, 1, 1), residual_scale=0.0):
 
 
 def _saag_mlp_inputs_hip(features, positions, scales, rotations, colors, opacities):
-    if not (features.is_cuda and positions.is_cuda):
-        raise B.FgsError("saag_mlp_inputs (backend 'hip') needs CUDA/ROCm tensors; there is no CPU fallback")
+    for t in (features, positions):
+        hip.need_cuda(t, "saag_mlp_inputs (backend 'hip')")
     _refuse_grad("saag_mlp_inputs", (("features", features),) + tuple(zip(_SAAG_NAMES, (positions, scales, rotations, colors, opacities))))
-    lib = B.load()
     Bn, C, H, W = features.shape
     N = positions.shape[1]
     feats = features.detach().float()
@@ -787,10 +751,8 @@ def _saag_mlp_inputs_hip(features, positions, scales, rotations, colors, opaciti
         strides = (C * H * W, H * W, W)
     cloud = [_f32c(t) for t in (positions, scales, rotations, colors, opacities)]
     d = _saag_dims(Bn, N, C, H, W, strides)
-    with torch.cuda.device(feats.device):
-        out = torch.empty((Bn, N, C + 14), dtype=torch.float32, device=feats.device)
-        B.check(lib.fgs_saag_inputs_forward(ctypes.byref(d), _ptr(feats), *[_ptr(t) for t in cloud], _ptr(out), _stream()),
-                "fgs_saag_inputs_forward")
+    out = torch.empty((Bn, N, C + 14), dtype=torch.float32, device=feats.device)
+    hip.call(feats.device, "fgs_saag_inputs_forward", d, feats, *cloud, out)
     return out
 
 
@@ -829,19 +791,16 @@ class _SaagRefineHip(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, raw, gains, positions, scales, rotations, colors, opacities, residual_scale):
-        if not (raw.is_cuda and gains.is_cuda and positions.is_cuda):
-            raise B.FgsError("saag_refine_head (backend 'hip') needs CUDA/ROCm tensors; there is no CPU fallback")
-        lib = B.load()
+        for t in (raw, gains, positions):
+            hip.need_cuda(t, "saag_refine_head (backend 'hip')")
         dev = raw.device
         Bn, N, _ = raw.shape
         raw_, gains_ = _f32c(raw), _f32c(gains)
         cloud = [_f32c(t) for t in (positions, scales, rotations, colors, opacities)]
         d = _saag_dims(Bn, N, residual_scale=residual_scale)
-        with torch.cuda.device(dev):
-            outs = [torch.empty(s, dtype=torch.float32, device=dev) for s in
-                    ((Bn, N, 3), (Bn, N, 3), (Bn, N, 4), (Bn, N, 3), (Bn, N), (Bn, N, 3), (Bn, N, 3), (Bn, N, 3), (Bn, N, 1))]
-            B.check(lib.fgs_saag_refine_forward(ctypes.byref(d), _ptr(raw_), *[_ptr(t) for t in cloud], _ptr(gains_),
-                                                *[_ptr(t) for t in outs], _stream()), "fgs_saag_refine_forward")
+        outs = [torch.empty(s, dtype=torch.float32, device=dev) for s in
+                ((Bn, N, 3), (Bn, N, 3), (Bn, N, 4), (Bn, N, 3), (Bn, N), (Bn, N, 3), (Bn, N, 3), (Bn, N, 3), (Bn, N, 1))]
+        hip.call(dev, "fgs_saag_refine_forward", d, raw_, *cloud, gains_, *outs)
         ctx.dims = d
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(raw_, gains_, *cloud[1:])
@@ -849,20 +808,14 @@ class _SaagRefineHip(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *g_outs):
-        lib = B.load()
         raw_, gains_, scales_, rot_, colors_, opa_ = ctx.saved_tensors
         d = ctx.dims
         gs = [_f32c(g) for g in g_outs]
         dev = raw_.device
-        with torch.cuda.device(dev):
-            nb = ctypes.c_size_t(0)
-            B.check(lib.fgs_saag_workspace_bytes(ctypes.byref(d), ctypes.byref(nb)), "fgs_saag_workspace_bytes")
-            g_raw = torch.empty_like(raw_)
-            g_gains = torch.empty((4,), dtype=torch.float32, device=dev)
-            scratch = torch.empty(nb.value, dtype=torch.uint8, device=dev)
-            B.check(lib.fgs_saag_refine_backward(ctypes.byref(d), _ptr(raw_), _ptr(scales_), _ptr(rot_), _ptr(colors_), _ptr(opa_),
-                                                 _ptr(gains_), *[_ptr(g) for g in gs], _ptr(g_raw), _ptr(g_gains), _ptr(scratch),
-                                                 _stream()), "fgs_saag_refine_backward")
+        g_raw = torch.empty_like(raw_)
+        g_gains = torch.empty((4,), dtype=torch.float32, device=dev)
+        scratch = torch.empty(B.sizes("fgs_saag_workspace_bytes", d), dtype=torch.uint8, device=dev)
+        hip.call(dev, "fgs_saag_refine_backward", d, raw_, scales_, rot_, colors_, opa_, gains_, *gs, g_raw, g_gains, scratch)
         return (g_raw, g_gains, None, None, None, None, None, None)
 
 
@@ -886,8 +839,8 @@ def saag_refine_head(raw: torch.Tensor, positions: torch.Tensor, scales: torch.T
         raise ValueError(f"gains must be (4,): pos, scale, colour, opacity; got {tuple(gains.shape)}")
     cloud = (positions, scales, rotations, colors, opacities)
     if backend == "hip":
-        if not (raw.is_cuda and gains.is_cuda and positions.is_cuda):
-            raise B.FgsError("saag_refine_head (backend 'hip') needs CUDA/ROCm tensors; there is no CPU fallback")
+        for t in (raw, gains, positions):
+            hip.need_cuda(t, "saag_refine_head (backend 'hip')")
         _refuse_grad("saag_refine_head", tuple(zip(_SAAG_NAMES, cloud)))
         outs = _SaagRefineHip.apply(raw, gains, *cloud, float(residual_scale))
     else:
@@ -1054,41 +1007,33 @@ class _PhysicsHeadHip(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, raw, base_xy, base_z, wavelength_raw, K, focal_depth, wavelength_min, wavelength_max, xy_gain):
-        if not (raw.is_cuda and base_z.is_cuda and wavelength_raw.is_cuda):
-            raise B.FgsError("physics_head (backend 'hip') needs CUDA/ROCm tensors; there is no CPU fallback")
-        lib = B.load()
+        for t in (raw, base_z, wavelength_raw):
+            hip.need_cuda(t, "physics_head (backend 'hip')")
         dev = raw.device
         Bn, P, KF, _ = raw.shape
         d = B.FgsPhysicsDims(Bn, P, KF, int(K), float(xy_gain), float(focal_depth), float(wavelength_min), float(wavelength_max))
         raw_, xy_, z_, wl_ = (_f32c(t) for t in (raw, base_xy, base_z, wavelength_raw))
         N = P * int(K)
-        with torch.cuda.device(dev):
-            nb = ctypes.c_size_t(0)
-            B.check(lib.fgs_physics_workspace_bytes(ctypes.byref(d), ctypes.byref(nb)), "fgs_physics_workspace_bytes")
-            outs = [torch.empty((Bn, N, w) if w else (Bn, N), dtype=torch.float32, device=dev) for w in (3, 3, 4, 3, 0, 0)]
-            rng = torch.empty(B.FGS_PHYSICS_RANGE_BYTES, dtype=torch.uint8, device=dev)
-            scratch = torch.empty(nb.value, dtype=torch.uint8, device=dev)
-            B.check(lib.fgs_physics_forward(ctypes.byref(d), _ptr(raw_), _ptr(xy_), _ptr(z_), _ptr(wl_), *[_ptr(t) for t in outs],
-                                            _ptr(rng), _ptr(scratch), _stream()), "fgs_physics_forward")
-        ctx.dims, ctx.scratch_bytes = d, nb.value
+        ctx.dims, ctx.scratch_bytes = d, B.sizes("fgs_physics_workspace_bytes", d)
+        outs = [torch.empty((Bn, N, w) if w else (Bn, N), dtype=torch.float32, device=dev) for w in (3, 3, 4, 3, 0, 0)]
+        rng = torch.empty(B.FGS_PHYSICS_RANGE_BYTES, dtype=torch.uint8, device=dev)
+        scratch = torch.empty(ctx.scratch_bytes, dtype=torch.uint8, device=dev)
+        hip.call(dev, "fgs_physics_forward", d, raw_, xy_, z_, wl_, *outs, rng, scratch)
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(raw_, z_, wl_, rng)
         return tuple(outs)
 
     @staticmethod
     def backward(ctx, *g_outs):
-        lib = B.load()
         raw_, z_, wl_, rng = ctx.saved_tensors
         d = ctx.dims
         gs = [_f32c(g) for g in g_outs]
         dev = raw_.device
-        with torch.cuda.device(dev):
-            g_raw = torch.empty_like(raw_)
-            g_z = torch.empty((d.batch, d.points), dtype=torch.float32, device=dev) if ctx.needs_input_grad[2] else None
-            g_wl = torch.empty((), dtype=torch.float32, device=dev) if ctx.needs_input_grad[3] else None
-            scratch = torch.empty(ctx.scratch_bytes, dtype=torch.uint8, device=dev)
-            B.check(lib.fgs_physics_backward(ctypes.byref(d), _ptr(raw_), _ptr(z_), _ptr(wl_), _ptr(rng), *[_ptr(g) for g in gs],
-                                             _ptr(g_raw), _ptr(g_z), _ptr(g_wl), _ptr(scratch), _stream()), "fgs_physics_backward")
+        g_raw = torch.empty_like(raw_)
+        g_z = torch.empty((d.batch, d.points), dtype=torch.float32, device=dev) if ctx.needs_input_grad[2] else None
+        g_wl = torch.empty((), dtype=torch.float32, device=dev) if ctx.needs_input_grad[3] else None
+        scratch = torch.empty(ctx.scratch_bytes, dtype=torch.uint8, device=dev)
+        hip.call(dev, "fgs_physics_backward", d, raw_, z_, wl_, rng, *gs, g_raw, g_z, g_wl, scratch)
         return (g_raw, None, g_z, g_wl, None, None, None, None, None)
 
 

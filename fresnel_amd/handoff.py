@@ -13,7 +13,6 @@ train_gaussian_decoder.py ("TGD"):
 The gather itself runs in libfgs_hip.so (fgs_gather_forward / fgs_gather_backward: one launch for all tensors); the
 draw is torch.multinomial on the device, as in the reference.
 """
-import ctypes
 import math
 from dataclasses import dataclass
 from typing import Dict, Optional, Tuple
@@ -22,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _binding as B
+from . import _hip as hip
 
 
 @dataclass
@@ -67,18 +67,12 @@ class HFTSConfig:
 _KEYS = ("positions", "scales", "rotations", "colors", "opacities")
 
 
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
 class _GatherGaussians(torch.autograd.Function):
     """(B,N,.) x indices (K,) -> (B,K,.) for all Gaussian tensors in one launch (fgs_gather_forward/backward)."""
 
     @staticmethod
     def forward(ctx, indices, pos, scale, quat, color, opacity, phase):
-        if not pos.is_cuda:
-            raise B.FgsError("importance_subsample (HIP gather) needs CUDA/ROCm tensors; there is no CPU fallback")
-        lib = B.load()
+        hip.need_cuda(pos, "importance_subsample (HIP gather)")
         Bn, N, K = pos.shape[0], pos.shape[1], indices.shape[0]
         ins = [t.detach().contiguous().float() for t in (pos, scale, quat, color, opacity)]
         ph = phase.detach().contiguous().float() if phase is not None else None
@@ -87,12 +81,9 @@ class _GatherGaussians(torch.autograd.Function):
         pc = 0 if ph is None else (int(ph.shape[2]) if ph.dim() == 3 else 1)  # floats per Gaussian the kernel moves
         idx = indices.detach().to(torch.int64).contiguous()
         dev = pos.device
-        with torch.cuda.device(dev):
-            outs = [torch.empty(Bn, K, *t.shape[2:], dtype=torch.float32, device=dev) for t in ins]
-            o_ph = torch.empty(Bn, K, *ph.shape[2:], dtype=torch.float32, device=dev) if ph is not None else None
-            B.check(lib.fgs_gather_forward(Bn, N, K, pc, _ptr(idx), *[_ptr(t) for t in ins], _ptr(ph),
-                                           *[_ptr(t) for t in outs], _ptr(o_ph),
-                                           ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "fgs_gather_forward")
+        outs = [torch.empty(Bn, K, *t.shape[2:], dtype=torch.float32, device=dev) for t in ins]
+        o_ph = torch.empty(Bn, K, *ph.shape[2:], dtype=torch.float32, device=dev) if ph is not None else None
+        hip.call(dev, "fgs_gather_forward", Bn, N, K, pc, idx, *ins, ph, *outs, o_ph)
         ctx.save_for_backward(idx)
         ctx.shape = (Bn, N, K, pc)
         ctx.trail = [t.shape[2:] for t in ins] + [ph.shape[2:] if ph is not None else None]
@@ -100,22 +91,18 @@ class _GatherGaussians(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *grads):
-        lib = B.load()
         (idx,) = ctx.saved_tensors
         Bn, N, K, pc = ctx.shape
         dev = idx.device
-        with torch.cuda.device(dev):
-            gs = []
-            for g, trail in zip(grads[:5], ctx.trail[:5]):
-                gs.append((g if g is not None else torch.zeros(Bn, K, *trail, device=dev)).contiguous().float())
-            g_ph = None
-            if pc:
-                g_ph = (grads[5] if grads[5] is not None else torch.zeros(Bn, K, *ctx.trail[5], device=dev)).contiguous().float()
-            outs = [torch.empty(Bn, N, *trail, dtype=torch.float32, device=dev) for trail in ctx.trail[:5]]
-            o_ph = torch.empty(Bn, N, *ctx.trail[5], dtype=torch.float32, device=dev) if pc else None
-            B.check(lib.fgs_gather_backward(Bn, N, K, pc, _ptr(idx), *[_ptr(t) for t in gs], _ptr(g_ph),
-                                            *[_ptr(t) for t in outs], _ptr(o_ph),
-                                            ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "fgs_gather_backward")
+        gs = []
+        for g, trail in zip(grads[:5], ctx.trail[:5]):
+            gs.append((g if g is not None else torch.zeros(Bn, K, *trail, device=dev)).contiguous().float())
+        g_ph = None
+        if pc:
+            g_ph = (grads[5] if grads[5] is not None else torch.zeros(Bn, K, *ctx.trail[5], device=dev)).contiguous().float()
+        outs = [torch.empty(Bn, N, *trail, dtype=torch.float32, device=dev) for trail in ctx.trail[:5]]
+        o_ph = torch.empty(Bn, N, *ctx.trail[5], dtype=torch.float32, device=dev) if pc else None
+        hip.call(dev, "fgs_gather_backward", Bn, N, K, pc, idx, *gs, g_ph, *outs, o_ph)
         return (None,) + tuple(outs) + (o_ph,)
 
 

@@ -14,7 +14,6 @@ PyTorch is plumbing here (device memory, streams, autograd graph); all arithmeti
 libfgs_hip.so through the C ABI of include/fgs.h.  There is NO CPU fallback: calling the
 renderer without CUDA tensors or without the built library raises.
 """
-import ctypes
 import math
 from typing import Optional, Sequence, Tuple, Union
 
@@ -22,6 +21,7 @@ import torch
 import torch.nn as nn
 
 from . import _binding as B
+from . import _hip as hip
 
 
 class Camera:
@@ -136,41 +136,6 @@ def _phase_channels(ph: torch.Tensor) -> int:
     if ph.dim() == 3 and ph.shape[2] in (1, 3):
         return int(ph.shape[2])
     raise ValueError(f"phases must be (N,) or (N,3) per image, got {tuple(ph.shape[1:])}")
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-
-
-def _stream_handle():
-    """hipStream_t of the current device's current stream.  (torch.cuda.current_stream().cuda_stream builds a Stream object
-    per call: ~7 us, twice per image on the per-image route; the raw getter is ~0.3 us.)"""
-    if _raw_stream is not None:
-        return ctypes.c_void_p(_raw_stream(torch.cuda.current_device()))
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-class _on_device:
-    """`with torch.cuda.device(dev)` without its cost when `dev` is current already (the usual case: ~11 us per image saved
-    on the per-image route, profiles/r05_host_profile_config1.txt)."""
-    __slots__ = ("idx", "prev")
-
-    def __init__(self, dev):
-        self.idx = dev.index
-
-    def __enter__(self):
-        self.prev = torch.cuda.current_device()
-        if self.idx is not None and self.idx != self.prev:
-            torch.cuda.set_device(self.idx)
-        else:
-            self.prev = None
-
-    def __exit__(self, *a):
-        if self.prev is not None:
-            torch.cuda.set_device(self.prev)
 
 
 class _Cfg:
@@ -345,8 +310,7 @@ def _scratch_for(dev, nbytes, shrink=False):
     # a cached buffer would be baked into the graph AND handed to later eager calls on a stream with the same handle
     if torch.cuda.is_current_stream_capturing():
         return torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    key = (dev.index, _raw_stream(dev.index if dev.index is not None else torch.cuda.current_device()) if _raw_stream is not None
-           else torch.cuda.current_stream(dev).cuda_stream)
+    key = (dev.index, hip.stream_handle(dev))
     buf = _SCRATCH.get(key)
     if buf is None or buf.numel() < nbytes or (shrink and buf.numel() > 2 * nbytes):
         buf = _SCRATCH[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
@@ -359,11 +323,7 @@ def release_scratch():
     _SCRATCH.clear()
 
 
-def _f32c(t):
-    """float32, contiguous, detached -- without a dispatcher call when the tensor already is (the usual case)."""
-    if t.dtype is torch.float32 and t.is_contiguous():
-        return t.detach() if t.requires_grad else t
-    return t.detach().contiguous().float()
+_f32c = hip.f32c
 
 
 def forward_raw(positions, scales, rotations, colors, opacities, phases, cam_tensor, cfg):
@@ -371,7 +331,6 @@ def forward_raw(positions, scales, rotations, colors, opacities, phases, cam_ten
     if not positions.is_cuda:
         raise B.FgsError("GaussianRenderer (HIP) needs CUDA/ROCm tensors; there is no CPU fallback "
                          "(the CPU oracle lives under oracle/ and is test infrastructure only)")
-    lib = B.load()
     Bn, N = positions.shape[0], positions.shape[1]
     dev = positions.device
     pos, scl, rot, col, opa = _f32c(positions), _f32c(scales), _f32c(rotations), _f32c(colors), _f32c(opacities)
@@ -392,14 +351,12 @@ def forward_raw(positions, scales, rotations, colors, opacities, phases, cam_ten
             capacity = state.tracker.capacity()
     dims, saved_bytes, scratch_bytes, counters_off = _dims_for(Bn, N, cfg, ph is not None, cam_tensor.shape[0], capacity)
     shrink = ws is not None and ws.mode != "worst"  # (the functional entry with a fixed dup_capacity keeps the grow-only cache)
-    with _on_device(dev):
+    with hip.on_device(dev) as held:  # (also for the scratch cache's capture test and the readback's event)
         saved = torch.empty(saved_bytes, dtype=torch.uint8, device=dev)
         scratch = _scratch_for(dev, scratch_bytes, shrink)
         out_rgb = torch.empty((Bn, 3, cfg.height, cfg.width), dtype=torch.float32, device=dev)
         out_depth = torch.empty((Bn, cfg.height, cfg.width), dtype=torch.float32, device=dev)
-        B.check(lib.fgs_forward(ctypes.byref(dims), _ptr(cam_tensor), _ptr(pos), _ptr(scl), _ptr(rot),
-                                _ptr(col), _ptr(opa), _ptr(ph), _ptr(out_rgb), _ptr(out_depth),
-                                _ptr(saved), _ptr(scratch), _stream_handle()), "fgs_forward")
+        hip.call(held, "fgs_forward", dims, cam_tensor, pos, scl, rot, col, opa, ph, out_rgb, out_depth, saved, scratch)
         if state is not None:
             state.capacity, state.bytes = capacity, saved_bytes + scratch_bytes
             if adaptive:
@@ -422,7 +379,7 @@ class GaussianRenderer(torch.autograd.Function):
         if getattr(cfg, "pair_counter", None) is not None:
             # unit of work of SURVEY 8d, counted on the device and accumulated asynchronously (no host sync)
             n = torch.empty(1, dtype=torch.int64, device=pos.device)
-            B.check(B.load().fgs_count_pairs(ctypes.byref(dims), _ptr(saved), _ptr(n), _stream_handle()), "fgs_count_pairs")
+            hip.call(pos.device, "fgs_count_pairs", dims, saved, n)
             cfg.pair_counter[:1] += n
             if cfg.pair_counter.numel() >= 3:  # [1]: tile duplicates D (saved.counters[0]), [2]: Gaussians -- for the algorithmic HBM bytes
                 L = B.saved_layout(dims)
@@ -439,7 +396,6 @@ class GaussianRenderer(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_rgb, g_depth):
-        lib = B.load()
         pos, scl, rot, col, opa, ph, cam_tensor, saved = ctx.saved_tensors
         dims = ctx.dims
         dev = pos.device
@@ -447,15 +403,13 @@ class GaussianRenderer(torch.autograd.Function):
         g_rgb = (g_rgb if g_rgb is not None else torch.zeros(dims.batch, 3, dims.height, dims.width, device=dev))
         g_depth = (g_depth if g_depth is not None else torch.zeros(dims.batch, dims.height, dims.width, device=dev))
         g_rgb, g_depth = _f32c(g_rgb), _f32c(g_depth)
-        with _on_device(dev):
+        with hip.on_device(dev) as held:
             scratch = _scratch_for(dev, ctx.scratch_bytes, ctx.shrink_scratch)
             g_pos, g_scl, g_rot = torch.empty_like(pos), torch.empty_like(scl), torch.empty_like(rot)
             g_col, g_opa = torch.empty_like(col), torch.empty_like(opa)
             g_ph = torch.empty_like(ph) if ph is not None else None
-            B.check(lib.fgs_backward(ctypes.byref(dims), _ptr(cam_tensor), _ptr(pos), _ptr(scl), _ptr(rot),
-                                     _ptr(col), _ptr(opa), _ptr(ph), _ptr(saved), _ptr(scratch), _ptr(g_rgb),
-                                     _ptr(g_depth), _ptr(g_pos), _ptr(g_scl), _ptr(g_rot), _ptr(g_col),
-                                     _ptr(g_opa), _ptr(g_ph), _stream_handle()), "fgs_backward")
+            hip.call(held, "fgs_backward", dims, cam_tensor, pos, scl, rot, col, opa, ph, saved, scratch, g_rgb, g_depth,
+                     g_pos, g_scl, g_rot, g_col, g_opa, g_ph)
         return g_pos, g_scl, g_rot, g_col, g_opa, g_ph, None, None
 
 
@@ -591,9 +545,7 @@ class AsmRenderer(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, positions, scales, rotations, colors, opacities, phases, wavelengths, cam_tensor, cfg):
-        if not positions.is_cuda:
-            raise B.FgsError("AsmRenderer (HIP) needs CUDA/ROCm tensors; there is no CPU fallback")
-        lib = B.load()
+        hip.need_cuda(positions, "AsmRenderer (HIP)")
         Bn, N = positions.shape[0], positions.shape[1]
         dev = positions.device
         pos, scl, rot, col, opa, ph = [t.detach().contiguous().float()
@@ -611,24 +563,18 @@ class AsmRenderer(torch.autograd.Function):
         d.phase_channels = _phase_channels(ph)
         d.num_cameras = cam_tensor.shape[0]
         d.bin_mode = int(cfg.get("bin_mode", 0))  # FgsAsmDims.bin_mode: list-building override for A/B runs and tests
-        sb, cb = ctypes.c_size_t(0), ctypes.c_size_t(0)
-        with _on_device(dev):
-            B.check(lib.fgs_asm_workspace_bytes(ctypes.byref(d), ctypes.byref(sb), ctypes.byref(cb)),
-                    "fgs_asm_workspace_bytes")
-            saved = torch.empty(sb.value, dtype=torch.uint8, device=dev)
-            scratch = torch.empty(cb.value, dtype=torch.uint8, device=dev)
-            out = torch.empty(Bn, 3, cfg["height"], cfg["width"], dtype=torch.float32, device=dev)
-            B.check(lib.fgs_asm_forward(ctypes.byref(d), _ptr(cam_tensor), _ptr(pos), _ptr(scl), _ptr(rot), _ptr(col),
-                                        _ptr(opa), _ptr(ph), _ptr(wl), _ptr(out), _ptr(saved), _ptr(scratch),
-                                        _stream_handle()), "fgs_asm_forward")
+        with hip.on_device(dev):  # (the query builds this device's hipFFT plans and returns their work size)
+            saved_bytes, ctx.scratch_bytes = B.sizes("fgs_asm_workspace_bytes", d)
+        saved = torch.empty(saved_bytes, dtype=torch.uint8, device=dev)
+        scratch = torch.empty(ctx.scratch_bytes, dtype=torch.uint8, device=dev)
+        out = torch.empty(Bn, 3, cfg["height"], cfg["width"], dtype=torch.float32, device=dev)
+        hip.call(dev, "fgs_asm_forward", d, cam_tensor, pos, scl, rot, col, opa, ph, wl, out, saved, scratch)
         ctx.dims = d
-        ctx.scratch_bytes = cb.value
         ctx.save_for_backward(pos, scl, rot, col, opa, ph, wl, cam_tensor, saved)
         return out
 
     @staticmethod
     def backward(ctx, g_out):
-        lib = B.load()
         pos, scl, rot, col, opa, ph, wl, cam_tensor, saved = ctx.saved_tensors
         # fgs_asm_backward turns the plane fields in `saved` into their gradients IN PLACE (fgs.h): a second backward through this
         # node (retain_graph=True, two losses sharing the graph) would read them as fields
@@ -639,15 +585,12 @@ class AsmRenderer(torch.autograd.Function):
         d = ctx.dims
         dev = pos.device
         g_out = g_out.contiguous().float()
-        with _on_device(dev):
-            scratch = torch.empty(ctx.scratch_bytes, dtype=torch.uint8, device=dev)
-            g_pos, g_scl, g_rot = torch.empty_like(pos), torch.empty_like(scl), torch.empty_like(rot)
-            g_col, g_opa, g_ph = torch.empty_like(col), torch.empty_like(opa), torch.empty_like(ph)
-            g_wl = torch.empty_like(wl)
-            B.check(lib.fgs_asm_backward(ctypes.byref(d), _ptr(cam_tensor), _ptr(pos), _ptr(scl), _ptr(rot),
-                                         _ptr(col), _ptr(opa), _ptr(ph), _ptr(wl), _ptr(saved), _ptr(scratch),
-                                         _ptr(g_out), _ptr(g_pos), _ptr(g_scl), _ptr(g_rot), _ptr(g_col),
-                                         _ptr(g_opa), _ptr(g_ph), _ptr(g_wl), _stream_handle()), "fgs_asm_backward")
+        scratch = torch.empty(ctx.scratch_bytes, dtype=torch.uint8, device=dev)
+        g_pos, g_scl, g_rot = torch.empty_like(pos), torch.empty_like(scl), torch.empty_like(rot)
+        g_col, g_opa, g_ph = torch.empty_like(col), torch.empty_like(opa), torch.empty_like(ph)
+        g_wl = torch.empty_like(wl)
+        hip.call(dev, "fgs_asm_backward", d, cam_tensor, pos, scl, rot, col, opa, ph, wl, saved, scratch, g_out,
+                 g_pos, g_scl, g_rot, g_col, g_opa, g_ph, g_wl)
         return g_pos, g_scl, g_rot, g_col, g_opa, g_ph, g_wl, None, None
 
 
@@ -656,43 +599,34 @@ class _AsmPropagate(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, field, z, wavelengths, pixel_pitch, band_limit):
-        if not field.is_cuda:
-            raise B.FgsError("AngularSpectrumPropagator (HIP) needs CUDA/ROCm tensors; there is no CPU fallback")
-        lib = B.load()
+        hip.need_cuda(field, "AngularSpectrumPropagator (HIP)")
         dev = field.device
         f = torch.view_as_real(field.detach().to(torch.complex64).contiguous())
         C, H, W = field.shape
         zt = z.detach().reshape(1).float().contiguous().to(dev)
         wl = wavelengths.detach().reshape(C).float().contiguous().to(dev)
-        cb = ctypes.c_size_t(0)
-        with _on_device(dev):
-            B.check(lib.fgs_asm_propagate_workspace_bytes(H, W, C, ctypes.byref(cb)), "fgs_asm_propagate_workspace_bytes")
-            scratch = torch.empty(cb.value, dtype=torch.uint8, device=dev)
-            out = torch.empty_like(f)
-            spec = torch.empty_like(f)
-            B.check(lib.fgs_asm_propagate_forward(H, W, C, float(pixel_pitch), 1 if band_limit else 0, _ptr(f), _ptr(zt),
-                                                  _ptr(wl), _ptr(out), _ptr(spec), _ptr(scratch), _stream_handle()),
-                    "fgs_asm_propagate_forward")
-        ctx.cfg = (H, W, C, float(pixel_pitch), 1 if band_limit else 0, cb.value)
+        with hip.on_device(dev):  # (the query builds this device's hipFFT plan and returns its work size)
+            scratch_bytes = B.sizes("fgs_asm_propagate_workspace_bytes", H, W, C)
+        scratch = torch.empty(scratch_bytes, dtype=torch.uint8, device=dev)
+        out = torch.empty_like(f)
+        spec = torch.empty_like(f)
+        hip.call(dev, "fgs_asm_propagate_forward", H, W, C, float(pixel_pitch), 1 if band_limit else 0, f, zt, wl, out, spec, scratch)
+        ctx.cfg = (H, W, C, float(pixel_pitch), 1 if band_limit else 0, scratch_bytes)
         ctx.shapes = (z.shape, wavelengths.shape)
         ctx.save_for_backward(spec, zt, wl)
         return torch.view_as_complex(out)
 
     @staticmethod
     def backward(ctx, g_out):
-        lib = B.load()
         spec, zt, wl = ctx.saved_tensors
         H, W, C, pitch, bl, cbytes = ctx.cfg
         dev = spec.device
         g = torch.view_as_real(g_out.detach().to(torch.complex64).contiguous())
-        with _on_device(dev):
-            scratch = torch.empty(cbytes, dtype=torch.uint8, device=dev)
-            g_field = torch.empty_like(g)
-            g_z = torch.empty(1, dtype=torch.float32, device=dev)
-            g_wl = torch.empty(C, dtype=torch.float32, device=dev)
-            B.check(lib.fgs_asm_propagate_backward(H, W, C, pitch, bl, _ptr(spec), _ptr(zt), _ptr(wl), _ptr(g), _ptr(g_field),
-                                                   _ptr(g_z), _ptr(g_wl), _ptr(scratch), _stream_handle()),
-                    "fgs_asm_propagate_backward")
+        scratch = torch.empty(cbytes, dtype=torch.uint8, device=dev)
+        g_field = torch.empty_like(g)
+        g_z = torch.empty(1, dtype=torch.float32, device=dev)
+        g_wl = torch.empty(C, dtype=torch.float32, device=dev)
+        hip.call(dev, "fgs_asm_propagate_backward", H, W, C, pitch, bl, spec, zt, wl, g, g_field, g_z, g_wl, scratch)
         return (torch.view_as_complex(g_field), g_z.reshape(ctx.shapes[0]) if ctx.needs_input_grad[1] else None,
                 g_wl.reshape(ctx.shapes[1]) if ctx.needs_input_grad[2] else None, None, None)
 
@@ -837,9 +771,7 @@ class WaveRenderer(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, positions, scales, rotations, colors, opacities, phases, cam_tensor, cfg):
-        if not positions.is_cuda:
-            raise B.FgsError("WaveRenderer (HIP) needs CUDA/ROCm tensors; there is no CPU fallback")
-        lib = B.load()
+        hip.need_cuda(positions, "WaveRenderer (HIP)")
         Bn, N = positions.shape[0], positions.shape[1]
         dev = positions.device
         pos, scl, rot, col, opa, ph = [t.detach().contiguous().float()
@@ -852,37 +784,28 @@ class WaveRenderer(torch.autograd.Function):
             d.background[i] = float(cfg["background"][i])
         d.phase_channels = _phase_channels(ph)
         d.num_cameras = cam_tensor.shape[0]
-        sb, cb = ctypes.c_size_t(0), ctypes.c_size_t(0)
-        with _on_device(dev):
-            B.check(lib.fgs_wave_workspace_bytes(ctypes.byref(d), ctypes.byref(sb), ctypes.byref(cb)),
-                    "fgs_wave_workspace_bytes")
-            saved = torch.empty(sb.value, dtype=torch.uint8, device=dev)
-            scratch = torch.empty(cb.value, dtype=torch.uint8, device=dev)
-            out = torch.empty(Bn, 3, cfg["height"], cfg["width"], dtype=torch.float32, device=dev)
-            dep = torch.empty(Bn, cfg["height"], cfg["width"], dtype=torch.float32, device=dev)
-            B.check(lib.fgs_wave_forward(ctypes.byref(d), _ptr(cam_tensor), _ptr(pos), _ptr(scl), _ptr(rot),
-                                         _ptr(col), _ptr(opa), _ptr(ph), _ptr(out), _ptr(dep), _ptr(saved),
-                                         _ptr(scratch), _stream_handle()), "fgs_wave_forward")
-        ctx.dims, ctx.scratch_bytes = d, cb.value
+        saved_bytes, ctx.scratch_bytes = B.sizes("fgs_wave_workspace_bytes", d)
+        saved = torch.empty(saved_bytes, dtype=torch.uint8, device=dev)
+        scratch = torch.empty(ctx.scratch_bytes, dtype=torch.uint8, device=dev)
+        out = torch.empty(Bn, 3, cfg["height"], cfg["width"], dtype=torch.float32, device=dev)
+        dep = torch.empty(Bn, cfg["height"], cfg["width"], dtype=torch.float32, device=dev)
+        hip.call(dev, "fgs_wave_forward", d, cam_tensor, pos, scl, rot, col, opa, ph, out, dep, saved, scratch)
+        ctx.dims = d
         ctx.save_for_backward(pos, scl, rot, col, opa, ph, cam_tensor, saved)
         return out, dep
 
     @staticmethod
     def backward(ctx, g_out, g_dep):
-        lib = B.load()
         pos, scl, rot, col, opa, ph, cam_tensor, saved = ctx.saved_tensors
         d = ctx.dims
         dev = pos.device
         g_out = (g_out if g_out is not None else torch.zeros(d.batch, 3, d.height, d.width, device=dev)).contiguous().float()
         g_dep = (g_dep if g_dep is not None else torch.zeros(d.batch, d.height, d.width, device=dev)).contiguous().float()
-        with _on_device(dev):
-            scratch = torch.empty(ctx.scratch_bytes, dtype=torch.uint8, device=dev)
-            g_pos, g_scl, g_rot = torch.empty_like(pos), torch.empty_like(scl), torch.empty_like(rot)
-            g_col, g_opa, g_ph = torch.empty_like(col), torch.empty_like(opa), torch.empty_like(ph)
-            B.check(lib.fgs_wave_backward(ctypes.byref(d), _ptr(cam_tensor), _ptr(pos), _ptr(scl), _ptr(rot),
-                                          _ptr(col), _ptr(opa), _ptr(ph), _ptr(saved), _ptr(scratch), _ptr(g_out),
-                                          _ptr(g_dep), _ptr(g_pos), _ptr(g_scl), _ptr(g_rot), _ptr(g_col),
-                                          _ptr(g_opa), _ptr(g_ph), _stream_handle()), "fgs_wave_backward")
+        scratch = torch.empty(ctx.scratch_bytes, dtype=torch.uint8, device=dev)
+        g_pos, g_scl, g_rot = torch.empty_like(pos), torch.empty_like(scl), torch.empty_like(rot)
+        g_col, g_opa, g_ph = torch.empty_like(col), torch.empty_like(opa), torch.empty_like(ph)
+        hip.call(dev, "fgs_wave_backward", d, cam_tensor, pos, scl, rot, col, opa, ph, saved, scratch, g_out, g_dep,
+                 g_pos, g_scl, g_rot, g_col, g_opa, g_ph)
         return g_pos, g_scl, g_rot, g_col, g_opa, g_ph, None, None
 
 
@@ -922,9 +845,7 @@ class FourierRenderer(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, positions, scales, rotations, colors, opacities, cam_tensor, cfg):
-        if not positions.is_cuda:
-            raise B.FgsError("FourierRenderer (HIP) needs CUDA/ROCm tensors; there is no CPU fallback")
-        lib = B.load()
+        hip.need_cuda(positions, "FourierRenderer (HIP)")
         Bn, N = positions.shape[0], positions.shape[1]
         dev = positions.device
         pos, scl, rot, col, opa = [_f32c(t) for t in (positions, scales, rotations, colors, opacities)]
@@ -934,35 +855,26 @@ class FourierRenderer(torch.autograd.Function):
         for i in range(3):
             d.background[i] = float(cfg["background"][i])
         d.num_cameras = cam_tensor.shape[0]
-        sb, cb = ctypes.c_size_t(0), ctypes.c_size_t(0)
-        with _on_device(dev):
-            B.check(lib.fgs_fourier_workspace_bytes(ctypes.byref(d), ctypes.byref(sb), ctypes.byref(cb)),
-                    "fgs_fourier_workspace_bytes")
-            saved = torch.empty(sb.value, dtype=torch.uint8, device=dev)
-            scratch = torch.empty(cb.value, dtype=torch.uint8, device=dev)
-            out = torch.empty(Bn, 3, cfg["height"], cfg["width"], dtype=torch.float32, device=dev)
-            B.check(lib.fgs_fourier_forward(ctypes.byref(d), _ptr(cam_tensor), _ptr(pos), _ptr(scl), _ptr(rot), _ptr(col),
-                                            _ptr(opa), _ptr(out), _ptr(saved), _ptr(scratch), _stream_handle()),
-                    "fgs_fourier_forward")
-        ctx.dims, ctx.scratch_bytes = d, cb.value
+        saved_bytes, ctx.scratch_bytes = B.sizes("fgs_fourier_workspace_bytes", d)
+        saved = torch.empty(saved_bytes, dtype=torch.uint8, device=dev)
+        scratch = torch.empty(ctx.scratch_bytes, dtype=torch.uint8, device=dev)
+        out = torch.empty(Bn, 3, cfg["height"], cfg["width"], dtype=torch.float32, device=dev)
+        hip.call(dev, "fgs_fourier_forward", d, cam_tensor, pos, scl, rot, col, opa, out, saved, scratch)
+        ctx.dims = d
         ctx.save_for_backward(pos, scl, rot, col, opa, cam_tensor, saved)
         return out
 
     @staticmethod
     def backward(ctx, g_out):
-        lib = B.load()
         pos, scl, rot, col, opa, cam_tensor, saved = ctx.saved_tensors
         d = ctx.dims
         dev = pos.device
         g_out = g_out.contiguous().float()
-        with _on_device(dev):
-            scratch = torch.empty(ctx.scratch_bytes, dtype=torch.uint8, device=dev)
-            g_pos, g_scl, g_rot = torch.empty_like(pos), torch.empty_like(scl), torch.empty_like(rot)
-            g_col, g_opa = torch.empty_like(col), torch.empty_like(opa)
-            B.check(lib.fgs_fourier_backward(ctypes.byref(d), _ptr(cam_tensor), _ptr(pos), _ptr(scl), _ptr(rot), _ptr(col),
-                                             _ptr(opa), _ptr(saved), _ptr(scratch), _ptr(g_out), _ptr(g_pos), _ptr(g_scl),
-                                             _ptr(g_rot), _ptr(g_col), _ptr(g_opa), _stream_handle()),
-                    "fgs_fourier_backward")
+        scratch = torch.empty(ctx.scratch_bytes, dtype=torch.uint8, device=dev)
+        g_pos, g_scl, g_rot = torch.empty_like(pos), torch.empty_like(scl), torch.empty_like(rot)
+        g_col, g_opa = torch.empty_like(col), torch.empty_like(opa)
+        hip.call(dev, "fgs_fourier_backward", d, cam_tensor, pos, scl, rot, col, opa, saved, scratch, g_out,
+                 g_pos, g_scl, g_rot, g_col, g_opa)
         return g_pos, g_scl, g_rot, g_col, g_opa, None, None
 
 

@@ -15,7 +15,6 @@ variant (the reference's experiment 3, decoder.FeatureGuidedSAAG): six of the ge
 `mods`, and autograd carries dL/d rows back to `mods` through fgs_surface_guided_backward.  There is no CPU fallback.
 """
 import argparse
-import ctypes
 import dataclasses
 import sys
 from pathlib import Path
@@ -23,6 +22,7 @@ from pathlib import Path
 import torch
 
 from . import _binding as B
+from . import _hip as hip
 
 KEYS = ("positions", "scales", "rotations", "colors", "opacities")
 # channels of a guide map, in the order of FeatureGuidedSAAG's dict (include/fgs.h, "Feature-guided SAAG")
@@ -91,21 +91,10 @@ class SurfaceGaussianParams:
         return 2 + self.shell_wall_segments + self.wrap_layers + self.density_extra_count
 
 
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def workspace_bytes(batch, height, width, params=None):
     """fgs_surface_workspace_bytes: validates dims and params (FgsError) without touching a device."""
     dims = B.FgsSurfaceDims(int(batch), int(height), int(width))
-    n = ctypes.c_size_t(0)
-    B.check(B.load().fgs_surface_workspace_bytes(ctypes.byref(dims), ctypes.byref((params or SurfaceGaussianParams()).to_c()),
-                                                 ctypes.byref(n)), "fgs_surface_workspace_bytes")
-    return n.value
+    return B.sizes("fgs_surface_workspace_bytes", dims, (params or SurfaceGaussianParams()).to_c())
 
 
 class SurfaceCount:
@@ -135,23 +124,18 @@ class SurfaceCount:
 def count(depth, image=None, params=None):
     """Phase 1 (fgs_surface_count): depth (B,H,W) fp32 DEVICE, already curve-adjusted -> SurfaceCount.  No host read."""
     params = params or SurfaceGaussianParams()
-    if not depth.is_cuda:
-        raise B.FgsError("surface_gaussians needs CUDA/ROCm tensors; there is no CPU fallback")
+    hip.need_cuda(depth, "surface_gaussians")
     if depth.dim() != 3 or (image is not None and (image.dim() != 4 or image.shape[1] != 3 or image.shape[0] != depth.shape[0]
                                                    or image.shape[2:] != depth.shape[1:])):
         raise B.FgsError(f"surface_gaussians: depth must be (B,H,W) and image (B,3,H,W), got {tuple(depth.shape)} and "
                          f"{None if image is None else tuple(image.shape)}")
-    lib = B.load()
     depth_ = depth.detach().contiguous().float()
     color_ = None if image is None else image.detach().to(depth.device).contiguous().float()
     Bn, H, W = depth_.shape
     dims, cp = B.FgsSurfaceDims(Bn, H, W), params.to_c()
-    n = ctypes.c_size_t(0)
-    B.check(lib.fgs_surface_workspace_bytes(ctypes.byref(dims), ctypes.byref(cp), ctypes.byref(n)), "fgs_surface_workspace_bytes")
-    scratch = torch.empty(n.value, dtype=torch.uint8, device=depth.device)
+    scratch = torch.empty(B.sizes("fgs_surface_workspace_bytes", dims, cp), dtype=torch.uint8, device=depth.device)
     offsets = torch.empty(Bn + 1, dtype=torch.int32, device=depth.device)
-    B.check(lib.fgs_surface_count(ctypes.byref(dims), ctypes.byref(cp), _ptr(depth_), _ptr(scratch), _ptr(offsets), _stream()),
-            "fgs_surface_count")
+    hip.call(depth.device, "fgs_surface_count", dims, cp, depth_, scratch, offsets)
     return SurfaceCount(dims, cp, params, depth_, color_, scratch, offsets)
 
 
@@ -178,9 +162,8 @@ def emit(state, capacity=None, outputs=None):
 
 def emit_raw(state, outputs, capacity):
     """fgs_surface_emit as it is: no host-side comparison of `capacity` with the total (the kernel makes it: state.status())."""
-    B.check(B.load().fgs_surface_emit(ctypes.byref(state.dims), ctypes.byref(state.cparams), _ptr(state.depth), _ptr(state.color),
-                                      _ptr(state.scratch), _ptr(state.offsets), *[_ptr(outputs[k]) for k in KEYS],
-                                      ctypes.c_int64(int(capacity)), _stream()), "fgs_surface_emit")
+    hip.call(state.depth.device, "fgs_surface_emit", state.dims, state.cparams, state.depth, state.color, state.scratch, state.offsets,
+             *[outputs[k] for k in KEYS], int(capacity))
 
 
 def surface_gaussians(depth, image=None, params=None, *, depth_exponent=0.7):
@@ -225,10 +208,8 @@ def _check_mods(state, mods):
 
 def emit_guided_raw(state, mods, outputs, point_rows, capacity):
     """fgs_surface_emit_guided as it is (mods: (B,6,Hp,Wp) fp32 contiguous)."""
-    B.check(B.load().fgs_surface_emit_guided(ctypes.byref(state.dims), ctypes.byref(state.cparams), _ptr(state.depth), _ptr(state.color),
-                                             _ptr(state.scratch), _ptr(state.offsets), _ptr(mods), int(mods.shape[2]),
-                                             int(mods.shape[3]), *[_ptr(outputs[k]) for k in KEYS], _ptr(point_rows),
-                                             ctypes.c_int64(int(capacity)), _stream()), "fgs_surface_emit_guided")
+    hip.call(state.depth.device, "fgs_surface_emit_guided", state.dims, state.cparams, state.depth, state.color, state.scratch,
+             state.offsets, mods, int(mods.shape[2]), int(mods.shape[3]), *[outputs[k] for k in KEYS], point_rows, int(capacity))
 
 
 def _emit_guided_detached(state, mods, capacity=None):
@@ -252,11 +233,8 @@ def _emit_guided_detached(state, mods, capacity=None):
 def guided_backward(state, mods, point_rows, g_positions=None, g_scales=None, g_rotations=None, g_opacities=None):
     """fgs_surface_guided_backward: upstream gradients of the rows (None = zeros) -> dL/d mods (B,6,Hp,Wp), every element written."""
     mods = _check_mods(state, mods)
-    lib = B.load()
     Hp, Wp = int(mods.shape[2]), int(mods.shape[3])
-    n = ctypes.c_size_t(0)
-    B.check(lib.fgs_surface_guided_backward_bytes(ctypes.byref(state.dims), ctypes.byref(state.cparams), Hp, Wp, ctypes.byref(n)),
-            "fgs_surface_guided_backward_bytes")
+    nbytes = B.sizes("fgs_surface_guided_backward_bytes", state.dims, state.cparams, Hp, Wp)
     total = state.offsets_host[-1] if state.offsets_host is not None else None
     grads = []
     for name, g, width in (("positions", g_positions, 3), ("scales", g_scales, 3), ("rotations", g_rotations, 4), ("opacities", g_opacities, 0)):
@@ -267,10 +245,9 @@ def guided_backward(state, mods, point_rows, g_positions=None, g_scales=None, g_
                 raise B.FgsError(f"guided_backward: the gradient of {name} has shape {tuple(g.shape)} for a cloud of {total} rows")
         grads.append(g)
     g_mods = torch.empty(mods.shape, dtype=torch.float32, device=mods.device)
-    bwd_scratch = torch.empty(n.value, dtype=torch.uint8, device=mods.device) if n.value else None
-    B.check(lib.fgs_surface_guided_backward(ctypes.byref(state.dims), ctypes.byref(state.cparams), _ptr(state.depth), _ptr(state.scratch),
-                                            _ptr(state.offsets), _ptr(mods), Hp, Wp, _ptr(point_rows), *[_ptr(g) for g in grads],
-                                            _ptr(g_mods), _ptr(bwd_scratch), _stream()), "fgs_surface_guided_backward")
+    bwd_scratch = torch.empty(nbytes, dtype=torch.uint8, device=mods.device) if nbytes else None
+    hip.call(mods.device, "fgs_surface_guided_backward", state.dims, state.cparams, state.depth, state.scratch, state.offsets, mods,
+             Hp, Wp, point_rows, *grads, g_mods, bwd_scratch)
     return g_mods
 
 
