@@ -92,6 +92,9 @@ int fgs_surface_guided_backward(FgsSurfaceDims* dims, FgsSurfaceParams* params, 
 int fgs_match_workspace_bytes(FgsMatchDims* dims, size_t* saved_bytes scratch_bytes)
 int fgs_match_forward(FgsMatchDims* dims, ptr pred target pred_keep target_keep terms counts saved scratch, stream)
 int fgs_match_backward(FgsMatchDims* dims, ptr pred target saved g_total g_pred scratch, stream)
+int fgs_slat_workspace_bytes(int32_t batch voxels per_voxel, size_t* scratch_bytes)
+int fgs_slat_head_forward(int32_t batch voxels per_voxel, ptr raw coords gains keep gaussians counts scratch, stream)
+int fgs_slat_head_backward(int32_t batch voxels per_voxel, ptr raw coords gains g_gaussians g_raw g_gains scratch, stream)
 int fgs_gather_forward(int32_t batch n_in n_out phase_channels, ptr indices pos scale quat color opacity phase o_pos o_scale o_quat
                        o_color o_opacity o_phase, stream)
 int fgs_gather_backward(int32_t batch n_in n_out phase_channels, ptr indices g_o_pos g_o_scale g_o_quat g_o_color g_o_opacity

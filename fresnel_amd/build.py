@@ -78,6 +78,8 @@ SOURCES = {
     # as fgs_nca.hip: the match distance d2 = (dx dx + dy dy) + dz dz and the gradient rows are DEFINED with every operation
     # rounded on its own, divisions and the square root IEEE (include/fgs.h); tests/match_checker.py restates them bit for bit
     "fgs_match.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
+    # as the head: the backward recomputes the forward from raw, and its clamp gates must be the forward's
+    "fgs_slat.hip": ["-ffp-contract=off"],
 }
 LINK_LIBS = ["-lhipfft"]
 

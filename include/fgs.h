@@ -830,6 +830,58 @@ int fgs_match_backward(const FgsMatchDims *dims, const float *pred, const float 
                        float *g_pred, void *scratch, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Gaussian-parameter head of the reference's distillation decoders (scripts/models/direct_slat_decoder.py, "DSD": GaussianHead,
+ * 255-358, behind DirectSLatDecoder and MLPSLatDecoder).  raw (B, N, G, 14) fp32 contiguous: the head MLP's output, G Gaussians per
+ * voxel; coords (B, N, 4) int32, columns 1..3 = x, y, z; gains: two DEVICE floats, position_offset_scale and scale_factor, never
+ * read on the host (the calls can be captured in a graph).  gaussians (B, N G, 14), row n G + k = Gaussian k of voxel n; a row is
+ * position 0..2, scale 3..5, quaternion 6..9, colour 10..12, opacity 13 -- GaussianMatchingLoss's layout above.  Per Gaussian, with
+ * r = clamp(raw, -10, 10) (+-Inf clamp to +-10, a NaN stays) and centre = clamp(coordinate, 0, 63) / 64 * 2 - 1 whatever the
+ * decoder's max_resolution:
+ *     position    clamp(centre + tanh(r[0:3]) position_offset_scale, -1, 1)
+ *     scale       clamp(softplus(r[3:6]) |scale_factor|, 1e-4, 1)
+ *     quaternion  r[6:10] / max(|r[6:10]|, 1e-6),  |q| = sqrt(((q0 q0 + q1 q1) + q2 q2) + q3 q3)
+ *     colour, opacity   sigmoid(r[10:14])
+ * every operation rounded to fp32 on its own (no FMA).
+ *
+ * NaN rule (a STATED DIFFERENCE from torch).  The reference looks for NaN on the host (isnan(...).any()) and then replaces every NaN
+ * output by 0 (nan_to_num).  Here nothing is read on the host: an output element that would be NaN is written as 0, all four
+ * components of a quaternion when any of its raw components is NaN -- the same forward values.  Such an output is a constant of the
+ * backward: the raw elements behind it get g_raw = 0 and it adds nothing to the gain gradients, where torch's gradient is
+ * NaN-tainted.
+ *
+ * Gradient.  Every clamp passes the gradient on the closed interval: raw in [-10, 10], the unclamped position in [-1, 1], the
+ * unclamped scale in [1e-4, 1].  d|s|/ds = sign(s), 0 at 0.  Quaternion: through the norm where |q| >= 1e-6, else g / 1e-6 per
+ * component (the norm is behind the clamp; an all-zero quaternion gives output 0 and gradient g 1e6).
+ *     g_raw (B, N, G, 14): every element written.
+ *     g_gains, two floats, or NULL: dL/d position_offset_scale = sum g tanh(r) over the open position elements and
+ *       dL/d scale_factor = sign(scale_factor) sum g softplus(r) over the open scale elements; the products are exact in double,
+ *       added in a fixed order (fixed-shape block tree, one partial pair per block of 256 rows in `scratch`, folded by one block:
+ *       thread t adds partials t, t + 256, ..., then a fixed tree) and rounded to fp32 once.  No atomics: two calls agree to the bit.
+ * The backward recomputes the forward from raw: nothing is saved.
+ *
+ * Gated forward (keep (B, N) uint8, non-NULL; inference).  gaussians is packed: the Gaussians of image b's kept voxels (keep byte
+ * non-zero), in ascending voxel order, are rows [0, counts[b] G); every row behind them is zero.  counts (B,) int32 = kept VOXELS
+ * per image.  Two launches: a scan (one block per image) that writes counts and every voxel's destination to `scratch`, and the head
+ * writing each row at its place -- a dropped voxel's threads write the zero rows of the tail, so every row is written exactly once
+ * and no atomic is used.  A kept row is bit for bit the ungated call's row of that Gaussian.
+ *
+ * fgs_slat_head_forward: one launch ungated (keep, counts and scratch may be NULL), two gated.  fgs_slat_head_backward: two
+ * launches (one when g_gains is NULL).  scratch (fgs_slat_workspace_bytes; the gated forward and the backward) is written, never
+ * read before it is written.  Every output element is written; inputs are never modified.  Neither call synchronises the host or
+ * allocates.
+ * Shapes: batch = B, voxels = N, per_voxel = G go as three plain integers, as in fgs_gather_* and fgs_asm_propagate_*, not in a dims
+ * structure: the set of structures this header declares is closed (tests/test_call_layer.py holds it, and its ctypes side, at
+ * fifteen), and three integers need none.  B, N, G >= 1, G <= 64,
+ * B N G < 2^31; otherwise FGS_EINVAL (bad dims, null pointers) / FGS_EUNSUPPORTED before anything touches the device. */
+int fgs_slat_workspace_bytes(int32_t batch, int32_t voxels, int32_t per_voxel /* B, N, G; B*N*G < 2^31, G <= 64 */, size_t *scratch_bytes);
+int fgs_slat_head_forward(int32_t batch, int32_t voxels, int32_t per_voxel, const float *raw, const int32_t *coords,
+                          const float *gains /* 2, device */, const uint8_t *keep /* (B,N) or NULL */, float *gaussians,
+                          int32_t *counts /* (B,), with keep */, void *scratch, void *stream);
+int fgs_slat_head_backward(int32_t batch, int32_t voxels, int32_t per_voxel, const float *raw, const int32_t *coords,
+                           const float *gains, const float *g_gaussians, float *g_raw, float *g_gains /* 2, or NULL */, void *scratch,
+                           void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Importance-subsampling hand-off between decoder and rasterizer (--stochastic_k; reference
  * scripts/training/train_gaussian_decoder.py:1160-1187): the n_out Gaussians whose indices torch.multinomial
  * drew (DEVICE int64 (n_out,), unique, shared by the batch) are gathered out of every (B, n_in, .) tensor into
