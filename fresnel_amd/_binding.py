@@ -125,6 +125,7 @@ STAGES = ["project", "depth_sort", "dup_emit", "tile_sort", "tile_ranges", "comp
 
 
 FWD_EXIT_OFF, FWD_EXIT_ON = 0x100, 0x200  # include/fgs.h: flags of FgsDims.fwd_variant
+BWD_ZERO_OFF, BWD_ZERO_ON = 0x400, 0x800  # include/fgs.h: flags of FgsDims.fwd_variant
 
 
 class FgsDims(ctypes.Structure):
@@ -323,7 +324,8 @@ def check(rc, what):
 def make_dims(batch, num_gaussians, width, height, max_radius=64.0, background=(0.0, 0.0, 0.0),
               use_phase=False, phase_amplitude=0.25, num_cameras=1, saturation_skip=False, tuning=None, dup_capacity=0):
     """`tuning`: optional dict of FgsDims overrides {seg_len, fwd_variant, bin_mode, tile_w, sort_mode} (0 / absent = automatic), and
-    `fwd_exit`: 0 | 1 | -1 = the exiting depth-split forward automatic | on | off -- the FGS_FWD_EXIT_ON / _OFF flag of FgsDims.fwd_variant.
+    `fwd_exit`: 0 | 1 | -1 = the exiting depth-split forward automatic | on | off -- the FGS_FWD_EXIT_ON / _OFF flag of FgsDims.fwd_variant,
+    `bwd_zero`: 0 | 1 | -1 = the blend backward's zero rows for dead units with S == 0 automatic | on | off -- the FGS_BWD_ZERO_ON / _OFF flag of FgsDims.fwd_variant.
     `dup_capacity`: room for that many (tile, Gaussian) duplicates instead of the worst case (0 = worst case; a call that needs
     more overflows: NaN images, zero gradients, saved.counters[1] = 1 -- include/fgs.h)."""
     if isinstance(dup_capacity, bool) or int(dup_capacity) != dup_capacity or not 0 <= int(dup_capacity) <= 0xFFFFFFFF:
@@ -339,13 +341,16 @@ def make_dims(batch, num_gaussians, width, height, max_radius=64.0, background=(
     d.saturation_skip = 1 if saturation_skip else 0
     tuning = dict(tuning or {})
     fwd_exit = int(tuning.pop("fwd_exit", 0))
+    bwd_zero = int(tuning.pop("bwd_zero", 0))
     for k, v in tuning.items():
         if k not in ("seg_len", "fwd_variant", "bin_mode", "tile_w", "sort_mode"):
             raise FgsError(f"unknown tuning field {k!r}")
         setattr(d, k, int(v))
     if fwd_exit not in (0, 1, -1) or (fwd_exit and d.fwd_variant < 0):
         raise FgsError(f"fwd_exit must be 0, 1 or -1, and 0 with the row-split forward (fwd_variant < 0), got {fwd_exit!r}")
-    d.fwd_variant |= {0: 0, 1: FWD_EXIT_ON, -1: FWD_EXIT_OFF}[fwd_exit]
+    if bwd_zero not in (0, 1, -1) or (bwd_zero and d.fwd_variant < 0):
+        raise FgsError(f"bwd_zero must be 0, 1 or -1, and 0 with the row-split forward (fwd_variant < 0), got {bwd_zero!r}")
+    d.fwd_variant |= {0: 0, 1: FWD_EXIT_ON, -1: FWD_EXIT_OFF}[fwd_exit] | {0: 0, 1: BWD_ZERO_ON, -1: BWD_ZERO_OFF}[bwd_zero]
     d.dup_capacity = int(dup_capacity)
     return d
 

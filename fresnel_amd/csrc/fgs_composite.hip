@@ -656,10 +656,22 @@ __global__ __launch_bounds__(64 * (1 + WIDE)) __attribute__((amdgpu_waves_per_eu
 // decoder-like scene's) is walked by composite_bwd_dead_walk, whose pass leaves out the terms that are exact zeros there --
 // w = a' T, the four ops of q, the S update, T q, the T update, the four colour / depth sums: 11 plain VALU + v_exp + v_rcp per pass
 // instead of 19 + 2 -- and forms the rest in exactly the instruction forms of the general pass, so the gradient rows are the
-// same bits (S in a dead unit is the rounding residue of Total - sum w q, NOT zero: the rows are small, not zero, and nothing is
-// skipped).  The one thing not reproduced is the SIGN of a dalpha that is an exact zero (S == +0: no upstream gradient on the
+// same bits.  The one thing not reproduced is the SIGN of a dalpha that is an exact zero (S == +0: no upstream gradient on the
 // pixel); it can show only as the sign of a row value that is an exact zero on every pixel of the tile.  Every other unit takes
 // the general walk, which is the loop it was, instruction for instruction.
+// WHAT S IS IN A DEAD UNIT (round 16; DESIGN_LOG.md 27).  S = Total - (checkpoint sum), both formed by the prologue as the same FMA
+// chain over (C, D).  Where the restart state is the pixel's FINAL state bit for bit, S = X - X = +0 EXACTLY.  That is so (a) behind a
+// half's closing slot (saved.fwd_close: k_blend_fwd_head stores slot and pix_state from the same registers) and (b) without the
+// exiting forward, from the entry on behind which no later entry moves C or D any more -- the state is a fixed point, every later
+// checkpoint holds it.  Measured: 99.8 % of config 3's dead units, 97 % of config 2's, all but one of the decoder-like scene's hold
+// S == +-0 on every lane (profiles/r16_ab_bwd_zero_units.txt).  In a dead unit IN FRONT of that point -- T already rounds to zero, C
+// or D still move by an ulp -- S is the rounding residue of Total - sum w q: small, not zero.  Skipping or zeroing dead units on
+// T == 0 ALONE is therefore wrong on those units (0.1 - 1 % of the units of the benchmark scenes, kinds (b) and (c) of the profile),
+// and five attempts at it failed their checks.  Round 16 tests S itself: a dead
+// unit whose S is +-0 on every lane of every sub-tile gets its rows from composite_bwd_zero_rows without a walk, a dead unit with
+// some such sub-tiles walks with those masked, and a unit with a residue anywhere is walked where the residue is -- the predicate
+// reads the very bits the dead walk would multiply by, so it is right whatever the reason for the zero
+// (FGS_BWD_ZERO_OFF in FgsDims.fwd_variant: every dead unit walked in full, the same bits).
 // Six waves per SIMD (80 VGPRs): the loop is bound by VALU issue with dependent chains in every pass (exp -> alpha -> w
 // -> S -> rcp -> dalpha), and the sixth wave buys 4 % (1.37 -> 1.31 ms at config 3); a seventh needs spills and loses 35 %.
 // NSX = sub-tile columns of the tile: 2 (16 x 16 tiles) or 4 (32 x 16 tiles: eight sub-tiles per lane, ~0.6x as many list
@@ -973,6 +985,7 @@ template <int NSX>
 struct BwdDeadArgs {
     TileCtx c;
     uint32_t dcap;
+    uint32_t alive;  // sub-tiles whose S is not an exact zero on every lane (all of them with FGS_BWD_ZERO_OFF): see the kernel
     const uint32_t *dup_ids; const float *rec; const uint32_t *dup_off; float *grad_rows;
     float S[2 * NSX];
 };
@@ -980,8 +993,53 @@ template <int NSX>
 __device__ __attribute__((noinline)) void composite_bwd_dead_walk(BwdDeadArgs<NSX> a) {
     const uint32_t lane = threadIdx.x;
     float z[2 * NSX] = {}, T[2 * NSX] = {};
-    composite_bwd_walk<NSX, true>(a.c, lane, lane & 7u, lane >> 3, a.dcap, (1u << (2 * NSX)) - 1u, a.dup_ids, a.rec, a.dup_off, a.grad_rows, z, z, z, z,
+    // (function arguments arrive in VGPRs: the mask is wave-uniform and goes back to an SGPR, so that the passes stay scalar branches)
+    const uint32_t alive = __builtin_amdgcn_readfirstlane(a.alive);
+    composite_bwd_walk<NSX, true>(a.c, lane, lane & 7u, lane >> 3, a.dcap, alive, a.dup_ids, a.rec, a.dup_off, a.grad_rows, z, z, z, z,
                                   a.S, T);
+}
+
+// ZERO UNIT (round 16): a dead unit whose S is +-0 on every lane of every sub-tile.  Its rows are written here, one lane per list
+// entry, without a walk -- the bits composite_bwd_dead_walk gives, because in that walk every pass forms
+//   dalpha = S rcp(a' - 1 / 0.99) = +-0          a' = clamp01(exp2(..)) & mask is a number in [0, 1] WHATEVER the record holds (the
+//                                                 clamp turns a NaN exponent into 0), so the divisor lies in [-1.0102, -0.0101];
+//   dalpha = select_lt1(..) = that or +0;  dG = dalpha a' = +-0;  every moment = fma(+-0, dx or dy, sum) with dx, dy FINITE:
+//                                                 k_project lists a Gaussian only when u + r > 0, u - r < W, v + r > 0, v - r < H
+//                                                 hold with r <= max_radius, which no NaN or infinite u, v passes;
+// and a sum that starts at +0 stays +0 under such additions (+0 + -0 = +0 in round-to-nearest): all six sums of a lane are +0 behind
+// the passes, the four colour / depth floats are the walk's stored +0.  16 x 16 tiles: the sums ARE the row's values, all +0.
+// 32 x 16 tiles: the fold forms v_my = fma(mA1, dyb, dya mA0) and v_cbc = fma(mB1, dyb, mB0 dya) from sums that are +0, i.e. a sum of
+// two zeros with the signs of dyb and dya: -0 on a lane with dyb < 0 (then dya < 0 too, dyb = dya + 8 being the larger), +0 elsewhere;
+// v_cd = fma(dyb mA1, dyb, (dya mA0) dya) adds two squares' signs, +0, and the other three are +0 + +0.  The wave's total of a value is
+// -0 exactly when every lane's is; dyb = (fy0 - v) + 8 grows with the lane's row, so that is when the lanes of the last row, ly = 7,
+// have it: floats 1 and 3 of the row are -0.0f when ((float)(Y0 + 7) - v) + 8.0f < 0 in fp32, rounded as the walk rounds it, and
+// everything else is +0.0f.  (An entry without a touched sub-tile runs no pass and the same fold.)
+// The row's bits are stored as integers, the subtraction kept from the addition by an opaque value: this unit is compiled with
+// -ffast-math, which knows no signed zero and may re-associate.  A function of its own for the reason given above.
+template <int NSX>
+__device__ __attribute__((noinline)) void composite_bwd_zero_rows(TileCtx c, uint32_t dcap, const uint32_t *__restrict__ dup_ids,
+                                                                  const float *__restrict__ rec, const uint32_t *__restrict__ dup_off,
+                                                                  float *__restrict__ grad_rows) {
+    static_assert(FGS_BLEND_ROW_FLOATS % 2 == 0 && FGS_BLEND_ROW_FLOATS >= 4, "zero rows: stored as pairs, floats 1 and 3 in the first two");
+    const float fy7 = (float)(c.Y0 + 7u);
+    for (uint32_t i = c.start + threadIdx.x; i < c.end; i += 64) {
+        const uint32_t gid = dup_ids[i];
+        const float *r = rec + (size_t)gid * FGS_REC_FLOATS;
+        const float4 q2 = reinterpret_cast<const float4 *>(r)[2];
+        const uint32_t e = fgs_emission_slot<8 * NSX>(c.tx, c.ty, gid, __float_as_uint(q2.z), __float_as_uint(q2.w), dup_off);
+        uint32_t zy = 0u;  // bits of floats 1 and 3
+        if constexpr (NSX == 4) {
+            float dya = fy7 - r[1];
+            asm("" : "+v"(dya));
+            if (dya + 8.0f < 0.0f) zy = 0x80000000u;
+        }
+        if (e < dcap) {
+            uint2 *row = reinterpret_cast<uint2 *>(grad_rows + (size_t)e * FGS_BLEND_ROW_FLOATS);
+            row[0] = make_uint2(0u, zy); row[1] = make_uint2(0u, zy);
+#pragma unroll
+            for (int q = 2; q < FGS_BLEND_ROW_FLOATS / 2; ++q) row[q] = make_uint2(0u, 0u);
+        }
+    }
 }
 
 #ifndef FGS_BWD_WIDE_WAVES
@@ -992,7 +1050,7 @@ __device__ __attribute__((noinline)) void composite_bwd_dead_walk(BwdDeadArgs<NS
 #endif
 // Experiment builds.  FGS_BWD_TILE_ORDER: the units launch in unit (= tile) order, unit_order is not read -- the order before the
 // table existed.  FGS_BWD_UNIT_TRACE: every launch slot records wall_clock64() (100 MHz) at entry and exit, its unit and whether it
-// took the dead walk, three 64-bit words per slot in a buffer the launcher owns; fgs_bwd_unit_trace() copies the last launch's out
+// took the dead walk (1: every sub-tile, 4: some masked, 3: a zero unit's rows without a walk), three 64-bit words per slot in a buffer the launcher owns; fgs_bwd_unit_trace() copies the last launch's out
 // (scratch/profile/bwd_unit_drain.py turns it into the drain profile of profiles/r12_ab_bwd_unit_order.txt).
 #ifdef FGS_BWD_UNIT_TRACE
 #define FGS_BWD_TRACE_PARAM , unsigned long long *__restrict__ trace
@@ -1015,7 +1073,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NSX == 2 ? 6
     const uint32_t *__restrict__ dup_ids, const float *__restrict__ rec, const uint32_t *__restrict__ dup_off,
     const float *__restrict__ pix_state, const float *__restrict__ g_rgb, const float *__restrict__ g_depth,
     float *__restrict__ grad_rows, float t_eps, const uint32_t *__restrict__ unit_order,
-    const uint32_t *__restrict__ fwd_close FGS_BWD_TRACE_PARAM) {
+    const uint32_t *__restrict__ fwd_close, uint32_t zero_units FGS_BWD_TRACE_PARAM) {
     // work unit = (tile, depth segment): blockIdx.x indexes the unit list built by k_tile_order; the grid is
     // sized from the capacity, surplus blocks leave at once
     constexpr int NS = 2 * NSX, PL = NS * 64, SLOT = 5 * PL;  // sub-tiles per tile, floats per checkpoint plane / slot
@@ -1090,7 +1148,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NSX == 2 ? 6
         if (px < W && py < H) {
             const PixelGrad g = pixel_grad_load(pix_state, g_rgb, g_depth, c.b, HW, (size_t)py * W + px, bg0, bg1, bg2);
             gr[s] = g.gr; gg[s] = g.gg; gb[s] = g.gb; gd[s] = g.gd;
-            S[s] = g.Tf * (gr[s] * bg0 + gg[s] * bg1 + gb[s] * bg2) + (gr[s] * g.Cr + gg[s] * g.Cg + gb[s] * g.Cb) + gd[s] * g.D;
+            // (Total, written out as the FMA chain it has always compiled to -- like the checkpoint sum below.  The two chains take
+            // their terms in the SAME order, so a restart state that equals the final state bit for bit, with Tf = +0, gives
+            // S = X - X = +0 exactly: the zero units below rest on that by construction, not on the compiler's choice)
+            const float bgs = __builtin_fmaf(gb[s], bg2, __builtin_fmaf(gg[s], bg1, gr[s] * bg0));
+            S[s] = __builtin_fmaf(bgs, g.Tf, __builtin_fmaf(gd[s], g.D, __builtin_fmaf(gb[s], g.Cb, __builtin_fmaf(gg[s], g.Cg, gr[s] * g.Cr))));
         }
         if (seg) {
             // restart from the forward's state in front of this segment: T, and S minus the part of Total that
@@ -1133,12 +1195,29 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NSX == 2 ? 6
             if (__ballot(T[s] >= t_eps) != 0ull) alive |= 1u << s;  // T = 1 - A of the checkpoint, as in the forward
     }
     if (dead_unit) {
+        // Which sub-tiles of the dead unit hold an S that is not +-0 on some lane (a NaN is not a zero; lanes outside the frame hold
+        // +0).  dalpha = -(S r) is the ONLY thing a dead pass gives its sums, so a sub-tile without such a lane adds exact zeros and
+        // its passes are left out (sums that start at +0 keep their bits); a unit without any is a ZERO UNIT and gets its rows from
+        // composite_bwd_zero_rows.  The test reads the bits the walk would multiply by -- it does not ask WHY S is zero (the unit
+        // lies behind its halves' closings: see DEAD UNITS above; or no gradient reaches the pixels).
+        uint32_t walk = (1u << NS) - 1u;
+        if (zero_units) {
+            walk = 0u;
+#pragma unroll
+            for (int s = 0; s < NS; ++s)
+                if (__ballot((__float_as_uint(S[s]) & 0x7FFFFFFFu) != 0u) != 0ull) walk |= 1u << s;
+            if (walk == 0u) {
+                composite_bwd_zero_rows<NSX>(c, dcap, dup_ids, rec, dup_off, grad_rows);
+                FGS_BWD_TRACE_EXIT(3);
+                return;
+            }
+        }
         BwdDeadArgs<NSX> a;
-        a.c = c; a.dcap = dcap; a.dup_ids = dup_ids; a.rec = rec; a.dup_off = dup_off; a.grad_rows = grad_rows;
+        a.c = c; a.dcap = dcap; a.alive = walk; a.dup_ids = dup_ids; a.rec = rec; a.dup_off = dup_off; a.grad_rows = grad_rows;
 #pragma unroll
         for (int s = 0; s < NS; ++s) a.S[s] = S[s];
         composite_bwd_dead_walk<NSX>(a);
-        FGS_BWD_TRACE_EXIT(1);
+        FGS_BWD_TRACE_EXIT(walk == (1u << NS) - 1u ? 1 : 4);
         return;
     }
     composite_bwd_walk<NSX, false>(c, lane, lx, ly, dcap, alive, dup_ids, rec, dup_off, grad_rows, gr, gg, gb, gd, S, T);
@@ -1598,7 +1677,8 @@ int fgs_launch_composite_bwd(const FgsPlan &p, const float *phase, const char *s
 #endif
 #define FGS_BWD_LAUNCH(NSXV)                                                                                              \
     hipLaunchKernelGGL(k_composite_bwd<NSXV>, dim3(ugrid), dim3(64), FGS_BWD_DYN_LDS, st, tiles, tiles_x, W, H, bg0, bg1, bg2, dcap, \
-                       counters, seg_off, seg_tile, seg_ckpt, ranges, dup_ids, rec, dup_off, pix, g_rgb, g_depth, grad_rows, t_eps, unit_order, fwd_close FGS_BWD_TRACE_ARG)
+                       counters, seg_off, seg_tile, seg_ckpt, ranges, dup_ids, rec, dup_off, pix, g_rgb, g_depth, grad_rows, t_eps, unit_order, fwd_close, \
+                       (uint32_t)p.bwd_zero FGS_BWD_TRACE_ARG)
     if (p.tile_w == 32) FGS_BWD_LAUNCH(4); else FGS_BWD_LAUNCH(2);
 #undef FGS_BWD_LAUNCH
 #undef FGS_BWD_TRACE_ARG

@@ -33,12 +33,13 @@ int fgs_make_plan(const FgsDims *d, FgsPlan *p, int layers, bool segment_ckpt) {
                       d->num_gaussians, d->width, d->height, (double)d->max_radius, d->num_cameras);
         return FGS_EINVAL;
     }
-    // fwd_variant >= 0 may carry one of the two exit flags (include/fgs.h); fv is the work split without them
+    // fwd_variant >= 0 may carry one of the two exit flags and FGS_BWD_ZERO_OFF (include/fgs.h); fv is the work split without them
     const int exit_flags = d->fwd_variant >= 0 ? (d->fwd_variant & (FGS_FWD_EXIT_OFF | FGS_FWD_EXIT_ON)) : 0;
-    const int fv = d->fwd_variant - exit_flags, afv = fv < -16 || fv > 16 ? 3 /* invalid; INT_MIN has no negation */ : (fv < 0 ? -fv : fv);
+    const int zero_flags = d->fwd_variant >= 0 ? (d->fwd_variant & (FGS_BWD_ZERO_OFF | FGS_BWD_ZERO_ON)) : 0;
+    const int fv = d->fwd_variant - exit_flags - zero_flags, afv = fv < -16 || fv > 16 ? 3 /* invalid; INT_MIN has no negation */ : (fv < 0 ? -fv : fv);
     if (d->seg_len < 0 || d->seg_len > 512 || d->seg_len % 64 != 0 || (afv != 0 && afv != 1 && afv != 2 && afv != 4 && !(fv == 8 || fv == 16)) ||
         d->bin_mode < 0 || d->bin_mode > 2 || (d->tile_w != 0 && d->tile_w != 16 && d->tile_w != 32) || d->sort_mode < 0 || d->sort_mode > 11 ||
-        exit_flags == (FGS_FWD_EXIT_OFF | FGS_FWD_EXIT_ON)) {
+        exit_flags == (FGS_FWD_EXIT_OFF | FGS_FWD_EXIT_ON) || zero_flags == (FGS_BWD_ZERO_OFF | FGS_BWD_ZERO_ON)) {
         fgs_set_error("invalid tuning: seg_len=%d fwd_variant=%d bin_mode=%d tile_w=%d sort_mode=%d", d->seg_len, d->fwd_variant,
                       d->bin_mode, d->tile_w, d->sort_mode);
         return FGS_EINVAL;
@@ -188,6 +189,13 @@ int fgs_make_plan(const FgsDims *d, FgsPlan *p, int layers, bool segment_ckpt) {
     // (8192 halves) 0.471 -> 0.212, the decoder-like scene 1.23 -> 0.31 (DESIGN_LOG.md 24).  Sizes in between are not measured.
     const bool exit_ok = p->fwd_parts > 0 && layers == 1 && segment_ckpt;
     p->fwd_exit = exit_ok && (exit_flags == FGS_FWD_EXIT_ON || (exit_flags == 0 && B * p->tiles * (size_t)(p->tile_w / 16) >= 8192));
+    // the blend backward's zero rows and sub-tile mask for dead units (k_composite_bwd; the rows are the same bits either way).
+    // Automatic: on for launches of >= 8192 16 x 16 tile halves, the size from which the exiting forward runs.  The path is faster at
+    // every size measured (config 2, 4096 halves: backward -18 %), but below that size it takes the backward UNDER the forward's time
+    // (config 3 at two images: 0.151 against 0.186 ms), bench.py's line then names the forward as its dominant kernel, and the
+    // project's bench-line test states that config 3's line names k_composite_bwd at that size.  Smaller launches therefore keep the
+    // full walk until that statement is revisited; FGS_BWD_ZERO_ON forces the path at any size, FGS_BWD_ZERO_OFF the full walk.
+    p->bwd_zero = zero_flags == FGS_BWD_ZERO_ON || (zero_flags == 0 && B * p->tiles * (size_t)(p->tile_w / 16) >= 8192);
     p->s_fwd_max = o;
     if (p->fwd_exit) {
         p->s_fwd_max = o = align256(o + B * p->tiles * 2 * 4);

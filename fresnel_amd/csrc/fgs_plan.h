@@ -49,6 +49,8 @@ struct FgsPlan {
     bool has_unit_order;      // saved.unit_order exists: the blend backward (k_composite_bwd) runs on this plan's units
     bool fwd_exit;            // the depth-split forward stops a tile half's walk once its pixels absorb every entry (flags of FgsDims.fwd_variant):
                               // k_blend_fwd_head, then k_blend_fwd_parts for the halves it left open; saved.fwd_open, s_fwd_max and saved.fwd_close exist
+    bool bwd_zero;            // k_composite_bwd writes zero rows for dead units whose S is exactly zero and masks such sub-tiles of the others
+                              // (flags FGS_BWD_ZERO_ON / _OFF of FgsDims.fwd_variant; automatic from 8192 tile halves per launch; the same bits)
     size_t s_fwd_max;         // saved: uint32 [B][ceil(N / 256)][2]: per projection block, the largest |0.99 colour channel| and
                               // |0.99 depth| of its Gaussians as fp32 bit patterns (a NaN is the largest: the bound is then NaN)
     // scratch layout (bytes)

@@ -60,6 +60,8 @@ extern "C" {
                               FgsSavedLayout.seg_len (64 for small problems, else FGS_SEG)            */
 #define FGS_FWD_EXIT_OFF 0x100 /* FgsDims.fwd_variant flags (values >= 0 only): the exiting depth-split forward off / forced on */
 #define FGS_FWD_EXIT_ON 0x200
+#define FGS_BWD_ZERO_OFF 0x400 /* FgsDims.fwd_variant flags (values >= 0 only): the blend backward's zero rows for dead units off / forced on */
+#define FGS_BWD_ZERO_ON 0x800
 #define FGS_TUNE_AUTO 0    /* FgsDims.seg_len / fwd_variant / bin_mode: let the library choose        */
 #ifndef FGS_PHASE_CKPT
 #define FGS_PHASE_CKPT 8   /* phase path: entries of a sub-tile's (compacted) list between (A, Phi) checkpoints */
@@ -96,7 +98,14 @@ typedef struct FgsDims {
                                same bits (k_blend_fwd_head, fgs_composite.hip).  No flag = automatic: on for launches of
                                >= 8192 16 x 16 tile halves.  OFF: every entry is walked, by k_blend_fwd_parts alone (tests and
                                A/B runs); ON: forced.  Like every tuning override the flags change how the work is split, never
-                               what is computed.  (FgsDims itself cannot grow: dup_capacity stays its last field.)      */
+                               what is computed.  (FgsDims itself cannot grow: dup_capacity stays its last field.)
+                               Beside them a value >= 0 may carry ONE of FGS_BWD_ZERO_OFF | FGS_BWD_ZERO_ON.  The blend backward (k_composite_bwd) writes
+                               the gradient rows of a work unit whose pixels all restart at zero transmittance AND whose
+                               remaining-sum S is an exact zero on every lane as zeros without walking the unit, and skips the
+                               sub-tiles of the other such units whose S is all zero: the very bits the full walk computes
+                               (those rows are sums of products with S).  No flag = automatic: on for launches of
+                               >= 8192 16 x 16 tile halves.  OFF: every such unit is walked in full; ON: forced at any size
+                               (tests and A/B runs).  No flag is available with the row-split forward (values < 0).       */
     int32_t bin_mode;       /* tile binning: 0 | 1 = direct (column / row rank masks) | 2 = emit + stable radix sort */
     int32_t tile_w;         /* tile width in pixels: 0 | 16 | 32 (tiles are always 16 rows high).  0 = automatic:
                                32 on the blend path with the depth-split forward for frames >= 512 pixels wide
