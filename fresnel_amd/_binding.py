@@ -126,6 +126,7 @@ STAGES = ["project", "depth_sort", "dup_emit", "tile_sort", "tile_ranges", "comp
 
 FWD_EXIT_OFF, FWD_EXIT_ON = 0x100, 0x200  # include/fgs.h: flags of FgsDims.fwd_variant
 BWD_ZERO_OFF, BWD_ZERO_ON = 0x400, 0x800  # include/fgs.h: flags of FgsDims.fwd_variant
+BWD_TAIL_OFF, BWD_TAIL_ON = 0x2000, 0x4000  # include/fgs.h: flags of FgsDims.fwd_variant
 
 
 class FgsDims(ctypes.Structure):
@@ -149,7 +150,7 @@ class FgsSavedLayout(ctypes.Structure):
                 ("seg_off", ctypes.c_size_t), ("seg_tile", ctypes.c_size_t), ("seg_ckpt", ctypes.c_size_t),
                 ("seg_capacity", ctypes.c_size_t), ("seg_len", ctypes.c_int32), ("tile_w", ctypes.c_int32),
                 ("unit_order", ctypes.c_size_t), ("fwd_open", ctypes.c_size_t),
-                ("fwd_close", ctypes.c_size_t)]
+                ("fwd_close", ctypes.c_size_t), ("rank_of", ctypes.c_size_t)]
 
 
 class FgsAsmDims(ctypes.Structure):
@@ -326,6 +327,8 @@ def make_dims(batch, num_gaussians, width, height, max_radius=64.0, background=(
     """`tuning`: optional dict of FgsDims overrides {seg_len, fwd_variant, bin_mode, tile_w, sort_mode} (0 / absent = automatic), and
     `fwd_exit`: 0 | 1 | -1 = the exiting depth-split forward automatic | on | off -- the FGS_FWD_EXIT_ON / _OFF flag of FgsDims.fwd_variant,
     `bwd_zero`: 0 | 1 | -1 = the blend backward's zero rows for dead units with S == 0 automatic | on | off -- the FGS_BWD_ZERO_ON / _OFF flag of FgsDims.fwd_variant.
+    `bwd_tail`: 0 | 1 | -1 = the blend backward's one verdict per closed tile automatic (on where the plan has what it needs) | the same | off
+    -- the FGS_BWD_TAIL_ON / _OFF flag of FgsDims.fwd_variant.
     `dup_capacity`: room for that many (tile, Gaussian) duplicates instead of the worst case (0 = worst case; a call that needs
     more overflows: NaN images, zero gradients, saved.counters[1] = 1 -- include/fgs.h)."""
     if isinstance(dup_capacity, bool) or int(dup_capacity) != dup_capacity or not 0 <= int(dup_capacity) <= 0xFFFFFFFF:
@@ -342,6 +345,7 @@ def make_dims(batch, num_gaussians, width, height, max_radius=64.0, background=(
     tuning = dict(tuning or {})
     fwd_exit = int(tuning.pop("fwd_exit", 0))
     bwd_zero = int(tuning.pop("bwd_zero", 0))
+    bwd_tail = int(tuning.pop("bwd_tail", 0))
     for k, v in tuning.items():
         if k not in ("seg_len", "fwd_variant", "bin_mode", "tile_w", "sort_mode"):
             raise FgsError(f"unknown tuning field {k!r}")
@@ -350,7 +354,10 @@ def make_dims(batch, num_gaussians, width, height, max_radius=64.0, background=(
         raise FgsError(f"fwd_exit must be 0, 1 or -1, and 0 with the row-split forward (fwd_variant < 0), got {fwd_exit!r}")
     if bwd_zero not in (0, 1, -1) or (bwd_zero and d.fwd_variant < 0):
         raise FgsError(f"bwd_zero must be 0, 1 or -1, and 0 with the row-split forward (fwd_variant < 0), got {bwd_zero!r}")
-    d.fwd_variant |= {0: 0, 1: FWD_EXIT_ON, -1: FWD_EXIT_OFF}[fwd_exit] | {0: 0, 1: BWD_ZERO_ON, -1: BWD_ZERO_OFF}[bwd_zero]
+    if bwd_tail not in (0, 1, -1) or (bwd_tail and d.fwd_variant < 0):
+        raise FgsError(f"bwd_tail must be 0, 1 or -1, and 0 with the row-split forward (fwd_variant < 0), got {bwd_tail!r}")
+    d.fwd_variant |= ({0: 0, 1: FWD_EXIT_ON, -1: FWD_EXIT_OFF}[fwd_exit] | {0: 0, 1: BWD_ZERO_ON, -1: BWD_ZERO_OFF}[bwd_zero]
+                      | {0: 0, 1: BWD_TAIL_ON, -1: BWD_TAIL_OFF}[bwd_tail])
     d.dup_capacity = int(dup_capacity)
     return d
 

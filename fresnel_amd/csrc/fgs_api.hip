@@ -205,7 +205,8 @@ int fgs_backward(const FgsDims *dims, const float *cameras, const float *pos, co
     if ((rc = fgs_launch_project_bwd(p, cameras, pos, scale, quat, sv,
                                      reinterpret_cast<const float *>(sc + p.s_grows), g_pos, g_scale, g_quat,
                                      g_color, g_opacity, p.d.use_phase ? g_phase : nullptr, st,
-                                     reinterpret_cast<float *>(sc + p.s_rsum))))
+                                     reinterpret_cast<float *>(sc + p.s_rsum),
+                                     p.bwd_tail ? reinterpret_cast<const uint32_t *>(sc + p.s_zero_from) : nullptr)))
         return rc;
     fgs_stage_end(ST_PROJECT_BWD, st);
     if (p.capacity_hinted) {

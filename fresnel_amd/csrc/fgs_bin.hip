@@ -338,7 +338,8 @@ __global__ __launch_bounds__(256) void k_mask_emit(uint32_t B, uint32_t N, uint3
                                                    const uint32_t *__restrict__ bsum,
                                                    uint32_t *__restrict__ dup_ids, uint32_t *__restrict__ dup_off,
                                                    const uint32_t *__restrict__ counters, uint32_t nub,
-                                                   const uint32_t *__restrict__ seg_off, uint32_t *__restrict__ unit_order) {
+                                                   const uint32_t *__restrict__ seg_off, uint32_t *__restrict__ unit_order,
+    uint32_t *__restrict__ rank_of /* saved.rank_of, or null: the inverse of `order`, written beside dup_off */) {
     __shared__ uint32_t park[4][ME_CAP];
     if (blockIdx.x < nub) {  // the first nub blocks: launch order of the backward's units, one slice each (first, so that they run
         // beside the list blocks instead of behind them)
@@ -354,7 +355,10 @@ __global__ __launch_bounds__(256) void k_mask_emit(uint32_t B, uint32_t N, uint3
         uint32_t g = 0, c = 0, tot;
         if (r < N) { g = b * N + order[b * N + r]; c = tile_count[g]; }
         const uint32_t ex = block_exclusive_scan_256(c, &tot);
-        if (r < N) dup_off[g] = bsum[bid] + ex;
+        if (r < N) {
+            dup_off[g] = bsum[bid] + ex;
+            if (rank_of) rank_of[g] = r;
+        }
         return;
     }
     const uint32_t ntb = gridDim.x - nrb - nub;
@@ -487,7 +491,8 @@ __global__ __launch_bounds__(256) void k_mask_emit_group(uint32_t B, uint32_t N,
                                                          const uint32_t *__restrict__ bsum,
                                                          uint32_t *__restrict__ dup_ids, uint32_t *__restrict__ dup_off,
                                                          const uint32_t *__restrict__ counters, uint32_t nub,
-                                                         const uint32_t *__restrict__ seg_off, uint32_t *__restrict__ unit_order) {
+                                                         const uint32_t *__restrict__ seg_off, uint32_t *__restrict__ unit_order,
+    uint32_t *__restrict__ rank_of /* saved.rank_of, or null: the inverse of `order`, written beside dup_off */) {
     __shared__ uint32_t park[16][MG_CAP];
     if (blockIdx.x < nub) {  // the first nub blocks: launch order of the backward's units, one slice each (first, so that they run
         // beside the list blocks instead of behind them)
@@ -501,7 +506,10 @@ __global__ __launch_bounds__(256) void k_mask_emit_group(uint32_t B, uint32_t N,
         uint32_t g = 0, c = 0, tot;
         if (r < N) { g = b * N + order[b * N + r]; c = tile_count[g]; }
         const uint32_t ex = block_exclusive_scan_256(c, &tot);
-        if (r < N) dup_off[g] = bsum[bid] + ex;
+        if (r < N) {
+            dup_off[g] = bsum[bid] + ex;
+            if (rank_of) rank_of[g] = r;
+        }
         return;
     }
     const uint32_t ntb = gridDim.x - nrb - nub;
@@ -577,7 +585,8 @@ __global__ __launch_bounds__(256) void k_mask_emit_block(uint32_t B, uint32_t N,
                                                          const uint32_t *__restrict__ bsum,
                                                          uint32_t *__restrict__ dup_ids, uint32_t *__restrict__ dup_off,
                                                          const uint32_t *__restrict__ counters, uint32_t nub,
-                                                         const uint32_t *__restrict__ seg_off, uint32_t *__restrict__ unit_order) {
+                                                         const uint32_t *__restrict__ seg_off, uint32_t *__restrict__ unit_order,
+    uint32_t *__restrict__ rank_of /* saved.rank_of, or null: the inverse of `order`, written beside dup_off */) {
     constexpr uint32_t CAP = 4u * ME_CAP;
     __shared__ uint32_t park[CAP];
     __shared__ uint32_t wtot[4];
@@ -593,7 +602,10 @@ __global__ __launch_bounds__(256) void k_mask_emit_block(uint32_t B, uint32_t N,
         uint32_t g = 0, c = 0, tot;
         if (r < N) { g = b * N + order[b * N + r]; c = tile_count[g]; }
         const uint32_t ex = block_exclusive_scan_256(c, &tot);
-        if (r < N) dup_off[g] = bsum[bid] + ex;
+        if (r < N) {
+            dup_off[g] = bsum[bid] + ex;
+            if (rank_of) rank_of[g] = r;
+        }
         return;
     }
     const uint32_t ntb = gridDim.x - nrb - nub;  // = number of lists
@@ -1132,6 +1144,7 @@ int fgs_launch_binning(const FgsPlan &p, char *saved, char *scratch, hipStream_t
         uint32_t *lens = vals0;
         uint32_t *plane_start = reinterpret_cast<uint32_t *>(scratch + p.s_plane);  // [B][layers + 1]
         uint32_t *dup_off = reinterpret_cast<uint32_t *>(saved + p.L.dup_off);
+        uint32_t *rank_of = p.bwd_tail ? reinterpret_cast<uint32_t *>(saved + p.L.rank_of) : nullptr;
         const uint32_t ntb = (ntiles_all + 3) / 4;  // four tiles (waves) per block
         // rank words a list spans: all of them, or its plane's share
         const uint32_t wspan = layers > 1 ? (w64p + layers - 1) / layers + 2 : w64p;
@@ -1162,10 +1175,10 @@ int fgs_launch_binning(const FgsPlan &p, char *saved, char *scratch, hipStream_t
         const uint32_t nub = unit_order ? 8u : 0u;  // blocks in front of the others that order the backward's units (unit_order_slice)
 #define FGS_MASK_EMIT(W) hipLaunchKernelGGL(k_mask_emit<W>, dim3(nrb + ntb + nub), dim3(256), 0, st, B, N, layers, plane_start, \
                                             (uint32_t)p.tiles, tiles_x, lines, w64p, nrb, bpi, dcap, masks, order,         \
-                                            tile_count, ranges, bsum, dup_ids, dup_off, counters, nub, seg_off, unit_order)
+                                            tile_count, ranges, bsum, dup_ids, dup_off, counters, nub, seg_off, unit_order, rank_of)
 #define FGS_MASK_EMIT_BLOCK(W) hipLaunchKernelGGL(k_mask_emit_block<W>, dim3(nrb + ntiles_all + nub), dim3(256), 0, st, B, N, layers, \
                                                   plane_start, (uint32_t)p.tiles, tiles_x, lines, w64p, nrb, bpi, dcap, masks, \
-                                                  order, tile_count, ranges, bsum, dup_ids, dup_off, counters, nub, seg_off, unit_order)
+                                                  order, tile_count, ranges, bsum, dup_ids, dup_off, counters, nub, seg_off, unit_order, rank_of)
         // few lists (<= 8192: the blend path's frames; the ASM renderer's (image, plane, tile) lists are many and short)
         // over more than 128 rank words (N > 8192 per image): a block per list, a quarter of the rank words per wave.
         // Measured: config 3 (4096 lists of ~1000 entries) 40 -> 28 us, decoder-like (~2500 entries) 119 -> 38 us;
@@ -1173,7 +1186,7 @@ int fgs_launch_binning(const FgsPlan &p, char *saved, char *scratch, hipStream_t
         if (grouped) {
             hipLaunchKernelGGL(k_mask_emit_group, dim3(nrb + ngb + nub), dim3(256), 0, st, B, N, layers, plane_start, (uint32_t)p.tiles,
                                tiles_x, lines, w64p, nrb, bpi, dcap, masks, order, tile_count, ranges, bsum, dup_ids, dup_off, counters,
-                               nub, seg_off, unit_order);
+                               nub, seg_off, unit_order, rank_of);
         } else if (ntiles_all <= FGS_EMIT_BLOCK_MAX_LISTS && wpl >= 4) {
             if (wpl == 4) FGS_MASK_EMIT_BLOCK(1); else FGS_MASK_EMIT_BLOCK(2);
         } else if (wpl == 1) FGS_MASK_EMIT(1); else if (wpl == 2) FGS_MASK_EMIT(2); else if (wpl == 4) FGS_MASK_EMIT(4); else FGS_MASK_EMIT(8);

@@ -672,6 +672,11 @@ __global__ __launch_bounds__(64 * (1 + WIDE)) __attribute__((amdgpu_waves_per_eu
 // some such sub-tiles walks with those masked, and a unit with a residue anywhere is walked where the residue is -- the predicate
 // reads the very bits the dead walk would multiply by, so it is right whatever the reason for the zero
 // (FGS_BWD_ZERO_OFF in FgsDims.fwd_variant: every dead unit walked in full, the same bits).
+// ONE VERDICT PER CLOSED TILE (round 17; DESIGN_LOG.md 28).  92 % of config 3's zero units are TAIL units -- behind the closing slot of
+// every half of their tile -- and all tail units of a tile run the same prologue on the same addresses.  k_bwd_tail_verdict runs it
+// once per tile in front of this kernel; a tail unit of a tile whose verdict is "zero units" leaves before its prologue and writes
+// NO rows, and k_row_sum does not read them (see both kernels).  Zero units in front of a closing, and every unit where the plan
+// has no tail verdict (FgsPlan.bwd_tail), still decide for themselves and store their rows with composite_bwd_zero_rows.
 // Six waves per SIMD (80 VGPRs): the loop is bound by VALU issue with dependent chains in every pass (exp -> alpha -> w
 // -> S -> rcp -> dalpha), and the sixth wave buys 4 % (1.37 -> 1.31 ms at config 3); a seventh needs spills and loses 35 %.
 // NSX = sub-tile columns of the tile: 2 (16 x 16 tiles) or 4 (32 x 16 tiles: eight sub-tiles per lane, ~0.6x as many list
@@ -1000,7 +1005,9 @@ __device__ __attribute__((noinline)) void composite_bwd_dead_walk(BwdDeadArgs<NS
 }
 
 // ZERO UNIT (round 16): a dead unit whose S is +-0 on every lane of every sub-tile.  Its rows are written here, one lane per list
-// entry, without a walk -- the bits composite_bwd_dead_walk gives, because in that walk every pass forms
+// entry, without a walk -- unless the unit is a TAIL unit of a tile that k_bwd_tail_verdict gave a rank (round 17): such a unit never
+// gets here, its rows stay unwritten and k_row_sum leaves them out, which is the same sum because the rows written here are +-0 and
+// k_row_sum's accumulators are never -0.  The rows are the bits composite_bwd_dead_walk gives, because in that walk every pass forms
 //   dalpha = S rcp(a' - 1 / 0.99) = +-0          a' = clamp01(exp2(..)) & mask is a number in [0, 1] WHATEVER the record holds (the
 //                                                 clamp turns a NaN exponent into 0), so the divisor lies in [-1.0102, -0.0101];
 //   dalpha = select_lt1(..) = that or +0;  dG = dalpha a' = +-0;  every moment = fma(+-0, dx or dy, sum) with dx, dy FINITE:
@@ -1042,103 +1049,21 @@ __device__ __attribute__((noinline)) void composite_bwd_zero_rows(TileCtx c, uin
     }
 }
 
-#ifndef FGS_BWD_WIDE_WAVES
-#define FGS_BWD_WIDE_WAVES 5  /* waves per SIMD of k_composite_bwd<4>; re-measured in round 3 under the clause scheduler: see DESIGN_LOG.md 10.3 */
-#endif
-#ifndef FGS_BWD_DYN_LDS
-#define FGS_BWD_DYN_LDS 0  /* experiment builds: unused dynamic LDS per block, to cap the waves per SIMD below what the registers allow */
-#endif
-// Experiment builds.  FGS_BWD_TILE_ORDER: the units launch in unit (= tile) order, unit_order is not read -- the order before the
-// table existed.  FGS_BWD_UNIT_TRACE: every launch slot records wall_clock64() (100 MHz) at entry and exit, its unit and whether it
-// took the dead walk (1: every sub-tile, 4: some masked, 3: a zero unit's rows without a walk), three 64-bit words per slot in a buffer the launcher owns; fgs_bwd_unit_trace() copies the last launch's out
-// (scratch/profile/bwd_unit_drain.py turns it into the drain profile of profiles/r12_ab_bwd_unit_order.txt).
-#ifdef FGS_BWD_UNIT_TRACE
-#define FGS_BWD_TRACE_PARAM , unsigned long long *__restrict__ trace
-#define FGS_BWD_TRACE_EXIT(dead)                                                                                        \
-    do {                                                                                                                \
-        if (threadIdx.x == 0) {                                                                                         \
-            trace[3 * (size_t)blockIdx.x + 1] = wall_clock64();                                                         \
-            trace[3 * (size_t)blockIdx.x + 2] = (unsigned long long)unit | ((unsigned long long)(dead) << 32) | (1ull << 63); \
-        }                                                                                                               \
-    } while (0)
-#else
-#define FGS_BWD_TRACE_PARAM
-#define FGS_BWD_TRACE_EXIT(dead) do { } while (0)
-#endif
+// The per-pixel prologue of a backward unit (tile c, segment `seg`, unit = its checkpoint slot): upstream gradients, S and T of this
+// lane's pixel in each of the tile's sub-tiles; returns whether an in-frame pixel of this lane restarts with T != 0.  ONE function
+// for k_composite_bwd and k_bwd_tail_verdict: the verdict kernel's S and T are a unit's own, bit for bit, because they are this code.
+// `kclose`: the closing slots of the tile's 16 x 16 halves (0xFFFFFFFF: none); `rebase_seg`: first segment of this segment's list
+// part if its checkpoint is part-local, else seg.
 template <int NSX>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NSX == 2 ? 6 : FGS_BWD_WIDE_WAVES, NSX == 2 ? 6 : FGS_BWD_WIDE_WAVES))) void k_composite_bwd(
-    uint32_t tiles, uint32_t tiles_x, uint32_t W, uint32_t H, float bg0, float bg1, float bg2, uint32_t dcap,
-    const uint32_t *__restrict__ counters, const uint32_t *__restrict__ seg_off,
-    const uint32_t *__restrict__ seg_tile, const float *__restrict__ seg_ckpt, const uint32_t *__restrict__ ranges,
-    const uint32_t *__restrict__ dup_ids, const float *__restrict__ rec, const uint32_t *__restrict__ dup_off,
-    const float *__restrict__ pix_state, const float *__restrict__ g_rgb, const float *__restrict__ g_depth,
-    float *__restrict__ grad_rows, float t_eps, const uint32_t *__restrict__ unit_order,
-    const uint32_t *__restrict__ fwd_close, uint32_t zero_units FGS_BWD_TRACE_PARAM) {
-    // work unit = (tile, depth segment): blockIdx.x indexes the unit list built by k_tile_order; the grid is
-    // sized from the capacity, surplus blocks leave at once
+__device__ __forceinline__ bool composite_bwd_prologue(const TileCtx &c, uint32_t unit, uint32_t seg, uint32_t rebase_seg,
+                                                       const uint32_t (&kclose)[NSX / 2], uint32_t lane, uint32_t lx, uint32_t ly,
+                                                       uint32_t W, uint32_t H, float bg0, float bg1, float bg2,
+                                                       const float *__restrict__ seg_ckpt, const float *__restrict__ pix_state,
+                                                       const float *__restrict__ g_rgb, const float *__restrict__ g_depth,
+                                                       float (&gr)[2 * NSX], float (&gg)[2 * NSX], float (&gb)[2 * NSX],
+                                                       float (&gd)[2 * NSX], float (&S)[2 * NSX], float (&T)[2 * NSX]) {
     constexpr int NS = 2 * NSX, PL = NS * 64, SLOT = 5 * PL;  // sub-tiles per tile, floats per checkpoint plane / slot
-    const uint32_t num_units = counters[2];
-    if (blockIdx.x >= num_units) return;
-#ifdef FGS_BWD_UNIT_TRACE
-    if (threadIdx.x == 0) trace[3 * (size_t)blockIdx.x] = wall_clock64();
-#endif
-    // units are listed tile by tile: an XCD gets a contiguous run of them, so neighbouring tiles -- which share
-    // Gaussians, and write adjacent 40-byte gradient rows -- meet in one L2.  Inside its run an XCD takes the full units first and
-    // the partial ones last, longest first (unit_order, fgs_bin.hip k_unit_order): the short units fill the launch's drain
-#ifdef FGS_BWD_TILE_ORDER
-    const uint32_t unit = fgs_xcd_remap(blockIdx.x, num_units);
-#else
-    const uint32_t unit = unit_order[fgs_xcd_remap(blockIdx.x, num_units)];
-#endif
-    // the split the forward ran with, as the forward recorded it (k_tile_order): segment length, and the number of
-    // list parts of the depth-split forward (> 1: checkpoints inside a later part are part-local)
-    const uint32_t seg_len = counters[4];
-    const uint32_t fwd_parts = (int32_t)counters[5] > 1 ? counters[5] : 0u;
-    const uint32_t unit_tile = seg_tile[unit];
-    // the closing slots of the tile's 16 x 16 halves (saved.fwd_close; null without the exiting forward: no half has one).  They
-    // depend on the tile alone and are loaded here, beside seg_off and the ranges, not behind them
-    uint32_t kclose[NSX / 2];
-#pragma unroll
-    for (int h = 0; h < NSX / 2; ++h) kclose[h] = 0xFFFFFFFFu;
-    if (fwd_close) {
-#pragma unroll
-        for (int h = 0; h < NSX / 2; ++h) kclose[h] = fwd_close[2u * unit_tile + h];
-    }
-    const uint32_t seg = unit - seg_off[unit_tile];
-    TileCtx c = tile_ctx_of(unit_tile, tiles, tiles_x, ranges, 8u * NSX);
-    uint32_t rebase_seg = seg;  // first segment of this segment's list part if its checkpoint is part-local
-    if (fwd_parts > 1) {
-        const uint32_t nseg = (c.end - c.start + seg_len - 1) / seg_len;
-        const uint32_t spp = (nseg + fwd_parts - 1) / fwd_parts, first = seg / spp * spp;
-        if (first != 0) rebase_seg = first;
-    }
-    c.start += seg * seg_len;
-    c.end = min(c.end, c.start + seg_len);
-    const uint32_t lane = threadIdx.x;
-    const uint32_t lx = lane & 7u, ly = lane >> 3;
     const size_t HW = (size_t)W * H;
-    if (t_eps > 0.0f) {
-        // FgsDims.saturation_skip: the forward stopped walking this tile's list after `live` segments (count
-        // parked in the checkpoint slot of segment 0); the entries of a dead segment get all-zero gradient rows
-        const uint32_t live = reinterpret_cast<const uint32_t *>(seg_ckpt + (size_t)seg_off[unit_tile] * SLOT)[0];
-        if (seg >= live) {
-            for (uint32_t i = c.start + lane; i < c.end; i += 64) {
-                const uint32_t gid = dup_ids[i];
-                const float4 q2 = reinterpret_cast<const float4 *>(rec + (size_t)gid * FGS_REC_FLOATS)[2];
-                const uint32_t e = fgs_emission_slot<8 * NSX>(c.tx, c.ty, gid, __float_as_uint(q2.z), __float_as_uint(q2.w), dup_off);
-                if (e < dcap) {
-                    float2 *row = reinterpret_cast<float2 *>(grad_rows + (size_t)e * FGS_BLEND_ROW_FLOATS);
-#pragma unroll
-                    for (int q = 0; q < FGS_BLEND_ROW_FLOATS / 2; ++q) row[q] = make_float2(0.0f, 0.0f);
-                }
-            }
-            FGS_BWD_TRACE_EXIT(2);
-            return;
-        }
-    }
-    // T: running transmittance (w = alpha T, T -= w: one instruction less per pixel than T = 1 - A, A += w)
-    // S: T_fin (gI.bg) + sum over not-yet-visited w q
-    float gr[NS], gg[NS], gb[NS], gd[NS], S[NS], T[NS];
     bool live_px = false;  // an in-frame pixel of this lane restarts with T != 0
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
@@ -1182,6 +1107,188 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NSX == 2 ? 6
             if (px < W && py < H && T[s] != 0.0f) live_px = true;  // (a NaN checkpoint is live: the general walk carries it)
         }
     }
+    return live_px;
+}
+
+// The zero-unit test of a DEAD unit (k_composite_bwd, at its call): the sub-tiles that hold an S that is not +-0 on some lane, by the
+// integer test (a NaN is not a zero; lanes outside the frame hold +0).  0: a ZERO UNIT.
+template <int NSX>
+__device__ __forceinline__ uint32_t composite_bwd_nonzero_subtiles(const float (&S)[2 * NSX]) {
+    uint32_t walk = 0u;
+#pragma unroll
+    for (int s = 0; s < 2 * NSX; ++s)
+        if (__ballot((__float_as_uint(S[s]) & 0x7FFFFFFFu) != 0u) != 0ull) walk |= 1u << s;
+    return walk;
+}
+
+// ONE VERDICT PER CLOSED TILE (round 17; FgsPlan.bwd_tail).  A TAIL unit of a tile lies behind the closing slot of EVERY 16 x 16 half
+// (seg >= kclose[h] for all h, every kclose[h] a slot): its prologue restarts every sub-tile from the halves' closing slots, whatever
+// its own segment -- all tail units of a tile read the same addresses, form the same S and T and reach the same zero-unit verdict
+// (measured: 92 % of config 3's zero units are tail units, 26 600 prologues per launch where one per tile says it all;
+// profiles/r17_ab_bwd_tail_verdict.txt).  This kernel, one wave per tile in front of k_composite_bwd, runs that prologue ONCE, for the
+// tile's first tail unit, seg = max_h kclose[h], and applies the tests a unit applies: dead (every in-frame pixel restarts at
+// T == +0) and S +-0 on every lane.  zero_from[tile] = the DEPTH RANK (saved.rank_of) of that unit's first list entry if they hold,
+// else 0xFFFFFFFF -- also for a tile without a tail: an open half, a closing in the last segment (fwd_close says 0xFFFFFFFF), an empty
+// list (every list after a capacity overflow).  Every word is written by every launch; k_bwd_tail_min then leaves each image's smallest.  A tail unit of a tile with a rank returns
+// from k_composite_bwd at once and writes no rows; its entries are exactly the tile's entries of rank >= zero_from[tile] (the lists of the
+// direct binning are in ascending rank), and k_row_sum leaves those rows out (fgs_project.hip).
+template <int NSX>
+__global__ __launch_bounds__(64) void k_bwd_tail_verdict(
+    uint32_t ntiles, uint32_t tiles, uint32_t tiles_x, uint32_t W, uint32_t H, float bg0, float bg1, float bg2, uint32_t dcap,
+    const uint32_t *__restrict__ counters, const uint32_t *__restrict__ seg_off, const float *__restrict__ seg_ckpt,
+    const uint32_t *__restrict__ ranges, const uint32_t *__restrict__ dup_ids, const float *__restrict__ pix_state,
+    const float *__restrict__ g_rgb, const float *__restrict__ g_depth, const uint32_t *__restrict__ fwd_close,
+    const uint32_t *__restrict__ rank_of, uint32_t *__restrict__ zero_from) {
+    constexpr int NS = 2 * NSX;
+    const uint32_t tile = blockIdx.x;
+    if (tile >= ntiles) return;
+    const uint32_t lane = threadIdx.x;
+    uint32_t verdict = 0xFFFFFFFFu;
+    const TileCtx c = tile_ctx_of(tile, tiles, tiles_x, ranges, 8u * NSX);
+    const uint32_t seg_len = counters[4];
+    uint32_t kclose[NSX / 2], seg = 0u;
+#pragma unroll
+    for (int h = 0; h < NSX / 2; ++h) { kclose[h] = fwd_close[2u * tile + h]; seg = max(seg, kclose[h]); }  // an open half: 0xFFFFFFFF
+    // (seg >= 1 for a closed half; the bounds below hold by the forward's construction and are tested all the same: the first entry
+    // of the unit must be an entry of the list, and of the buffer)
+    const uint32_t len = c.end - c.start;
+    const bool tail = c.end > c.start && seg_len != 0u && seg != 0xFFFFFFFFu && seg != 0u && (unsigned long long)seg * seg_len < len &&
+                      (unsigned long long)c.start + (unsigned long long)seg * seg_len < dcap;
+    if (tail) {
+        float gr[NS], gg[NS], gb[NS], gd[NS], S[NS], T[NS];
+        const bool live_px = composite_bwd_prologue<NSX>(c, seg_off[tile] + seg, seg, seg, kclose, lane, lane & 7u, lane >> 3, W, H, bg0, bg1,
+                                                         bg2, seg_ckpt, pix_state, g_rgb, g_depth, gr, gg, gb, gd, S, T);
+        if (__ballot(live_px) == 0ull && composite_bwd_nonzero_subtiles<NSX>(S) == 0u) verdict = rank_of[dup_ids[c.start + seg * seg_len]];
+    }
+    if (lane == 0) zero_from[tile] = verdict;
+}
+
+// The smallest word of each image's tiles, behind the tiles' words: zero_from[images * tiles + b].  One block per image, behind
+// k_bwd_tail_verdict.  k_row_sum looks nothing up for a Gaussian of a lower rank (every Gaussian where nothing closes).  5.4 us per
+// launch at config 3 (8 blocks of 4096 words), beside 25.7 us of the verdict kernel (profiles/r17_profile_bwd_tail_verdict.txt).
+__global__ __launch_bounds__(256) void k_bwd_tail_min(uint32_t tiles, uint32_t *__restrict__ zero_from) {
+    __shared__ uint32_t part[4];
+    const uint32_t *z = zero_from + (size_t)blockIdx.x * tiles;
+    uint32_t m = 0xFFFFFFFFu;
+    for (uint32_t t = threadIdx.x; t < tiles; t += 256u) m = min(m, z[t]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = min(m, (uint32_t)__shfl_xor(m, o, 64));
+    if ((threadIdx.x & 63u) == 0u) part[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) zero_from[(size_t)gridDim.x * tiles + blockIdx.x] = min(min(part[0], part[1]), min(part[2], part[3]));
+}
+
+#ifndef FGS_BWD_WIDE_WAVES
+#define FGS_BWD_WIDE_WAVES 5  /* waves per SIMD of k_composite_bwd<4>; re-measured in round 3 under the clause scheduler: see DESIGN_LOG.md 10.3 */
+#endif
+#ifndef FGS_BWD_DYN_LDS
+#define FGS_BWD_DYN_LDS 0  /* experiment builds: unused dynamic LDS per block, to cap the waves per SIMD below what the registers allow */
+#endif
+// Experiment builds.  FGS_BWD_TILE_ORDER: the units launch in unit (= tile) order, unit_order is not read -- the order before the
+// table existed.  FGS_BWD_UNIT_TRACE: every launch slot records wall_clock64() (100 MHz) at entry and exit, its unit and whether it
+// took the dead walk (1: every sub-tile, 4: some masked, 3: a zero unit's rows without a walk, 5: a tail unit that left on its tile's verdict), three 64-bit words per slot in a buffer the launcher owns; fgs_bwd_unit_trace() copies the last launch's out
+// (scratch/profile/bwd_unit_drain.py turns it into the drain profile of profiles/r12_ab_bwd_unit_order.txt).
+#ifdef FGS_BWD_UNIT_TRACE
+#define FGS_BWD_TRACE_PARAM , unsigned long long *__restrict__ trace
+#define FGS_BWD_TRACE_EXIT(dead)                                                                                        \
+    do {                                                                                                                \
+        if (threadIdx.x == 0) {                                                                                         \
+            trace[3 * (size_t)blockIdx.x + 1] = wall_clock64();                                                         \
+            trace[3 * (size_t)blockIdx.x + 2] = (unsigned long long)unit | ((unsigned long long)(dead) << 32) | (1ull << 63); \
+        }                                                                                                               \
+    } while (0)
+#else
+#define FGS_BWD_TRACE_PARAM
+#define FGS_BWD_TRACE_EXIT(dead) do { } while (0)
+#endif
+template <int NSX>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NSX == 2 ? 6 : FGS_BWD_WIDE_WAVES, NSX == 2 ? 6 : FGS_BWD_WIDE_WAVES))) void k_composite_bwd(
+    uint32_t tiles, uint32_t tiles_x, uint32_t W, uint32_t H, float bg0, float bg1, float bg2, uint32_t dcap,
+    const uint32_t *__restrict__ counters, const uint32_t *__restrict__ seg_off,
+    const uint32_t *__restrict__ seg_tile, const float *__restrict__ seg_ckpt, const uint32_t *__restrict__ ranges,
+    const uint32_t *__restrict__ dup_ids, const float *__restrict__ rec, const uint32_t *__restrict__ dup_off,
+    const float *__restrict__ pix_state, const float *__restrict__ g_rgb, const float *__restrict__ g_depth,
+    float *__restrict__ grad_rows, float t_eps, const uint32_t *__restrict__ unit_order,
+    const uint32_t *__restrict__ fwd_close, uint32_t zero_units, const uint32_t *__restrict__ zero_from FGS_BWD_TRACE_PARAM) {
+    // work unit = (tile, depth segment): blockIdx.x indexes the unit list built by k_tile_order; the grid is
+    // sized from the capacity, surplus blocks leave at once
+    constexpr int NS = 2 * NSX, PL = NS * 64, SLOT = 5 * PL;  // sub-tiles per tile, floats per checkpoint plane / slot
+    const uint32_t num_units = counters[2];
+    if (blockIdx.x >= num_units) return;
+#ifdef FGS_BWD_UNIT_TRACE
+    if (threadIdx.x == 0) trace[3 * (size_t)blockIdx.x] = wall_clock64();
+#endif
+    // units are listed tile by tile: an XCD gets a contiguous run of them, so neighbouring tiles -- which share
+    // Gaussians, and write adjacent 40-byte gradient rows -- meet in one L2.  Inside its run an XCD takes the full units first and
+    // the partial ones last, longest first (unit_order, fgs_bin.hip k_unit_order): the short units fill the launch's drain
+#ifdef FGS_BWD_TILE_ORDER
+    const uint32_t unit = fgs_xcd_remap(blockIdx.x, num_units);
+#else
+    const uint32_t unit = unit_order[fgs_xcd_remap(blockIdx.x, num_units)];
+#endif
+    // the split the forward ran with, as the forward recorded it (k_tile_order): segment length, and the number of
+    // list parts of the depth-split forward (> 1: checkpoints inside a later part are part-local)
+    const uint32_t seg_len = counters[4];
+    const uint32_t fwd_parts = (int32_t)counters[5] > 1 ? counters[5] : 0u;
+    const uint32_t unit_tile = seg_tile[unit];
+    // the closing slots of the tile's 16 x 16 halves (saved.fwd_close; null without the exiting forward: no half has one).  They
+    // depend on the tile alone and are loaded here, beside seg_off and the ranges, not behind them
+    uint32_t kclose[NSX / 2];
+#pragma unroll
+    for (int h = 0; h < NSX / 2; ++h) kclose[h] = 0xFFFFFFFFu;
+    if (fwd_close) {
+#pragma unroll
+        for (int h = 0; h < NSX / 2; ++h) kclose[h] = fwd_close[2u * unit_tile + h];
+    }
+    const uint32_t seg = unit - seg_off[unit_tile];
+    // TAIL UNIT (FgsPlan.bwd_tail; zero_from is null without it): behind the closing slot of EVERY half of its tile (an open half's
+    // 0xFFFFFFFF is behind no segment).  k_bwd_tail_verdict ran this unit's prologue -- the one every tail unit of the tile runs -- and
+    // left a rank where the unit is a zero unit: it then writes no rows (k_row_sum does not read them) and leaves here.  A tail
+    // unit of a tile whose verdict was no, and every other unit, goes on as it always did.
+    if (zero_from) {
+        bool tail = true;
+#pragma unroll
+        for (int h = 0; h < NSX / 2; ++h) tail = tail && seg >= kclose[h];
+        if (tail && zero_from[unit_tile] != 0xFFFFFFFFu) {
+            FGS_BWD_TRACE_EXIT(5);
+            return;
+        }
+    }
+    TileCtx c = tile_ctx_of(unit_tile, tiles, tiles_x, ranges, 8u * NSX);
+    uint32_t rebase_seg = seg;  // first segment of this segment's list part if its checkpoint is part-local
+    if (fwd_parts > 1) {
+        const uint32_t nseg = (c.end - c.start + seg_len - 1) / seg_len;
+        const uint32_t spp = (nseg + fwd_parts - 1) / fwd_parts, first = seg / spp * spp;
+        if (first != 0) rebase_seg = first;
+    }
+    c.start += seg * seg_len;
+    c.end = min(c.end, c.start + seg_len);
+    const uint32_t lane = threadIdx.x;
+    const uint32_t lx = lane & 7u, ly = lane >> 3;
+    if (t_eps > 0.0f) {
+        // FgsDims.saturation_skip: the forward stopped walking this tile's list after `live` segments (count
+        // parked in the checkpoint slot of segment 0); the entries of a dead segment get all-zero gradient rows
+        const uint32_t live = reinterpret_cast<const uint32_t *>(seg_ckpt + (size_t)seg_off[unit_tile] * SLOT)[0];
+        if (seg >= live) {
+            for (uint32_t i = c.start + lane; i < c.end; i += 64) {
+                const uint32_t gid = dup_ids[i];
+                const float4 q2 = reinterpret_cast<const float4 *>(rec + (size_t)gid * FGS_REC_FLOATS)[2];
+                const uint32_t e = fgs_emission_slot<8 * NSX>(c.tx, c.ty, gid, __float_as_uint(q2.z), __float_as_uint(q2.w), dup_off);
+                if (e < dcap) {
+                    float2 *row = reinterpret_cast<float2 *>(grad_rows + (size_t)e * FGS_BLEND_ROW_FLOATS);
+#pragma unroll
+                    for (int q = 0; q < FGS_BLEND_ROW_FLOATS / 2; ++q) row[q] = make_float2(0.0f, 0.0f);
+                }
+            }
+            FGS_BWD_TRACE_EXIT(2);
+            return;
+        }
+    }
+    // T: running transmittance (w = alpha T, T -= w: one instruction less per pixel than T = 1 - A, A += w)
+    // S: T_fin (gI.bg) + sum over not-yet-visited w q
+    float gr[NS], gg[NS], gb[NS], gd[NS], S[NS], T[NS];
+    const bool live_px = composite_bwd_prologue<NSX>(c, unit, seg, rebase_seg, kclose, lane, lx, ly, W, H, bg0, bg1, bg2, seg_ckpt, pix_state,
+                                                     g_rgb, g_depth, gr, gg, gb, gd, S, T);
     // DEAD UNIT: every in-frame pixel of the tile restarts with T == +0.0f (the forward's A rounded to 1.0f: its T <= 2^-25) and
     // keeps it for the whole unit (fma(+0, -0.99, +0) = +0).  Lanes outside the frame (T = 1, g = 0, S = 0) do not veto: the
     // bboxes are clipped to the frame (k_project), so stage_decode_w's column / row bits mask their a' to zero and they add
@@ -1202,10 +1309,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NSX == 2 ? 6
         // lies behind its halves' closings: see DEAD UNITS above; or no gradient reaches the pixels).
         uint32_t walk = (1u << NS) - 1u;
         if (zero_units) {
-            walk = 0u;
-#pragma unroll
-            for (int s = 0; s < NS; ++s)
-                if (__ballot((__float_as_uint(S[s]) & 0x7FFFFFFFu) != 0u) != 0ull) walk |= 1u << s;
+            walk = composite_bwd_nonzero_subtiles<NSX>(S);
             if (walk == 0u) {
                 composite_bwd_zero_rows<NSX>(c, dcap, dup_ids, rec, dup_off, grad_rows);
                 FGS_BWD_TRACE_EXIT(3);
@@ -1662,6 +1766,19 @@ int fgs_launch_composite_bwd(const FgsPlan &p, const float *phase, const char *s
     // the closing slots of the exiting forward's closed halves; null where that forward did not run (the plan is a pure function of
     // the dims: the forward's choice)
     const uint32_t *fwd_close = p.fwd_exit ? fgs_at<const uint32_t>(saved, p.L.fwd_close) : nullptr;
+    // one verdict per closed tile, in front of the units (FgsPlan.bwd_tail): every word of zero_from is written by this launch
+    uint32_t *zero_from = p.bwd_tail ? fgs_at<uint32_t>(scratch, p.s_zero_from) : nullptr;
+    if (zero_from) {
+        const uint32_t *rank_of = fgs_at<const uint32_t>(saved, p.L.rank_of);
+#define FGS_VERDICT_LAUNCH(NSXV)                                                                                          \
+    hipLaunchKernelGGL(k_bwd_tail_verdict<NSXV>, dim3(grid), dim3(64), 0, st, grid, tiles, tiles_x, W, H, bg0, bg1, bg2, dcap, counters, \
+                       seg_off, seg_ckpt, ranges, dup_ids, pix, g_rgb, g_depth, fwd_close, rank_of, zero_from)
+        if (p.tile_w == 32) FGS_VERDICT_LAUNCH(4); else FGS_VERDICT_LAUNCH(2);
+#undef FGS_VERDICT_LAUNCH
+        FGS_LAUNCH_CHECK("k_bwd_tail_verdict");
+        hipLaunchKernelGGL(k_bwd_tail_min, dim3((uint32_t)p.d.batch), dim3(256), 0, st, tiles, zero_from);
+        FGS_LAUNCH_CHECK("k_bwd_tail_min");
+    }
 #ifdef FGS_BWD_UNIT_TRACE
     if (g_bwd_trace_slots < ugrid) {
         if (g_bwd_trace) (void)hipFree(g_bwd_trace);
@@ -1678,7 +1795,7 @@ int fgs_launch_composite_bwd(const FgsPlan &p, const float *phase, const char *s
 #define FGS_BWD_LAUNCH(NSXV)                                                                                              \
     hipLaunchKernelGGL(k_composite_bwd<NSXV>, dim3(ugrid), dim3(64), FGS_BWD_DYN_LDS, st, tiles, tiles_x, W, H, bg0, bg1, bg2, dcap, \
                        counters, seg_off, seg_tile, seg_ckpt, ranges, dup_ids, rec, dup_off, pix, g_rgb, g_depth, grad_rows, t_eps, unit_order, fwd_close, \
-                       (uint32_t)p.bwd_zero FGS_BWD_TRACE_ARG)
+                       (uint32_t)p.bwd_zero, (const uint32_t *)zero_from FGS_BWD_TRACE_ARG)
     if (p.tile_w == 32) FGS_BWD_LAUNCH(4); else FGS_BWD_LAUNCH(2);
 #undef FGS_BWD_LAUNCH
 #undef FGS_BWD_TRACE_ARG

@@ -32,7 +32,8 @@ int fgs_launch_project(const FgsPlan &p, const float *cams, const float *pos, co
 int fgs_launch_project_bwd(const FgsPlan &p, const float *cams, const float *pos, const float *scale,
                            const float *quat, const char *saved, const float *grad_rows, float *g_pos,
                            float *g_scale, float *g_quat, float *g_color, float *g_opacity, float *g_phase,
-                           hipStream_t st, float *row_sums = nullptr /* scratch [B*N][12]: blend path row totals */);
+                           hipStream_t st, float *row_sums = nullptr /* scratch [B*N][12]: blend path row totals */,
+                           const uint32_t *zero_from = nullptr /* scratch [B*tiles] of this backward's k_bwd_tail_verdict (FgsPlan.bwd_tail) */);
 
 int fgs_launch_asm_project_bwd(const FgsPlan &p, const float *cams, const float *pos, const float *scale,
                                const float *quat, const float *color, const float *phase, int phase_channels,

@@ -33,13 +33,15 @@ int fgs_make_plan(const FgsDims *d, FgsPlan *p, int layers, bool segment_ckpt) {
                       d->num_gaussians, d->width, d->height, (double)d->max_radius, d->num_cameras);
         return FGS_EINVAL;
     }
-    // fwd_variant >= 0 may carry one of the two exit flags and FGS_BWD_ZERO_OFF (include/fgs.h); fv is the work split without them
+    // fwd_variant >= 0 may carry one of the two exit flags, one of FGS_BWD_ZERO_* and one of FGS_BWD_TAIL_* (include/fgs.h); fv is the work split without them
     const int exit_flags = d->fwd_variant >= 0 ? (d->fwd_variant & (FGS_FWD_EXIT_OFF | FGS_FWD_EXIT_ON)) : 0;
     const int zero_flags = d->fwd_variant >= 0 ? (d->fwd_variant & (FGS_BWD_ZERO_OFF | FGS_BWD_ZERO_ON)) : 0;
-    const int fv = d->fwd_variant - exit_flags - zero_flags, afv = fv < -16 || fv > 16 ? 3 /* invalid; INT_MIN has no negation */ : (fv < 0 ? -fv : fv);
+    const int tail_flags = d->fwd_variant >= 0 ? (d->fwd_variant & (FGS_BWD_TAIL_OFF | FGS_BWD_TAIL_ON)) : 0;
+    const int fv = d->fwd_variant - exit_flags - zero_flags - tail_flags, afv = fv < -16 || fv > 16 ? 3 /* invalid; INT_MIN has no negation */ : (fv < 0 ? -fv : fv);
     if (d->seg_len < 0 || d->seg_len > 512 || d->seg_len % 64 != 0 || (afv != 0 && afv != 1 && afv != 2 && afv != 4 && !(fv == 8 || fv == 16)) ||
         d->bin_mode < 0 || d->bin_mode > 2 || (d->tile_w != 0 && d->tile_w != 16 && d->tile_w != 32) || d->sort_mode < 0 || d->sort_mode > 11 ||
-        exit_flags == (FGS_FWD_EXIT_OFF | FGS_FWD_EXIT_ON) || zero_flags == (FGS_BWD_ZERO_OFF | FGS_BWD_ZERO_ON)) {
+        exit_flags == (FGS_FWD_EXIT_OFF | FGS_FWD_EXIT_ON) || zero_flags == (FGS_BWD_ZERO_OFF | FGS_BWD_ZERO_ON) ||
+        tail_flags == (FGS_BWD_TAIL_OFF | FGS_BWD_TAIL_ON)) {
         fgs_set_error("invalid tuning: seg_len=%d fwd_variant=%d bin_mode=%d tile_w=%d sort_mode=%d", d->seg_len, d->fwd_variant,
                       d->bin_mode, d->tile_w, d->sort_mode);
         return FGS_EINVAL;
@@ -205,7 +207,17 @@ int fgs_make_plan(const FgsDims *d, FgsPlan *p, int layers, bool segment_ckpt) {
     // k_composite_bwd restarts the half's later units from that one slot).  Behind the maxima, so that every older offset stays.
     L.fwd_close = o;
     if (p->fwd_exit) o = align256(o + B * p->tiles * 2 * 4);
+    // one verdict per closed tile (k_bwd_tail_verdict).  Behind a tile's closing slots (the exiting forward) every unit restarts from
+    // the same state, so the zero-unit test of k_composite_bwd (bwd_zero) has one answer for all of them; the answer is kept as a depth
+    // rank, which needs the rank-ordered lists of the direct binning and its dup-offset blocks (saved.rank_of), and the units
+    // are the blend backward's (unit_order).  Automatic = on wherever the four hold; FGS_BWD_TAIL_OFF: every unit decides for
+    // itself; FGS_BWD_TAIL_ON cannot add what the plan lacks.  Elsewhere no table exists and no kernel looks for one.
+    p->bwd_tail = p->fwd_exit && p->bwd_zero && p->direct_binning && p->has_unit_order && tail_flags != FGS_BWD_TAIL_OFF;
+    // the inverse of `order`, behind every older section
+    L.rank_of = o;
+    if (p->bwd_tail) o = align256(o + B * N * 4);
     L.total_bytes = o;
+    if (!p->bwd_tail) L.rank_of = o;
     L.dup_capacity = dcap;
     L.tiles_x = tx; L.tiles_y = ty;
 
@@ -241,7 +253,10 @@ int fgs_make_plan(const FgsDims *d, FgsPlan *p, int layers, bool segment_ckpt) {
     p->s_plane = o; o = align256(o + B * ((size_t)layers + 1) * 4);
     p->s_rsum = o; o = align256(o + B * N * 12 * 4);
     p->s_bucket = o; o = align256(o + B * FGS_SORT_BUCKET_WORDS * 4);
+    p->s_zero_from = o;
+    if (p->bwd_tail) o = align256(o + (B * (size_t)p->tiles + B) * 4);  // one word per tile, then one per image (the smallest)
     p->s_total = o;
+    if (!p->bwd_tail) p->s_zero_from = o;
     return FGS_OK;
 }
 

@@ -51,6 +51,9 @@ struct FgsPlan {
                               // k_blend_fwd_head, then k_blend_fwd_parts for the halves it left open; saved.fwd_open, s_fwd_max and saved.fwd_close exist
     bool bwd_zero;            // k_composite_bwd writes zero rows for dead units whose S is exactly zero and masks such sub-tiles of the others
                               // (flags FGS_BWD_ZERO_ON / _OFF of FgsDims.fwd_variant; automatic from 8192 tile halves per launch; the same bits)
+    bool bwd_tail;            // one verdict per closed tile (k_bwd_tail_verdict): the units behind every half's closing slot of a tile whose
+                              // verdict is "zero units" return at once, and k_row_sum skips their rows.  Where fwd_exit, bwd_zero,
+                              // direct_binning and has_unit_order all hold, unless FGS_BWD_TAIL_OFF; saved.rank_of and s_zero_from exist with it
     size_t s_fwd_max;         // saved: uint32 [B][ceil(N / 256)][2]: per projection block, the largest |0.99 colour channel| and
                               // |0.99 depth| of its Gaussians as fp32 bit patterns (a NaN is the largest: the bound is then NaN)
     // scratch layout (bytes)
@@ -65,6 +68,10 @@ struct FgsPlan {
     size_t s_plane;           // uint32 [B][layers + 1]: first depth rank of every layer (layered direct binning)
     size_t s_rsum;            // float [B*N][12]: per-Gaussian totals of the blend path's rows (k_row_sum -> k_project_bwd)
     size_t s_bucket;          // uint32 [B][FGS_SORT_BUCKET_WORDS]: the bucket depth sort's per-image table (fgs_sort.hip)
+    size_t s_zero_from;       // uint32 [B * tiles] (bwd_tail only; == s_total elsewhere): per tile the depth rank of the first list entry
+                              // behind its closing slots when the units there are zero units, else 0xFFFFFFFF.  Written for every
+                              // tile by every backward (k_bwd_tail_verdict), read by k_composite_bwd and k_row_sum of the same call.
+                              // Then uint32 [B]: the smallest word of each image's tiles (k_bwd_tail_min, every call): a Gaussian of a lower rank has no row left out and k_row_sum looks nothing up for it
 };
 
 // `segment_ckpt`: reserve the per-segment forward checkpoints of the tile-based compositing path (the splat

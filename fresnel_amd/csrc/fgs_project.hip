@@ -264,12 +264,21 @@ __global__ __launch_bounds__(256) void k_fourier_project(
 // sums.  The totals get the factors of the chain through m' = K m, G = exp2(m'), alpha = G opacity (first moments x
 // ln2 opacity, second moments x K ln2 opacity; the opacity is already IN the rows of a Gaussian whose opacity the blend
 // kernels fold into the exponent, see below) and go to sums[input index][12].  Streaming kernel: ~40 VGPRs, full occupancy.
-__global__ __launch_bounds__(256) void k_row_sum(int32_t total, int32_t N, uint32_t dcap,
+// ROWS NOT WRITTEN (zero_from non-null: FgsPlan.bwd_tail).  k_bwd_tail_verdict (fgs_composite.hip) leaves per tile the depth rank
+// from which on the tile's list entries belong to zero units that wrote NO rows (0xFFFFFFFF: none).  Row k of a Gaussian of rank r
+// with tile rectangle (tx0, ty0, w) -- the record's bbox words, as fgs_emission_slot reads them -- is the row of tile
+// (tx0 + k % w, ty0 + k / w) of its image; it is loaded and added only if r < zero_from[that tile].  The rows left out were +-0
+// (composite_bwd_zero_rows), the accumulators start at +0 and only add, so none is ever -0, and x + (+-0) = x for every such
+// x: the same bits, the remaining additions in the same order; 37 MB read instead of 164 at config 3.
+// (waves_per_eu 8: with the tile lookup the allocator took 72 VGPRs where it had taken 56; held to full occupancy it needs 54, no spill.)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_row_sum(int32_t total, int32_t N, uint32_t dcap,
                                                  const uint32_t *__restrict__ order,
                                                  const uint32_t *__restrict__ dup_off,
                                                  const uint32_t *__restrict__ tile_count,
                                                  const float *__restrict__ grad_rows, const float *__restrict__ rec,
-                                                 float *__restrict__ sums) {
+                                                 float *__restrict__ sums, const uint32_t *__restrict__ zero_from,
+                                                 const uint32_t *__restrict__ zero_min, uint32_t tiles, uint32_t tiles_x,
+                                                 uint32_t tile_w) {
     const int32_t tid = blockIdx.x * 256 + threadIdx.x;
     const int32_t ri = tid >> 2;
     const uint32_t sub = threadIdx.x & 3u;
@@ -284,6 +293,31 @@ __global__ __launch_bounds__(256) void k_row_sum(int32_t total, int32_t N, uint3
         double m[6] = {0, 0, 0, 0, 0, 0};
         const float *base = grad_rows + (size_t)off * FGS_BLEND_ROW_FLOATS;
         uint32_t k = sub;
+        // is row k one that was written?  (always, without the table; a tile index outside the image's tiles cannot come from a
+        // rectangle k_project made -- such a row is read, as it always was.)  zf: the image's table, moved to the rectangle's first tile
+        const uint32_t rank = (uint32_t)(ri - ri / N * N);
+        const uint32_t *zf = nullptr;
+        uint32_t t0 = 0u, rw = 1u;
+        float inv_rw = 1.0f;
+        // (zero_min[image]: the smallest word of the image's tiles (k_bwd_tail_min).  A Gaussian of a lower rank has every row
+        // written: nothing is looked up for it -- in a scene where nothing closes that is every Gaussian)
+        if (zero_from && cnt != 0u && rank >= zero_min[ri / N]) {
+            const uint32_t bbx = __float_as_uint(rec[(size_t)idx * FGS_REC_FLOATS + R_BBX]), bby = __float_as_uint(rec[(size_t)idx * FGS_REC_FLOATS + R_BBY]);
+            const uint32_t tx0 = (bbx & 0xFFFFu) / tile_w;
+            t0 = (bby & 0xFFFFu) / FGS_TILE * tiles_x + tx0;
+            rw = max(((bbx >> 16) - 1u) / tile_w - tx0 + 1u, 1u);
+            inv_rw = 1.0f / (float)rw;
+            zf = zero_from + (size_t)(ri / N) * tiles;
+        }
+        auto written = [&](uint32_t row) -> bool {
+            if (!zf) return true;
+            // row / rw without the integer division: (row + 0.5) / rw is at least 0.5 / rw from an integer, rw <= the tile columns
+            // and row < 2^22, so the fp32 product rounds down to the quotient
+            const uint32_t ky = (uint32_t)(((float)row + 0.5f) * inv_rw), t = t0 + ky * tiles_x + (row - ky * rw);
+            return t >= tiles || rank < zf[t];
+        };
+        // A row left out is simply not added: the additions that remain keep their order (this unit is compiled without fast-math
+        // and without contraction: every += below is one IEEE addition, in program order).
 #if FGS_BLEND_ROW_FLOATS == 16
         // 64-byte rows (build experiment): three aligned 16-byte loads per row
         auto add_row = [&](const float4 a, const float4 b, const float4 c) {
@@ -293,29 +327,43 @@ __global__ __launch_bounds__(256) void k_row_sum(int32_t total, int32_t N, uint3
         for (; k + 4 < cnt; k += 8) {
             const float4 *r = reinterpret_cast<const float4 *>(base + (size_t)k * 16);
             const float4 *r2 = reinterpret_cast<const float4 *>(base + (size_t)(k + 4) * 16);
-            const float4 a = r[0], b = r[1], c = r[2], a2 = r2[0], b2 = r2[1], c2 = r2[2];
-            add_row(a, b, c); add_row(a2, b2, c2);
+            const bool w1 = written(k), w2 = written(k + 4);
+            if (w1 && w2) {
+                const float4 a = r[0], b = r[1], c = r[2], a2 = r2[0], b2 = r2[1], c2 = r2[2];
+                add_row(a, b, c); add_row(a2, b2, c2);
+            } else if (w1) {
+                add_row(r[0], r[1], r[2]);
+            } else if (w2) {
+                add_row(r2[0], r2[1], r2[2]);
+            }
         }
-        if (k < cnt) {
+        if (k < cnt && written(k)) {
             const float4 *r = reinterpret_cast<const float4 *>(base + (size_t)k * 16);
             add_row(r[0], r[1], r[2]);
         }
 #else
+        auto add_row = [&](const float2 a, const float2 bq, const float2 cq, const float2 dq, const float2 eq) {
+            m[0] += a.x; m[1] += a.y; m[2] += bq.x; m[3] += bq.y; m[4] += cq.x; m[5] += cq.y;
+            acc[6] += dq.x; acc[7] += dq.y; acc[8] += eq.x; acc[9] += eq.y;
+        };
         for (; k + 4 < cnt; k += 8) {  // rows k and k + 4
             const float2 *r = reinterpret_cast<const float2 *>(base + (size_t)k * FGS_BLEND_ROW_FLOATS);
             const float2 *r2 = reinterpret_cast<const float2 *>(base + (size_t)(k + 4) * FGS_BLEND_ROW_FLOATS);
-            const float2 a = r[0], bq = r[1], cq = r[2], dq = r[3], eq = r[4];
-            const float2 a2 = r2[0], bq2 = r2[1], cq2 = r2[2], dq2 = r2[3], eq2 = r2[4];
-            m[0] += a.x; m[1] += a.y; m[2] += bq.x; m[3] += bq.y; m[4] += cq.x; m[5] += cq.y;
-            acc[6] += dq.x; acc[7] += dq.y; acc[8] += eq.x; acc[9] += eq.y;
-            m[0] += a2.x; m[1] += a2.y; m[2] += bq2.x; m[3] += bq2.y; m[4] += cq2.x; m[5] += cq2.y;
-            acc[6] += dq2.x; acc[7] += dq2.y; acc[8] += eq2.x; acc[9] += eq2.y;
+            const bool w1 = written(k), w2 = written(k + 4);
+            if (w1 && w2) {
+                const float2 a = r[0], bq = r[1], cq = r[2], dq = r[3], eq = r[4];
+                const float2 a2 = r2[0], bq2 = r2[1], cq2 = r2[2], dq2 = r2[3], eq2 = r2[4];
+                add_row(a, bq, cq, dq, eq);
+                add_row(a2, bq2, cq2, dq2, eq2);
+            } else if (w1) {
+                add_row(r[0], r[1], r[2], r[3], r[4]);
+            } else if (w2) {
+                add_row(r2[0], r2[1], r2[2], r2[3], r2[4]);
+            }
         }
-        if (k < cnt) {
+        if (k < cnt && written(k)) {
             const float2 *r = reinterpret_cast<const float2 *>(base + (size_t)k * FGS_BLEND_ROW_FLOATS);
-            const float2 a = r[0], bq = r[1], cq = r[2], dq = r[3], eq = r[4];
-            m[0] += a.x; m[1] += a.y; m[2] += bq.x; m[3] += bq.y; m[4] += cq.x; m[5] += cq.y;
-            acc[6] += dq.x; acc[7] += dq.y; acc[8] += eq.x; acc[9] += eq.y;
+            add_row(r[0], r[1], r[2], r[3], r[4]);
         }
 #endif
         // k_composite_bwd works with a' = alpha / 0.99 = clamp01(exp2(m' + log2(opacity / 0.99))) and 0.99 x colours, and accumulates
@@ -681,7 +729,7 @@ int fgs_launch_project(const FgsPlan &p, const float *cams, const float *pos, co
 int fgs_launch_project_bwd(const FgsPlan &p, const float *cams, const float *pos, const float *scale,
                            const float *quat, const char *saved, const float *grad_rows, float *g_pos,
                            float *g_scale, float *g_quat, float *g_color, float *g_opacity, float *g_phase,
-                           hipStream_t st, float *row_sums) {
+                           hipStream_t st, float *row_sums, const uint32_t *zero_from) {
     const int32_t total = p.d.batch * p.d.num_gaussians;
     const int grid = (int)(((size_t)total * 4 + 255) / 256);
     const uint32_t *depth_key = reinterpret_cast<const uint32_t *>(saved + p.L.depth_key);
@@ -693,7 +741,9 @@ int fgs_launch_project_bwd(const FgsPlan &p, const float *cams, const float *pos
         if (!row_sums) { fgs_set_error("fgs_launch_project_bwd: the blend path needs the row-sum scratch"); return FGS_EINVAL; }
         // blend path: streaming row sums at full occupancy, then one thread per Gaussian for the adjoint
         hipLaunchKernelGGL(k_row_sum, dim3(grid), dim3(256), 0, st, total, p.d.num_gaussians,
-                           (uint32_t)p.L.dup_capacity, order, dup_off, tile_count, grad_rows, rec, row_sums);
+                           (uint32_t)p.L.dup_capacity, order, dup_off, tile_count, grad_rows, rec, row_sums,
+                           p.bwd_tail ? zero_from : nullptr, p.bwd_tail && zero_from ? zero_from + (size_t)p.d.batch * p.tiles : nullptr,
+                           (uint32_t)p.tiles, (uint32_t)p.L.tiles_x, (uint32_t)p.tile_w);
         FGS_LAUNCH_CHECK("k_row_sum");
         hipLaunchKernelGGL((k_project_bwd<0, true>), dim3((total + 255) / 256), dim3(256), 0, st, total,
                            p.d.num_gaussians, p.d.num_cameras, (uint32_t)p.L.dup_capacity, cams, pos, scale, quat,

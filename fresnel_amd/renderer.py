@@ -534,6 +534,8 @@ def inspect_saved(saved: torch.Tensor, dims) -> dict:
             out["fwd_open"] = view(L.fwd_open, Bn * T * 2, torch.int32).view(Bn, T, 2)
         if 0 < L.fwd_close < L.total_bytes:  # closing slot of the halves the head closed, -1 (0xFFFFFFFF) elsewhere (include/fgs.h)
             out["fwd_close"] = view(L.fwd_close, Bn * T * 2, torch.int32).view(Bn, T, 2)
+        if 0 < L.rank_of < L.total_bytes:  # depth rank of every Gaussian in its image (the blend backward's tail verdict, tuning key bwd_tail)
+            out["rank_of"] = view(L.rank_of, Bn * N, torch.int32).view(Bn, N)
     return out
 
 

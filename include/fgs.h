@@ -62,6 +62,8 @@ extern "C" {
 #define FGS_FWD_EXIT_ON 0x200
 #define FGS_BWD_ZERO_OFF 0x400 /* FgsDims.fwd_variant flags (values >= 0 only): the blend backward's zero rows for dead units off / forced on */
 #define FGS_BWD_ZERO_ON 0x800
+#define FGS_BWD_TAIL_OFF 0x2000 /* FgsDims.fwd_variant flags (values >= 0 only): the blend backward's one verdict per closed tile off / forced on */
+#define FGS_BWD_TAIL_ON 0x4000
 #define FGS_TUNE_AUTO 0    /* FgsDims.seg_len / fwd_variant / bin_mode: let the library choose        */
 #ifndef FGS_PHASE_CKPT
 #define FGS_PHASE_CKPT 8   /* phase path: entries of a sub-tile's (compacted) list between (A, Phi) checkpoints */
@@ -105,7 +107,15 @@ typedef struct FgsDims {
                                sub-tiles of the other such units whose S is all zero: the very bits the full walk computes
                                (those rows are sums of products with S).  No flag = automatic: on for launches of
                                >= 8192 16 x 16 tile halves.  OFF: every such unit is walked in full; ON: forced at any size
-                               (tests and A/B runs).  No flag is available with the row-split forward (values < 0).       */
+                               (tests and A/B runs).
+                               Beside them a value >= 0 may carry ONE of FGS_BWD_TAIL_OFF | FGS_BWD_TAIL_ON.  Where the exiting forward,
+                               the zero rows above, the direct binning and the blend backward's unit table all exist, one wave
+                               per tile (k_bwd_tail_verdict) decides for ALL the units behind the closing slots of every half of
+                               its tile whether they are such zero units; if so they return without writing rows and k_row_sum
+                               leaves those rows out of its sums (adding +-0 to a sum that is never -0 changes no bit).  No flag
+                               = automatic: on wherever the four exist.  OFF: every unit decides for itself and writes its rows;
+                               ON: as automatic (it cannot create what the plan lacks).
+                               No flag is available with the row-split forward (values < 0).       */
     int32_t bin_mode;       /* tile binning: 0 | 1 = direct (column / row rank masks) | 2 = emit + stable radix sort */
     int32_t tile_w;         /* tile width in pixels: 0 | 16 | 32 (tiles are always 16 rows high).  0 = automatic:
                                32 on the blend path with the depth-split forward for frames >= 512 pixels wide
@@ -193,6 +203,10 @@ typedef struct FgsSavedLayout {
                             0xFFFFFFFF everywhere else: a half left open, a list that ended, a closing inside the last segment,
                             index 1 on 16 x 16 tiles.  Behind the per-block maxima that follow fwd_open; exists where fwd_open
                             exists; == total_bytes elsewhere */
+    size_t rank_of;      /* uint32 [B][N]: depth rank of each Gaussian within its image, the inverse of `order` (written beside
+                            dup_off by the direct binning).  k_bwd_tail_verdict turns the first list entry behind a tile's closing
+                            slots into the rank threshold that k_row_sum compares a Gaussian's rank with.  Behind fwd_close;
+                            exists only with the tail verdict of the blend backward (FGS_BWD_TAIL_* above); == total_bytes elsewhere */
 } FgsSavedLayout;
 
 /* Sizes of the two caller-provided device buffers.  `saved` must stay untouched between

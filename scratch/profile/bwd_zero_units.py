@@ -5,7 +5,10 @@ selected through FGS_LIB.  Every launch slot records its unit and its walk: 0 ge
 with some sub-tiles masked (their S is +-0 on every lane), 3 a zero unit (S is +-0 on every lane of every sub-tile: rows written without
 a walk).  This script runs the benchmark's batch (bench.synth_batch; default config3 saag), reads the records of the last backward and
 prints the share of every kind out of all units and out of all list entries -- the premise figures of
-profiles/r16_ab_bwd_zero_units.txt section 1.  `tuning` as bench.py --tuning takes it, e.g. tile_w=16."""
+profiles/r16_ab_bwd_zero_units.txt section 1.  `tuning` as bench.py --tuning takes it, e.g. tile_w=16.
+It also prints how many of the units are TAIL units (behind the closing slot of every half of their tile, saved.fwd_close), how many zero
+units are among them, and the summed launch-slot time (exit - entry clock) of every kind, 5 = a tail unit that left on its tile's
+verdict (k_bwd_tail_verdict) -- profiles/r17_ab_bwd_tail_verdict.txt sections 1 and 4."""
 import ctypes
 import os
 import sys
@@ -74,3 +77,35 @@ for code, name in ((0, "general walk"), (3, "(a) zero units: S == +-0 on every l
 dead = walk != 0
 print(f"  dead units in all: {100.0 * dead.sum() / U:.1f} % of the units, {100.0 * ulen[dead].sum() / E:.1f} % of the entries; "
       f"kind (a) is {100.0 * (walk == 3).sum() / max(int(dead.sum()), 1):.1f} % of the dead units")
+# TAIL units (profiles/r17_ab_bwd_tail_verdict.txt section 1): segment >= the closing slot of EVERY 16 x 16 half of the tile, every
+# half having one (saved.fwd_close).  All tail units of a tile restart from the same slots: one verdict per tile covers them.
+if "fwd_close" in st:
+    halves = int(st["layout"].tile_w) // 16
+    fc = st["fwd_close"].cpu().numpy().astype(np.int64).reshape(-1, 2)[:, :halves]
+    closed = (fc >= 0).all(axis=1)
+    first_tail = np.where(closed, fc.max(axis=1), np.iinfo(np.int64).max)
+    seg = unit - seg_off[seg_tile[unit]]
+    tail = seg >= first_tail[seg_tile[unit]]
+    zero = (walk == 3) | (walk == 5)  # (5: a tail unit that took its tile's verdict -- a zero unit that did not have to find out)
+    tz = tail & zero
+    print(f"  tail units: {int(tail.sum())} = {100.0 * tail.sum() / U:.1f} % of the units, {int(ulen[tail].sum())} entries = "
+          f"{100.0 * ulen[tail].sum() / E:.1f} %; tiles with a tail: {int(np.unique(seg_tile[unit][tail]).size)} of {len(lens)}")
+    print(f"  tail zero units: {int(tz.sum())} = {100.0 * tz.sum() / max(int(zero.sum()), 1):.1f} % of the zero units, "
+          f"{int(ulen[tz].sum())} entries = {100.0 * ulen[tz].sum() / max(int(ulen[zero].sum()), 1):.1f} % of the zero units' entries, "
+          f"{100.0 * ulen[tz].sum() / E:.1f} % of all entries; tail units that are NOT zero units: {int((tail & ~zero).sum())}")
+    # a tile's tail units all take one verdict: tiles whose tail holds both zero and non-zero units would contradict that
+    tt = seg_tile[unit][tail]
+    zc = np.bincount(tt, weights=zero[tail].astype(np.float64), minlength=len(lens))
+    ac = np.bincount(tt, minlength=len(lens))
+    print(f"  tiles whose tail units disagree about the verdict: {int(((zc > 0) & (zc < ac)).sum())}")
+else:
+    print("  (no saved.fwd_close: the exiting forward did not run, no unit is a tail unit)")
+# slot time: exit - entry clock (100 MHz) of every launch slot, by kind
+dt = (rec[:, 1].astype(np.int64) - rec[:, 0].astype(np.int64)).astype(np.float64)
+span = float(rec[:, 1].max() - rec[:, 0].min())
+for code, name in ((0, "general"), (1, "dead, full"), (4, "dead, masked"), (3, "zero units"), (5, "tail exits")):
+    m = walk == code
+    if m.any():
+        print(f"  slot time {name:13s} {dt[m].sum() / 100.0:10.1f} us summed = {100.0 * dt[m].sum() / dt.sum():5.1f} % of all slots' "
+              f"({100.0 * m.sum() / U:5.1f} % of the launch slots), mean {dt[m].mean() / 100.0:6.2f} us")
+print(f"  all slots: {dt.sum() / 100.0:.1f} us summed over {U} slots; first entry to last exit {span / 100.0:.1f} us")
