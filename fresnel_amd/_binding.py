@@ -24,6 +24,7 @@ int fgs_forward(FgsDims* dims, ptr cameras pos scale quat color opacity phase ou
 int fgs_backward(FgsDims* dims, ptr cameras pos scale quat color opacity phase saved scratch g_rgb g_depth g_pos g_scale g_quat g_color
                  g_opacity g_phase, stream)
 int fgs_count_pairs(FgsDims* dims, ptr saved out_pairs, stream)
+int fgs_row_sum(FgsDims* dims, ptr saved grad_rows zero_from row_sums, stream)
 int fgs_asm_workspace_bytes(FgsAsmDims* dims, size_t* saved_bytes scratch_bytes)
 int fgs_asm_forward(FgsAsmDims* dims, ptr cameras pos scale quat color opacity phase wavelengths out_rgb saved scratch, stream)
 int fgs_asm_backward(FgsAsmDims* dims, ptr cameras pos scale quat color opacity phase wavelengths saved scratch g_rgb g_pos g_scale
@@ -127,6 +128,7 @@ STAGES = ["project", "depth_sort", "dup_emit", "tile_sort", "tile_ranges", "comp
 FWD_EXIT_OFF, FWD_EXIT_ON = 0x100, 0x200  # include/fgs.h: flags of FgsDims.fwd_variant
 BWD_ZERO_OFF, BWD_ZERO_ON = 0x400, 0x800  # include/fgs.h: flags of FgsDims.fwd_variant
 BWD_TAIL_OFF, BWD_TAIL_ON = 0x2000, 0x4000  # include/fgs.h: flags of FgsDims.fwd_variant
+BWD_SUB_OFF, BWD_SUB_ON = 0x8000, 0x10000  # include/fgs.h: flags of FgsDims.fwd_variant
 
 
 class FgsDims(ctypes.Structure):
@@ -329,6 +331,8 @@ def make_dims(batch, num_gaussians, width, height, max_radius=64.0, background=(
     `bwd_zero`: 0 | 1 | -1 = the blend backward's zero rows for dead units with S == 0 automatic | on | off -- the FGS_BWD_ZERO_ON / _OFF flag of FgsDims.fwd_variant.
     `bwd_tail`: 0 | 1 | -1 = the blend backward's one verdict per closed tile automatic (on where the plan has what it needs) | the same | off
     -- the FGS_BWD_TAIL_ON / _OFF flag of FgsDims.fwd_variant.
+    `bwd_sub`: 0 | 1 | -1 = the blend backward's zero sub-tiles of general units automatic (on wherever bwd_zero is) | on | off
+    -- the FGS_BWD_SUB_ON / _OFF flag of FgsDims.fwd_variant.
     `dup_capacity`: room for that many (tile, Gaussian) duplicates instead of the worst case (0 = worst case; a call that needs
     more overflows: NaN images, zero gradients, saved.counters[1] = 1 -- include/fgs.h)."""
     if isinstance(dup_capacity, bool) or int(dup_capacity) != dup_capacity or not 0 <= int(dup_capacity) <= 0xFFFFFFFF:
@@ -346,6 +350,7 @@ def make_dims(batch, num_gaussians, width, height, max_radius=64.0, background=(
     fwd_exit = int(tuning.pop("fwd_exit", 0))
     bwd_zero = int(tuning.pop("bwd_zero", 0))
     bwd_tail = int(tuning.pop("bwd_tail", 0))
+    bwd_sub = int(tuning.pop("bwd_sub", 0))
     for k, v in tuning.items():
         if k not in ("seg_len", "fwd_variant", "bin_mode", "tile_w", "sort_mode"):
             raise FgsError(f"unknown tuning field {k!r}")
@@ -356,8 +361,10 @@ def make_dims(batch, num_gaussians, width, height, max_radius=64.0, background=(
         raise FgsError(f"bwd_zero must be 0, 1 or -1, and 0 with the row-split forward (fwd_variant < 0), got {bwd_zero!r}")
     if bwd_tail not in (0, 1, -1) or (bwd_tail and d.fwd_variant < 0):
         raise FgsError(f"bwd_tail must be 0, 1 or -1, and 0 with the row-split forward (fwd_variant < 0), got {bwd_tail!r}")
+    if bwd_sub not in (0, 1, -1) or (bwd_sub and d.fwd_variant < 0):
+        raise FgsError(f"bwd_sub must be 0, 1 or -1, and 0 with the row-split forward (fwd_variant < 0), got {bwd_sub!r}")
     d.fwd_variant |= ({0: 0, 1: FWD_EXIT_ON, -1: FWD_EXIT_OFF}[fwd_exit] | {0: 0, 1: BWD_ZERO_ON, -1: BWD_ZERO_OFF}[bwd_zero]
-                      | {0: 0, 1: BWD_TAIL_ON, -1: BWD_TAIL_OFF}[bwd_tail])
+                      | {0: 0, 1: BWD_TAIL_ON, -1: BWD_TAIL_OFF}[bwd_tail] | {0: 0, 1: BWD_SUB_ON, -1: BWD_SUB_OFF}[bwd_sub])
     d.dup_capacity = int(dup_capacity)
     return d
 

@@ -220,6 +220,16 @@ int fgs_backward(const FgsDims *dims, const float *cameras, const float *pos, co
     return FGS_OK;
 }
 
+int fgs_row_sum(const FgsDims *dims, const void *saved, const float *grad_rows, const uint32_t *zero_from, float *row_sums,
+                void *stream) {
+    FgsPlan p;
+    const int rc = fgs_make_plan(dims, &p);
+    if (rc) return rc;
+    if (!saved || !grad_rows || !row_sums) { fgs_set_error("fgs_row_sum: null pointer"); return FGS_EINVAL; }
+    if (p.d.use_phase) { fgs_set_error("fgs_row_sum: the blend path only"); return FGS_EUNSUPPORTED; }
+    return fgs_launch_row_sum(p, reinterpret_cast<const char *>(saved), grad_rows, row_sums, zero_from, reinterpret_cast<hipStream_t>(stream));
+}
+
 int fgs_count_pairs(const FgsDims *dims, const void *saved, uint64_t *out_pairs, void *stream) {
     FgsPlan p;
     const int rc = fgs_make_plan(dims, &p);

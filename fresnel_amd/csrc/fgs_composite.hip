@@ -677,6 +677,37 @@ __global__ __launch_bounds__(64 * (1 + WIDE)) __attribute__((amdgpu_waves_per_eu
 // once per tile in front of this kernel; a tail unit of a tile whose verdict is "zero units" leaves before its prologue and writes
 // NO rows, and k_row_sum does not read them (see both kernels).  Zero units in front of a closing, and every unit where the plan
 // has no tail verdict (FgsPlan.bwd_tail), still decide for themselves and store their rows with composite_bwd_zero_rows.
+// ZERO SUB-TILES OF A GENERAL UNIT (round 18; DESIGN_LOG.md 29; FgsPlan.bwd_sub, bit 1 of the kernel's zero_units).  A unit is general as
+// soon as ONE in-frame pixel restarts with T != 0, and then walked every touched sub-tile of every entry -- also the sub-tiles of a
+// half that closed earlier than the other, of a closed half beside one whose list ends open, and single sub-tiles that saturated
+// before their half did: 11.3 % of the general units' passes at config 3, 21 % in the decoder-like scene
+// (profiles/r18_ab_bwd_zero_subtiles.txt).  The prologue now takes out of `alive` every sub-tile s with T[s] == +0 BY ITS BITS on every
+// in-frame lane and S[s] == +-0 on EVERY lane (composite_bwd_zero_subtiles; lanes outside the frame hold T = 1, S = +0, g = 0 and do
+// not veto on T).  The list loop is the parent's, instruction for instruction: it has always formed msk = fl & alive.  An entry whose
+// mask becomes empty runs no pass, parks ten sums and stores its row as before.  Why no output bit changes, against the instructions
+// the general pass compiles to (v_mul w; v_fma S; v_mul, v_fmac dalpha; v_fmamk T; v_mul / v_fmac sums):
+//   w = T a' = (+0) a' = +0                       a' = clamp01(exp2(..)) & mask lies in [0, 1] whatever the record holds;
+//   S' = fma(-w, q, S) = +-0                      q = fma chain of g and the entry's colours / depth, FINITE: a non-finite upstream
+//                                                 gradient makes the prologue's S a NaN or an infinity, never +-0 -- NaN x C = NaN,
+//                                                 Inf x C = Inf for C != 0 (and Inf - Inf = NaN against the checkpoint sum), Inf x 0 =
+//                                                 NaN for a colour state that is exactly zero -- so such a sub-tile is not in the set;
+//                                                 a non-finite colour or depth of the ENTRY is the dead walk's premise too (DEAD UNITS:
+//                                                 that walk never forms q) and, as there, differs from the full walk only for an entry
+//                                                 behind a closing that the forward never composited;
+//   dalpha = fma(q, T, S' rcp(a' - 1 / 0.99)) = +-0   the divisor lies in [-1.0102, -0.0101], its reciprocal is finite;
+//   the clamp select returns dalpha or +0;  dG = dalpha a' = +-0;  T' = fma(w, -0.99, T) = -0 + +0 = +0: the sub-tile stays zero
+//   for the whole unit, and S stays +-0;
+//   every moment and colour / depth term = (+-0) x finite = +-0 (dx, dy finite: see composite_bwd_zero_rows), ADDED to a sum
+//   by v_fmac: x + (+-0) = x for x != 0, and +0 + (-0) = +0.
+// The one place where a bit of a lane's sum can differ is the FIRST pass of a sub-tile row (s = 0 and s = NSX): the compiler knows
+// that the row's sums start at zero and ASSIGNS them (v_mul where the others have v_fmac; -ffast-math knows no signed zero), so a zero
+// sub-tile 0 could leave -0 in a sum that is +0 without its pass.  A later non-zero term erases the difference; otherwise it is the sign
+// of a lane value that is an exact zero, which survives the fold (products with dya / dyb, sums) and the wave's total only as the sign
+// of a row value that is an exact zero on EVERY lane -- and k_row_sum adds the rows to sums that start at +0 and are never -0
+// (fgs_project.hip, ROWS NOT WRITTEN), so the seven outputs are the same bits.  That is the dead walk's statement about the sign of an
+// exact zero (DEAD UNITS), not more.  A general unit always keeps a live sub-tile, so `alive` never becomes empty here.
+// The predicate costs eight ballots per unit; at opacity 0.05, where it never fires, config 3's step and the backward's stage time
+// are inside the parent's spread (profiles/r18_ab_bwd_zero_subtiles.txt).
 // Six waves per SIMD (80 VGPRs): the loop is bound by VALU issue with dependent chains in every pass (exp -> alpha -> w
 // -> S -> rcp -> dalpha), and the sixth wave buys 4 % (1.37 -> 1.31 ms at config 3); a seventh needs spills and loses 35 %.
 // NSX = sub-tile columns of the tile: 2 (16 x 16 tiles) or 4 (32 x 16 tiles: eight sub-tiles per lane, ~0.6x as many list
@@ -690,6 +721,11 @@ __shared__ uint32_t bwd_she[CH];
 __shared__ __attribute__((aligned(16))) float bwd_red[10 * FGS_RED_PITCH];
 __shared__ __attribute__((aligned(16))) float bwd_red_pairs[12 * FGS_RED_PITCH];
 #define FGS_BWD_G __attribute__((address_space(1)))  /* global memory, also where the pointer arrives as a function argument */
+#ifdef FGS_BWD_UNIT_TRACE
+// experiment builds: [0] the zero sub-tiles of a general unit (whether or not the walk masks them), [1] its sub-tile passes with
+// none masked, [2] those of them that lie in [0] -- counted by the general walk, recorded by the kernel (scratch/profile/bwd_zero_units.py)
+__shared__ uint32_t bwd_trace_sub[3];
+#endif
 
 // The chunk / list loop of k_composite_bwd over the unit's entries [c.start, c.end), in two instantiations: DEAD = false the general
 // walk, inlined into the kernel; DEAD = true the walk of a dead unit (see the kernel), whose pass computes only what is not an exact
@@ -716,6 +752,9 @@ __device__ __forceinline__ void composite_bwd_walk(const TileCtx &c, uint32_t la
     // index).  One wave's LDS instructions execute in order, so the read-back of entry j is served before entry j + 1 parks its own
     // sums in the same cells.  e_prev: row of the entry whose sums are parked (none yet: no row passes e < dcap).
     uint32_t e_prev = ~0u;
+#ifdef FGS_BWD_UNIT_TRACE
+    [[maybe_unused]] uint32_t trace_passes = 0u, trace_zero_passes = 0u;
+#endif
     auto reduce_parked = [&]() {
         const float tot = wave_sum_addtid_finish(red, lane, 10u);
         // (16-float rows: all sixteen quads' last lanes store, lanes >= 40 a zero -- one whole 64-byte line)
@@ -891,6 +930,9 @@ __device__ __forceinline__ void composite_bwd_walk(const TileCtx &c, uint32_t la
             e_prev = e;
             const uint32_t fl = __builtin_amdgcn_readfirstlane(__float_as_uint(q2.w));  // stage_decode_w flags
             const uint32_t msk = fl & alive;
+#ifdef FGS_BWD_UNIT_TRACE
+            trace_passes += __builtin_popcount(fl & ((1u << NS) - 1u)); trace_zero_passes += __builtin_popcount(fl & bwd_trace_sub[0]);
+#endif
             const uint32_t cbits = __float_as_uint(q2.z), rbits = __float_as_uint(q2.w);  // column bits; row bits at 16+
             const float ca = q0.z, cbc = q0.w, cd = q1.x, lop = q1.y;  // conic pre-multiplied by K = -log2(e)/2; log2(opacity / 0.99)
             // terms shared by the sub-tiles of a column / row, formed once per list entry; the row's term of the exponent carries lop
@@ -982,6 +1024,9 @@ __device__ __forceinline__ void composite_bwd_walk(const TileCtx &c, uint32_t la
         __syncthreads();
     }
     if constexpr (DEAD) reduce_parked_dead(); else reduce_parked();  // the unit's last entry (or pair)
+#ifdef FGS_BWD_UNIT_TRACE
+    if (!DEAD) { bwd_trace_sub[1] = trace_passes; bwd_trace_sub[2] = trace_zero_passes; }
+#endif
 }
 
 // The dead unit's walk as a function of its own, CALLED by the kernel: inlined next to the general walk it cost that walk registers
@@ -1119,6 +1164,23 @@ __device__ __forceinline__ uint32_t composite_bwd_nonzero_subtiles(const float (
     for (int s = 0; s < 2 * NSX; ++s)
         if (__ballot((__float_as_uint(S[s]) & 0x7FFFFFFFu) != 0u) != 0ull) walk |= 1u << s;
     return walk;
+}
+
+// The zero sub-tiles of a GENERAL unit (k_composite_bwd, at its call; see ZERO SUB-TILES OF A GENERAL UNIT there): sub-tile s is in the
+// set when no lane vetoes -- an in-frame lane whose T[s] is not +0 by its BITS (a NaN, and a -0, veto), or any lane whose S[s] is not
+// +-0 by the integer test of composite_bwd_nonzero_subtiles (a NaN vetoes).  Lanes outside the frame (T = 1, S = +0) do not veto on T,
+// as in the dead-unit test.  One ballot per sub-tile, in the prologue only.
+template <int NSX>
+__device__ __forceinline__ uint32_t composite_bwd_zero_subtiles(const TileCtx &c, uint32_t lx, uint32_t ly, uint32_t W, uint32_t H,
+                                                                const float (&S)[2 * NSX], const float (&T)[2 * NSX]) {
+    uint32_t zero = 0u;
+#pragma unroll
+    for (int s = 0; s < 2 * NSX; ++s) {
+        const uint32_t px = c.X0 + 8u * (s % NSX) + lx, py = c.Y0 + 8u * (s / NSX) + ly;
+        const bool veto = (px < W && py < H && __float_as_uint(T[s]) != 0u) || (__float_as_uint(S[s]) & 0x7FFFFFFFu) != 0u;
+        if (__ballot(veto) == 0ull) zero |= 1u << s;
+    }
+    return zero;
 }
 
 // ONE VERDICT PER CLOSED TILE (round 17; FgsPlan.bwd_tail).  A TAIL unit of a tile lies behind the closing slot of EVERY 16 x 16 half
@@ -1308,7 +1370,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NSX == 2 ? 6
         // composite_bwd_zero_rows.  The test reads the bits the walk would multiply by -- it does not ask WHY S is zero (the unit
         // lies behind its halves' closings: see DEAD UNITS above; or no gradient reaches the pixels).
         uint32_t walk = (1u << NS) - 1u;
-        if (zero_units) {
+        if (zero_units & 1u) {
             walk = composite_bwd_nonzero_subtiles<NSX>(S);
             if (walk == 0u) {
                 composite_bwd_zero_rows<NSX>(c, dcap, dup_ids, rec, dup_off, grad_rows);
@@ -1324,8 +1386,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NSX == 2 ? 6
         FGS_BWD_TRACE_EXIT(walk == (1u << NS) - 1u ? 1 : 4);
         return;
     }
+    // ZERO SUB-TILES OF A GENERAL UNIT (round 18; bit 1 of zero_units = FgsPlan.bwd_sub): they leave `alive`, which the list loop
+    // applies to every entry's flags anyway -- the loop itself is the parent's.  Never for segment 0, never with saturation_skip.
+#ifdef FGS_BWD_UNIT_TRACE
+    bwd_trace_sub[0] = seg != 0 && !(t_eps > 0.0f) ? composite_bwd_zero_subtiles<NSX>(c, lx, ly, W, H, S, T) : 0u;
+#endif
+    if ((zero_units & 2u) && seg != 0 && !(t_eps > 0.0f)) alive &= ~composite_bwd_zero_subtiles<NSX>(c, lx, ly, W, H, S, T);
     composite_bwd_walk<NSX, false>(c, lane, lx, ly, dcap, alive, dup_ids, rec, dup_off, grad_rows, gr, gg, gb, gd, S, T);
-    FGS_BWD_TRACE_EXIT(0);
+    FGS_BWD_TRACE_EXIT((unsigned long long)bwd_trace_sub[1] << 3 | (unsigned long long)bwd_trace_sub[2] << 16 | (unsigned long long)(bwd_trace_sub[0] != 0u) << 29);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1795,7 +1863,7 @@ int fgs_launch_composite_bwd(const FgsPlan &p, const float *phase, const char *s
 #define FGS_BWD_LAUNCH(NSXV)                                                                                              \
     hipLaunchKernelGGL(k_composite_bwd<NSXV>, dim3(ugrid), dim3(64), FGS_BWD_DYN_LDS, st, tiles, tiles_x, W, H, bg0, bg1, bg2, dcap, \
                        counters, seg_off, seg_tile, seg_ckpt, ranges, dup_ids, rec, dup_off, pix, g_rgb, g_depth, grad_rows, t_eps, unit_order, fwd_close, \
-                       (uint32_t)p.bwd_zero, (const uint32_t *)zero_from FGS_BWD_TRACE_ARG)
+                       (uint32_t)p.bwd_zero | (p.bwd_sub ? 2u : 0u) /* zero_units: bit 0 zero rows, bit 1 zero sub-tiles of general units */, (const uint32_t *)zero_from FGS_BWD_TRACE_ARG)
     if (p.tile_w == 32) FGS_BWD_LAUNCH(4); else FGS_BWD_LAUNCH(2);
 #undef FGS_BWD_LAUNCH
 #undef FGS_BWD_TRACE_ARG

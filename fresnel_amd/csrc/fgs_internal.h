@@ -35,6 +35,10 @@ int fgs_launch_project_bwd(const FgsPlan &p, const float *cams, const float *pos
                            hipStream_t st, float *row_sums = nullptr /* scratch [B*N][12]: blend path row totals */,
                            const uint32_t *zero_from = nullptr /* scratch [B*tiles] of this backward's k_bwd_tail_verdict (FgsPlan.bwd_tail) */);
 
+// the row-sum stage of the blend path's projection backward alone (k_row_sum): fgs_launch_project_bwd's first kernel, and fgs_row_sum
+int fgs_launch_row_sum(const FgsPlan &p, const char *saved, const float *grad_rows, float *row_sums,
+                       const uint32_t *zero_from /* [B*tiles] words, then one per image (their smallest); null: no table */, hipStream_t st);
+
 int fgs_launch_asm_project_bwd(const FgsPlan &p, const float *cams, const float *pos, const float *scale,
                                const float *quat, const float *color, const float *phase, int phase_channels,
                                const char *saved, const float *grad_rows, float *g_pos, float *g_scale,

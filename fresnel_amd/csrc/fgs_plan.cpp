@@ -33,15 +33,16 @@ int fgs_make_plan(const FgsDims *d, FgsPlan *p, int layers, bool segment_ckpt) {
                       d->num_gaussians, d->width, d->height, (double)d->max_radius, d->num_cameras);
         return FGS_EINVAL;
     }
-    // fwd_variant >= 0 may carry one of the two exit flags, one of FGS_BWD_ZERO_* and one of FGS_BWD_TAIL_* (include/fgs.h); fv is the work split without them
+    // fwd_variant >= 0 may carry one of the two exit flags, one of FGS_BWD_ZERO_*, one of FGS_BWD_TAIL_* and one of FGS_BWD_SUB_* (include/fgs.h); fv is the work split without them
     const int exit_flags = d->fwd_variant >= 0 ? (d->fwd_variant & (FGS_FWD_EXIT_OFF | FGS_FWD_EXIT_ON)) : 0;
     const int zero_flags = d->fwd_variant >= 0 ? (d->fwd_variant & (FGS_BWD_ZERO_OFF | FGS_BWD_ZERO_ON)) : 0;
     const int tail_flags = d->fwd_variant >= 0 ? (d->fwd_variant & (FGS_BWD_TAIL_OFF | FGS_BWD_TAIL_ON)) : 0;
-    const int fv = d->fwd_variant - exit_flags - zero_flags - tail_flags, afv = fv < -16 || fv > 16 ? 3 /* invalid; INT_MIN has no negation */ : (fv < 0 ? -fv : fv);
+    const int sub_flags = d->fwd_variant >= 0 ? (d->fwd_variant & (FGS_BWD_SUB_OFF | FGS_BWD_SUB_ON)) : 0;
+    const int fv = d->fwd_variant - exit_flags - zero_flags - tail_flags - sub_flags, afv = fv < -16 || fv > 16 ? 3 /* invalid; INT_MIN has no negation */ : (fv < 0 ? -fv : fv);
     if (d->seg_len < 0 || d->seg_len > 512 || d->seg_len % 64 != 0 || (afv != 0 && afv != 1 && afv != 2 && afv != 4 && !(fv == 8 || fv == 16)) ||
         d->bin_mode < 0 || d->bin_mode > 2 || (d->tile_w != 0 && d->tile_w != 16 && d->tile_w != 32) || d->sort_mode < 0 || d->sort_mode > 11 ||
         exit_flags == (FGS_FWD_EXIT_OFF | FGS_FWD_EXIT_ON) || zero_flags == (FGS_BWD_ZERO_OFF | FGS_BWD_ZERO_ON) ||
-        tail_flags == (FGS_BWD_TAIL_OFF | FGS_BWD_TAIL_ON)) {
+        tail_flags == (FGS_BWD_TAIL_OFF | FGS_BWD_TAIL_ON) || sub_flags == (FGS_BWD_SUB_OFF | FGS_BWD_SUB_ON)) {
         fgs_set_error("invalid tuning: seg_len=%d fwd_variant=%d bin_mode=%d tile_w=%d sort_mode=%d", d->seg_len, d->fwd_variant,
                       d->bin_mode, d->tile_w, d->sort_mode);
         return FGS_EINVAL;
@@ -198,6 +199,9 @@ int fgs_make_plan(const FgsDims *d, FgsPlan *p, int layers, bool segment_ckpt) {
     // project's bench-line test states that config 3's line names k_composite_bwd at that size.  Smaller launches therefore keep the
     // full walk until that statement is revisited; FGS_BWD_ZERO_ON forces the path at any size, FGS_BWD_ZERO_OFF the full walk.
     p->bwd_zero = zero_flags == FGS_BWD_ZERO_ON || (zero_flags == 0 && B * p->tiles * (size_t)(p->tile_w / 16) >= 8192);
+    // the zero sub-tiles of GENERAL units (k_composite_bwd: sub-tiles that restart at T == +0 with S == +-0 leave the unit's walk; the
+    // same bits).  Automatic: wherever bwd_zero holds; FGS_BWD_SUB_ON forces it at any size, FGS_BWD_SUB_OFF gives the full walk.
+    p->bwd_sub = sub_flags == FGS_BWD_SUB_ON || (sub_flags == 0 && p->bwd_zero);
     p->s_fwd_max = o;
     if (p->fwd_exit) {
         p->s_fwd_max = o = align256(o + B * p->tiles * 2 * 4);

@@ -270,7 +270,12 @@ __global__ __launch_bounds__(256) void k_fourier_project(
 // (tx0 + k % w, ty0 + k / w) of its image; it is loaded and added only if r < zero_from[that tile].  The rows left out were +-0
 // (composite_bwd_zero_rows), the accumulators start at +0 and only add, so none is ever -0, and x + (+-0) = x for every such
 // x: the same bits, the remaining additions in the same order; 37 MB read instead of 164 at config 3.
+// ALL OF A LANE'S ROWS ARE DECIDED BEFORE ANY IS LOADED (round 18; DESIGN_LOG.md 29): see DECIDE FIRST, THEN LOAD in the kernel.
+// A lane's rows are sub, sub + 4, ...: at most FGS_ROW_SUM_MASK_ROWS of them fit the mask.  The host derives the largest rectangle
+// from k_project's radius clamp (fgs_row_sum_max_rows) and turns the path off where it could be larger (the loop as it was); a
+// Gaussian below zero_min, and a launch without the table, run that loop without its tests -- every row is written.
 // (waves_per_eu 8: with the tile lookup the allocator took 72 VGPRs where it had taken 56; held to full occupancy it needs 54, no spill.)
+#define FGS_ROW_SUM_MASK_ROWS 32u /* rows of one lane whose "written" answers fit one mask word */
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_row_sum(int32_t total, int32_t N, uint32_t dcap,
                                                  const uint32_t *__restrict__ order,
                                                  const uint32_t *__restrict__ dup_off,
@@ -278,7 +283,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
                                                  const float *__restrict__ grad_rows, const float *__restrict__ rec,
                                                  float *__restrict__ sums, const uint32_t *__restrict__ zero_from,
                                                  const uint32_t *__restrict__ zero_min, uint32_t tiles, uint32_t tiles_x,
-                                                 uint32_t tile_w) {
+                                                 uint32_t tile_w, [[maybe_unused]] uint32_t prefetch) {
     const int32_t tid = blockIdx.x * 256 + threadIdx.x;
     const int32_t ri = tid >> 2;
     const uint32_t sub = threadIdx.x & 3u;
@@ -346,7 +351,61 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
             m[0] += a.x; m[1] += a.y; m[2] += bq.x; m[3] += bq.y; m[4] += cq.x; m[5] += cq.y;
             acc[6] += dq.x; acc[7] += dq.y; acc[8] += eq.x; acc[9] += eq.y;
         };
-        for (; k + 4 < cnt; k += 8) {  // rows k and k + 4
+        // DECIDE FIRST, THEN LOAD (round 18; `prefetch`: the host's bound says a lane has at most 32 rows).  A Gaussian that looks rows
+        // up issues the table loads of ALL its lane's rows sub, sub + 4, ... four at a time, independent of one another, and keeps
+        // the answers as a bit mask; then it loads and adds the written rows in ascending k, two in flight -- the additions of the
+        // loop below, in its order.  That loop puts a dependent table load in front of every pair of row loads.
+        if (prefetch && zf && cnt <= 4u * FGS_ROW_SUM_MASK_ROWS) {
+            const uint32_t mine = cnt > sub ? (cnt - sub + 3u) >> 2 : 0u;  // rows of this lane: <= 32
+            uint32_t wmask = 0u;
+            for (uint32_t i0 = 0; i0 < mine; i0 += 4u) {
+                uint32_t z[4];
+#pragma unroll
+                for (uint32_t j = 0; j < 4u; ++j) {
+                    const uint32_t row = sub + 4u * (i0 + j);
+                    const uint32_t ky = (uint32_t)(((float)row + 0.5f) * inv_rw), t = t0 + ky * tiles_x + (row - ky * rw);
+                    // (behind the lane's last row: never written; a tile outside the image's: always, as `written` says)
+                    z[j] = i0 + j < mine ? (t < tiles ? zf[t] : 0xFFFFFFFFu) : 0u;
+                }
+#pragma unroll
+                for (uint32_t j = 0; j < 4u; ++j)
+                    if (rank < z[j]) wmask |= 1u << (i0 + j);
+            }
+            while (wmask) {
+                const uint32_t i1 = (uint32_t)__builtin_ctz(wmask);
+                wmask &= wmask - 1u;
+                const float2 *r = reinterpret_cast<const float2 *>(base + (size_t)(sub + 4u * i1) * FGS_BLEND_ROW_FLOATS);
+                if (wmask) {
+                    const uint32_t i2 = (uint32_t)__builtin_ctz(wmask);
+                    wmask &= wmask - 1u;
+                    const float2 *r2 = reinterpret_cast<const float2 *>(base + (size_t)(sub + 4u * i2) * FGS_BLEND_ROW_FLOATS);
+                    const float2 a = r[0], bq = r[1], cq = r[2], dq = r[3], eq = r[4];
+                    const float2 a2 = r2[0], bq2 = r2[1], cq2 = r2[2], dq2 = r2[3], eq2 = r2[4];
+                    add_row(a, bq, cq, dq, eq);
+                    add_row(a2, bq2, cq2, dq2, eq2);
+                } else {
+                    add_row(r[0], r[1], r[2], r[3], r[4]);
+                }
+            }
+            k = cnt;  // nothing is left for the loop below
+        } else if (!zf) {
+            // a Gaussian that looks nothing up (no table, or a rank below the image's smallest word): every row is written -- the
+            // loop below without its tests, the same additions in the same order
+            for (; k + 4 < cnt; k += 8) {
+                const float2 *r = reinterpret_cast<const float2 *>(base + (size_t)k * FGS_BLEND_ROW_FLOATS);
+                const float2 *r2 = reinterpret_cast<const float2 *>(base + (size_t)(k + 4) * FGS_BLEND_ROW_FLOATS);
+                const float2 a = r[0], bq = r[1], cq = r[2], dq = r[3], eq = r[4];
+                const float2 a2 = r2[0], bq2 = r2[1], cq2 = r2[2], dq2 = r2[3], eq2 = r2[4];
+                add_row(a, bq, cq, dq, eq);
+                add_row(a2, bq2, cq2, dq2, eq2);
+            }
+            if (k < cnt) {
+                const float2 *r = reinterpret_cast<const float2 *>(base + (size_t)k * FGS_BLEND_ROW_FLOATS);
+                add_row(r[0], r[1], r[2], r[3], r[4]);
+            }
+            k = cnt;
+        }
+        for (; k + 4 < cnt; k += 8) {  // rows k and k + 4 (a launch whose rectangles can exceed the mask)
             const float2 *r = reinterpret_cast<const float2 *>(base + (size_t)k * FGS_BLEND_ROW_FLOATS);
             const float2 *r2 = reinterpret_cast<const float2 *>(base + (size_t)(k + 4) * FGS_BLEND_ROW_FLOATS);
             const bool w1 = written(k), w2 = written(k + 4);
@@ -726,6 +785,32 @@ int fgs_launch_project(const FgsPlan &p, const float *cams, const float *pos, co
     return FGS_OK;
 }
 
+// The largest tile rectangle k_project can give a Gaussian (= its gradient rows): r <= max_radius (clamp_max), x0 = trunc(u - r),
+// x1 = trunc(u + r) + 1 in fp64 and clipped to the frame, so x1 - x0 <= ceil(2 r) + 1 pixels, which lie in at most
+// floor(ceil(2 r) / tile_w) + 1 tile columns (and no more than the frame has); rows alike with 16.  max_radius = 64: 5 x 9 tiles of
+// 32 x 16, 9 x 9 of 16 x 16 -- 81 rows, 21 per lane of k_row_sum.
+static uint32_t fgs_row_sum_max_rows(const FgsPlan &p) {
+    const double span = ceil(2.0 * (double)p.d.max_radius);
+    const double cols = fmin(floor(span / (double)p.tile_w) + 1.0, (double)p.L.tiles_x);
+    const double rows = fmin(floor(span / (double)FGS_TILE) + 1.0, (double)p.L.tiles_y);
+    const double n = cols * rows;
+    return n > 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)n;
+}
+
+int fgs_launch_row_sum(const FgsPlan &p, const char *saved, const float *grad_rows, float *row_sums, const uint32_t *zero_from,
+                       hipStream_t st) {
+    const int32_t total = p.d.batch * p.d.num_gaussians;
+    const int grid = (int)(((size_t)total * 4 + 255) / 256);
+    hipLaunchKernelGGL(k_row_sum, dim3(grid), dim3(256), 0, st, total, p.d.num_gaussians, (uint32_t)p.L.dup_capacity,
+                       reinterpret_cast<const uint32_t *>(saved + p.L.order), reinterpret_cast<const uint32_t *>(saved + p.L.dup_off),
+                       reinterpret_cast<const uint32_t *>(saved + p.L.tile_count), grad_rows,
+                       reinterpret_cast<const float *>(saved + p.L.rec), row_sums, zero_from,
+                       zero_from ? zero_from + (size_t)p.d.batch * p.tiles : nullptr, (uint32_t)p.tiles, (uint32_t)p.L.tiles_x,
+                       (uint32_t)p.tile_w, fgs_row_sum_max_rows(p) <= 4u * FGS_ROW_SUM_MASK_ROWS ? 1u : 0u);
+    FGS_LAUNCH_CHECK("k_row_sum");
+    return FGS_OK;
+}
+
 int fgs_launch_project_bwd(const FgsPlan &p, const float *cams, const float *pos, const float *scale,
                            const float *quat, const char *saved, const float *grad_rows, float *g_pos,
                            float *g_scale, float *g_quat, float *g_color, float *g_opacity, float *g_phase,
@@ -740,11 +825,7 @@ int fgs_launch_project_bwd(const FgsPlan &p, const float *cams, const float *pos
     if (!p.d.use_phase) {
         if (!row_sums) { fgs_set_error("fgs_launch_project_bwd: the blend path needs the row-sum scratch"); return FGS_EINVAL; }
         // blend path: streaming row sums at full occupancy, then one thread per Gaussian for the adjoint
-        hipLaunchKernelGGL(k_row_sum, dim3(grid), dim3(256), 0, st, total, p.d.num_gaussians,
-                           (uint32_t)p.L.dup_capacity, order, dup_off, tile_count, grad_rows, rec, row_sums,
-                           p.bwd_tail ? zero_from : nullptr, p.bwd_tail && zero_from ? zero_from + (size_t)p.d.batch * p.tiles : nullptr,
-                           (uint32_t)p.tiles, (uint32_t)p.L.tiles_x, (uint32_t)p.tile_w);
-        FGS_LAUNCH_CHECK("k_row_sum");
+        if (const int rc = fgs_launch_row_sum(p, saved, grad_rows, row_sums, p.bwd_tail ? zero_from : nullptr, st)) return rc;
         hipLaunchKernelGGL((k_project_bwd<0, true>), dim3((total + 255) / 256), dim3(256), 0, st, total,
                            p.d.num_gaussians, p.d.num_cameras, (uint32_t)p.L.dup_capacity, cams, pos, scale, quat,
                            depth_key, order, dup_off, tile_count, row_sums, g_pos, g_scale, g_quat, g_color, g_opacity,

@@ -64,6 +64,8 @@ extern "C" {
 #define FGS_BWD_ZERO_ON 0x800
 #define FGS_BWD_TAIL_OFF 0x2000 /* FgsDims.fwd_variant flags (values >= 0 only): the blend backward's one verdict per closed tile off / forced on */
 #define FGS_BWD_TAIL_ON 0x4000
+#define FGS_BWD_SUB_OFF 0x8000 /* FgsDims.fwd_variant flags (values >= 0 only): the blend backward's zero sub-tiles of general units off / forced on */
+#define FGS_BWD_SUB_ON 0x10000
 #define FGS_TUNE_AUTO 0    /* FgsDims.seg_len / fwd_variant / bin_mode: let the library choose        */
 #ifndef FGS_PHASE_CKPT
 #define FGS_PHASE_CKPT 8   /* phase path: entries of a sub-tile's (compacted) list between (A, Phi) checkpoints */
@@ -115,6 +117,11 @@ typedef struct FgsDims {
                                leaves those rows out of its sums (adding +-0 to a sum that is never -0 changes no bit).  No flag
                                = automatic: on wherever the four exist.  OFF: every unit decides for itself and writes its rows;
                                ON: as automatic (it cannot create what the plan lacks).
+                               Beside them a value >= 0 may carry ONE of FGS_BWD_SUB_OFF | FGS_BWD_SUB_ON.  A work unit of the blend
+                               backward that is NOT such a dead unit still leaves out the 8 x 8 sub-tiles in which every in-frame
+                               pixel restarts at zero transmittance and the remaining-sum S is an exact zero on every lane: their
+                               passes add exact zeros to sums that start at +0.  No flag = automatic: on wherever the zero rows
+                               above are on.  OFF: every touched sub-tile is composited; ON: forced at any size.
                                No flag is available with the row-split forward (values < 0).       */
     int32_t bin_mode;       /* tile binning: 0 | 1 = direct (column / row rank masks) | 2 = emit + stable radix sort */
     int32_t tile_w;         /* tile width in pixels: 0 | 16 | 32 (tiles are always 16 rows high).  0 = automatic:
@@ -235,6 +242,15 @@ int fgs_backward(const FgsDims *dims, const float *cameras, const float *pos, co
  * (SURVEY §8d unit of work): enqueues a reduction that writes one uint64 to
  * `out_pairs` (device). */
 int fgs_count_pairs(const FgsDims *dims, const void *saved, uint64_t *out_pairs, void *stream);
+
+/* The row-sum stage of fgs_backward's projection backward ALONE (blend path): per Gaussian the sum of its gradient rows, in the
+ * stage's fixed order, with the stage's factors -> row_sums [B*N][12] floats (ten used), by input index.  Reads of `saved` only
+ * rec, order, dup_off and tile_count (FgsSavedLayout); grad_rows [dup_capacity][10] floats.  zero_from: NULL, or B * tiles words
+ * (per tile the depth rank from which on a Gaussian's row of that tile is left out, 0xFFFFFFFF: none) followed by B words, each
+ * image's smallest -- the table fgs_backward builds for itself where the plan has the tail verdict.  For tests and tools: the order
+ * of the additions is the contract (tests/test_row_sum_prefetch_order.py). */
+int fgs_row_sum(const FgsDims *dims, const void *saved, const float *grad_rows, const uint32_t *zero_from, float *row_sums,
+                void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Angular-spectrum wave-field renderer: replaces ASMWaveFieldRenderer.forward (DR:1150-1344)

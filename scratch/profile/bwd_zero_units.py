@@ -8,7 +8,10 @@ prints the share of every kind out of all units and out of all list entries -- t
 profiles/r16_ab_bwd_zero_units.txt section 1.  `tuning` as bench.py --tuning takes it, e.g. tile_w=16.
 It also prints how many of the units are TAIL units (behind the closing slot of every half of their tile, saved.fwd_close), how many zero
 units are among them, and the summed launch-slot time (exit - entry clock) of every kind, 5 = a tail unit that left on its tile's
-verdict (k_bwd_tail_verdict) -- profiles/r17_ab_bwd_tail_verdict.txt sections 1 and 4."""
+verdict (k_bwd_tail_verdict) -- profiles/r17_ab_bwd_tail_verdict.txt sections 1 and 4.
+For the general units it prints their sub-tile passes and the share that lies in sub-tiles zero at the unit's restart (T == +0 on every
+in-frame lane, S == +-0 on every lane), counted by the trace build whether or not the walk masks them (tuning key bwd_sub) --
+profiles/r18_ab_bwd_zero_subtiles.txt section 1.  `--opacity X` (anywhere on the line) sets every opacity of the batch to X."""
 import ctypes
 import os
 import sys
@@ -23,12 +26,19 @@ bench._import_compute()
 from fresnel_amd import _binding as B  # noqa: E402
 from fresnel_amd import renderer as R  # noqa: E402
 
+opacity = None  # --opacity X: every opacity of the batch set to X (scratch/ab/opacity_batch.py's batch)
+if "--opacity" in sys.argv:
+    i = sys.argv.index("--opacity")
+    opacity = float(sys.argv[i + 1])
+    del sys.argv[i:i + 2]
 workload = sys.argv[1] if len(sys.argv) > 1 else "config3"
 distribution = sys.argv[2] if len(sys.argv) > 2 else "saag"
 tuning = sys.argv[3] if len(sys.argv) > 3 else ""
 dev = torch.device("cuda:0")
 N, S, Bn = bench.WORKLOADS[workload]
 pos, scale, quat, col, opa = bench.synth_batch(Bn, N, 1000 * int(workload[-1]), dev, distribution)
+if opacity is not None:
+    opa.fill_(opacity)
 leaves = [t.requires_grad_(True) for t in (pos, scale, quat, col, opa)]
 cam = R.Camera(0.8 * S, 0.8 * S, S / 2, S / 2, S, S)
 ren = R.TileBasedRenderer(S, S).to(dev)
@@ -74,6 +84,18 @@ for code, name in ((0, "general walk"), (3, "(a) zero units: S == +-0 on every l
                    (4, "(b) dead, some but not all sub-tiles all-zero"), (1, "(c) dead, no sub-tile all-zero")):
     m = walk == code
     print(f"  {name:62s} {int(m.sum()):7d} units = {100.0 * m.sum() / U:5.1f} %   {int(ulen[m].sum()):9d} entries = {100.0 * ulen[m].sum() / E:5.1f} %")
+# ZERO SUB-TILES OF GENERAL UNITS (profiles/r18_ab_bwd_zero_subtiles.txt section 1).  A general unit's record carries, behind the walk
+# code: bits 3-15 its sub-tile passes with none masked (sum over its entries of the touched sub-tiles), bits 16-28 those of them that
+# lie in a sub-tile that is zero at the unit's restart (T == +0 on every in-frame lane, S == +-0 on every lane), bit 29 whether it has
+# such a sub-tile at all.  Counted whether or not the walk masks them (tuning key bwd_sub).
+code = (rec[:, 2] >> np.uint64(32)).astype(np.int64)
+gen = walk == 0
+passes, zpasses, has = (code >> 3) & 0x1FFF, (code >> 16) & 0x1FFF, (code >> 29) & 1
+if gen.any():
+    print(f"  general units: {int(passes[gen].sum())} sub-tile passes ({passes[gen].sum() / max(int(ulen[gen].sum()), 1):.2f} per entry), "
+          f"{int(zpasses[gen].sum())} = {100.0 * zpasses[gen].sum() / max(int(passes[gen].sum()), 1):.2f} % in sub-tiles zero at restart; "
+          f"{int(has[gen].sum())} = {100.0 * has[gen].sum() / gen.sum():.1f} % of the general units have such a sub-tile, "
+          f"{int((zpasses[gen] > 0).sum())} of them a pass in one")
 dead = walk != 0
 print(f"  dead units in all: {100.0 * dead.sum() / U:.1f} % of the units, {100.0 * ulen[dead].sum() / E:.1f} % of the entries; "
       f"kind (a) is {100.0 * (walk == 3).sum() / max(int(dead.sum()), 1):.1f} % of the dead units")
