@@ -96,6 +96,10 @@ int fgs_match_backward(FgsMatchDims* dims, ptr pred target saved g_total g_pred 
 int fgs_slat_workspace_bytes(int32_t batch voxels per_voxel, size_t* scratch_bytes)
 int fgs_slat_head_forward(int32_t batch voxels per_voxel, ptr raw coords gains keep gaussians counts scratch, stream)
 int fgs_slat_head_backward(int32_t batch voxels per_voxel, ptr raw coords gains g_gaussians g_raw g_gains scratch, stream)
+int fgs_attn_workspace_bytes(int32_t batch queries keys heads head_dim, size_t* saved_bytes scratch_bytes)
+int fgs_attn_forward(int32_t batch queries keys heads head_dim, float scale dropout_p, ptr q kv row_keep seed out saved, stream)
+int fgs_attn_backward(int32_t batch queries keys heads head_dim, float scale dropout_p, ptr q kv row_keep seed out saved g_out g_q
+                      g_kv scratch, stream)
 int fgs_gather_forward(int32_t batch n_in n_out phase_channels, ptr indices pos scale quat color opacity phase o_pos o_scale o_quat
                        o_color o_opacity o_phase, stream)
 int fgs_gather_backward(int32_t batch n_in n_out phase_channels, ptr indices g_o_pos g_o_scale g_o_quat g_o_color g_o_opacity
@@ -271,6 +275,11 @@ class FgsMatchDims(ctypes.Structure):
     _fields_ = [("batch", ctypes.c_int32), ("num_pred", ctypes.c_int32), ("num_target", ctypes.c_int32),
                 ("w_pos", ctypes.c_float), ("w_scale", ctypes.c_float), ("w_rot", ctypes.c_float),
                 ("w_color", ctypes.c_float), ("w_opacity", ctypes.c_float), ("w_coverage", ctypes.c_float)]
+
+
+# the fused cross-attention's seams (include/fgs.h; tests/test_call_layer.py holds every macro restated here against the header):
+# queries per workgroup, keys per LDS tile, keys per workgroup of the key-block backward, largest head dimension
+FGS_ATTN_QUERY_BLOCK, FGS_ATTN_KEY_TILE, FGS_ATTN_KEY_BLOCK, FGS_ATTN_MAX_HEAD_DIM = 128, 32, 128, 128
 
 
 class FgsError(RuntimeError):

@@ -80,6 +80,9 @@ SOURCES = {
     "fgs_match.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     # as the head: the backward recomputes the forward from raw, and its clamp gates must be the forward's
     "fgs_slat.hip": ["-ffp-contract=off"],
+    # no FMA contraction: the backward recomputes p = exp(score - saved) and must round the score, S scale, as the forward did;
+    # fused into the subtraction it differs from the forward's by up to 2^-24 |score|, which at scores near 80 put g_q 6e-5 off
+    "fgs_attn.hip": ["-ffp-contract=off"],
 }
 LINK_LIBS = ["-lhipfft"]
 

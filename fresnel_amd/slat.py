@@ -7,11 +7,16 @@ reference's, so its checkpoints load with strict=True.  Embeddings, attention an
 behind the head MLP is `slat_gaussian_head`: the reference's torch expressions (backend "torch", runs anywhere) or the fused HIP
 kernels of csrc/fgs_slat.hip (backend "hip", CUDA/ROCm tensors only, no fallback).
 
+The attention between CrossAttention's Linear layers is `cross_attention`: the reference's op sequence (backend "torch") or the fused,
+flash-style HIP kernels of csrc/fgs_attn.hip (backend "hip": no score tensor, device-side dropout, bitwise repeatable); `DirectSLatDecoder`
+selects it with `attn_backend`, independently of the head.
+
 Both decoders take one extra keyword, `head_backend`.  With "torch" every host check of the reference stays (its
 `isnan(...).any()` tests and the per-image loop of the occupancy-gated inference).  With "hip" nothing in a training forward reads
 the host: the reference's conditional `nan_to_num` calls run unconditionally (the same values), the head applies the NaN rule of
 include/fgs.h on the device, and the gated inference is one compacting launch pair and ONE host copy of the per-image counts.
 """
+import ctypes
 from typing import Dict, Optional
 
 import torch
@@ -187,6 +192,119 @@ def slat_gaussian_head(raw: torch.Tensor, coords: torch.Tensor, position_offset_
     return _pack_torch(gaussians, keep, G) if keep is not None else gaussians
 
 
+# ---- the attention ----------------------------------------------------------------------------------------------------------------
+ATTN_BACKENDS = ("torch", "hip")
+
+
+def _check_attn_backend(attn_backend):
+    if attn_backend not in ATTN_BACKENDS:
+        raise ValueError(f"unknown attn_backend {attn_backend!r}: one of {ATTN_BACKENDS}")
+    return attn_backend
+
+
+def _attend_torch(q, k, v, scale, mask, drop, host_checks):
+    """The reference's attention of one block of queries (DSD:118-146): q (B, H, n, d), k and v (B, H, M, d) -> (B, n, H d).  `drop`
+    maps the probabilities to the dropped ones."""
+    Bn, H, n, d = q.shape
+    attn = (q @ k.transpose(-2, -1)) * scale
+    if mask is not None:
+        attn = attn.masked_fill(~mask.unsqueeze(1).unsqueeze(-1), -1e4)
+    attn = attn - attn.max(dim=-1, keepdim=True).values
+    attn = attn.softmax(dim=-1)
+    attn = drop(attn)
+    attn = _clean(attn, host_checks, nan=1.0 / attn.shape[-1])
+    return (attn @ v).transpose(1, 2).reshape(Bn, n, H * d)
+
+
+class _CrossAttnHip(torch.autograd.Function):
+    """fgs_attn_forward / _backward.  Saved: the inputs, the output and one float per (b, h, n); the backward regenerates the
+    dropout mask from the seed tensor.  Nothing synchronises with the host."""
+
+    @staticmethod
+    def forward(ctx, q, kv, row_keep, seed, num_heads, dropout_p):
+        dev = q.device
+        Bn, N, D = q.shape
+        dims = (Bn, N, kv.shape[1], num_heads, D // num_heads)
+        scale = float((D // num_heads) ** -0.5)
+        q_, kv_ = _f32c(q), _f32c(kv)
+        saved_bytes, _ = B.sizes("fgs_attn_workspace_bytes", *dims)
+        out = torch.empty((Bn, N, D), dtype=torch.float32, device=dev)
+        saved = torch.empty(saved_bytes, dtype=torch.uint8, device=dev)
+        hip.call(dev, "fgs_attn_forward", *dims, scale, dropout_p, q_, kv_, row_keep, seed, out, saved)
+        ctx.dims, ctx.scale, ctx.dropout_p = dims, scale, dropout_p
+        ctx.save_for_backward(q_, kv_, row_keep, seed, out, saved)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out):
+        q_, kv_, row_keep, seed, out, saved = ctx.saved_tensors
+        dev = q_.device
+        g_q, g_kv = torch.empty_like(q_), torch.empty_like(kv_)
+        _, scratch_bytes = B.sizes("fgs_attn_workspace_bytes", *ctx.dims)
+        scratch = torch.empty(scratch_bytes, dtype=torch.uint8, device=dev)
+        hip.call(dev, "fgs_attn_backward", *ctx.dims, ctx.scale, ctx.dropout_p, q_, kv_, row_keep, seed, out, saved, _f32c(g_out), g_q,
+                 g_kv, scratch)
+        return g_q, g_kv, None, None, None, None
+
+
+def cross_attention(q: torch.Tensor, kv: torch.Tensor, num_heads: int, *, mask: Optional[torch.Tensor] = None,
+                    dropout_p: float = 0.0, seed: Optional[torch.Tensor] = None, backend: str = "torch") -> torch.Tensor:
+    """The attention of the reference's CrossAttention between its Linear layers (DSD:105-146): q (B, N, D), the output of the query
+    projection, and kv (B, M, 2, H, d) or (B, M, 2 D), the output of the key/value projection (keys kv[:, :, 0], values kv[:, :, 1],
+    D = H d) -> (B, N, D), ready for the output projection.  Scores scale <q, k> with scale = d^-0.5; `mask` (B, N) bool: a False
+    row has every score filled with -1e4, so it attends uniformly (its output is the mean of v); softmax; dropout of the
+    probabilities with `dropout_p` in [0, 1) (0 = none; the caller decides whether it is training); a NaN probability becomes 1 / M.
+
+    backend "torch": the reference's op sequence, any device; dropout is torch's own (`seed` is not used).  backend "hip":
+    csrc/fgs_attn.hip -- one launch forward, three backward, fp32 on the matrix cores, nothing of size N x M stored, bitwise
+    repeatable, nothing read on the host; CUDA/ROCm tensors only, d <= 128, inputs cast to fp32 under autocast, no double
+    backward.  Its NaN rule (include/fgs.h): a row whose scores hold a NaN or +Inf, or are all -Inf, gets 1 / M each without
+    dropout -- the reference's values -- but is a constant of the backward (zero g_q row, g_kv through v only) where torch's
+    gradient is NaN-tainted.  Its dropout keeps element (b, h, n, m) by a stated counter-based function of `seed` (include/fgs.h),
+    a one-element int64 tensor on q's device; with dropout_p > 0 and no seed one is drawn by torch.randint on the device (it
+    follows torch.manual_seed, and nothing is read on the host)."""
+    _check_attn_backend(backend)
+    if isinstance(num_heads, bool) or int(num_heads) != num_heads or num_heads < 1:
+        raise ValueError(f"num_heads must be a positive integer, got {num_heads!r}")
+    num_heads = int(num_heads)
+    if q.dim() != 3 or q.shape[-1] % num_heads or 0 in q.shape:
+        raise ValueError(f"q must be (B, N, D) with D a multiple of num_heads = {num_heads} and no empty axis, got {tuple(q.shape)}")
+    Bn, N, D = q.shape
+    d = D // num_heads
+    if kv.dim() == 3 and kv.shape[-1] == 2 * D:
+        kv = kv.reshape(kv.shape[0], kv.shape[1], 2, num_heads, d)
+    if kv.dim() != 5 or kv.shape[0] != Bn or tuple(kv.shape[2:]) != (2, num_heads, d) or kv.shape[1] < 1:
+        raise ValueError(f"kv must be ({Bn}, M, 2, {num_heads}, {d}) or ({Bn}, M, {2 * D}) with M >= 1, got {tuple(kv.shape)}")
+    if mask is not None and (mask.dtype is not torch.bool or tuple(mask.shape) != (Bn, N)):
+        raise ValueError(f"mask must be a ({Bn}, {N}) bool tensor, got {tuple(mask.shape)} {mask.dtype}")
+    dropout_p = ctypes.c_float(dropout_p).value   # as the library sees it: fp32 (1 - 1e-9 is 1.0 there)
+    if not 0.0 <= dropout_p < 1.0:
+        raise ValueError(f"dropout_p must be in [0, 1), got {dropout_p!r}")
+    if backend == "torch":
+        k, v = kv.permute(2, 0, 3, 1, 4)
+        qh = q.reshape(Bn, N, num_heads, d).permute(0, 2, 1, 3)
+        drop = (lambda a: F.dropout(a, dropout_p, training=True)) if dropout_p > 0.0 else (lambda a: a)
+        return _attend_torch(qh, k, v, d ** -0.5, mask, drop, False)
+    who = "cross_attention (backend 'hip')"
+    if d > B.FGS_ATTN_MAX_HEAD_DIM:
+        raise ValueError(f"{who}: head dimension {d} > {B.FGS_ATTN_MAX_HEAD_DIM} is not supported")
+    if Bn * num_heads * N >= 2 ** 31:
+        raise ValueError(f"{who}: B x H x N = {Bn} x {num_heads} x {N} is beyond the supported size")
+    if not kv.is_contiguous() or not q.is_contiguous():
+        raise ValueError(f"{who}: q and kv must be contiguous -- the Linear layers' outputs as they are, not a permuted view")
+    if seed is not None and (not torch.is_tensor(seed) or seed.dtype is not torch.int64 or seed.numel() != 1):
+        raise ValueError(f"{who}: seed must be a one-element int64 tensor on q's device")
+    for t in (q, kv) + tuple(t for t in (mask, seed) if t is not None):
+        hip.need_cuda(t, who)
+        if t.device != q.device:
+            raise B.FgsError(f"{who}: tensors on {t.device} and {q.device}")
+    if dropout_p > 0.0 and seed is None:
+        seed = torch.randint(0, 2 ** 62, (1,), dtype=torch.int64, device=q.device)
+    row_keep = None if mask is None else mask.detach().contiguous().view(torch.uint8)  # a bool's byte is 0 or 1
+    return _CrossAttnHip.apply(q, kv, row_keep, seed if dropout_p > 0.0 else None, num_heads, dropout_p)
+
+
 # ---- the modules ------------------------------------------------------------------------------------------------------------------
 class PositionalEncoding3D(nn.Module):
     """Learnable per-axis embeddings of a voxel's coordinates (DSD:24-60): d_model // 3 channels for x and for y, the rest for z;
@@ -210,7 +328,9 @@ class CrossAttention(nn.Module):
     """Cross-attention from the voxels (queries) to the image features (keys, values) (DSD:63-182).  More than `chunk_size` queries
     are processed in chunks.  `mask` (B, N) masks whole QUERY rows with -1e4: every score of a padded voxel is the same, so it
     attends uniformly (the reference's behaviour, kept).  `host_checks` (an attribute, True as in the reference): test for NaN on
-    the host before replacing it; False replaces unconditionally."""
+    the host before replacing it; False replaces unconditionally.  `backend` (an attribute, "torch" as in the reference): "hip" runs
+    `cross_attention(..., backend="hip")` -- the query projection once for all N and ONE fused call whatever `chunk_size` is, with
+    attention dropout active iff the module is training and `attn_drop.p > 0`."""
 
     def __init__(self, dim: int, num_heads: int = 8, qkv_bias: bool = True, attn_drop: float = 0.0, proj_drop: float = 0.0,
                  chunk_size: int = 1024):
@@ -225,23 +345,22 @@ class CrossAttention(nn.Module):
         self.proj = nn.Linear(dim, dim)
         self.proj_drop = nn.Dropout(proj_drop)
         self.host_checks = True
+        self.backend = "torch"
 
     def _attend(self, x, k, v, mask):
         """One block of queries x (B, n, D) against all keys -> (B, n, D), before the output projection."""
         Bn, n, D = x.shape
         q = self.q(x).reshape(Bn, n, self.num_heads, self.head_dim).permute(0, 2, 1, 3)
-        attn = (q @ k.transpose(-2, -1)) * self.scale
-        if mask is not None:
-            attn = attn.masked_fill(~mask.unsqueeze(1).unsqueeze(-1), -1e4)
-        attn = attn - attn.max(dim=-1, keepdim=True).values
-        attn = attn.softmax(dim=-1)
-        attn = self.attn_drop(attn)
-        attn = _clean(attn, self.host_checks, nan=1.0 / attn.shape[-1])
-        return (attn @ v).transpose(1, 2).reshape(Bn, n, D)
+        return _attend_torch(q, k, v, self.scale, mask, self.attn_drop, self.host_checks)
 
     def forward(self, x: torch.Tensor, context: torch.Tensor, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         Bn, N, D = x.shape
         M = context.shape[1]
+        if _check_attn_backend(self.backend) == "hip":
+            p = self.attn_drop.p if self.training else 0.0
+            x = cross_attention(self.q(x), self.kv(context).reshape(Bn, M, 2, self.num_heads, self.head_dim), self.num_heads,
+                                mask=mask, dropout_p=p, backend="hip")
+            return self.proj_drop(self.proj(x))
         kv = self.kv(context).reshape(Bn, M, 2, self.num_heads, self.head_dim).permute(2, 0, 3, 1, 4)
         k, v = kv[0], kv[1]
         if N > self.chunk_size:
@@ -319,13 +438,18 @@ class DirectSLatDecoder(nn.Module):
     the gated inference computes keep = (sigmoid(logits) > threshold) & coord_mask, runs the head MLP on ALL voxels, calls the gated
     head once and reads the per-image counts with one host copy; the list entries are views of the packed tensor.  ONE RESTRICTION
     against the reference there: the gated head is inference-only, so on "hip" `forward(..., apply_occupancy_mask=True)` must run
-    under `torch.no_grad()` (a ValueError says so otherwise); the reference and the "torch" backend also accept it with grad enabled."""
+    under `torch.no_grad()` (a ValueError says so otherwise); the reference and the "torch" backend also accept it with grad enabled.
+
+    `attn_backend` "torch": the reference's chunked attention.  "hip": every block's cross-attention is the fused kernel of
+    `cross_attention` (no score tensor, no chunking, device-side dropout).  The two backends are independent."""
 
     def __init__(self, feature_dim: int = 1024, hidden_dim: int = 512, num_layers: int = 6, num_heads: int = 8,
                  num_gaussians_per_voxel: int = 8, max_resolution: int = 64, dropout: float = 0.1, use_checkpoint: bool = False,
-                 predict_occupancy: bool = True, occupancy_threshold: float = 0.5, head_backend: str = "torch"):
+                 predict_occupancy: bool = True, occupancy_threshold: float = 0.5, head_backend: str = "torch",
+                 attn_backend: str = "torch"):
         super().__init__()
         self.head_backend = _check_backend(head_backend)
+        self.attn_backend = _check_attn_backend(attn_backend)
         self.feature_dim = feature_dim
         self.hidden_dim = hidden_dim
         self.num_gaussians_per_voxel = num_gaussians_per_voxel
@@ -344,6 +468,7 @@ class DirectSLatDecoder(nn.Module):
         self.gaussian_head.backend = head_backend
         for block in self.blocks:
             block.cross_attn.host_checks = head_backend == "torch"
+            block.cross_attn.backend = attn_backend
 
     def _init_weights(self):
         """Every Linear gets Xavier-uniform weights -- gain 0.1 where the module's path contains "q", "kv" or "proj", 0.5 elsewhere --

@@ -921,6 +921,61 @@ int fgs_slat_head_backward(int32_t batch, int32_t voxels, int32_t per_voxel, con
                            void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Fused cross-attention of the distillation decoder (DSD: CrossAttention, 63-182): the voxels' queries against the image patches'
+ * keys and values, flash-style -- nothing of size N x M is stored.  The inputs are what the module's two Linear layers produce:
+ *   q   (B, N, H d) fp32 contiguous, the output of `self.q`;
+ *   kv  (B, M, 2, H, d) fp32 contiguous, the output of `self.kv`: kv[:, :, 0] the keys, kv[:, :, 1] the values (DSD:109);
+ *   out (B, N, H d), the tensor behind `.transpose(1, 2).reshape(B, N, D)`, ready for `self.proj`.
+ * For image b, head h, query n:
+ *   scores      s_m = scale <q, k_m> for m < M (the product is formed first, then scaled, as the reference does);
+ *   masked row  row_keep (B, N) bytes, may be NULL: where it is 0 every score is -1e4 (the reference's masked_fill).  Such a row
+ *               attends uniformly, its output is the mean of v (dropout applies to it), it contributes to g_kv through v only,
+ *               and its g_q row is zero;
+ *   softmax     p = softmax(s - max(s));
+ *   NaN rule    a row is BAD iff its NaN-propagating maximum is not finite: some score is NaN or +Inf, or all are -Inf.  A bad
+ *               row's probabilities are 1 / M each (the reference's nan_to_num(nan = 1 / M) behind its softmax), WITHOUT dropout
+ *               (the reference drops first and cleans second: the NaN stays NaN and becomes 1 / M unscaled).  A masked row is
+ *               never bad: the fill replaces its scores.  Stated difference, as for fgs_slat_*: a bad row is a constant of the
+ *               backward -- it contributes to g_kv through v only and its g_q row is zero, where torch's gradient is NaN-tainted;
+ *   dropout     dropout_p in [0, 1), 0 = none: p_m <- keep(b, h, n, m) p_m / (1 - dropout_p).  keep is a pure function of a 64-bit
+ *               seed -- ONE DEVICE int64, never read on the host; may be NULL when dropout_p is 0 -- and the indices.  With
+ *               fmix(x): x ^= x >> 16; x *= 0x85EBCA6B; x ^= x >> 13; x *= 0xC2B2AE35; x ^= x >> 16 (murmur3's finaliser, uint32
+ *               arithmetic), lo / hi the seed's low / high 32 bits and row = (b H + h) N + n:
+ *                   x = fmix(fmix(row ^ lo) ^ hi ^ (m * 0x9E3779B1));      keep iff (x >> 8) >= T,
+ *               T = dropout_p (as fp32) x 2^24 rounded to nearest, ties to even.  tests/attn_checker.py restates it in numpy.
+ *               The backward regenerates the mask from the same seed;
+ *   output      out = sum_m p_m v_m.  A NaN in v reaches the output as in torch.
+ * Backward, with a_m the probabilities after dropout, c_m = keep / (1 - dropout_p), dA_m = <g_out, v_m>, delta = <g_out, out>:
+ * dS_m = p_m (c_m dA_m - delta) on open rows and 0 on masked and bad ones; g_q = scale sum_m dS_m k_m; g_k(m) = scale sum_n dS_nm q_n;
+ * g_v(m) = sum_n a_nm g_out_n.
+ *
+ * fp32 end to end on the fp32-input matrix cores (exact fp32 FMA chains).  fgs_attn_forward: ONE launch; a workgroup owns
+ * FGS_ATTN_QUERY_BLOCK queries of one (b, h) and walks the keys in LDS tiles of FGS_ATTN_KEY_TILE with an online softmax; any
+ * head_dim <= FGS_ATTN_MAX_HEAD_DIM runs zero-padded to 32, 64 or 128.  saved: one float per (b, h, n), max + ln(sum), +Inf for a
+ * bad row.  fgs_attn_backward: three launches (delta; g_q by query blocks; g_kv by blocks of FGS_ATTN_KEY_BLOCK keys that sweep all
+ * queries) --
+ * no float atomics, nothing summed across workgroups, so two calls agree to the bit and an image's result does not depend on
+ * its batch.  `out` is the forward's output.  Every element of out, saved, g_q (zero rows included) and g_kv (both halves) is
+ * written; scratch is written before it is read; inputs are never modified.  No call synchronises the host or allocates; with
+ * a seed TENSOR the calls can be captured (the seed is read at replay).
+ * The backward recomputes p = exp(s - saved) with s rounded exactly as in the forward (the unit is compiled without FMA contraction).
+ * Shapes go as plain integers (the set of structures of this header is closed): batch = B, queries = N, keys = M, heads = H,
+ * head_dim = d, all >= 1; d <= 128; B H N < 2^31; 0 <= dropout_p < 1; otherwise FGS_EINVAL / FGS_EUNSUPPORTED before anything
+ * touches the device. */
+#define FGS_ATTN_QUERY_BLOCK 128
+#define FGS_ATTN_KEY_TILE 32
+#define FGS_ATTN_KEY_BLOCK 128
+#define FGS_ATTN_MAX_HEAD_DIM 128
+int fgs_attn_workspace_bytes(int32_t batch, int32_t queries, int32_t keys, int32_t heads, int32_t head_dim, size_t *saved_bytes,
+                             size_t *scratch_bytes);
+int fgs_attn_forward(int32_t batch, int32_t queries, int32_t keys, int32_t heads, int32_t head_dim, float scale, float dropout_p,
+                     const float *q, const float *kv, const uint8_t *row_keep /* (B,N) or NULL */,
+                     const int64_t *seed /* 1, device; NULL with dropout_p 0 */, float *out, void *saved, void *stream);
+int fgs_attn_backward(int32_t batch, int32_t queries, int32_t keys, int32_t heads, int32_t head_dim, float scale, float dropout_p,
+                      const float *q, const float *kv, const uint8_t *row_keep, const int64_t *seed, const float *out,
+                      const void *saved, const float *g_out, float *g_q, float *g_kv, void *scratch, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Importance-subsampling hand-off between decoder and rasterizer (--stochastic_k; reference
  * scripts/training/train_gaussian_decoder.py:1160-1187): the n_out Gaussians whose indices torch.multinomial
  * drew (DEVICE int64 (n_out,), unique, shared by the batch) are gathered out of every (B, n_in, .) tensor into
