@@ -100,6 +100,10 @@ int fgs_attn_workspace_bytes(int32_t batch queries keys heads head_dim, size_t* 
 int fgs_attn_forward(int32_t batch queries keys heads head_dim, float scale dropout_p, ptr q kv row_keep seed out saved, stream)
 int fgs_attn_backward(int32_t batch queries keys heads head_dim, float scale dropout_p, ptr q kv row_keep seed out saved g_out g_q
                       g_kv scratch, stream)
+int fgs_wave_attn_workspace_bytes(int32_t batch grid_h grid_w heads head_dim, size_t* saved_bytes scratch_bytes)
+int fgs_wave_attn_forward(int32_t batch grid_h grid_w heads head_dim, float scale, ptr qkv wavelength out saved, stream)
+int fgs_wave_attn_backward(int32_t batch grid_h grid_w heads head_dim, float scale, ptr qkv wavelength out saved g_out g_qkv
+                           g_wavelength scratch, stream)
 int fgs_gather_forward(int32_t batch n_in n_out phase_channels, ptr indices pos scale quat color opacity phase o_pos o_scale o_quat
                        o_color o_opacity o_phase, stream)
 int fgs_gather_backward(int32_t batch n_in n_out phase_channels, ptr indices g_o_pos g_o_scale g_o_quat g_o_color g_o_opacity
@@ -280,6 +284,7 @@ class FgsMatchDims(ctypes.Structure):
 # the fused cross-attention's seams (include/fgs.h; tests/test_call_layer.py holds every macro restated here against the header):
 # queries per workgroup, keys per LDS tile, keys per workgroup of the key-block backward, largest head dimension
 FGS_ATTN_QUERY_BLOCK, FGS_ATTN_KEY_TILE, FGS_ATTN_KEY_BLOCK, FGS_ATTN_MAX_HEAD_DIM = 128, 32, 128, 128
+FGS_WAVE_ATTN_MAX_TOKENS = 4096
 
 
 class FgsError(RuntimeError):

@@ -976,6 +976,61 @@ int fgs_attn_backward(int32_t batch, int32_t queries, int32_t keys, int32_t head
                       const void *saved, const float *g_out, float *g_q, float *g_kv, void *scratch, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Fused wave self-attention of the consistency view synthesizer (scripts/models/consistency_view_synthesis.py, "CVS":
+ * FresnelWaveAttention, 191-246): multi-head self-attention over the N = grid_h grid_w tokens of a feature map, with an interference
+ * term that depends on the two tokens' grid distance added to the logits, flash-style -- nothing of size N x N is stored.
+ *   qkv         (B, N, 3, H, d) fp32 contiguous, the output of `to_qkv` as it is (chunk(3, -1), then view(B, N, H, d)): qkv[:, :, 0]
+ *               the queries, [:, :, 1] the keys, [:, :, 2] the values.  Read in place;
+ *   token n     sits at y = n / grid_w, x = n % grid_w;
+ *   wavelength  ONE DEVICE float (the module's learnable scalar), read by the kernels, never on the host;
+ *   out         (B, N, H d), the tensor behind `.transpose(1, 2).reshape(B, N, H d)`, ready for `to_out`.
+ * For image b, head h, query n and key m, with dy, dx the tokens' coordinate differences and lambda = wavelength:
+ *   score       s(n, m) = (<q_n, k_m> scale) + bias(n, m): the product is formed first, then scaled; the bias is NOT scaled;
+ *   bias        every operation rounded to fp32 on its own, in the reference's order (CVS:229-238), divide and square root IEEE,
+ *               cosf / sinf the accurate ones (phases reach hundreds of radians at the default wavelength):
+ *                   dist = sqrtf((dy*dy + dx*dx) + 1e-8f)
+ *                   den  = fabsf(lambda) * (float)grid_h + 1e-6f        -- grid_h, not grid_w, whatever the grid's shape
+ *                   phi  = (6.2831855f * dist) / den
+ *                   bias = 0.1f * cosf(phi)
+ *   softmax     p = softmax(s - max(s)) as in fgs_attn_*, without mask and without dropout (the module has neither);
+ *   NaN         the module has no nan_to_num and none is added.  A row whose NaN-propagating maximum is not finite (a NaN or +Inf
+ *               score, or every score -Inf) gets a NaN output row, as torch's softmax gives, and its `saved` value is NaN; the other
+ *               rows keep the bits of a clean run.  The backward lets it propagate as torch does: NaN in that (b, h)'s g_qkv and
+ *               in g_wavelength; every other (b, h) keeps the bits of a clean run;
+ *   output      out = sum_m p_m v_m.
+ * Backward, with dA(n, m) = <g_out_n, v_m>, delta_n = <g_out_n, out_n>: dS(n, m) = p (dA - delta); g_q = scale sum_m dS k_m;
+ * g_k(m) = scale sum_n dS q_n; g_v(m) = sum_n p g_out_n; and, dS entering UNSCALED,
+ *   g_wavelength = sign(lambda) grid_h / den  sum_{b, h, n, m} dS(n, m) 0.1 sin(phi(n, m)) phi(n, m),
+ * which is 0 at lambda == 0 (torch's subgradient of abs).  In this factor phi = 6.283185307179586 sqrt((dy*dy + dx*dx) + 1e-8) / den is
+ * evaluated in double (den the fp32 value above) and 0.1 sin(phi) phi rounded to fp32 once: the fp32 rounding of a phase of
+ * thousands of radians, harmless behind the cosine of the forward, is multiplied by phi here.  The sum is formed in double: per lane,
+ * per workgroup in a fixed-shape tree, and over the workgroups in a fixed order by one small launch.
+ *
+ * fp32 end to end on the fp32-input matrix cores with the tiling of fgs_attn_* (FGS_ATTN_QUERY_BLOCK queries per workgroup, key
+ * tiles of FGS_ATTN_KEY_TILE, key blocks of FGS_ATTN_KEY_BLOCK in the backward, head_dim zero-padded to 32, 64 or 128).  The bias
+ * depends on (|dy|, |dx|) only: each workgroup builds a table of grid_h grid_w floats in LDS once and adds it by lookup.
+ * fgs_wave_attn_forward: ONE launch.  saved: one float per (b, h, n), max + ln(sum).  fgs_wave_attn_backward: four launches (delta;
+ * g_q by query blocks, with the wavelength partials; g_k and g_v by key blocks that sweep all queries; the fold -- three when
+ * g_wavelength is NULL).  No float atomics, nothing summed across workgroups except by the fold: two calls agree to the bit in every
+ * output, and out and g_qkv of an image do not depend on the batch it sits in (g_wavelength sums over the batch).  The backward
+ * recomputes p = exp(s - saved) with s rounded exactly as in the forward (the unit is compiled without FMA contraction).
+ * saved_bytes: 4 B H N rounded up to 256.  scratch_bytes: the same (delta) plus 8 B H ceil(N / FGS_ATTN_QUERY_BLOCK) rounded up to 256
+ * (the partials).  Every element of out, saved, g_qkv (all three thirds) and g_wavelength is written; scratch is written before it
+ * is read; inputs are never modified.  No call synchronises the host or allocates: the calls can be captured, and a replay reads
+ * the wavelength again.
+ * Shapes go as plain integers: batch = B, grid_h, grid_w, heads = H, head_dim = d, all >= 1; d <= FGS_ATTN_MAX_HEAD_DIM;
+ * grid_h grid_w <= FGS_WAVE_ATTN_MAX_TOKENS (the tables live in LDS); B H N < 2^31; scale finite; otherwise FGS_EINVAL (bad dims,
+ * null pointers, scale) / FGS_EUNSUPPORTED before anything touches the device. */
+#define FGS_WAVE_ATTN_MAX_TOKENS 4096
+int fgs_wave_attn_workspace_bytes(int32_t batch, int32_t grid_h, int32_t grid_w, int32_t heads, int32_t head_dim, size_t *saved_bytes,
+                                  size_t *scratch_bytes);
+int fgs_wave_attn_forward(int32_t batch, int32_t grid_h, int32_t grid_w, int32_t heads, int32_t head_dim, float scale,
+                          const float *qkv, const float *wavelength /* 1, device */, float *out, void *saved, void *stream);
+int fgs_wave_attn_backward(int32_t batch, int32_t grid_h, int32_t grid_w, int32_t heads, int32_t head_dim, float scale,
+                           const float *qkv, const float *wavelength, const float *out, const void *saved, const float *g_out,
+                           float *g_qkv, float *g_wavelength /* 1, or NULL */, void *scratch, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Importance-subsampling hand-off between decoder and rasterizer (--stochastic_k; reference
  * scripts/training/train_gaussian_decoder.py:1160-1187): the n_out Gaussians whose indices torch.multinomial
  * drew (DEVICE int64 (n_out,), unique, shared by the batch) are gathered out of every (B, n_in, .) tensor into
