@@ -104,6 +104,10 @@ int fgs_wave_attn_workspace_bytes(int32_t batch grid_h grid_w heads head_dim, si
 int fgs_wave_attn_forward(int32_t batch grid_h grid_w heads head_dim, float scale, ptr qkv wavelength out saved, stream)
 int fgs_wave_attn_backward(int32_t batch grid_h grid_w heads head_dim, float scale, ptr qkv wavelength out saved g_out g_qkv
                            g_wavelength scratch, stream)
+int fgs_gn_silu_workspace_bytes(int32_t batch channels hw groups, size_t* saved_bytes scratch_bytes)
+int fgs_gn_silu_forward(int32_t batch channels hw groups act, float eps, ptr x channel_bias weight bias out saved scratch, stream)
+int fgs_gn_silu_backward(int32_t batch channels hw groups act, float eps, ptr x channel_bias weight bias saved g_out g_x g_channel_bias
+                         g_weight g_bias scratch, stream)
 int fgs_gather_forward(int32_t batch n_in n_out phase_channels, ptr indices pos scale quat color opacity phase o_pos o_scale o_quat
                        o_color o_opacity o_phase, stream)
 int fgs_gather_backward(int32_t batch n_in n_out phase_channels, ptr indices g_o_pos g_o_scale g_o_quat g_o_color g_o_opacity
@@ -285,6 +289,7 @@ class FgsMatchDims(ctypes.Structure):
 # queries per workgroup, keys per LDS tile, keys per workgroup of the key-block backward, largest head dimension
 FGS_ATTN_QUERY_BLOCK, FGS_ATTN_KEY_TILE, FGS_ATTN_KEY_BLOCK, FGS_ATTN_MAX_HEAD_DIM = 128, 32, 128, 128
 FGS_WAVE_ATTN_MAX_TOKENS = 4096
+FGS_GN_SEGMENT = 4096  # floats of one channel row per wave of the fused GroupNorm-SiLU: longer rows are cut there (include/fgs.h)
 
 
 class FgsError(RuntimeError):

@@ -88,6 +88,9 @@ SOURCES = {
     # DEFINED with every operation rounded on its own (include/fgs.h), and a phase of thousands of radians (wavelength 1e-3) turns an
     # ulp of the quotient into 1e-4 of a radian.  No fast-math: cosf / sinf are the accurate ones, with the large-argument reduction
     "fgs_wave_attn.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
+    # no FMA contraction: forward, segment sums and backward apply recompute xhat and y from x with the same roundings, so the
+    # g_y the sums saw is the g_y the apply uses (a one-element group's g_x then cancels to exactly zero)
+    "fgs_gn_silu.hip": ["-ffp-contract=off"],
 }
 LINK_LIBS = ["-lhipfft"]
 

@@ -1,8 +1,17 @@
-"""The attention block of the consistency view synthesizer (scripts/models/consistency_view_synthesis.py, "CVS").
+"""The consistency view synthesizer (scripts/models/consistency_view_synthesis.py, "CVS").
 
-`GroupNorm32`, `CrossAttention`, `FresnelWaveAttention` and `AttentionBlock` mirror the reference's classes of the same names:
-constructor arguments and defaults, module tree, parameter names and returned tensors are the reference's, so its state dicts load
-with strict=True.  The rest of the U-Net (ResBlock, sampling, pose encoder, the synthesizer and its losses) is not here.
+`CVSConfig`, `SinusoidalPosEmbed`, `GroupNorm32`, `ResBlock`, `CrossAttention`, `FresnelWaveAttention`, `AttentionBlock`,
+`Downsample`, `Upsample`, `PluckerPoseEncoder`, `ImageFeatureAdapter`, `ConsistencyUNet`, `ConsistencyViewSynthesizer`,
+`create_ema_model`, `update_ema` and `get_relative_pose` mirror the reference's classes and functions of the same names: constructor
+arguments and defaults, module tree, parameter names and returned tensors are the reference's, so its state dicts load with
+strict=True.  Its losses (ConsistencyLoss, QualityAwareCVSLoss) and train_cvs.py are not here.
+
+The GroupNorm32 -> SiLU pairs of the U-Net are `group_norm_act`: backend "torch" is the reference's op sequence (the broadcast add
+of the time embedding, group_norm, silu: seven passes over the activation, three tensors of its size kept for the backward);
+backend "hip" is csrc/fgs_gn_silu.hip (definition: include/fgs.h, fgs_gn_silu_*): the add folded into the read, two launches
+forward, four backward, the backward recomputed from x, nothing of the activation's size stored but the output.  Every ResBlock and
+AttentionBlock has a `norm_backend` attribute, "torch" by default; `ConsistencyUNet(config, norm_backend=, attn_backend=)` and the
+synthesizer set them all.
 
 The attention between FresnelWaveAttention's Linear layers is `fresnel_wave_attention`: self-attention over the H x W tokens of a
 feature map with the interference term 0.1 cos(2 pi dist / (|wavelength| H + 1e-6)) added to the logits.  backend "torch" is the
@@ -17,7 +26,8 @@ to_k / to_v weights, have exactly the layout `fresnel_amd.slat.cross_attention(b
 Every attention module has a `backend` attribute, "torch" by default; `AttentionBlock(..., attn_backend="hip")` sets both.
 """
 import math
-from typing import Tuple
+from dataclasses import dataclass
+from typing import Dict, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -29,7 +39,15 @@ from . import _hip as hip
 from .slat import cross_attention
 
 ATTN_BACKENDS = ("torch", "hip")
+NORM_BACKENDS = ("torch", "hip")
+NORM_ACTS = ("none", "silu")   # the index is fgs_gn_silu_*'s `act`
 _f32c = hip.f32c
+
+
+def _check_norm_backend(norm_backend):
+    if norm_backend not in NORM_BACKENDS:
+        raise ValueError(f"unknown norm_backend {norm_backend!r}: one of {NORM_BACKENDS}")
+    return norm_backend
 
 
 def _check_attn_backend(attn_backend):
@@ -135,12 +153,170 @@ def fresnel_wave_attention(qkv: torch.Tensor, grid: Tuple[int, int], wavelength:
     return _WaveAttnHip.apply(qkv, wavelength, (H, W), num_heads)
 
 
+# ---- GroupNorm -> SiLU -------------------------------------------------------------------------------------------------------------
+class _GroupNormActHip(torch.autograd.Function):
+    """fgs_gn_silu_forward / _backward.  Saved: x, the channel bias, the norm's weight and bias, and (mean, rstd) per (b, group) --
+    nothing else of the activation's size: not the sum x + channel_bias, not the normalised tensor, not the output."""
+
+    @staticmethod
+    def forward(ctx, x, channel_bias, weight, bias, groups, act, eps):
+        dev = x.device
+        Bn, C = x.shape[:2]
+        dims = (Bn, C, x.numel() // (Bn * C), groups)
+        x_, cb_, w_, b_ = _f32c(x), _f32c(channel_bias), _f32c(weight), _f32c(bias)
+        if x_.data_ptr() % 16:   # (a contiguous view that starts inside its storage)
+            x_ = x_.clone()
+        saved_bytes, scratch_bytes = B.sizes("fgs_gn_silu_workspace_bytes", *dims)
+        out = torch.empty(x.shape, dtype=torch.float32, device=dev)
+        saved = torch.empty(saved_bytes, dtype=torch.uint8, device=dev)
+        scratch = torch.empty(scratch_bytes, dtype=torch.uint8, device=dev)
+        hip.call(dev, "fgs_gn_silu_forward", *dims, act, eps, x_, cb_, w_, b_, out, saved, scratch)
+        ctx.dims, ctx.act, ctx.eps = dims, act, eps
+        ctx.save_for_backward(x_, cb_, w_, b_, saved)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out):
+        x_, cb_, w_, b_, saved = ctx.saved_tensors
+        dev = x_.device
+        g_ = _f32c(g_out)
+        if g_.data_ptr() % 16:
+            g_ = g_.clone()
+        g_x = torch.empty_like(x_)
+        g_cb = torch.empty_like(cb_) if cb_ is not None else None
+        g_w, g_b = torch.empty_like(w_), torch.empty_like(b_)
+        _, scratch_bytes = B.sizes("fgs_gn_silu_workspace_bytes", *ctx.dims)
+        scratch = torch.empty(scratch_bytes, dtype=torch.uint8, device=dev)
+        hip.call(dev, "fgs_gn_silu_backward", *ctx.dims, ctx.act, ctx.eps, x_, cb_, w_, b_, saved, g_, g_x, g_cb, g_w, g_b, scratch)
+        return g_x, g_cb, g_w, g_b, None, None, None
+
+
+def group_norm_act(x: torch.Tensor, num_groups: int, weight: torch.Tensor, bias: torch.Tensor, *, channel_bias=None,
+                   act: str = "silu", eps: float = 1e-5, backend: str = "torch") -> torch.Tensor:
+    """GroupNorm32 followed by SiLU, with an optional per-(image, channel) bias added first -- the two norms of the reference's
+    ResBlock (CVS:121-131; `channel_bias` is `time_proj(t_emb)`, the time embedding the block adds before its second norm):
+    x (B, C, ...) -> act(group_norm(x.float() + channel_bias[:, :, None, None], num_groups, weight, bias, eps)).type(x.dtype), act
+    "silu" or "none".
+
+    backend "torch": exactly those ops, any device.  backend "hip": csrc/fgs_gn_silu.hip (definition: include/fgs.h,
+    fgs_gn_silu_*) -- two launches forward, four backward; the sum and the normalised tensor are never stored, the backward
+    recomputes them from x; two-pass moments per segment combined in double; bitwise repeatable; CUDA/ROCm tensors only, B C HW < 2^31,
+    inputs cast to fp32, no double backward."""
+    if backend not in NORM_BACKENDS:
+        raise ValueError(f"unknown norm_backend {backend!r}: one of {NORM_BACKENDS}")
+    if act not in NORM_ACTS:
+        raise ValueError(f"unknown act {act!r}: one of {NORM_ACTS}")
+    if isinstance(num_groups, bool) or int(num_groups) != num_groups or num_groups < 1:
+        raise ValueError(f"num_groups must be a positive integer, got {num_groups!r}")
+    num_groups = int(num_groups)
+    if x.dim() < 2 or 0 in x.shape or x.shape[1] % num_groups:
+        raise ValueError(f"x must be (B, C, ...) with C a multiple of num_groups = {num_groups} and no empty axis, got {tuple(x.shape)}")
+    Bn, C = x.shape[:2]
+    for name, t in (("weight", weight), ("bias", bias)):
+        if not torch.is_tensor(t) or tuple(t.shape) != (C,):
+            raise ValueError(f"{name} must be a tensor of shape ({C},), got {tuple(t.shape) if torch.is_tensor(t) else t!r}")
+    if channel_bias is not None and (not torch.is_tensor(channel_bias) or tuple(channel_bias.shape) != (Bn, C)):
+        raise ValueError(f"channel_bias must be a tensor of shape ({Bn}, {C}), got "
+                         f"{tuple(channel_bias.shape) if torch.is_tensor(channel_bias) else channel_bias!r}")
+    eps = float(eps)
+    if not (math.isfinite(eps) and eps > 0.0):
+        raise ValueError(f"eps must be a finite positive number, got {eps!r}")
+    if backend == "torch":
+        u = x.float()
+        if channel_bias is not None:
+            u = u + channel_bias[(..., *([None] * (x.dim() - 2)))]
+        y = F.group_norm(u, num_groups, weight, bias, eps)
+        return (F.silu(y) if act == "silu" else y).type(x.dtype)
+    who = "group_norm_act (backend 'hip')"
+    if x.numel() >= 2 ** 31:
+        raise ValueError(f"{who}: {x.numel()} elements are beyond the supported size (2^31)")
+    for t in (x, weight, bias, channel_bias):
+        if t is not None:
+            hip.need_cuda(t, who)
+            if t.device != x.device:
+                raise B.FgsError(f"{who}: tensors on {t.device} and {x.device}")
+    return _GroupNormActHip.apply(x, channel_bias, weight, bias, num_groups, NORM_ACTS.index(act), eps).type(x.dtype)
+
+
 # ---- the modules ------------------------------------------------------------------------------------------------------------------
+@dataclass
+class CVSConfig:
+    """The synthesizer's configuration (CVS:27-59); `channels` = base_channels x channel_mult."""
+    image_size: int = 256
+    latent_channels: int = 4
+    base_channels: int = 128
+    channel_mult: Tuple[int, ...] = (1, 2, 3, 4)
+    num_res_blocks: int = 2
+    attention_resolutions: Tuple[int, ...] = (16, 8)
+    pose_embed_dim: int = 256
+    image_embed_dim: int = 384
+    cross_attention_dim: int = 384
+    time_embed_dim: int = 256
+    num_timesteps: int = 1000
+    beta_start: float = 0.00085
+    beta_end: float = 0.012
+    ema_decay: float = 0.9999
+
+    def __post_init__(self):
+        self.channels = [self.base_channels * m for m in self.channel_mult]
+
+
+class SinusoidalPosEmbed(nn.Module):
+    """Timesteps (B,) -> (B, dim): sines, then cosines, of t x 10000^(-i / (dim / 2 - 1)) (CVS:66-80)."""
+
+    def __init__(self, dim: int):
+        super().__init__()
+        self.dim = dim
+
+    def forward(self, t: torch.Tensor) -> torch.Tensor:
+        half = self.dim // 2
+        step = math.log(10000) / (half - 1)
+        freq = torch.exp(torch.arange(half, device=t.device) * -step)
+        angle = t[:, None] * freq[None, :]
+        return torch.cat([torch.sin(angle), torch.cos(angle)], dim=-1)
+
+
 class GroupNorm32(nn.GroupNorm):
     """GroupNorm computed in float32 (CVS:83-87)."""
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         return super().forward(x.float()).type(x.dtype)
+
+
+def _norm_hip(norm, x, act, channel_bias=None):
+    return group_norm_act(x, norm.num_groups, norm.weight, norm.bias, channel_bias=channel_bias, act=act, eps=norm.eps, backend="hip")
+
+
+class ResBlock(nn.Module):
+    """norm1 -> SiLU -> conv1, + time_proj(t_emb) per channel, norm2 -> SiLU -> dropout -> conv2, + skip(x) (CVS:90-134).
+    `norm_backend` (an attribute, "torch" as in the reference): with "hip" each norm -> SiLU pair is ONE `group_norm_act` call, and
+    the second takes the time embedding as its `channel_bias` -- the sum conv1(..) + embedding is never materialised.  Dropout stays
+    torch's, on the fused output."""
+
+    def __init__(self, in_channels: int, out_channels: int, time_embed_dim: int, dropout: float = 0.0):
+        super().__init__()
+        self.in_channels = in_channels
+        self.out_channels = out_channels
+        self.norm1 = GroupNorm32(32, in_channels)
+        self.conv1 = nn.Conv2d(in_channels, out_channels, 3, padding=1)
+        self.time_proj = nn.Sequential(nn.SiLU(), nn.Linear(time_embed_dim, out_channels))
+        self.norm2 = GroupNorm32(32, out_channels)
+        self.dropout = nn.Dropout(dropout)
+        self.conv2 = nn.Conv2d(out_channels, out_channels, 3, padding=1)
+        self.skip = nn.Conv2d(in_channels, out_channels, 1) if in_channels != out_channels else nn.Identity()
+        self.norm_backend = "torch"
+
+    def forward(self, x: torch.Tensor, t_emb: torch.Tensor) -> torch.Tensor:
+        if _check_norm_backend(self.norm_backend) == "hip":
+            h = self.conv1(_norm_hip(self.norm1, x, "silu"))
+            h = _norm_hip(self.norm2, h, "silu", channel_bias=self.time_proj(t_emb))
+        else:
+            h = self.conv1(F.silu(self.norm1(x)))
+            h = h + self.time_proj(t_emb)[:, :, None, None]
+            h = F.silu(self.norm2(h))
+        h = self.conv2(self.dropout(h))
+        return h + self.skip(x)
 
 
 class CrossAttention(nn.Module):
@@ -208,10 +384,13 @@ class FresnelWaveAttention(nn.Module):
 
 class AttentionBlock(nn.Module):
     """x + self_attn(norm1(x)), then x + cross_attn(norm2(x), context) (CVS:249-288).  `use_fresnel=False` makes the self-attention
-    a CrossAttention of the feature map to its own tokens.  `attn_backend` sets the `backend` of both attention modules."""
+    a CrossAttention of the feature map to its own tokens.  `attn_backend` sets the `backend` of both attention modules;
+    `norm_backend` (an attribute of the same name, "torch" by default): with "hip" both norms run as `group_norm_act(act="none")`."""
 
-    def __init__(self, channels: int, context_dim: int, use_fresnel: bool = True, attn_backend: str = "torch"):
+    def __init__(self, channels: int, context_dim: int, use_fresnel: bool = True, attn_backend: str = "torch",
+                 norm_backend: str = "torch"):
         super().__init__()
+        self.norm_backend = _check_norm_backend(norm_backend)
         self.norm1 = GroupNorm32(32, channels)
         if use_fresnel:
             self.self_attn = FresnelWaveAttention(channels)
@@ -222,14 +401,269 @@ class AttentionBlock(nn.Module):
         self.self_attn.backend = self.cross_attn.backend = _check_attn_backend(attn_backend)
 
     def forward(self, x: torch.Tensor, context: torch.Tensor) -> torch.Tensor:
-        h = self.norm1(x)
+        fused = _check_norm_backend(self.norm_backend) == "hip"
+        h = _norm_hip(self.norm1, x, "none") if fused else self.norm1(x)
         if isinstance(self.self_attn, FresnelWaveAttention):
             h = self.self_attn(h)
         else:
             h_flat = h.view(h.shape[0], h.shape[1], -1).permute(0, 2, 1)
             h = self.self_attn(h, h_flat)
         x = x + h
-        h = self.norm2(x)
+        h = _norm_hip(self.norm2, x, "none") if fused else self.norm2(x)
         h = self.cross_attn(h, context)
         x = x + h
         return x
+
+
+class Downsample(nn.Module):
+    """Stride-2 3 x 3 convolution (CVS:291-299)."""
+
+    def __init__(self, channels: int):
+        super().__init__()
+        self.conv = nn.Conv2d(channels, channels, 3, stride=2, padding=1)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return self.conv(x)
+
+
+class Upsample(nn.Module):
+    """Nearest-neighbour doubling, then a 3 x 3 convolution (CVS:302-311)."""
+
+    def __init__(self, channels: int):
+        super().__init__()
+        self.conv = nn.Conv2d(channels, channels, 3, padding=1)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return self.conv(F.interpolate(x, scale_factor=2, mode='nearest'))
+
+
+class PluckerPoseEncoder(nn.Module):
+    """Relative pose (R_rel (B, 3, 3), t_rel (B, 3)) -> (B, 16, cross_attention_dim) tokens (CVS:318-409): the first two columns of
+    R_rel, t_rel and the Pluecker coordinates (d, o x d) of the ray from the origin along t_rel -- 15 numbers -- through an MLP
+    with a LayerNorm and a projection, added to 16 learnt queries."""
+
+    def __init__(self, embed_dim: int = 256, cross_attention_dim: int = 384):
+        super().__init__()
+        self.embed_dim = embed_dim
+        self.cross_attention_dim = cross_attention_dim
+        self.encoder = nn.Sequential(nn.Linear(15, 128), nn.SiLU(), nn.Linear(128, 256), nn.SiLU(), nn.Linear(256, embed_dim),
+                                     nn.LayerNorm(embed_dim))
+        self.proj = nn.Linear(embed_dim, cross_attention_dim)
+        self.pose_queries = nn.Parameter(torch.randn(16, cross_attention_dim) * 0.02)
+
+    def rotation_6d_to_matrix(self, r6d: torch.Tensor) -> torch.Tensor:
+        """(B, 6) -> (B, 3, 3) by Gram-Schmidt on the two 3-vectors; the results are the matrix's columns."""
+        b1 = F.normalize(r6d[:, :3], dim=-1)
+        a2 = r6d[:, 3:6]
+        b2 = F.normalize(a2 - (b1 * a2).sum(dim=-1, keepdim=True) * b1, dim=-1)
+        return torch.stack([b1, b2, torch.cross(b1, b2, dim=-1)], dim=-1)
+
+    def compute_plucker(self, origin: torch.Tensor, direction: torch.Tensor) -> torch.Tensor:
+        d = F.normalize(direction, dim=-1)
+        return torch.cat([d, torch.cross(origin, d, dim=-1)], dim=-1)
+
+    def forward(self, R_rel: torch.Tensor, t_rel: torch.Tensor) -> torch.Tensor:
+        Bn = R_rel.shape[0]
+        r6d = R_rel[:, :, :2].reshape(Bn, 6)
+        plucker = self.compute_plucker(torch.zeros(Bn, 3, device=R_rel.device), t_rel)
+        embed = self.proj(self.encoder(torch.cat([r6d, t_rel, plucker], dim=-1)))
+        return self.pose_queries.unsqueeze(0).expand(Bn, -1, -1) + embed.unsqueeze(1)
+
+
+class ImageFeatureAdapter(nn.Module):
+    """DINOv2 features (B, h, w, in_dim) -> (B, num_tokens, out_dim) (CVS:416-470): position embeddings, an MLP with a LayerNorm,
+    then `num_tokens` learnt queries attend to the h w tokens (nn.MultiheadAttention, 8 heads)."""
+
+    def __init__(self, in_dim: int = 384, out_dim: int = 384, num_tokens: int = 256):
+        super().__init__()
+        self.num_tokens = num_tokens
+        self.proj = nn.Sequential(nn.Linear(in_dim, out_dim), nn.SiLU(), nn.Linear(out_dim, out_dim), nn.LayerNorm(out_dim))
+        self.pos_embed = nn.Parameter(torch.randn(1369, out_dim) * 0.02)
+        self.compress_queries = nn.Parameter(torch.randn(num_tokens, out_dim) * 0.02)
+        self.compress_attn = nn.MultiheadAttention(out_dim, 8, batch_first=True)
+
+    def forward(self, features: torch.Tensor) -> torch.Tensor:
+        Bn = features.shape[0]
+        x = features.view(Bn, -1, features.shape[-1])
+        x = self.proj(x + self.pos_embed[:x.shape[1]])
+        queries = self.compress_queries.unsqueeze(0).expand(Bn, -1, -1)
+        return self.compress_attn(queries, x, x)[0]
+
+
+class ConsistencyUNet(nn.Module):
+    """The U-Net of the synthesizer (CVS:477-672): x (B, 3, S, S) noisy target, t (B,) timesteps, image_cond (B, N, D) and pose_cond
+    (B, M, D) tokens -> (B, 3, S, S), the predicted clean image.  Module tree and state-dict keys are the reference's, the `None`
+    entries of encoder_attns / decoder_attns included.  `norm_backend` / `attn_backend` set the backend of every ResBlock and
+    AttentionBlock at construction; with norm_backend "hip" the GroupNorm -> SiLU head of `out_conv` (which stays an nn.Sequential,
+    for its keys) runs as one `group_norm_act` call too."""
+
+    def __init__(self, config: CVSConfig, norm_backend: str = "torch", attn_backend: str = "torch"):
+        super().__init__()
+        self.config = config
+        self.norm_backend = _check_norm_backend(norm_backend)
+        self.attn_backend = _check_attn_backend(attn_backend)
+        base, tdim, cdim = config.base_channels, config.time_embed_dim, config.cross_attention_dim
+
+        def res(c_in, c_out):
+            block = ResBlock(c_in, c_out, tdim)
+            block.norm_backend = norm_backend
+            return block
+
+        def attn_at(resolution, ch):
+            if resolution not in config.attention_resolutions:
+                return None
+            return AttentionBlock(ch, cdim, use_fresnel=True, attn_backend=attn_backend, norm_backend=norm_backend)
+
+        self.in_conv = nn.Conv2d(3, base, 3, padding=1)
+        self.out_conv = nn.Sequential(GroupNorm32(32, base), nn.SiLU(), nn.Conv2d(base, 3, 3, padding=1))
+        self.time_embed = nn.Sequential(SinusoidalPosEmbed(tdim), nn.Linear(tdim, tdim * 4), nn.SiLU(), nn.Linear(tdim * 4, tdim))
+
+        self.encoder = nn.ModuleList()
+        self.encoder_attns = nn.ModuleList()
+        widths = [base] + list(config.channels)
+        resolution = config.image_size
+        for c_in, c_out in zip(widths[:-1], widths[1:]):
+            self.encoder.append(nn.ModuleList([res(c_in if j == 0 else c_out, c_out) for j in range(config.num_res_blocks)]))
+            self.encoder_attns.append(attn_at(resolution, c_out))
+            resolution //= 2
+        self.downsamplers = nn.ModuleList([Downsample(ch) for ch in config.channels[:-1]])
+
+        mid = config.channels[-1]
+        self.mid_block1 = res(mid, mid)
+        self.mid_attn = AttentionBlock(mid, cdim, use_fresnel=True, attn_backend=attn_backend, norm_backend=norm_backend)
+        self.mid_block2 = res(mid, mid)
+        self.pose_proj = nn.Linear(cdim, mid)
+
+        self.decoder = nn.ModuleList()
+        self.decoder_attns = nn.ModuleList()
+        self.upsamplers = nn.ModuleList()
+        down = list(reversed(config.channels))
+        resolution = config.image_size // (2 ** len(config.channels))
+        for c_in, c_out in zip(down[:-1], down[1:]):   # the first block of a stage reads the stage's input and a skip of equal width
+            self.decoder.append(nn.ModuleList([res(2 * c_in if j == 0 else c_out, c_out) for j in range(config.num_res_blocks + 1)]))
+            resolution *= 2
+            self.decoder_attns.append(attn_at(resolution, c_out))
+            self.upsamplers.append(Upsample(c_out))
+        self.final_decoder = nn.ModuleList([res(down[-1] + base if j == 0 else base, base) for j in range(config.num_res_blocks + 1)])
+
+    def forward(self, x: torch.Tensor, t: torch.Tensor, image_cond: torch.Tensor, pose_cond: torch.Tensor) -> torch.Tensor:
+        t_emb = self.time_embed(t)
+        context = torch.cat([image_cond, pose_cond], dim=1)
+        h = self.in_conv(x)
+        skips = [h]
+        for i, (blocks, attn) in enumerate(zip(self.encoder, self.encoder_attns)):
+            for block in blocks:
+                h = block(h, t_emb)
+            if attn is not None:
+                h = attn(h, context)
+            skips.append(h)
+            if i < len(self.downsamplers):
+                h = self.downsamplers[i](h)
+        h = self.mid_block1(h, t_emb)
+        h = self.mid_attn(h, context)
+        h = h + self.pose_proj(pose_cond.mean(dim=1))[:, :, None, None]
+        h = self.mid_block2(h, t_emb)
+        for i, (blocks, attn) in enumerate(zip(self.decoder, self.decoder_attns)):
+            h = torch.cat([h, skips.pop()], dim=1)
+            for block in blocks:
+                h = block(h, t_emb)
+            if attn is not None:
+                h = attn(h, context)
+            if i < len(self.upsamplers):
+                h = self.upsamplers[i](h)
+        h = torch.cat([h, skips.pop()], dim=1)
+        for block in self.final_decoder:
+            h = block(h, t_emb)
+        if _check_norm_backend(self.norm_backend) == "hip":
+            return self.out_conv[2](_norm_hip(self.out_conv[0], h, "silu"))
+        return self.out_conv(h)
+
+
+class ConsistencyViewSynthesizer(nn.Module):
+    """The whole model (CVS:679-837): ImageFeatureAdapter, PluckerPoseEncoder and ConsistencyUNet, with the cosine noise schedule
+    in five buffers (betas, alphas, alphas_cumprod, sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod).  `forward` with a
+    target image is a training step's prediction ({x0_pred, target, noisy, noise, timestep}), without one a one-step generation
+    ({generated}); `generate` refines over `num_steps`.  `norm_backend` / `attn_backend` go to the U-Net."""
+
+    def __init__(self, config: Optional[CVSConfig] = None, norm_backend: str = "torch", attn_backend: str = "torch"):
+        super().__init__()
+        self.config = config or CVSConfig()
+        self.norm_backend, self.attn_backend = _check_norm_backend(norm_backend), _check_attn_backend(attn_backend)
+        self.image_adapter = ImageFeatureAdapter(in_dim=384, out_dim=self.config.cross_attention_dim)
+        self.pose_encoder = PluckerPoseEncoder(embed_dim=self.config.pose_embed_dim, cross_attention_dim=self.config.cross_attention_dim)
+        self.unet = ConsistencyUNet(self.config, norm_backend=norm_backend, attn_backend=attn_backend)
+        self.register_buffer('betas', self._cosine_beta_schedule())
+        self.register_buffer('alphas', 1.0 - self.betas)
+        self.register_buffer('alphas_cumprod', torch.cumprod(self.alphas, dim=0))
+        self.register_buffer('sqrt_alphas_cumprod', torch.sqrt(self.alphas_cumprod))
+        self.register_buffer('sqrt_one_minus_alphas_cumprod', torch.sqrt(1.0 - self.alphas_cumprod))
+
+    def _cosine_beta_schedule(self) -> torch.Tensor:
+        """betas of alphas_cumprod(t) = cos^2(((t / T + s) / (1 + s)) pi / 2), s = 0.008, clamped to [1e-4, 0.9999]."""
+        steps, s = self.config.num_timesteps, 0.008
+        t = torch.linspace(0, steps, steps + 1)
+        cumprod = torch.cos((t / steps + s) / (1 + s) * math.pi / 2) ** 2
+        cumprod = cumprod / cumprod[0]
+        return torch.clamp(1 - cumprod[1:] / cumprod[:-1], 0.0001, 0.9999)
+
+    def add_noise(self, x: torch.Tensor, t: torch.Tensor, noise: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        if noise is None:
+            noise = torch.randn_like(x)
+        keep = self.sqrt_alphas_cumprod[t][:, None, None, None]
+        spread = self.sqrt_one_minus_alphas_cumprod[t][:, None, None, None]
+        return keep * x + spread * noise, noise
+
+    def forward(self, input_image: torch.Tensor, input_features: torch.Tensor, R_rel: torch.Tensor, t_rel: torch.Tensor,
+                target_image: Optional[torch.Tensor] = None, timestep: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        Bn, device = input_image.shape[0], input_image.device
+        image_cond = self.image_adapter(input_features)
+        pose_cond = self.pose_encoder(R_rel, t_rel)
+        if target_image is None:
+            z = torch.randn(Bn, 3, self.config.image_size, self.config.image_size, device=device)
+            t = torch.full((Bn,), self.config.num_timesteps - 1, device=device)
+            return {'generated': self.unet(z, t.float(), image_cond, pose_cond)}
+        if timestep is None:
+            timestep = torch.randint(0, self.config.num_timesteps, (Bn,), device=device)
+        noisy, noise = self.add_noise(target_image, timestep)
+        x0_pred = self.unet(noisy, timestep.float(), image_cond, pose_cond)
+        return {'x0_pred': x0_pred, 'target': target_image, 'noisy': noisy, 'noise': noise, 'timestep': timestep}
+
+    @torch.no_grad()
+    def generate(self, input_image: torch.Tensor, input_features: torch.Tensor, R_rel: torch.Tensor, t_rel: torch.Tensor,
+                 num_steps: int = 1) -> torch.Tensor:
+        Bn, device = input_image.shape[0], input_image.device
+        last = self.config.num_timesteps - 1
+        image_cond = self.image_adapter(input_features)
+        pose_cond = self.pose_encoder(R_rel, t_rel)
+        z = torch.randn(Bn, 3, self.config.image_size, self.config.image_size, device=device)
+        if num_steps == 1:
+            return self.unet(z, torch.full((Bn,), last, device=device, dtype=torch.float), image_cond, pose_cond)
+        timesteps = torch.linspace(last, 0, num_steps + 1, device=device).long()
+        for i in range(num_steps):
+            z = self.unet(z, timesteps[i].expand(Bn).float(), image_cond, pose_cond)
+            if i < num_steps - 1:   # half the next level's noise back in
+                z = z + self.sqrt_one_minus_alphas_cumprod[timesteps[i + 1]] * torch.randn_like(z) * 0.5
+        return z
+
+
+def create_ema_model(model: nn.Module) -> nn.Module:
+    """A frozen copy of `model` for the exponential moving average (CVS:948-953); a mirror's backends go with it."""
+    backends = {k: getattr(model, k) for k in ("norm_backend", "attn_backend") if hasattr(model, k)}
+    ema = type(model)(model.config, **backends)
+    ema.load_state_dict(model.state_dict())
+    ema.requires_grad_(False)
+    return ema
+
+
+def update_ema(model: nn.Module, ema: nn.Module, decay: float = 0.9999):
+    """p_ema <- decay p_ema + (1 - decay) p, parameter by parameter (CVS:956-960)."""
+    with torch.no_grad():
+        for p, p_ema in zip(model.parameters(), ema.parameters()):
+            p_ema.data.mul_(decay).add_(p.data, alpha=1 - decay)
+
+
+def get_relative_pose(R_source: torch.Tensor, t_source: torch.Tensor, R_target: torch.Tensor,
+                      t_target: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """R_rel = R_target R_source^T, t_rel = t_target - R_rel t_source (CVS:963-982)."""
+    R_rel = torch.bmm(R_target, R_source.transpose(-1, -2))
+    return R_rel, t_target - torch.bmm(R_rel, t_source.unsqueeze(-1)).squeeze(-1)

@@ -1031,6 +1031,51 @@ int fgs_wave_attn_backward(int32_t batch, int32_t grid_h, int32_t grid_w, int32_
                            float *g_qkv, float *g_wavelength /* 1, or NULL */, void *scratch, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Fused GroupNorm -> SiLU of the consistency view synthesizer's U-Net (CVS: ResBlock, 90-134; the norms of AttentionBlock and of
+ * out_conv), with the broadcast add of the time embedding folded into the read.  For x (B, C, HW) fp32 contiguous (NCHW),
+ * `groups` dividing C, cpg = C / groups, m = cpg HW; group (b, g) is the cpg ADJACENT channels g cpg ... of image b:
+ *   u    = x + channel_bias[b, c]                    (channel_bias (B, C), or NULL -> u = x)
+ *   mean = sum_group(u) / m,  var = sum_group((u - mean)^2) / m  (biased),  rstd = 1 / sqrt(var + eps)  (eps INSIDE the root)
+ *   y    = weight[c] (u - mean) rstd + bias[c]
+ *   out  = y sigmoid(y)   (act = 1, SiLU)   |   out = y   (act = 0)
+ * Backward, exact: with s = sigmoid(y), g_y = g_out s (1 + y (1 - s)) (act 0: g_y = g_out), xhat = (u - mean) rstd:
+ *   g_weight[c] = sum_{b, hw} g_y xhat;   g_bias[c] = sum_{b, hw} g_y;
+ *   g_u = rstd (weight g_y - mean_group(weight g_y) - xhat mean_group(weight g_y xhat));   g_x = g_u;
+ *   g_channel_bias[b, c] = sum_hw g_u.
+ * Neither u nor y is ever stored: `saved` holds (mean, rstd) per (b, group) and nothing of the activation's size; the backward
+ * recomputes xhat, y and sigmoid(y) from x.
+ * Moments (this is the definition): TWO-PASS sums of segments, combined pairwise.  A segment is up to FGS_GN_SEGMENT consecutive
+ * floats of one channel row, cut at row-relative multiples of FGS_GN_SEGMENT.  Per segment, held in registers: the fp32 sum gives a
+ * shift mu; d = sum(u - mu) and q = sum((u - mu)^2) follow in fp32 per lane and in double across the lanes; the segment's pair is
+ * (mu + d / n, q - d^2 / n) in double -- exact in mu, so the fp32 rounding of mu does not enter.  A group's pairs are combined by
+ * Chan's update in double in a fixed order; mean and rstd are rounded to fp32 once.  E[u^2] - mean^2 is formed nowhere: a group whose
+ * mean is 30 standard deviations from zero has the moments of the centred one.
+ * The work is cut by segments, not by groups: one wave per segment, B C ceil(HW / FGS_GN_SEGMENT) of them; the cuts are relative to
+ * the row, so out, g_x and g_channel_bias of an image do not depend on the batch it sits in.  With HW % 4 == 0 the segments are read
+ * and written as float4; with any other HW (groups then start at offsets that are not 16-byte aligned) the same loops run scalar.
+ * fgs_gn_silu_forward: two launches (segment moments; fold at the head of the apply launch).  fgs_gn_silu_backward: four (segment
+ * sums; per (b, group) fold with g_channel_bias; g_weight and g_bias over the batch, in order, in double; apply).  No float atomics,
+ * nothing summed across waves except in a fixed order: two calls agree to the bit in every output.
+ * NaN: as in torch, a non-finite value makes its group's output non-finite (and the g_weight / g_bias of its channels); every other
+ * (b, group) keeps the bits of a clean run in out, g_x and g_channel_bias.
+ * saved_bytes: 8 B groups rounded up to 256.  scratch_bytes: 24 per segment + 24 B C + 8 B groups, each rounded up to 256.  Every
+ * element of out, g_x, g_channel_bias, g_weight, g_bias and of saved's B groups pairs is written; scratch is written before it is
+ * read; inputs are never modified.  No call synchronises the host or allocates: the calls can be captured.
+ * Shapes go as plain integers: batch, channels, hw, groups >= 1, channels % groups == 0; act 0 | 1; eps finite and > 0; x, out, g_out,
+ * g_x and scratch 16-byte aligned; B C HW < 2^31 (32-bit indices); otherwise FGS_EINVAL (dims, act, eps, null or misaligned pointers)
+ * / FGS_EUNSUPPORTED (size) before anything touches the device. */
+#define FGS_GN_SEGMENT 4096
+int fgs_gn_silu_workspace_bytes(int32_t batch, int32_t channels, int32_t hw, int32_t groups, size_t *saved_bytes,
+                                size_t *scratch_bytes);
+int fgs_gn_silu_forward(int32_t batch, int32_t channels, int32_t hw, int32_t groups, int32_t act, float eps, const float *x,
+                        const float *channel_bias /* (B,C) or NULL */, const float *weight, const float *bias, float *out,
+                        void *saved, void *scratch, void *stream);
+int fgs_gn_silu_backward(int32_t batch, int32_t channels, int32_t hw, int32_t groups, int32_t act, float eps, const float *x,
+                         const float *channel_bias, const float *weight, const float *bias, const void *saved, const float *g_out,
+                         float *g_x, float *g_channel_bias /* (B,C) or NULL */, float *g_weight, float *g_bias, void *scratch,
+                         void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Importance-subsampling hand-off between decoder and rasterizer (--stochastic_k; reference
  * scripts/training/train_gaussian_decoder.py:1160-1187): the n_out Gaussians whose indices torch.multinomial
  * drew (DEVICE int64 (n_out,), unique, shared by the batch) are gathered out of every (B, n_in, .) tensor into
