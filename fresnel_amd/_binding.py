@@ -141,6 +141,7 @@ FWD_EXIT_OFF, FWD_EXIT_ON = 0x100, 0x200  # include/fgs.h: flags of FgsDims.fwd_
 BWD_ZERO_OFF, BWD_ZERO_ON = 0x400, 0x800  # include/fgs.h: flags of FgsDims.fwd_variant
 BWD_TAIL_OFF, BWD_TAIL_ON = 0x2000, 0x4000  # include/fgs.h: flags of FgsDims.fwd_variant
 BWD_SUB_OFF, BWD_SUB_ON = 0x8000, 0x10000  # include/fgs.h: flags of FgsDims.fwd_variant
+FWD_PREWALK_OFF, FWD_PREWALK_ON = 0x40000, 0x80000  # include/fgs.h: flags of FgsDims.fwd_variant
 
 
 class FgsDims(ctypes.Structure):
@@ -352,6 +353,8 @@ def make_dims(batch, num_gaussians, width, height, max_radius=64.0, background=(
     -- the FGS_BWD_TAIL_ON / _OFF flag of FgsDims.fwd_variant.
     `bwd_sub`: 0 | 1 | -1 = the blend backward's zero sub-tiles of general units automatic (on wherever bwd_zero is) | on | off
     -- the FGS_BWD_SUB_ON / _OFF flag of FgsDims.fwd_variant.
+    `fwd_prewalk`: 0 | 1 | -1 = the exiting forward's head launch walks the later parts of short lists automatic (off: it measured slower) |
+    on (where the exiting forward runs with more than one part) | off -- the FGS_FWD_PREWALK_ON / _OFF flag of FgsDims.fwd_variant.
     `dup_capacity`: room for that many (tile, Gaussian) duplicates instead of the worst case (0 = worst case; a call that needs
     more overflows: NaN images, zero gradients, saved.counters[1] = 1 -- include/fgs.h)."""
     if isinstance(dup_capacity, bool) or int(dup_capacity) != dup_capacity or not 0 <= int(dup_capacity) <= 0xFFFFFFFF:
@@ -370,6 +373,7 @@ def make_dims(batch, num_gaussians, width, height, max_radius=64.0, background=(
     bwd_zero = int(tuning.pop("bwd_zero", 0))
     bwd_tail = int(tuning.pop("bwd_tail", 0))
     bwd_sub = int(tuning.pop("bwd_sub", 0))
+    fwd_prewalk = int(tuning.pop("fwd_prewalk", 0))
     for k, v in tuning.items():
         if k not in ("seg_len", "fwd_variant", "bin_mode", "tile_w", "sort_mode"):
             raise FgsError(f"unknown tuning field {k!r}")
@@ -382,8 +386,11 @@ def make_dims(batch, num_gaussians, width, height, max_radius=64.0, background=(
         raise FgsError(f"bwd_tail must be 0, 1 or -1, and 0 with the row-split forward (fwd_variant < 0), got {bwd_tail!r}")
     if bwd_sub not in (0, 1, -1) or (bwd_sub and d.fwd_variant < 0):
         raise FgsError(f"bwd_sub must be 0, 1 or -1, and 0 with the row-split forward (fwd_variant < 0), got {bwd_sub!r}")
+    if fwd_prewalk not in (0, 1, -1) or (fwd_prewalk and d.fwd_variant < 0):
+        raise FgsError(f"fwd_prewalk must be 0, 1 or -1, and 0 with the row-split forward (fwd_variant < 0), got {fwd_prewalk!r}")
     d.fwd_variant |= ({0: 0, 1: FWD_EXIT_ON, -1: FWD_EXIT_OFF}[fwd_exit] | {0: 0, 1: BWD_ZERO_ON, -1: BWD_ZERO_OFF}[bwd_zero]
-                      | {0: 0, 1: BWD_TAIL_ON, -1: BWD_TAIL_OFF}[bwd_tail] | {0: 0, 1: BWD_SUB_ON, -1: BWD_SUB_OFF}[bwd_sub])
+                      | {0: 0, 1: BWD_TAIL_ON, -1: BWD_TAIL_OFF}[bwd_tail] | {0: 0, 1: BWD_SUB_ON, -1: BWD_SUB_OFF}[bwd_sub]
+                      | {0: 0, 1: FWD_PREWALK_ON, -1: FWD_PREWALK_OFF}[fwd_prewalk])
     d.dup_capacity = int(dup_capacity)
     return d
 

@@ -321,6 +321,7 @@ __global__ __launch_bounds__(64 * FWD_WAVES) void k_composite_fwd(
 // the backward unit of a later segment of part p > 0 re-bases its local checkpoint with that slot
 // (k_composite_bwd, `fwd_parts`).  Hand-over between the waves goes through the checkpoint slots themselves
 // (the slot of the next part's first segment; the last part uses the tile's slot 0, which nothing else reads).
+// Behind the head launch (REST) the hand-over goes through LDS instead, part by part: see the chain in the kernel.
 struct BlendState { float Cr, Cg, Cb, T, D; };
 __device__ __forceinline__ BlendState compose(const BlendState &a, const BlendState &b) {
     return {a.Cr + a.T * b.Cr, a.Cg + a.T * b.Cg, a.Cb + a.T * b.Cb, a.T * b.T, a.D + a.T * b.D};
@@ -407,11 +408,13 @@ __global__ __launch_bounds__(64 * NP * (1 + WIDE)) __attribute__((amdgpu_waves_p
     const uint32_t *__restrict__ tile_order, const uint32_t *__restrict__ ranges,
     const uint32_t *__restrict__ dup_ids, const float *__restrict__ rec, float *__restrict__ pix_state,
     float *__restrict__ out_rgb, float *__restrict__ out_depth, const uint32_t *__restrict__ seg_off,
-    float *__restrict__ seg_ckpt, uint32_t seg_len, uint32_t order_groups, const uint32_t *__restrict__ fwd_open, uint32_t head_segs) {
+    float *__restrict__ seg_ckpt, uint32_t seg_len, uint32_t order_groups, const uint32_t *__restrict__ fwd_open, uint32_t head_segs,
+    uint32_t prewalk) {
     constexpr int NW = NP * (1 + WIDE);                   // waves per block
     constexpr int TSX = WIDE ? 4 : 2;                     // sub-tile columns of the whole tile
     constexpr int PL = 2 * TSX * 64, SLOT = 5 * PL;       // floats per checkpoint plane / slot: [5][2 TSX][64]
-    __shared__ float4 sh0[NW][64], sh1[NW][64], sh2[NW][64];
+    __shared__ float4 shb[3][NW][64];                     // the waves' staging rows; behind the walks the hand-over chain's states (REST)
+    float4 (&sh0)[NW][64] = shb[0], (&sh1)[NW][64] = shb[1], (&sh2)[NW][64] = shb[2];
     // launch order: tile_order holds the tiles of XCD group 0 heavy-first, then group 1's, ... (fgs_bin.hip tile_group);
     // blocks are dealt round-robin over the XCDs, so XCD g walks group g -- one image (or band of tile rows) per L2
     const uint32_t slot_in_order = order_groups > 1u ? fgs_xcd_remap(blockIdx.x, gridDim.x) : blockIdx.x;
@@ -458,7 +461,10 @@ __global__ __launch_bounds__(64 * NP * (1 + WIDE)) __attribute__((amdgpu_waves_p
         }
         wstart = c.start + hs * seg_len;
     }
-    const uint32_t wend = (!REST || mine) ? pend : wstart;
+    // PRE-WALKED tile (REST, the head launch ran its pre-walk blocks, a list of at most NP segments: spp == 1): the hand-over slots of
+    // parts 1.. hold their local results already -- those waves neither walk nor store, they keep the barrier; part 0 composes as ever
+    const bool walked = REST && NP > 1 && prewalk != 0u && nseg <= (uint32_t)NP && part != 0u;
+    const uint32_t wend = ((!REST || mine) && !walked) ? pend : wstart;
     for (uint32_t base = wstart; base < wend; base += 64) {
         const uint32_t n = min(64u, wend - base);
         if (base != wstart && ((base - c.start) % seg_len) == 0) {  // LOCAL state in front of this segment
@@ -470,15 +476,79 @@ __global__ __launch_bounds__(64 * NP * (1 + WIDE)) __attribute__((amdgpu_waves_p
     }
     // ---- hand the part results over and compose them (the part-0 wave of each half) ----
     const uint32_t last = nseg ? (nseg - 1) / spp : 0u;
-    if (NP > 1 && nseg > spp) {  // more than one part
-        if (active && part != 0 && (!REST || mine)) {
+    if (REST && NP > 1 && nseg > spp) {
+        // REST: the parts of an open half hand over through LDS, part by part in list order.  The wave of part q takes the absolute
+        // state in front of its part from the half's LDS cells, composes it with its own local result -- held in registers as the
+        // checkpoint planes would hold it, A = 1 - T, and taken as 1 - A: the operands, the expression, the order and so the bits of
+        // the composition through the slots -- stores the absolute state in front of part q + 1 into that part's first slot (what the backward
+        // reads) and passes it on; the wave of the last part stores the pixels.  No local result travels through memory, the loads
+        // and stores of the parts belong to different waves, and no wave waits for a store to come back before its load.
+        static_assert(NP < 2 || 20 * 64 * (1 + WIDE) * sizeof(float) <= sizeof(shb), "the hand-over states need the staging rows' room");
+        float *xf = reinterpret_cast<float *>(&shb[0][0][0]) + half * (20u * 64u) + lane;
+        const bool chained = mine && part <= last;
+        if (chained && part != 0) {
+            if (walked) {  // the pre-walk's result, from the hand-over slot it stored (this part's own store below comes later)
+                const float *ck = (part == last) ? slot0 : slot0 + (size_t)((part + 1) * spp) * SLOT;
+#pragma unroll
+                for (int s = 0; s < 4; ++s) {
+                    const float *k = ck + cell(s);
+                    Cr[s] = nt_load(k); Cg[s] = nt_load(k + PL); Cb[s] = nt_load(k + 2 * PL); T[s] = nt_load(k + 3 * PL); Dm[s] = nt_load(k + 4 * PL);
+                }
+            } else {
+#pragma unroll
+                for (int s = 0; s < 4; ++s) {
+                    float a = 1.0f - T[s];
+                    asm("" : "+v"(a));  // opaque, as a value loaded from the plane is: 1 - (1 - T) is not T and must not be folded to it
+                    T[s] = a;
+                }
+            }
+        }  // a later part now holds A = 1 - T where T was: what its hand-over slot's A plane holds, and ckpt_load's expression below
+        __syncthreads();  // every walk of the block is over: the staging rows are free
+        for (uint32_t q = 0; q <= last; ++q) {
+            if (chained && part == q) {
+                float *nxt = slot0 + (size_t)((q + 1) * spp) * SLOT;  // the first slot of part q + 1
+                if (q != 0) {
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) {
+                        const float *x = xf + (5 * s) * 64;
+                        const float aT = x[192], bT = 1.0f - T[s];
+                        const BlendState acc = compose(BlendState{x[0], x[64], x[128], aT, x[256]}, BlendState{Cr[s], Cg[s], Cb[s], bT, Dm[s]});
+                        Cr[s] = acc.Cr; Cg[s] = acc.Cg; Cb[s] = acc.Cb; T[s] = acc.T; Dm[s] = acc.D;
+                        // The A plane of the slot is ONE fma, 1 - a.T b.T, beside the rounded product a.T b.T that is carried on: that is
+                        // how the composition through the slots comes out of the compiler (ckpt_store of compose's result under this
+                        // unit's contraction), and the two differ by an ulp of A wherever T is not small.  Written out here.
+                        if (q != last) {
+                            float *k = nxt + cell(s);
+                            nt_store(k, acc.Cr); nt_store(k + PL, acc.Cg); nt_store(k + 2 * PL, acc.Cb);
+                            nt_store(k + 3 * PL, __builtin_fmaf(-bT, aT, 1.0f)); nt_store(k + 4 * PL, acc.D);
+                        }
+                        __builtin_amdgcn_sched_barrier(0);  // one sub-tile's five reads at a time: all twenty in flight beside the state spill
+                    }
+                } else if (min(spp, head_segs) != spp) {
+                    // (part 0 that resumed at its own end walked nothing: slot spp holds this very state since the A plane was put right)
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) ckpt_store<PL>(nxt + cell(s), BlendState{Cr[s], Cg[s], Cb[s], T[s], Dm[s]});
+                }
+                if (q != last) {
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) {
+                        float *x = xf + (5 * s) * 64;
+                        x[0] = Cr[s]; x[64] = Cg[s]; x[128] = Cb[s]; x[192] = T[s]; x[256] = Dm[s];
+                    }
+                }
+            }
+            if (q != last) __syncthreads();
+        }
+        if (!chained || part != last) return;
+    } else if (NP > 1 && nseg > spp) {  // more than one part, without the head launch: the hand-over goes through the slots
+        if (active && part != 0) {
             float *ck = (part == last) ? slot0 : slot0 + (size_t)((part + 1) * spp) * SLOT;
 #pragma unroll
             for (int s = 0; s < 4; ++s) ckpt_store<PL>(ck + cell(s), BlendState{Cr[s], Cg[s], Cb[s], T[s], Dm[s]});
         }
         __threadfence_block();
         __syncthreads();
-        if (part != 0 || (REST && !mine)) return;
+        if (part != 0) return;
         // part 0: its own result is the absolute state in front of part 1
         {
             float *ck = slot0 + (size_t)spp * SLOT;
@@ -536,6 +606,22 @@ __global__ __launch_bounds__(64 * NP * (1 + WIDE)) __attribute__((amdgpu_waves_p
 //     A plane, and fwd_open[tile][half] = 1: part 0's wave of the rest kernel resumes from it, the other parts run as they did.
 // head_segs bounds the launch for scenes that never saturate: one wave per half for a quarter of the longest list would leave
 // most of the chip waiting.
+//
+// PRE-WALK (FgsPlan.fwd_prewalk; np > 1).  Parts 1.. of a list of at most np segments (spp == 1, the head's reach is segment 0) start
+// from T = 1 and need nothing of part 0, so they need not wait for the rest launch: behind the head blocks -- from the next multiple
+// of 8 on, so that a block's index modulo 8 still names its XCD -- the launch has one block per (launch slot, part p = 1 .. np - 1),
+// of the head's shape: one wave per half, the same LDS.  A block of a longer list (nseg > np) or of a part the list does not have
+// (p >= nseg) leaves behind its scalar loads.  Any other walks its one segment through blend_fwd_chunk and stores the local result
+// into the hand-over slot of k_blend_fwd_parts: slot p + 1, slot 0 for the last part -- bit for bit what that kernel's wave of the
+// part stores there.  It reads no mark and no slot and writes nothing else.  The rest launch then composes only.  Why no bit moves:
+//   the head blocks are the code they were, so fwd_open and fwd_close are the words they were;
+//   an open half's hand-over slots hold what the rest launch's own waves would have stored, and the same composition follows;
+//   a half the head closed has k = 1 (one segment of reach): the pre-walk writes slots 2.. and slot 0 of ITS cells, behind the closing
+//     slot, which k_composite_bwd and k_bwd_tail_verdict never read for such a half (they read slot k alone), and the rest launch's
+//     waves of a closed half touch nothing;
+//   nothing writes slot 1 but the head.
+// Measured (DESIGN_LOG.md 30): the walk costs the VALU-bound head launch more than it saves the rest launch (config 3 forward
+// 0.180 -> 0.206 ms); automatic is OFF, FGS_FWD_PREWALK_ON turns it on.
 template <int WIDE>
 __global__ __launch_bounds__(64 * (1 + WIDE)) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_blend_fwd_head(
     uint32_t tiles, uint32_t tiles_x, uint32_t W, uint32_t H, float bg0, float bg1, float bg2,
@@ -543,17 +629,44 @@ __global__ __launch_bounds__(64 * (1 + WIDE)) __attribute__((amdgpu_waves_per_eu
     const uint32_t *__restrict__ dup_ids, const float *__restrict__ rec, float *__restrict__ pix_state,
     float *__restrict__ out_rgb, float *__restrict__ out_depth, const uint32_t *__restrict__ seg_off,
     float *__restrict__ seg_ckpt, uint32_t seg_len, uint32_t order_groups, uint32_t *__restrict__ fwd_open, uint32_t head_segs,
-    uint32_t np, const uint32_t *__restrict__ fwd_max, uint32_t max_recs, uint32_t *__restrict__ fwd_close) {
+    uint32_t np, const uint32_t *__restrict__ fwd_max, uint32_t max_recs, uint32_t *__restrict__ fwd_close, uint32_t head_blocks) {
     constexpr int NW = 1 + WIDE;
     constexpr int TSX = WIDE ? 4 : 2;
     constexpr int PL = 2 * TSX * 64, SLOT = 5 * PL;
     __shared__ float4 sh0[NW][64], sh1[NW][64], sh2[NW][64];
-    const uint32_t slot_in_order = order_groups > 1u ? fgs_xcd_remap(blockIdx.x, gridDim.x) : blockIdx.x;
-    const TileCtx c = tile_ctx_of(tile_order[slot_in_order], tiles, tiles_x, ranges, 8u * TSX);
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t half = WIDE ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : 0u;
-    const uint32_t X0 = c.X0 + 16u * half;
     const uint32_t lx = lane & 7u, ly = lane >> 3;
+    if (blockIdx.x >= head_blocks) {
+        // PRE-WALK (see above): block j of the range behind the head blocks, which begins at a multiple of 8 so that j & 7 is the
+        // block's XCD; XCD g takes (launch slot, part) pairs of ITS group of the tile order, heavy-first, the parts of a tile in a row
+        const uint32_t pad = (head_blocks + 7u) & ~7u;
+        if (blockIdx.x < pad) return;
+        const uint32_t j = blockIdx.x - pad, i = j >> 3;
+        const uint32_t bid = (j & 7u) + 8u * (i / (np - 1u)), part = 1u + i % (np - 1u);
+        if (bid >= head_blocks) return;  // the groups are not all of one size
+        const TileCtx c = tile_ctx_of(tile_order[order_groups > 1u ? fgs_xcd_remap(bid, head_blocks) : bid], tiles, tiles_x, ranges, 8u * TSX);
+        const uint32_t nseg = (c.end - c.start + seg_len - 1) / seg_len;
+        if (nseg > np || part >= nseg) return;  // spp > 1: the rest launch's walk; no such part
+        const uint32_t X0 = c.X0 + 16u * half;
+        float *slot0 = seg_ckpt + (size_t)seg_off[c.tile] * SLOT + 2u * half * 64u + lane;
+        auto cell = [](int s) { return ((s >> 1) * TSX + (s & 1)) * 64; };
+        float T[4], Cr[4], Cg[4], Cb[4], Dm[4];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) { T[s] = 1.0f; Cr[s] = 0; Cg[s] = 0; Cb[s] = 0; Dm[s] = 0; }
+        BlendLane ln = {lx, 16u + ly, (float)(X0 + lx), (float)(X0 + lx + 8u), (float)(c.Y0 + ly)};
+        asm("" : "+v"(ln.fx0), "+v"(ln.fx1), "+v"(ln.fy0));
+        const uint32_t pstart = c.start + part * seg_len, pend = min(c.end, pstart + seg_len);  // spp == 1: segment `part`
+        for (uint32_t base = pstart; base < pend; base += 64u)
+            blend_fwd_chunk(sh0[half], sh1[half], sh2[half], lane, base, min(64u, pend - base), X0, c.Y0, dup_ids, rec, ln, T, Cr, Cg, Cb, Dm);
+        float *ck = (part == nseg - 1u) ? slot0 : slot0 + (size_t)(part + 1u) * SLOT;  // k_blend_fwd_parts' hand-over slot
+#pragma unroll
+        for (int s = 0; s < 4; ++s) ckpt_store<PL>(ck + cell(s), BlendState{Cr[s], Cg[s], Cb[s], T[s], Dm[s]});
+        return;
+    }
+    const uint32_t slot_in_order = order_groups > 1u ? fgs_xcd_remap(blockIdx.x, head_blocks) : blockIdx.x;
+    const TileCtx c = tile_ctx_of(tile_order[slot_in_order], tiles, tiles_x, ranges, 8u * TSX);
+    const uint32_t X0 = c.X0 + 16u * half;
     const uint32_t len = c.end - c.start;
     const uint32_t nseg = (len + seg_len - 1) / seg_len;
     const uint32_t spp = (nseg + np - 1) / np;
@@ -1741,16 +1854,25 @@ int fgs_launch_composite_fwd(const FgsPlan &p, const float *phase, char *saved, 
         // The exiting forward: the head kernel (one wave per tile half over the front of part 0), then the parts kernel for the
         // halves it left open.  One part: the head walks the whole list and there is nothing left.
         const bool exiting = p.fwd_exit;
+        const uint32_t prewalk = p.fwd_prewalk ? 1u : 0u;  // only with `exiting` and np > 1 (fgs_make_plan)
         uint32_t *fwd_open = exiting ? fgs_at<uint32_t>(saved, p.L.fwd_open) : nullptr;
         const uint32_t head_segs = FGS_FWD_HEAD_ENTRIES / seg_len > 0u ? FGS_FWD_HEAD_ENTRIES / seg_len : 1u;
         if (exiting) {
             const uint32_t *fwd_max = fgs_at<const uint32_t>(saved, p.s_fwd_max);
             const uint32_t max_recs = ((uint32_t)p.d.num_gaussians + 255u) / 256u;
             uint32_t *fwd_close = fgs_at<uint32_t>(saved, p.L.fwd_close);
+            // the pre-walk blocks (FgsPlan.fwd_prewalk) stand behind the head blocks, from the next multiple of 8 on: per XCD
+            // ceil(grid / 8) launch slots x (np - 1) parts; the surplus ones leave at once
+            uint32_t head_grid = grid;
+            if (prewalk) {
+                const uint64_t want = (uint64_t)((grid + 7u) & ~7u) + (uint64_t)((grid + 7u) / 8u) * 8u * (uint32_t)(np - 1);
+                if (want > 0x7FFFFFFFull) { fgs_set_error("k_blend_fwd_head: the pre-walk grid exceeds 2^31 blocks"); return FGS_EINVAL; }
+                head_grid = (uint32_t)want;
+            }
 #define FGS_HEAD_LAUNCH(WD)                                                                                               \
-    hipLaunchKernelGGL((k_blend_fwd_head<WD>), dim3(grid), dim3(64 * (1 + WD)), 0, st, tiles, tiles_x, W, H, bg0, bg1, bg2, tile_order, \
+    hipLaunchKernelGGL((k_blend_fwd_head<WD>), dim3(head_grid), dim3(64 * (1 + WD)), 0, st, tiles, tiles_x, W, H, bg0, bg1, bg2, tile_order, \
                        ranges, dup_ids, rec, pix, out_rgb, out_depth, seg_off, seg_ckpt, seg_len, order_groups, fwd_open, head_segs, \
-                       (uint32_t)np, fwd_max, max_recs, fwd_close)
+                       (uint32_t)np, fwd_max, max_recs, fwd_close, grid)
             if (p.tile_w == 32) FGS_HEAD_LAUNCH(1); else FGS_HEAD_LAUNCH(0);
 #undef FGS_HEAD_LAUNCH
             FGS_LAUNCH_CHECK("k_blend_fwd_head");
@@ -1761,11 +1883,11 @@ int fgs_launch_composite_fwd(const FgsPlan &p, const float *phase, char *saved, 
         if (exiting)                                                                                                      \
             hipLaunchKernelGGL((k_blend_fwd_parts<NP, WD, true>), dim3(grid), dim3(64 * NP * (1 + WD)), 0, st, tiles, tiles_x, W, H, bg0, \
                                bg1, bg2, tile_order, ranges, dup_ids, rec, pix, out_rgb, out_depth, seg_off, seg_ckpt, seg_len,   \
-                               order_groups, fwd_open, head_segs);                                                        \
+                               order_groups, fwd_open, head_segs, prewalk);                                                        \
         else                                                                                                              \
             hipLaunchKernelGGL((k_blend_fwd_parts<NP, WD, false>), dim3(grid), dim3(64 * NP * (1 + WD)), 0, st, tiles, tiles_x, W, H, bg0, \
                                bg1, bg2, tile_order, ranges, dup_ids, rec, pix, out_rgb, out_depth, seg_off, seg_ckpt, seg_len,   \
-                               order_groups, fwd_open, head_segs);                                                        \
+                               order_groups, fwd_open, head_segs, prewalk);                                                        \
     } while (0)
         if (p.tile_w == 32) {
             if (np == 1) FGS_PARTS_LAUNCH(1, 1); else if (np == 2) FGS_PARTS_LAUNCH(2, 1); else if (np == 4) FGS_PARTS_LAUNCH(4, 1);

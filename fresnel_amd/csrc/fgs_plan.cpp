@@ -33,16 +33,18 @@ int fgs_make_plan(const FgsDims *d, FgsPlan *p, int layers, bool segment_ckpt) {
                       d->num_gaussians, d->width, d->height, (double)d->max_radius, d->num_cameras);
         return FGS_EINVAL;
     }
-    // fwd_variant >= 0 may carry one of the two exit flags, one of FGS_BWD_ZERO_*, one of FGS_BWD_TAIL_* and one of FGS_BWD_SUB_* (include/fgs.h); fv is the work split without them
+    // fwd_variant >= 0 may carry one of the two exit flags, one of FGS_BWD_ZERO_*, one of FGS_BWD_TAIL_*, one of FGS_BWD_SUB_* and one of FGS_FWD_PREWALK_* (include/fgs.h); fv is the work split without them
     const int exit_flags = d->fwd_variant >= 0 ? (d->fwd_variant & (FGS_FWD_EXIT_OFF | FGS_FWD_EXIT_ON)) : 0;
     const int zero_flags = d->fwd_variant >= 0 ? (d->fwd_variant & (FGS_BWD_ZERO_OFF | FGS_BWD_ZERO_ON)) : 0;
     const int tail_flags = d->fwd_variant >= 0 ? (d->fwd_variant & (FGS_BWD_TAIL_OFF | FGS_BWD_TAIL_ON)) : 0;
     const int sub_flags = d->fwd_variant >= 0 ? (d->fwd_variant & (FGS_BWD_SUB_OFF | FGS_BWD_SUB_ON)) : 0;
-    const int fv = d->fwd_variant - exit_flags - zero_flags - tail_flags - sub_flags, afv = fv < -16 || fv > 16 ? 3 /* invalid; INT_MIN has no negation */ : (fv < 0 ? -fv : fv);
+    const int pre_flags = d->fwd_variant >= 0 ? (d->fwd_variant & (FGS_FWD_PREWALK_OFF | FGS_FWD_PREWALK_ON)) : 0;
+    const int fv = d->fwd_variant - exit_flags - zero_flags - tail_flags - sub_flags - pre_flags, afv = fv < -16 || fv > 16 ? 3 /* invalid; INT_MIN has no negation */ : (fv < 0 ? -fv : fv);
     if (d->seg_len < 0 || d->seg_len > 512 || d->seg_len % 64 != 0 || (afv != 0 && afv != 1 && afv != 2 && afv != 4 && !(fv == 8 || fv == 16)) ||
         d->bin_mode < 0 || d->bin_mode > 2 || (d->tile_w != 0 && d->tile_w != 16 && d->tile_w != 32) || d->sort_mode < 0 || d->sort_mode > 11 ||
         exit_flags == (FGS_FWD_EXIT_OFF | FGS_FWD_EXIT_ON) || zero_flags == (FGS_BWD_ZERO_OFF | FGS_BWD_ZERO_ON) ||
-        tail_flags == (FGS_BWD_TAIL_OFF | FGS_BWD_TAIL_ON) || sub_flags == (FGS_BWD_SUB_OFF | FGS_BWD_SUB_ON)) {
+        tail_flags == (FGS_BWD_TAIL_OFF | FGS_BWD_TAIL_ON) || sub_flags == (FGS_BWD_SUB_OFF | FGS_BWD_SUB_ON) ||
+        pre_flags == (FGS_FWD_PREWALK_OFF | FGS_FWD_PREWALK_ON)) {
         fgs_set_error("invalid tuning: seg_len=%d fwd_variant=%d bin_mode=%d tile_w=%d sort_mode=%d", d->seg_len, d->fwd_variant,
                       d->bin_mode, d->tile_w, d->sort_mode);
         return FGS_EINVAL;
@@ -202,6 +204,12 @@ int fgs_make_plan(const FgsDims *d, FgsPlan *p, int layers, bool segment_ckpt) {
     // the zero sub-tiles of GENERAL units (k_composite_bwd: sub-tiles that restart at T == +0 with S == +-0 leave the unit's walk; the
     // same bits).  Automatic: wherever bwd_zero holds; FGS_BWD_SUB_ON forces it at any size, FGS_BWD_SUB_OFF gives the full walk.
     p->bwd_sub = sub_flags == FGS_BWD_SUB_ON || (sub_flags == 0 && p->bwd_zero);
+    // the later parts of lists of at most fwd_parts segments walked by extra blocks of the head launch, the rest launch composing
+    // only (k_blend_fwd_head; the same slots, the same bits).  Automatic is OFF: the walk costs the VALU-bound head launch more than it
+    // saves the rest launch (config 3 forward 0.180 -> 0.206 ms; DESIGN_LOG.md 30).  FGS_FWD_PREWALK_ON turns
+    // it on where the exiting forward runs with more than one part; the flags mean nothing elsewhere.  No section of either
+    // workspace depends on it.
+    p->fwd_prewalk = p->fwd_exit && p->fwd_parts > 1 && pre_flags == FGS_FWD_PREWALK_ON;
     p->s_fwd_max = o;
     if (p->fwd_exit) {
         p->s_fwd_max = o = align256(o + B * p->tiles * 2 * 4);

@@ -51,6 +51,8 @@ struct FgsPlan {
                               // k_blend_fwd_head, then k_blend_fwd_parts for the halves it left open; saved.fwd_open, s_fwd_max and saved.fwd_close exist
     bool bwd_zero;            // k_composite_bwd writes zero rows for dead units whose S is exactly zero and masks such sub-tiles of the others
                               // (flags FGS_BWD_ZERO_ON / _OFF of FgsDims.fwd_variant; automatic from 8192 tile halves per launch; the same bits)
+    bool fwd_prewalk;         // the head launch also walks parts 1.. of lists of at most fwd_parts segments, the rest launch only composes them
+                              // (flag FGS_FWD_PREWALK_ON of FgsDims.fwd_variant, where fwd_exit holds with fwd_parts > 1; automatic is off: measured slower; the same bits)
     bool bwd_sub;             // k_composite_bwd takes the sub-tiles of a general unit that restart at T == +0 with S == +-0 on every lane out of
                               // the unit's walk (flags FGS_BWD_SUB_ON / _OFF of FgsDims.fwd_variant; automatic wherever bwd_zero holds; the same bits)
     bool bwd_tail;            // one verdict per closed tile (k_bwd_tail_verdict): the units behind every half's closing slot of a tile whose

@@ -66,6 +66,8 @@ extern "C" {
 #define FGS_BWD_TAIL_ON 0x4000
 #define FGS_BWD_SUB_OFF 0x8000 /* FgsDims.fwd_variant flags (values >= 0 only): the blend backward's zero sub-tiles of general units off / forced on */
 #define FGS_BWD_SUB_ON 0x10000
+#define FGS_FWD_PREWALK_OFF 0x40000 /* FgsDims.fwd_variant flags (values >= 0 only): the exiting forward's pre-walk of short lists' later parts off / forced on */
+#define FGS_FWD_PREWALK_ON 0x80000
 #define FGS_TUNE_AUTO 0    /* FgsDims.seg_len / fwd_variant / bin_mode: let the library choose        */
 #ifndef FGS_PHASE_CKPT
 #define FGS_PHASE_CKPT 8   /* phase path: entries of a sub-tile's (compacted) list between (A, Phi) checkpoints */
@@ -122,6 +124,13 @@ typedef struct FgsDims {
                                pixel restarts at zero transmittance and the remaining-sum S is an exact zero on every lane: their
                                passes add exact zeros to sums that start at +0.  No flag = automatic: on wherever the zero rows
                                above are on.  OFF: every touched sub-tile is composited; ON: forced at any size.
+                               Beside them a value >= 0 may carry ONE of FGS_FWD_PREWALK_OFF | FGS_FWD_PREWALK_ON.  Where the exiting
+                               forward runs with more than one list part, the later parts of a list of at most that many
+                               segments are walked by extra blocks of the head launch (they start from T = 1 and need nothing
+                               of part 0), and the rest launch only composes them: the same hand-over slots, the same bits.
+                               No flag = automatic = OFF: the walk measured slower inside the head launch than in the rest
+                               launch at the benchmark's default size.  ON: on where the exiting forward runs with more than one
+                               part (tests and A/B runs); ignored elsewhere.
                                No flag is available with the row-split forward (values < 0).       */
     int32_t bin_mode;       /* tile binning: 0 | 1 = direct (column / row rank masks) | 2 = emit + stable radix sort */
     int32_t tile_w;         /* tile width in pixels: 0 | 16 | 32 (tiles are always 16 rows high).  0 = automatic:
