@@ -108,6 +108,13 @@ int fgs_gn_silu_workspace_bytes(int32_t batch channels hw groups, size_t* saved_
 int fgs_gn_silu_forward(int32_t batch channels hw groups act, float eps, ptr x channel_bias weight bias out saved scratch, stream)
 int fgs_gn_silu_backward(int32_t batch channels hw groups act, float eps, ptr x channel_bias weight bias saved g_out g_x g_channel_bias
                          g_weight g_bias scratch, stream)
+int fgs_cvs_loss_workspace_bytes(int32_t images channels height width flags, size_t* saved_bytes scratch_bytes)
+int fgs_cvs_quality_mask(int32_t images height width, float threshold sharpness, ptr depth mask, stream)
+int fgs_cvs_loss_forward(int32_t images channels height width flags, float threshold sharpness, ptr pred target depth ema out saved
+                         scratch, stream)
+int fgs_cvs_loss_backward(int32_t images channels height width flags, float threshold sharpness, ptr pred target depth ema saved
+                          g_terms g_pred, stream)
+int fgs_cvs_euler_step(int32_t images channels hw steps, ptr sqrt_alphas_cumprod timestep x0_pred noisy x_prev t_prev, stream)
 int fgs_gather_forward(int32_t batch n_in n_out phase_channels, ptr indices pos scale quat color opacity phase o_pos o_scale o_quat
                        o_color o_opacity o_phase, stream)
 int fgs_gather_backward(int32_t batch n_in n_out phase_channels, ptr indices g_o_pos g_o_scale g_o_quat g_o_color g_o_opacity
@@ -291,6 +298,10 @@ class FgsMatchDims(ctypes.Structure):
 FGS_ATTN_QUERY_BLOCK, FGS_ATTN_KEY_TILE, FGS_ATTN_KEY_BLOCK, FGS_ATTN_MAX_HEAD_DIM = 128, 32, 128, 128
 FGS_WAVE_ATTN_MAX_TOKENS = 4096
 FGS_GN_SEGMENT = 4096  # floats of one channel row per wave of the fused GroupNorm-SiLU: longer rows are cut there (include/fgs.h)
+
+# the fused CVS loss (include/fgs.h): flags of its terms; threads per block and the largest grid of its streaming kernels
+FGS_CVS_QUALITY, FGS_CVS_CONS_L1, FGS_CVS_CONS_MSE, FGS_CVS_BOUNDARY, FGS_CVS_GRADIENT = 1, 2, 4, 8, 16
+FGS_CVS_THREADS, FGS_CVS_MAX_GRID = 256, 2048
 
 
 class FgsError(RuntimeError):

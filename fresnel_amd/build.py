@@ -91,6 +91,10 @@ SOURCES = {
     # no FMA contraction: forward, segment sums and backward apply recompute xhat and y from x with the same roundings, so the
     # g_y the sums saw is the g_y the apply uses (a one-element group's g_x then cancels to exactly zero)
     "fgs_gn_silu.hip": ["-ffp-contract=off"],
+    # no fast-math (a NaN / Inf in pred must reach every term it enters, as in torch).  No FMA contraction and IEEE division: the
+    # terms are DEFINED with every operation rounded on its own (include/fgs.h), and the backward's sgn is taken by comparison of
+    # the very values the forward subtracted
+    "fgs_cvs_loss.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
 }
 LINK_LIBS = ["-lhipfft"]
 

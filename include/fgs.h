@@ -1085,6 +1085,85 @@ int fgs_gn_silu_backward(int32_t batch, int32_t channels, int32_t hw, int32_t gr
                          void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Pixel terms of the consistency view synthesizer's losses (QualityAwareCVSLoss, scripts/models/quality_aware_losses.py "QAL";
+ * ConsistencyLoss, CVS:844-941) and the Euler step of the latter.  All tensors fp32, contiguous, DEVICE: pred, target, ema and
+ * g_pred (B, C, H, W); depth, mask and saved's plane (B, 1, H, W); B = images, C = channels.  Shapes and flags go as plain integers.
+ * All arithmetic on the data is in fp32, each operation rounded on its own (no FMA contraction, IEEE division); the sums are in double.
+ *
+ * Mask (QAL:21-68).  lap = |(((d[y-1] + d[y+1]) + d[x-1]) + d[x+1]) - 4 d|, the neighbour indices taken modulo H / W as torch.roll
+ * does: with H == 1 a vertical neighbour is the pixel itself, with H == 2 both are the same row; likewise W.
+ *   m = sigmoid(-sharpness (lap - threshold)) = 1 / (1 + exp(sharpness (lap - threshold)))
+ * Without FGS_CVS_QUALITY m = 1 and depth is not read for it.  fgs_cvs_loss_forward writes m to `saved` when the flag is set and
+ * fgs_cvs_loss_backward reads it from there; nothing else of the images' size is kept.  fgs_cvs_quality_mask writes the same plane
+ * alone; a pixel's m depends on its own image only.
+ *
+ * Terms, out = float[4]; a term that is not requested is written as 0.
+ *   out[0] l1_weighted  mean over B C H W of m |p - t|                                                        (always)
+ *   out[1] consistency  mean over B C H W of |p - e| (FGS_CVS_CONS_L1, QAL:265) or of (p - e)^2 (FGS_CVS_CONS_MSE, CVS:935);
+ *                       the two flags exclude each other.  With m = 1 and the MSE form the same kernels serve ConsistencyLoss
+ *   out[2] boundary     (FGS_CVS_BOUNDARY, QAL:275-291)  pe = (sum_c |p - t|) / C;
+ *                       bx[y, x] = (|d[y, x] - d[y, x+1]| > 0.01f), by[y, x] = (|d[y, x] - d[y+1, x]| > 0.01f), over the W - 1 /
+ *                       H - 1 interior differences, no wrap.  (torch's `tensor > 0.01` on fp32 is exactly "greater than the fp32
+ *                       value of 0.01": no fp32 value lies between that and the double 0.01.)
+ *                       term = sum(pe bx) / (B H (W-1)) + sum(pe by) / (B (H-1) W); pe bx is a PRODUCT: a NaN pe reaches the
+ *                       term through a zero bit too, as in torch
+ *   out[3] gradient     (FGS_CVS_GRADIENT, QAL:71-100)  sum |p[y, x] - p[y, x+1]| m[y, x] / (B C H (W-1))
+ *                       + sum |p[y, x] - p[y+1, x]| m[y, x] / (B C (H-1) W)
+ *
+ * Backward: ONE launch, a gather -- every element of g_pred is written exactly once by the thread that owns it.  g_terms = DEVICE
+ * float[4], the upstream gradients of the four terms, read on the device (the entry of a term that is off is not read): the call
+ * can be captured and its caller never reads the host.  sgn(a, b) = (a > b) - (a < b): 0 on a tie, decided by comparison and never
+ * by the sign of a difference (which may be a flushed denormal).  g_pred[b, c, y, x] is the sum of
+ *   g0 sgn(p, t) m / (B C H W)
+ *   g1 sgn(p, e) / (B C H W)                    | g1 2 (p - e) / (B C H W) with FGS_CVS_CONS_MSE
+ *   g2 sgn(p, t) / C (bx[y, x] [x < W-1] / (B H (W-1)) + by[y, x] [y < H-1] / (B (H-1) W))
+ *   g3 (([x < W-1] m[y, x] sgn(p[y, x], p[y, x+1]) - [x > 0] m[y, x-1] sgn(p[y, x-1], p[y, x])) / (B C H (W-1))
+ *       + ([y < H-1] m[y, x] sgn(p[y, x], p[y+1, x]) - [y > 0] m[y-1, x] sgn(p[y-1, x], p[y, x])) / (B C (H-1) W))
+ * The gradient reaches pred only (the reference's op sequence would also differentiate depth, target and ema; the product wrapper
+ * refuses such inputs with backend "hip").
+ *
+ * Kernels.  A work item is a group of V consecutive pixels of one row of one image, looping over the C planes; mask and boundary bits
+ * are computed once per pixel.  V = 4 (16-byte accesses) when W % 4 == 0 and every pointer of the call is 16-byte aligned, else V = 1.
+ * FGS_CVS_THREADS threads, grid-stride, at most FGS_CVS_MAX_GRID blocks.  Neighbour reads of depth, pred and mask go to global memory
+ * through the caches.  A thread sums its items in order, a block its threads in a fixed order, a one-block final kernel the blocks
+ * in a fixed order, in double; no atomics: two runs give the same bits.  fgs_cvs_loss_forward: two launches (the pass, the final
+ * kernel); fgs_cvs_loss_backward, fgs_cvs_quality_mask, fgs_cvs_euler_step: one each.  No fast-math: a NaN / Inf in pred makes every
+ * term it enters non-finite and no other (m comes from depth alone).
+ * saved_bytes: 4 B H W rounded up to 256 with FGS_CVS_QUALITY, else 0 (saved may then be NULL).  scratch_bytes: 6 doubles per block
+ * of the largest grid, rounded up to 256.  Every element of out[4], g_pred, mask and saved's plane is written; scratch is written
+ * before it is read; inputs are never modified.  No call synchronises the host or allocates.
+ * Checks, on the host, before anything touches the device: every extent >= 1; B C H W < 2^31; known flags, not both consistency forms;
+ * with FGS_CVS_BOUNDARY or FGS_CVS_GRADIENT H >= 2 and W >= 2 (the reference returns NaN there, the mean of an empty tensor);
+ * threshold and sharpness finite with FGS_CVS_QUALITY; depth non-NULL with FGS_CVS_QUALITY or _BOUNDARY, ema with a consistency
+ * form; otherwise FGS_EINVAL.
+ *
+ * Euler step (CVS:916-926).  t = timestep[b] (int64), a = sac[t], a' = sac[max(t - 1, 0)], sac = sqrt_alphas_cumprod, float[steps]:
+ *   x_prev = clamp(a' x0 + ((1 - a') / ((1 - a) + 1e-8f)) (noisy - a x0), -1, 1)   in this association order, torch's
+ *   t_prev[b] = float(max(t - 1, 0))
+ * over (images, channels, hw) tensors; V = 4 when channels hw % 4 == 0 and x0_pred, noisy and x_prev are 16-byte aligned.  A timestep
+ * outside [0, steps) is clamped into the table: memory-safe, and a difference from torch, which would assert. */
+#define FGS_CVS_QUALITY 1
+#define FGS_CVS_CONS_L1 2
+#define FGS_CVS_CONS_MSE 4       /* exclusive with FGS_CVS_CONS_L1 */
+#define FGS_CVS_BOUNDARY 8
+#define FGS_CVS_GRADIENT 16
+#define FGS_CVS_THREADS 256
+#define FGS_CVS_MAX_GRID 2048
+int fgs_cvs_loss_workspace_bytes(int32_t images, int32_t channels, int32_t height, int32_t width, int32_t flags,
+                                 size_t *saved_bytes, size_t *scratch_bytes);
+int fgs_cvs_quality_mask(int32_t images, int32_t height, int32_t width, float threshold, float sharpness, const float *depth,
+                         float *mask, void *stream);
+int fgs_cvs_loss_forward(int32_t images, int32_t channels, int32_t height, int32_t width, int32_t flags, float threshold,
+                         float sharpness, const float *pred, const float *target, const float *depth /* or NULL */,
+                         const float *ema /* or NULL */, float *out /* 4 */, void *saved, void *scratch, void *stream);
+int fgs_cvs_loss_backward(int32_t images, int32_t channels, int32_t height, int32_t width, int32_t flags, float threshold,
+                          float sharpness, const float *pred, const float *target, const float *depth, const float *ema,
+                          const void *saved, const float *g_terms /* 4 */, float *g_pred, void *stream);
+int fgs_cvs_euler_step(int32_t images, int32_t channels, int32_t hw, int32_t steps, const float *sqrt_alphas_cumprod,
+                       const int64_t *timestep, const float *x0_pred, const float *noisy, float *x_prev,
+                       float *t_prev /* images */, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Importance-subsampling hand-off between decoder and rasterizer (--stochastic_k; reference
  * scripts/training/train_gaussian_decoder.py:1160-1187): the n_out Gaussians whose indices torch.multinomial
  * drew (DEVICE int64 (n_out,), unique, shared by the batch) are gathered out of every (B, n_in, .) tensor into
