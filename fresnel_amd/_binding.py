@@ -100,6 +100,11 @@ int fgs_attn_workspace_bytes(int32_t batch queries keys heads head_dim, size_t* 
 int fgs_attn_forward(int32_t batch queries keys heads head_dim, float scale dropout_p, ptr q kv row_keep seed out saved, stream)
 int fgs_attn_backward(int32_t batch queries keys heads head_dim, float scale dropout_p, ptr q kv row_keep seed out saved g_out g_q
                       g_kv scratch, stream)
+int fgs_attn_half_workspace_bytes(int32_t batch queries keys heads head_dim, size_t* saved_bytes scratch_bytes)
+int fgs_attn_half_forward(int32_t dtype batch queries keys heads head_dim, float scale dropout_p, ptr q kv row_keep seed out saved,
+                          stream)
+int fgs_attn_half_backward(int32_t dtype batch queries keys heads head_dim, float scale dropout_p, ptr q kv row_keep seed out saved
+                           g_out g_q g_kv scratch, stream)
 int fgs_wave_attn_workspace_bytes(int32_t batch grid_h grid_w heads head_dim, size_t* saved_bytes scratch_bytes)
 int fgs_wave_attn_forward(int32_t batch grid_h grid_w heads head_dim, float scale, ptr qkv wavelength out saved, stream)
 int fgs_wave_attn_backward(int32_t batch grid_h grid_w heads head_dim, float scale, ptr qkv wavelength out saved g_out g_qkv
@@ -296,6 +301,8 @@ class FgsMatchDims(ctypes.Structure):
 # the fused cross-attention's seams (include/fgs.h; tests/test_call_layer.py holds every macro restated here against the header):
 # queries per workgroup, keys per LDS tile, keys per workgroup of the key-block backward, largest head dimension
 FGS_ATTN_QUERY_BLOCK, FGS_ATTN_KEY_TILE, FGS_ATTN_KEY_BLOCK, FGS_ATTN_MAX_HEAD_DIM = 128, 32, 128, 128
+# its 16-bit form (csrc/fgs_attn_half.hip): the `dtype` argument's two values, keys per LDS tile
+FGS_ATTN_F16, FGS_ATTN_BF16, FGS_ATTN_HALF_KEY_TILE = 1, 2, 32
 FGS_WAVE_ATTN_MAX_TOKENS = 4096
 FGS_GN_SEGMENT = 4096  # floats of one channel row per wave of the fused GroupNorm-SiLU: longer rows are cut there (include/fgs.h)
 

@@ -83,6 +83,8 @@ SOURCES = {
     # no FMA contraction: the backward recomputes p = exp(score - saved) and must round the score, S scale, as the forward did;
     # fused into the subtraction it differs from the forward's by up to 2^-24 |score|, which at scores near 80 put g_q 6e-5 off
     "fgs_attn.hip": ["-ffp-contract=off"],
+    # the 16-bit form of the cross-attention, a unit of its own: fgs_attn.hip stays as it is.  No FMA contraction, for the same reason
+    "fgs_attn_half.hip": ["-ffp-contract=off"],
     # a unit of its own, so that its flags never touch the cross-attention.  No FMA contraction, as fgs_attn.hip: the backward must
     # round the score (S scale) + bias as the forward did.  IEEE divide and square root: the bias chain dist -> phi -> 0.1 cosf(phi) is
     # DEFINED with every operation rounded on its own (include/fgs.h), and a phase of thousands of radians (wavelength 1e-3) turns an

@@ -9,7 +9,8 @@ kernels of csrc/fgs_slat.hip (backend "hip", CUDA/ROCm tensors only, no fallback
 
 The attention between CrossAttention's Linear layers is `cross_attention`: the reference's op sequence (backend "torch") or the fused,
 flash-style HIP kernels of csrc/fgs_attn.hip (backend "hip": no score tensor, device-side dropout, bitwise repeatable); `DirectSLatDecoder`
-selects it with `attn_backend`, independently of the head.
+selects it with `attn_backend`, independently of the head.  Under mixed precision the fused attention has a 16-bit form
+(csrc/fgs_attn_half.hip: fp16 or bf16 tensors, fp32 scores and softmax), selected with `compute_dtype` / `attn_dtype`.
 
 Both decoders take one extra keyword, `head_backend`.  With "torch" every host check of the reference stays (its
 `isnan(...).any()` tests and the per-image loop of the occupancy-gated inference).  With "hip" nothing in a training forward reads
@@ -248,8 +249,54 @@ class _CrossAttnHip(torch.autograd.Function):
         return g_q, g_kv, None, None, None, None
 
 
+# the 16-bit compute dtypes of the fused attention -> the library's `dtype` argument (include/fgs.h)
+ATTN_HALF_DTYPES = {torch.float16: B.FGS_ATTN_F16, torch.bfloat16: B.FGS_ATTN_BF16}
+
+
+def _check_compute_dtype(compute_dtype, allow_autocast=False):
+    if compute_dtype is None or compute_dtype in ATTN_HALF_DTYPES or (allow_autocast and compute_dtype == "autocast"):
+        return compute_dtype
+    raise ValueError(f"unknown attention compute dtype {compute_dtype!r}: None (fp32), torch.float16 or torch.bfloat16"
+                     + (', or "autocast"' if allow_autocast else ""))
+
+
+class _CrossAttnHalfHip(torch.autograd.Function):
+    """fgs_attn_half_forward / _backward on 16-bit q and kv (contiguous, of one dtype: `cross_attention` sees to it).  Saved: the
+    inputs, the 16-bit output and one fp32 per (b, h, n).  Nothing synchronises with the host."""
+
+    @staticmethod
+    def forward(ctx, q, kv, row_keep, seed, num_heads, dropout_p):
+        dev = q.device
+        Bn, N, D = q.shape
+        dims = (Bn, N, kv.shape[1], num_heads, D // num_heads)
+        scale = float((D // num_heads) ** -0.5)
+        code = ATTN_HALF_DTYPES[q.dtype]
+        saved_bytes, _ = B.sizes("fgs_attn_half_workspace_bytes", *dims)
+        out = torch.empty((Bn, N, D), dtype=q.dtype, device=dev)
+        saved = torch.empty(saved_bytes, dtype=torch.uint8, device=dev)
+        hip.call(dev, "fgs_attn_half_forward", code, *dims, scale, dropout_p, q, kv, row_keep, seed, out, saved)
+        ctx.dims, ctx.scale, ctx.dropout_p, ctx.code = dims, scale, dropout_p, code
+        ctx.save_for_backward(q, kv, row_keep, seed, out, saved)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out):
+        q, kv, row_keep, seed, out, saved = ctx.saved_tensors
+        dev = q.device
+        if g_out.dtype != q.dtype or not g_out.is_contiguous():
+            g_out = g_out.to(q.dtype).contiguous()
+        g_q, g_kv = torch.empty_like(q), torch.empty_like(kv)
+        _, scratch_bytes = B.sizes("fgs_attn_half_workspace_bytes", *ctx.dims)
+        scratch = torch.empty(scratch_bytes, dtype=torch.uint8, device=dev)
+        hip.call(dev, "fgs_attn_half_backward", ctx.code, *ctx.dims, ctx.scale, ctx.dropout_p, q, kv, row_keep, seed, out, saved, g_out,
+                 g_q, g_kv, scratch)
+        return g_q, g_kv, None, None, None, None
+
+
 def cross_attention(q: torch.Tensor, kv: torch.Tensor, num_heads: int, *, mask: Optional[torch.Tensor] = None,
-                    dropout_p: float = 0.0, seed: Optional[torch.Tensor] = None, backend: str = "torch") -> torch.Tensor:
+                    dropout_p: float = 0.0, seed: Optional[torch.Tensor] = None, backend: str = "torch",
+                    compute_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
     """The attention of the reference's CrossAttention between its Linear layers (DSD:105-146): q (B, N, D), the output of the query
     projection, and kv (B, M, 2, H, d) or (B, M, 2 D), the output of the key/value projection (keys kv[:, :, 0], values kv[:, :, 1],
     D = H d) -> (B, N, D), ready for the output projection.  Scores scale <q, k> with scale = d^-0.5; `mask` (B, N) bool: a False
@@ -263,8 +310,21 @@ def cross_attention(q: torch.Tensor, kv: torch.Tensor, num_heads: int, *, mask: 
     dropout -- the reference's values -- but is a constant of the backward (zero g_q row, g_kv through v only) where torch's
     gradient is NaN-tainted.  Its dropout keeps element (b, h, n, m) by a stated counter-based function of `seed` (include/fgs.h),
     a one-element int64 tensor on q's device; with dropout_p > 0 and no seed one is drawn by torch.randint on the device (it
-    follows torch.manual_seed, and nothing is read on the host)."""
+    follows torch.manual_seed, and nothing is read on the host).
+
+    `compute_dtype` (backend "hip" only).  None: the fp32 kernels and an fp32 `out`, under autocast as well.  torch.float16 /
+    torch.bfloat16: csrc/fgs_attn_half.hip -- the same definition on 16-bit tensors: q and kv are used in place when they already are
+    contiguous tensors of that dtype (under autocast the Linear layers' outputs are) and cast once otherwise, `out` has that dtype,
+    the gradients reach q and kv in their own dtypes, an upstream gradient of another dtype or layout is cast once; still one launch
+    forward and three backward, whatever the autocast state.  Products take 16-bit operands and accumulate in fp32, the scores and the
+    softmax stay fp32, only the probabilities and dS are rounded ahead of the second products (the contract: include/fgs.h).  Stated
+    differences from torch under autocast: an fp16 score beyond 65504 stays finite here (torch's overflows and its row becomes 1 / M
+    each); dS in fp16 can underflow for small upstream gradients, which is what a GradScaler is for.  With backend "torch" the
+    caller's autocast decides the precision, so a compute_dtype there is a ValueError."""
     _check_attn_backend(backend)
+    _check_compute_dtype(compute_dtype)
+    if backend == "torch" and compute_dtype is not None:
+        raise ValueError("cross_attention (backend 'torch'): compute_dtype is for backend 'hip'; here the caller's autocast decides")
     if isinstance(num_heads, bool) or int(num_heads) != num_heads or num_heads < 1:
         raise ValueError(f"num_heads must be a positive integer, got {num_heads!r}")
     num_heads = int(num_heads)
@@ -291,7 +351,7 @@ def cross_attention(q: torch.Tensor, kv: torch.Tensor, num_heads: int, *, mask: 
         raise ValueError(f"{who}: head dimension {d} > {B.FGS_ATTN_MAX_HEAD_DIM} is not supported")
     if Bn * num_heads * N >= 2 ** 31:
         raise ValueError(f"{who}: B x H x N = {Bn} x {num_heads} x {N} is beyond the supported size")
-    if not kv.is_contiguous() or not q.is_contiguous():
+    if compute_dtype is None and (not kv.is_contiguous() or not q.is_contiguous()):
         raise ValueError(f"{who}: q and kv must be contiguous -- the Linear layers' outputs as they are, not a permuted view")
     if seed is not None and (not torch.is_tensor(seed) or seed.dtype is not torch.int64 or seed.numel() != 1):
         raise ValueError(f"{who}: seed must be a one-element int64 tensor on q's device")
@@ -302,6 +362,10 @@ def cross_attention(q: torch.Tensor, kv: torch.Tensor, num_heads: int, *, mask: 
     if dropout_p > 0.0 and seed is None:
         seed = torch.randint(0, 2 ** 62, (1,), dtype=torch.int64, device=q.device)
     row_keep = None if mask is None else mask.detach().contiguous().view(torch.uint8)  # a bool's byte is 0 or 1
+    if compute_dtype is not None:
+        # (a differentiable cast: autograd returns the gradient in the tensor's own dtype and layout)
+        q, kv = (t if t.dtype == compute_dtype and t.is_contiguous() else t.to(compute_dtype).contiguous() for t in (q, kv))
+        return _CrossAttnHalfHip.apply(q, kv, row_keep, seed if dropout_p > 0.0 else None, num_heads, dropout_p)
     return _CrossAttnHip.apply(q, kv, row_keep, seed if dropout_p > 0.0 else None, num_heads, dropout_p)
 
 
@@ -330,7 +394,11 @@ class CrossAttention(nn.Module):
     attends uniformly (the reference's behaviour, kept).  `host_checks` (an attribute, True as in the reference): test for NaN on
     the host before replacing it; False replaces unconditionally.  `backend` (an attribute, "torch" as in the reference): "hip" runs
     `cross_attention(..., backend="hip")` -- the query projection once for all N and ONE fused call whatever `chunk_size` is, with
-    attention dropout active iff the module is training and `attn_drop.p > 0`."""
+    attention dropout active iff the module is training and `attn_drop.p > 0`.  `compute_dtype` (an attribute, None by default; read
+    with backend "hip" only): None runs the fp32 kernels; torch.float16 / torch.bfloat16 run the 16-bit kernels of
+    `cross_attention(..., compute_dtype=...)` on the Linear layers' outputs as they are -- under autocast in that dtype they already
+    have it, so nothing is copied; "autocast" means torch.get_autocast_dtype("cuda") while CUDA autocast is enabled and fp32
+    otherwise."""
 
     def __init__(self, dim: int, num_heads: int = 8, qkv_bias: bool = True, attn_drop: float = 0.0, proj_drop: float = 0.0,
                  chunk_size: int = 1024):
@@ -346,6 +414,17 @@ class CrossAttention(nn.Module):
         self.proj_drop = nn.Dropout(proj_drop)
         self.host_checks = True
         self.backend = "torch"
+        self.compute_dtype = None
+
+    def _hip_compute_dtype(self):
+        """The attribute resolved for this call: None (fp32) or a 16-bit dtype."""
+        cd = _check_compute_dtype(self.compute_dtype, allow_autocast=True)
+        if cd != "autocast":
+            return cd
+        if not torch.is_autocast_enabled("cuda"):
+            return None
+        cd = torch.get_autocast_dtype("cuda")
+        return cd if cd in ATTN_HALF_DTYPES else None
 
     def _attend(self, x, k, v, mask):
         """One block of queries x (B, n, D) against all keys -> (B, n, D), before the output projection."""
@@ -359,7 +438,9 @@ class CrossAttention(nn.Module):
         if _check_attn_backend(self.backend) == "hip":
             p = self.attn_drop.p if self.training else 0.0
             x = cross_attention(self.q(x), self.kv(context).reshape(Bn, M, 2, self.num_heads, self.head_dim), self.num_heads,
-                                mask=mask, dropout_p=p, backend="hip")
+                                mask=mask, dropout_p=p, backend="hip", compute_dtype=self._hip_compute_dtype())
+            if x.dtype != self.proj.weight.dtype and not torch.is_autocast_enabled("cuda"):
+                x = x.to(self.proj.weight.dtype)   # a 16-bit compute_dtype outside autocast: the projection runs in its own dtype
             return self.proj_drop(self.proj(x))
         kv = self.kv(context).reshape(Bn, M, 2, self.num_heads, self.head_dim).permute(2, 0, 3, 1, 4)
         k, v = kv[0], kv[1]
@@ -441,15 +522,19 @@ class DirectSLatDecoder(nn.Module):
     under `torch.no_grad()` (a ValueError says so otherwise); the reference and the "torch" backend also accept it with grad enabled.
 
     `attn_backend` "torch": the reference's chunked attention.  "hip": every block's cross-attention is the fused kernel of
-    `cross_attention` (no score tensor, no chunking, device-side dropout).  The two backends are independent."""
+    `cross_attention` (no score tensor, no chunking, device-side dropout).  The two backends are independent.
+
+    `attn_dtype` sets every block's `CrossAttention.compute_dtype` (read with attn_backend "hip"): None, torch.float16,
+    torch.bfloat16 or "autocast" -- the 16-bit fused attention whenever the model runs under CUDA autocast, fp32 otherwise."""
 
     def __init__(self, feature_dim: int = 1024, hidden_dim: int = 512, num_layers: int = 6, num_heads: int = 8,
                  num_gaussians_per_voxel: int = 8, max_resolution: int = 64, dropout: float = 0.1, use_checkpoint: bool = False,
                  predict_occupancy: bool = True, occupancy_threshold: float = 0.5, head_backend: str = "torch",
-                 attn_backend: str = "torch"):
+                 attn_backend: str = "torch", attn_dtype=None):
         super().__init__()
         self.head_backend = _check_backend(head_backend)
         self.attn_backend = _check_attn_backend(attn_backend)
+        self.attn_dtype = _check_compute_dtype(attn_dtype, allow_autocast=True)
         self.feature_dim = feature_dim
         self.hidden_dim = hidden_dim
         self.num_gaussians_per_voxel = num_gaussians_per_voxel
@@ -469,6 +554,7 @@ class DirectSLatDecoder(nn.Module):
         for block in self.blocks:
             block.cross_attn.host_checks = head_backend == "torch"
             block.cross_attn.backend = attn_backend
+            block.cross_attn.compute_dtype = attn_dtype
 
     def _init_weights(self):
         """Every Linear gets Xavier-uniform weights -- gain 0.1 where the module's path contains "q", "kv" or "proj", 0.5 elsewhere --

@@ -985,6 +985,51 @@ int fgs_attn_backward(int32_t batch, int32_t queries, int32_t keys, int32_t head
                       const void *saved, const float *g_out, float *g_q, float *g_kv, void *scratch, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The fused cross-attention with 16-bit tensors, for the distillation step under mixed precision (csrc/fgs_attn_half.hip).
+ * dtype selects fp16 (FGS_ATTN_F16) or bf16 (FGS_ATTN_BF16); q, kv, out, g_out, g_q, g_kv are tensors of that ONE type with the
+ * shapes and layouts of fgs_attn_*; row_keep, seed, saved (one FP32 per (b, h, n): max + ln(sum), +Inf for a bad row) and scratch
+ * (delta, fp32) are as there.
+ *
+ * DEFINITION: the result is fgs_attn_*'s definition above, evaluated on the 16-bit inputs.  Masked rows, the NaN rule -- decided
+ * on the fp32 scores -- and dropout's keep function of (seed, b, h, n, m) are unchanged: the same seed keeps the same elements in
+ * every precision.
+ *
+ * NUMERICAL CONTRACT (the roundings are error against the definition, not part of it):
+ *   - every matrix product takes 16-bit operands and accumulates in fp32 in the matrix cores' accumulators;
+ *   - scores are never rounded to 16 bits: the scale, the -1e4 row fill, the online softmax (maximum, exp, running sum, rescale),
+ *     delta = <g_out, out> (on the stored, rounded `out`) and `saved` are fp32;
+ *   - only the operands of the second-stage products are rounded to the 16-bit type, to nearest even: P (after dropout's keep, before
+ *     the fp32 normalisation 1 / ((1 - dropout_p) sum)) ahead of O^T += V^T P^T, the probabilities a = c p ahead of dV^T += dO^T A, and
+ *     dS = p (c dA - delta) scale ahead of dQ^T += K^T dS^T and dK^T += Q^T dS.  A bad row's 1 / M is applied in fp32 to an exact sum
+ *     of v in the forward; in g_v it is a rounded operand like any other probability;
+ *   - out, g_q, g_kv are rounded once, at the store.
+ * Stated differences from torch's op sequence under autocast: (1) a score beyond 65504 is finite here, where torch's fp16 product
+ * overflows to Inf and the row falls to its nan_to_num (1 / M each): a row with one dominant such score returns that key's value
+ * row here and the mean of v there; (2) dS in fp16 can underflow for small upstream gradients -- what a gradient scaler is for; bf16
+ * needs none.
+ *
+ * Determinism and buffers as fgs_attn_*: one launch forward, three backward, no float atomics, every sum in a fixed order, bitwise
+ * repeatable, an image's out / g_q / g_kv do not depend on its batch, nothing read on the host, capturable; every element of out,
+ * saved, g_q and g_kv is written, scratch is written before it is read, the initial content of any of them is irrelevant, inputs are
+ * never modified.  The key tile (and the query tile of the key-block backward) is FGS_ATTN_HALF_KEY_TILE; query and key blocks are
+ * FGS_ATTN_QUERY_BLOCK and FGS_ATTN_KEY_BLOCK; head_dim runs zero-padded to 32, 64 or 128.  Rows are read with 16-byte loads and
+ * written with 8-byte stores when head_dim % 8 == 0 and every 16-bit tensor of the call starts on a 16-byte boundary; any other
+ * head_dim or base (a tensor needs 2-byte alignment only) runs the same loops element by element, with the same results.
+ * saved_bytes = scratch_bytes = 4 B H N rounded up to 256.  Limits and errors as fgs_attn_*, plus FGS_EINVAL for an unknown dtype;
+ * all of it before anything touches the device. */
+#define FGS_ATTN_F16 1
+#define FGS_ATTN_BF16 2
+#define FGS_ATTN_HALF_KEY_TILE 32
+int fgs_attn_half_workspace_bytes(int32_t batch, int32_t queries, int32_t keys, int32_t heads, int32_t head_dim, size_t *saved_bytes,
+                                  size_t *scratch_bytes);
+int fgs_attn_half_forward(int32_t dtype, int32_t batch, int32_t queries, int32_t keys, int32_t heads, int32_t head_dim, float scale,
+                          float dropout_p, const void *q, const void *kv, const uint8_t *row_keep /* (B,N) or NULL */,
+                          const int64_t *seed /* 1, device; NULL with dropout_p 0 */, void *out, void *saved, void *stream);
+int fgs_attn_half_backward(int32_t dtype, int32_t batch, int32_t queries, int32_t keys, int32_t heads, int32_t head_dim, float scale,
+                           float dropout_p, const void *q, const void *kv, const uint8_t *row_keep, const int64_t *seed,
+                           const void *out, const void *saved, const void *g_out, void *g_q, void *g_kv, void *scratch, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Fused wave self-attention of the consistency view synthesizer (scripts/models/consistency_view_synthesis.py, "CVS":
  * FresnelWaveAttention, 191-246): multi-head self-attention over the N = grid_h grid_w tokens of a feature map, with an interference
  * term that depends on the two tokens' grid distance added to the logits, flash-style -- nothing of size N x N is stored.
