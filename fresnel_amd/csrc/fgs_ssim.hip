@@ -195,7 +195,8 @@ __global__ __launch_bounds__(NTHR) void k_ssim_fwd(Geo g, Taps taps, int n_rt, f
     if (threadIdx.x == 0) part[blockIdx.x] = t;
 }
 
-// per-plane means -> cs (double, in `saved`), then the requested output.  Wave w sums planes w, w + 4, ...
+// per-plane means -> cs (double, in `saved`), then the requested output.  Wave w sums planes 8w .. 8w + 7, then 32 on.
+// The relu clips what compares <= 0, so a NaN mean reaches the output (the training step's NaN skip reads it).
 __global__ __launch_bounds__(RT) void k_ssim_reduce(int images, int channels, int tiles, double inv_count, int flags,
                                                     const double *__restrict__ part, double *__restrict__ cs,
                                                     float *__restrict__ out) {
@@ -223,13 +224,13 @@ __global__ __launch_bounds__(RT) void k_ssim_reduce(int images, int channels, in
             double v = 0.0;
             for (int c = 0; c < channels; ++c) {
                 const double s = cs[b * channels + c];
-                v += relu ? (s > 0.0 ? s : 0.0) : s;
+                v += (relu && s <= 0.0) ? 0.0 : s;  // (as torch.relu: a NaN mean stays NaN)
             }
             out[b] = (float)(v / channels);
         }
     } else {  // thread t sums planes t, t + RT, ... in order, then the threads in a fixed order: no serial chain of loads
         double v = 0.0;
-        for (int p = threadIdx.x; p < planes; p += RT) v += relu ? (cs[p] > 0.0 ? cs[p] : 0.0) : cs[p];
+        for (int p = threadIdx.x; p < planes; p += RT) v += (relu && cs[p] <= 0.0) ? 0.0 : cs[p];
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
         __shared__ double ws[RT / 64];
@@ -268,7 +269,7 @@ __global__ __launch_bounds__(NTHR) void k_ssim_bwd(Geo g, Taps rtaps, int n_rt, 
     const bool per_image = flags & FGS_SSIM_PER_IMAGE;
     const float gsel = g_out[per_image ? plane / channels : 0];
     const double cval = cs[plane];
-    const bool live = !(flags & FGS_SSIM_NONNEGATIVE) || cval > 0.0;
+    const bool live = !((flags & FGS_SSIM_NONNEGATIVE) && cval <= 0.0);  // (a NaN mean is not clipped: relu'(NaN) = 1 in torch)
     const float s = live ? (float)((double)gsel / ((per_image ? (double)channels : (double)images * channels) *
                                                   (double)g.Ho * (double)g.Wo)) : 0.0f;
     if (!live) {  // a clipped plane: its gradient is exactly zero (block-uniform branch)

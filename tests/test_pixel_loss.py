@@ -458,6 +458,41 @@ def test_hip_pixel_losses_match_the_checker(shape, combo):
         _check_depth_grad(rdd.grad, w_gd, umv, f"{shape} {combo}")
 
 
+# Shapes past the grid cap (2048 blocks x 256 threads = 524 288 work items a trip): every larger shape above is one trip.
+#   1x725x725: H W is odd, so the loads are scalar; 525 625 pixels, 1 337 threads take a second trip.
+#   1x1448x1452: H W is a multiple of 4, so the loads are 16 bytes; 525 624 groups of 4 pixels, 1 336 threads take a second trip.
+# A skipped or doubly counted trip moves a term by ~7e-4 and leaves gradient pixels wrong by the whole maximum.  (Seed 30: 5 of
+# 525 625 and 14 of 2 102 496 pixels are near ties on the fp64 checker, 9.5e-6 and 6.7e-6 of them, within the 1e-4 cap.)
+SECOND_TRIP_SHAPES = {"1x3x725x725_scalar": (1, 725, 725), "1x3x1448x1452_vector": (1, 1448, 1452)}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", list(SECOND_TRIP_SHAPES))
+def test_hip_pixel_losses_second_grid_stride_trip(shape):
+    from fresnel_amd.losses import pixel_losses
+    dev = _dev()
+    Bn, H, W = SECOND_TRIP_SHAPES[shape]
+    groups = Bn * H * W // (4 if (H * W) % 4 == 0 else 1)
+    assert 2048 * 256 < groups < 2 * 2048 * 256 and 3 * Bn * H * W < 2 ** 31
+    use_den, zones, use_rd, use_td = COMBOS["all_soft"]
+    r, t, rd, td, den = _inputs((Bn, H, W), 30, dtype=torch.float32)
+    g = dict(rgb=0.9, boundary=0.35, depth=0.2)
+    want, w_gr, w_gd, umv = _reference(r, t, rd, td, den, zones, g)
+    rr, rdd = r.to(dev).requires_grad_(True), rd.to(dev).requires_grad_(True)
+    terms = pixel_losses(rr, t.to(dev), rdd, td.to(dev), den.to(dev), 0.5, zones)
+    assert set(terms) == set(want) == {"rgb", "boundary", "depth"}
+    sum(g[k] * v for k, v in terms.items()).backward()
+    for k in want:
+        err = abs(float(terms[k].detach()) - want[k])
+        print(f"{shape}: {k} {float(terms[k].detach()):.7f} checker {want[k]:.7f} |diff| {err:.2e}")
+        assert err <= 1e-5, (k, float(terms[k].detach()), want[k])
+    err = rel_to_max(rr.grad.cpu().numpy(), w_gr.numpy())
+    print(f"{shape}: rendered gradient {err:.3e} of max")
+    assert err <= 1e-4
+    assert float(rr.grad[0, :, :5, :7].abs().max()) == 0.0  # the block of exact ties: exactly zero
+    _check_depth_grad(rdd.grad, w_gd, umv, shape)
+
+
 @pytest.mark.gpu
 def test_hip_pixel_losses_single_terms_and_unaligned_views():
     """The staged API with the rgb term off (boundary alone, depth alone), and inputs whose pointers are not 16-byte aligned

@@ -1,8 +1,9 @@
 """SSIM loss (fresnel_amd/losses.py ssim / SSIM -> fgs_ssim_* in libfgs_hip.so, csrc/fgs_ssim.hip): the SSIM term of the
 reference's training loss, `pytorch_msssim.ssim(clamp(rendered, 0, 1), target, data_range=1.0)` (TGD:904).
 
-The checker below restates pytorch_msssim.ssim in fp64 torch (the package is not a dependency): separable Gaussian window
-applied "valid" with grouped conv2d along H then W, C1 = (K1 R)^2, C2 = (K2 R)^2, per-channel means, optional relu, mean.
+The checker (tests/ssim_checker.py) restates pytorch_msssim.ssim in fp64 torch (the package is not a dependency): separable
+Gaussian window applied "valid" with grouped conv2d along H then W, C1 = (K1 R)^2, C2 = (K2 R)^2, per-channel means,
+optional relu, mean.
 CPU: the checker against the definition's known answers and torch's gradcheck; the closed-form backward the kernels
 implement against the checker's autograd; the library's SSIM ABI and the API's argument checks; the training step's
 default SSIM behaviour.  GPU: the product against the checker (loss <= 1e-5 absolute, every gradient <= 1e-4 of its
@@ -14,75 +15,7 @@ import torch
 import torch.nn.functional as F
 
 from helpers import rel_to_max
-
-
-# ---- the checker: pytorch_msssim.ssim restated in fp64 -------------------------------------------------------------
-def gauss_window(win_size=11, win_sigma=1.5):
-    """pytorch_msssim._fspecial_gauss_1d: built in fp32 (what the package and the kernels use)."""
-    coords = torch.arange(win_size, dtype=torch.float32)
-    coords -= win_size // 2
-    g = torch.exp(-(coords ** 2) / (2 * win_sigma ** 2))
-    g /= g.sum()
-    return g
-
-
-def _filter(x, win):
-    """pytorch_msssim.gaussian_filter: valid grouped correlation along H, then along W."""
-    C = x.shape[1]
-    n = win.numel()
-    w = win.to(x.dtype).reshape(1, 1, 1, n).repeat(C, 1, 1, 1)
-    return F.conv2d(F.conv2d(x, w.transpose(2, 3), groups=C), w, groups=C)
-
-
-def _filter_t(m, win):
-    """The transpose of _filter: the zero-padded full convolution back to H x W."""
-    C = m.shape[1]
-    n = win.numel()
-    w = win.to(m.dtype).reshape(1, 1, 1, n).repeat(C, 1, 1, 1)
-    return F.conv_transpose2d(F.conv_transpose2d(m, w, groups=C), w.transpose(2, 3), groups=C)
-
-
-def _moments(X, Y, win, data_range, K):
-    c1, c2 = (K[0] * data_range) ** 2, (K[1] * data_range) ** 2
-    mux, muy = _filter(X, win), _filter(Y, win)
-    sxx = _filter(X * X, win) - mux * mux
-    syy = _filter(Y * Y, win) - muy * muy
-    sxy = _filter(X * Y, win) - mux * muy
-    return mux, muy, 2 * mux * muy + c1, mux * mux + muy * muy + c1, 2 * sxy + c2, sxx + syy + c2
-
-
-def ref_ssim(X, Y, data_range=255, size_average=True, win_size=11, win_sigma=1.5, win=None, K=(0.01, 0.03),
-             nonnegative_ssim=False, per_channel=False):
-    X, Y = X.double(), Y.double()
-    win = gauss_window(win_size, win_sigma) if win is None else win
-    _, _, A1, B1, A2, B2 = _moments(X, Y, win, data_range, K)
-    S = (A1 / B1) * (A2 / B2)
-    cs = S.flatten(2).mean(-1)
-    if nonnegative_ssim:
-        cs = torch.relu(cs)
-    if per_channel:
-        return cs
-    return cs.mean() if size_average else cs.mean(1)
-
-
-def closed_form_grads(X, Y, g_out, data_range=255, size_average=True, win=None, K=(0.01, 0.03), nonnegative_ssim=False):
-    """The backward fgs_ssim_backward implements: factor maps dS/dmu_x, dS/dE[x^2], dS/dE[xy] (and dS/dmu_y), weighted by
-    the plane's share s of the loss, through the transposed filter and combined pointwise with X and Y."""
-    win = gauss_window() if win is None else win
-    mux, muy, A1, B1, A2, B2 = _moments(X, Y, win, data_range, K)
-    S = (A1 / B1) * (A2 / B2)
-    Bn, C = X.shape[:2]
-    cs = S.flatten(2).mean(-1)
-    mask = (cs > 0).to(X.dtype) if nonnegative_ssim else torch.ones_like(cs)
-    per_plane = g_out.reshape(()).expand(Bn, C) / (Bn * C) if size_average else g_out.reshape(Bn, 1).expand(Bn, C) / C
-    s = (per_plane * mask / S[0, 0].numel())[:, :, None, None]
-    d_mux = S * (2 * muy / A1 - 2 * mux / B1 - 2 * muy / A2 + 2 * mux / B2)
-    d_muy = S * (2 * mux / A1 - 2 * muy / B1 - 2 * mux / A2 + 2 * muy / B2)
-    d_e2, d_exy = -S / B2, 2 * S / A2
-    G1, G2 = _filter_t(s * d_e2, win), _filter_t(s * d_exy, win)
-    dX = _filter_t(s * d_mux, win) + 2 * X * G1 + Y * G2
-    dY = _filter_t(s * d_muy, win) + 2 * Y * G1 + X * G2
-    return dX, dY
+from ssim_checker import closed_form_grads, gauss_window, ref_ssim
 
 
 # ---- CPU ------------------------------------------------------------------------------------------------------------
